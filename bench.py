@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mrays/s of the path-tracing hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--workload m1|c2|c3|c4]
+  python bench.py --gpus N --steps K --warmup W [--workload m1|c2|c3|c4] [--dump-outputs DIR] [--full]
 
 A *step* is one full render pass of the workload's frame through the C ABI (renderPassDevice ->
 yafgpu_render_tiles, then the film combine; for N > 1 each rank renders its tile shard, combines its
@@ -16,11 +16,18 @@ Workloads:
   c3  1M-triangle diffuse soup, 1024x1024, 256 spp, 2 bounces                           (configs[2])
   c4  1M-triangle soup, 50% glossy, 2 area lights (BSDF sampling + MIS), 1024x1024, 64 spp  (configs[3])
 
-Output: one JSON line with the contract fields plus `roofline` (dominant kernel: wf_trace; `achieved` =
-SURVEY 8(d) algorithmic bytes / launch time measured live with HIP events; `traffic` and `hbm_measured_GBps`
-= the memory-side bytes of the committed rocprofv3 PMC run of this workload) and `cpu_baseline` (the CPU
-oracle — a port of the reference's algorithm — timed single-threaded and on all host cores of this box's
-CPU share on a bounded sample of the same scene).
+Output: one JSON line with the contract fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`
+= wall milliseconds of one timed step) and the workload's `config`.  A plain run does only that: set up, warm up, time
+the steps, print.  `--full` adds what takes passes or runs of its own: `roofline` (dominant kernel: wf_trace; `achieved` =
+SURVEY 8(d) algorithmic bytes / launch time measured live with HIP events in two extra, untimed passes; `traffic` and
+`hbm_measured_GBps` = the memory-side bytes of the committed rocprofv3 PMC run of this workload) and `cpu_baseline` (the
+CPU oracle — a port of the reference's algorithm — timed single-threaded and on all host cores of this box's CPU share
+on a bounded sample of the same scene; `--no-cpu-baseline` leaves it out).
+
+`--dump-outputs DIR` writes what the last timed step computed, as rank 0's caller receives it: DIR/film.npy (the
+combined [H][W][5] float32 film: RGBA sums and the filter weight per pixel) and DIR/ray_counts.npy (float64: closest-hit
+rays, shadow rays and camera samples per timed step).  The scene is generated from the workload's fixed seed, so the
+same arguments give the same inputs on every run.
 """
 import argparse
 import hashlib
@@ -199,7 +206,11 @@ def main():
     ap.add_argument("--workload", default="m1", choices=sorted(WORKLOADS))
     ap.add_argument("--res", type=int, default=0, help="override resolution (debug)")
     ap.add_argument("--spp", type=int, default=0, help="override samples per pixel (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline (two extra profiled passes) and the CPU baseline; a plain run times the steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's film and ray counts to DIR/<name>.npy (rank 0)")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="N-rank rehearsal on a ONE-GPU box: every rank uses cuda:0 and the film reduce goes through gloo "
                          "(host staging). Exercises sharding + reduce + combine with the real kernels; not a measurement.")
@@ -209,6 +220,8 @@ def main():
                     help="film reduce of an N-rank run: 'rccl' = the C ABI's ncclReduce (yafaray_reduceFilm), 'torch' = torch.distributed.reduce, "
                          "'auto' = rccl, falling back to torch (and saying so) if the communicator cannot be created")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -307,18 +320,21 @@ def main():
         step()
     barrier()
     counters.zero_()
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    # HIP events around each step's render pass feed the roofline only (--full)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if args.full else None
     barrier()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        ev[k][0].record()
+        if ev:
+            ev[k][0].record()
         yi.renderPassDevice(planes.data_ptr(), counters.data_ptr(), stream)
-        ev[k][1].record()
+        if ev:
+            ev[k][1].record()
         yi_mod.film_combine(planes.data_ptr(), film.data_ptr(), W, H, stream)
         reduce()
     barrier()
     elapsed = time.perf_counter() - t0
-    kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))   # render_kernel (+ its memset/tile upload), same stream
+    kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if ev else None   # render_kernel (+ its memset/tile upload), same stream
 
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     cnt = counters.clone()
@@ -331,7 +347,52 @@ def main():
     c = cnt.cpu().numpy()
     rays_total = int(c[0] + c[1])
     value = rays_total / elapsed / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, film.cpu().numpy(), c, args.steps)
 
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "Mrays/sec (primary+secondary) on the path-tracing hot path", "value": round(value, 3), "unit": "Mrays/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": w["desc"], "triangles": int(stats0.n_triangles), "width": W, "height": H, "spp": w["spp"],
+                       "bounces": w["bounces"], "lights": w["lights"], "parallelism": f"pixel-tile shard x{world}", "film_reduce": reduce_kind,
+                       "rays_per_step": rays_total // args.steps, "rays_per_camera_sample": round(rays_total / max(int(c[5]), 1), 3),
+                       "kd_nodes": int(stats0.kd_nodes), "kd_leaf_refs": int(stats0.kd_leaf_refs), "kd_max_depth": int(stats0.kd_max_depth),
+                       "scene_device_MB": round(stats0.scene_device_bytes / 1e6, 1), "setup_s": round(setup_s, 2),
+                       "tree_build_s": round(stats0.tree_build_seconds, 2)},
+        }
+    if args.full:
+        roofline = measure_roofline(args, yi, planes, counters, stream, kernel_ms, world)
+        if rank == 0:
+            out["roofline"] = roofline
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args.workload)
+    if rank == 0:
+        if args.rehearse_one_gpu:
+            f = film.cpu().numpy()
+            out["film_checksum"] = {"sum_rgb": float(f[..., :3].astype(np.float64).sum()), "sum_weight": float(f[..., 4].astype(np.float64).sum()),
+                                    "crc": int(np.frombuffer(f.tobytes(), dtype=np.uint32).astype(np.uint64).sum() & 0xffffffff)}
+        print(json.dumps(out))
+    if comm is not None:
+        yi.setComm(None)
+        comm.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, film, counters, steps):
+    """the timed path's result as its caller receives it: the combined film (float32, 5 MB at 512^2, 21 MB at 1024^2) and
+    the step's ray counts (the counters summed over the timed steps, whose passes render the same frame, / steps)"""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "film.npy"), np.ascontiguousarray(film, dtype=np.float32))
+    np.save(os.path.join(path, "ray_counts.npy"), np.array([counters[0], counters[1], counters[5]], dtype=np.float64) / steps)
+
+
+def measure_roofline(args, yi, planes, counters, stream, kernel_ms, world):
+    """--full: the `roofline` object of the result line (every rank runs the passes; rank 0 reports)"""
+    import torch
     # per-ray traversal averages for the algorithmic-bytes figure + per-kernel device time: one extra,
     # untimed pass of the counting variant of the traversal kernels with HIP events around every launch
     os.environ["YAFGPU_STATS"] = "1"
@@ -369,59 +430,35 @@ def main():
     avg_launch_s = trace_ms * 1e-3 / max(trace_launches, 1)
     hbm_measured = (traffic / avg_launch_s / 1e9) if traffic else None
 
-    if rank == 0:
-        out = {
-            "metric": "Mrays/sec (primary+secondary) on the path-tracing hot path", "value": round(value, 3), "unit": "Mrays/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": w["desc"], "triangles": int(stats0.n_triangles), "width": W, "height": H, "spp": w["spp"],
-                       "bounces": w["bounces"], "lights": w["lights"], "parallelism": f"pixel-tile shard x{world}", "film_reduce": reduce_kind,
-                       "rays_per_step": rays_total // args.steps, "rays_per_camera_sample": round(rays_total / max(int(c[5]), 1), 3),
-                       "kd_nodes": int(stats0.kd_nodes), "kd_leaf_refs": int(stats0.kd_leaf_refs), "kd_max_depth": int(stats0.kd_max_depth),
-                       "scene_device_MB": round(stats0.scene_device_bytes / 1e6, 1), "setup_s": round(setup_s, 2),
-                       "tree_build_s": round(stats0.tree_build_seconds, 2)},
-            # `bound` names what limits the kernel (PMC: VALU issue slots ~0.8 busy at < 0.5 lane utilisation, working set cache-resident,
-            # counter-side HBM rate 0.2-0.4 of peak); `achieved` / `peak` / `frac` are nevertheless the bench contract's accounting
-            # against the HBM roofline (`accounting`), with the counter-side figure beside them (`hbm_measured_*`)
-            "roofline": {"bound": "valu-issue (cache-resident)", "accounting": "hbm: SURVEY 8(d) algorithmic bytes / measured launch time over the 8 TB/s HBM peak",
-                         "kernel": "wf_trace (closest-hit + any-hit kd traversal)", "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                         "pmc_stale": bool(pmc_stale), "kernel_key": kernel_key(),
-                         "pmc_file": None if pmc is None else pmc.get("_file"),
-                         # `achieved` / `frac` follow the bench contract: SURVEY 8(d) ALGORITHMIC bytes / measured launch time.
-                         # The memory-side figure is beside it: counter bytes (traffic) / the same launch time.  The scene
-                         # (~100 MB at 1M triangles) is L2 / Infinity-Cache resident, so the kernel is bound by vector
-                         # instruction issue under divergence, not by HBM (see `limiter`).
-                         "algorithmic_GBps": round(achieved, 2),
-                         "hbm_measured_GBps": None if hbm_measured is None else round(hbm_measured, 2),
-                         "hbm_measured_frac": None if hbm_measured is None else round(hbm_measured / HBM_PEAK_GBS, 5),
-                         "limiter": "VALU issue under SIMT divergence (working set cache-resident)",
-                         "pmc": None if (pmc is None or pmc_stale) else {k: pmc[k] for k in ("source", "fetch_correction", "fetch_bytes_per_launch_raw",
-                                                                            "write_bytes_per_launch", "lane_utilisation", "salu_per_valu",
-                                                                            "shade") if k in pmc},
-                         "algorithmic_bytes_per_launch": round(bytes_per_ray * rays_launch / max(trace_launches, 1)),
-                         "launches_per_pass": int(trace_launches), "avg_launch_ms": round(trace_ms / max(trace_launches, 1), 4),
-                         "rays_per_launch": round(rays_launch / max(trace_launches, 1)),
-                         "pass_ms": {k: round(v[0], 3) for k, v in prof.items()}, "pass_ms_total": round(kernel_ms, 3),
-                         "bytes_per_ray": round(bytes_per_ray, 1),
-                         "per_ray": {"interior_nodes": round(n_int, 2), "leaves": round(n_leaf, 2), "tri_tests": round(n_tri, 2),
-                                     "restarts": round(s[6] / rays_launch, 5)},
-                         # lanes doing a step per wave round of that kind / 64 (stats pass only)
-                         "simt": {"node_rounds": round((int(s[2]) + int(s[3])) / max(64 * (int(s[7]) & 0xffffffff), 1), 3),
-                                  "tri_rounds": round(int(s[4]) / max(64 * (int(s[7]) >> 32), 1), 3)}},
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.workload)
-        if args.rehearse_one_gpu:
-            f = film.cpu().numpy()
-            out["film_checksum"] = {"sum_rgb": float(f[..., :3].astype(np.float64).sum()), "sum_weight": float(f[..., 4].astype(np.float64).sum()),
-                                    "crc": int(np.frombuffer(f.tobytes(), dtype=np.uint32).astype(np.uint64).sum() & 0xffffffff)}
-        print(json.dumps(out))
-    if comm is not None:
-        yi.setComm(None)
-        comm.close()
-    if world > 1:
-        dist.destroy_process_group()
+    # `bound` names what limits the kernel (PMC: VALU issue slots ~0.8 busy at < 0.5 lane utilisation, working set cache-resident,
+    # counter-side HBM rate 0.2-0.4 of peak); `achieved` / `peak` / `frac` are nevertheless the bench contract's accounting
+    # against the HBM roofline (`accounting`), with the counter-side figure beside them (`hbm_measured_*`)
+    return {"bound": "valu-issue (cache-resident)", "accounting": "hbm: SURVEY 8(d) algorithmic bytes / measured launch time over the 8 TB/s HBM peak",
+            "kernel": "wf_trace (closest-hit + any-hit kd traversal)", "achieved": round(achieved, 2),
+            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+            "pmc_stale": bool(pmc_stale), "kernel_key": kernel_key(),
+            "pmc_file": None if pmc is None else pmc.get("_file"),
+            # `achieved` / `frac` follow the bench contract: SURVEY 8(d) ALGORITHMIC bytes / measured launch time.
+            # The memory-side figure is beside it: counter bytes (traffic) / the same launch time.  The scene
+            # (~100 MB at 1M triangles) is L2 / Infinity-Cache resident, so the kernel is bound by vector
+            # instruction issue under divergence, not by HBM (see `limiter`).
+            "algorithmic_GBps": round(achieved, 2),
+            "hbm_measured_GBps": None if hbm_measured is None else round(hbm_measured, 2),
+            "hbm_measured_frac": None if hbm_measured is None else round(hbm_measured / HBM_PEAK_GBS, 5),
+            "limiter": "VALU issue under SIMT divergence (working set cache-resident)",
+            "pmc": None if (pmc is None or pmc_stale) else {k: pmc[k] for k in ("source", "fetch_correction", "fetch_bytes_per_launch_raw",
+                                                               "write_bytes_per_launch", "lane_utilisation", "salu_per_valu",
+                                                               "shade") if k in pmc},
+            "algorithmic_bytes_per_launch": round(bytes_per_ray * rays_launch / max(trace_launches, 1)),
+            "launches_per_pass": int(trace_launches), "avg_launch_ms": round(trace_ms / max(trace_launches, 1), 4),
+            "rays_per_launch": round(rays_launch / max(trace_launches, 1)),
+            "pass_ms": {k: round(v[0], 3) for k, v in prof.items()}, "pass_ms_total": round(kernel_ms, 3),
+            "bytes_per_ray": round(bytes_per_ray, 1),
+            "per_ray": {"interior_nodes": round(n_int, 2), "leaves": round(n_leaf, 2), "tri_tests": round(n_tri, 2),
+                        "restarts": round(s[6] / rays_launch, 5)},
+            # lanes doing a step per wave round of that kind / 64 (stats pass only)
+            "simt": {"node_rounds": round((int(s[2]) + int(s[3])) / max(64 * (int(s[7]) & 0xffffffff), 1), 3),
+                     "tri_rounds": round(int(s[4]) / max(64 * (int(s[7]) >> 32), 1), 3)}}
 
 
 if __name__ == "__main__":

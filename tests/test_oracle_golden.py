@@ -353,22 +353,18 @@ def test_light_material(gold):
     check(variant, got, g["lm_emit3"], "LightMaterial::emit")
 
 
-@pytest.mark.container
 def test_faure_tables_match_reference_file():
     """The oracle regenerates the Faure permutations and the 9-digit inverse primes instead of copying
-    them; compare with the numbers in the reference's files (read as text, container only)."""
-    import re
+    them; compare with the numbers in the reference's files (tests/golden/faure_tables.json.gz, taken from the
+    reference's table by tests/golden/make_golden.py)."""
     L = po.lib()
-    txt = open("/root/reference/src/common/faure_tables.cc").read()
-    arrays = {int(m.group(1)): [int(v) for v in m.group(2).replace("\n", " ").split(",") if v.strip()]
-              for m in re.finditer(r"int fp_(\d+)__\[\] = \{([^}]*)\}", txt)}
-    order = re.search(r"faure__\[\] = \{([^}]*)\}", txt).group(1)
-    names = [int(v) for v in re.findall(r"fp_(\d+)__", order)]
-    assert len(names) == 51
+    with gzip.open(os.path.join(HERE, "golden", "faure_tables.json.gz"), "rt") as f:
+        d = json.load(f)
+    assert d["n_table_entries"] == 51 and len(d["perms"]) == 50
     for dim in range(50):
         n = C.c_int()
         p = L.yor_faure_perm(dim, C.byref(n))
-        assert [p[i] for i in range(n.value)] == arrays[names[dim]], dim
+        assert [p[i] for i in range(n.value)] == d["perms"][dim], dim
 
 
 def test_whole_path_against_the_references_expected_png():

@@ -3,6 +3,6 @@
 for b in host device; do
   for w in "$@"; do
     echo "== YAFGPU_BUILD=$b workload=$w"
-    YAFGPU_BUILD=$b timeout -k 10 300 python bench.py --steps 5 --warmup 2 --workload $w --no-cpu-baseline || exit 1
+    YAFGPU_BUILD=$b timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --workload $w --no-cpu-baseline || exit 1
   done
 done

@@ -7,7 +7,7 @@ out="$1"; var="$2"; vals="$3"; wls="$4"; shift 4
 for rep in 1 2; do
 for wl in $wls; do
 for v in $vals; do
-	line=$(env "$var=$v" timeout -k 10 240 python3 bench.py --no-cpu-baseline --workload "$wl" --steps 6 --warmup 2 "$@" 2>/dev/null | tail -1)
+	line=$(env "$var=$v" timeout -k 10 240 python3 bench.py --full --no-cpu-baseline --workload "$wl" --steps 6 --warmup 2 "$@" 2>/dev/null | tail -1)
 	python3 - "$wl" "$var=$v" "$line" >> "$out" <<'PY'
 import json, sys
 wl, tag, line = sys.argv[1:4]

@@ -9,7 +9,7 @@ for wl in $wls; do
 for spec in "$@"; do
 	name="${spec%%=*}"; lib="${spec#*=}"
 	st="--steps 6 --warmup 2"; [ "$wl" = c4 ] && st="--steps 3 --warmup 1"; [ "$wl" = c3 ] && st="--steps 2 --warmup 1"
-	line=$(env YAFARAY_LIBRARY="$PWD/$lib" timeout -k 10 300 python3 bench.py --no-cpu-baseline --workload $wl $st 2>/dev/null | tail -1)
+	line=$(env YAFARAY_LIBRARY="$PWD/$lib" timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --workload $wl $st 2>/dev/null | tail -1)
 	python3 - "$wl $name" "$line" >> "$out" <<'PY'
 import json, sys
 tag, line = sys.argv[1:3]

@@ -7,7 +7,7 @@ out="$1"; wls="$2"; crs="$3"; ebs="$4"
 for wl in $wls; do
 for cr in $crs; do
 for eb in $ebs; do
-	line=$(env YAFGPU_COST_RATIO=$cr YAFGPU_EMPTY_BONUS=$eb timeout -k 10 240 python3 bench.py --no-cpu-baseline --workload "$wl" --steps 6 --warmup 2 2>/dev/null | tail -1)
+	line=$(env YAFGPU_COST_RATIO=$cr YAFGPU_EMPTY_BONUS=$eb timeout -k 10 240 python3 bench.py --full --no-cpu-baseline --workload "$wl" --steps 6 --warmup 2 2>/dev/null | tail -1)
 	python3 - "$wl" "cost_ratio=$cr empty_bonus=$eb" "$line" >> "$out" <<'PY'
 import json, sys
 wl, tag, line = sys.argv[1:4]

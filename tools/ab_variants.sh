@@ -9,7 +9,7 @@ for r in $(seq 1 "$rounds"); do
   for lib in default $(ls libyafaray_amd/variants/*.so 2>/dev/null); do
     name="$(basename "$lib" .so)"
     if [ "$lib" = default ]; then unset YAFARAY_LIBRARY; else export YAFARAY_LIBRARY="$PWD/$lib"; fi
-    timeout -k 10 300 python3 bench.py --no-cpu-baseline --steps 10 --warmup 2 "$@" 2>/dev/null | python3 -c "
+    timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 2 "$@" 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

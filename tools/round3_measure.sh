@@ -8,15 +8,15 @@ repo="$PWD"; tag="${1:-r03}"; out="$repo/gpurun_out"
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd "$repo"
 echo "== m1 bench (default command)"
-timeout -k 10 600 python3 bench.py > "$out/${tag}_m1_bench.json" 2> "$out/${tag}_m1_bench.err" || echo "bench failed"
+timeout -k 10 600 python3 bench.py --full > "$out/${tag}_m1_bench.json" 2> "$out/${tag}_m1_bench.err" || echo "bench failed"
 cut -c1-400 "$out/${tag}_m1_bench.json"
 echo "== m1 rocprofv3 kernel stats (same command, no cpu baseline; YAFGPU_OVERLAP=0: one kernel on the GPU at a time, like the profiled pass the roofline's durations come from)"
-YAFGPU_OVERLAP=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_m1_prof" -- python3 bench.py --no-cpu-baseline > "$out/${tag}_m1_prof.log" 2>&1 || echo "rocprof failed"
+YAFGPU_OVERLAP=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_m1_prof" -- python3 bench.py --full --no-cpu-baseline > "$out/${tag}_m1_prof.log" 2>&1 || echo "rocprof failed"
 f=$(find "$out/${tag}_m1_prof" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$out/${tag}_m1_kernel_stats.csv" && head -8 "$out/${tag}_m1_kernel_stats.csv"
 echo "== m1 PMC passes"
 bash tools/pmc.sh "gpurun_out/${tag}_m1_pmc" --workload m1 > "$out/${tag}_m1_pmc.txt" 2>&1; tail -3 "$out/${tag}_m1_pmc.txt"
 for wl in c2; do
-  timeout -k 10 600 python3 bench.py --workload $wl --no-cpu-baseline --steps 10 --warmup 2 > "$out/${tag}_${wl}_bench.json" 2> "$out/${tag}_${wl}_bench.err" || echo "bench $wl failed"
+  timeout -k 10 600 python3 bench.py --full --workload $wl --no-cpu-baseline --steps 10 --warmup 2 > "$out/${tag}_${wl}_bench.json" 2> "$out/${tag}_${wl}_bench.err" || echo "bench $wl failed"
   cut -c1-300 "$out/${tag}_${wl}_bench.json"
 done
 echo "== what one rank of N does per pass (shard 0 of N of the metric frame on this one GPU; reduce not included)"
@@ -30,9 +30,9 @@ for l in sys.stdin:
 done
 for wl in c3 c4; do
   echo "== $wl bench + kernel stats"
-  timeout -k 10 600 python3 bench.py --workload $wl --steps 2 --warmup 1 --no-cpu-baseline > "$out/${tag}_${wl}_bench.json" 2> "$out/${tag}_${wl}_bench.err" || echo "bench $wl failed"
+  timeout -k 10 600 python3 bench.py --full --workload $wl --steps 2 --warmup 1 --no-cpu-baseline > "$out/${tag}_${wl}_bench.json" 2> "$out/${tag}_${wl}_bench.err" || echo "bench $wl failed"
   cut -c1-300 "$out/${tag}_${wl}_bench.json"
-  YAFGPU_OVERLAP=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_${wl}_prof" -- python3 bench.py --workload $wl --steps 2 --warmup 1 --no-cpu-baseline > "$out/${tag}_${wl}_prof.log" 2>&1 || echo "rocprof $wl failed"
+  YAFGPU_OVERLAP=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_${wl}_prof" -- python3 bench.py --full --workload $wl --steps 2 --warmup 1 --no-cpu-baseline > "$out/${tag}_${wl}_prof.log" 2>&1 || echo "rocprof $wl failed"
   f=$(find "$out/${tag}_${wl}_prof" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$out/${tag}_${wl}_kernel_stats.csv"
 done
 echo "== c4 PMC passes"

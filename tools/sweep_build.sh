@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 flags="$1"; shift
 YAFGPU_EXTRA_FLAGS="$flags" bash libyafaray_amd/csrc/build.sh > /dev/null 2>&1
 echo "== $flags"
-python3 bench.py --no-cpu-baseline "$@" 2>/dev/null | python3 -c "import sys,json
+python3 bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python3 -c "import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
         d=json.loads(l); r=d['roofline']; print('   Mrays/s', d['value'], 'ms/step', d['ms_per_step'], r['pass_ms'], 'B/ray', r['bytes_per_ray'], r['per_ray'])"
