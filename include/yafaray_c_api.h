@@ -85,6 +85,9 @@ yafaray_bool_t yafaray_endCurveMesh(yafaray_interface_t *yi, const yafaray_mater
 yafaray_bool_t yafaray_addInstance(yafaray_interface_t *yi, unsigned int base_object_id, const float *obj_to_world_16); /* :73 */
 /* extension (test support): the per-triangle-corner normals smoothMesh computed, n_tris*9 floats; an all-zero triple = geometric normal */
 yafaray_bool_t yafaray_getMeshCornerNormals(yafaray_interface_t *yi, unsigned int id, float *out, int n_floats);
+/* extension (test support): the scene's enabled lights in Scene::addLight order, as the device gets them: up to max_lights
+ * yafgpu_light records (include/yafgpu.h, 136 bytes each) into out; returns how many lights the scene has */
+int yafaray_getLights(yafaray_interface_t *yi, void *out, int max_lights);
 /* extension (not in the reference): bulk form of addVertex/addTriangle for large meshes;
  * verts = n_verts*3 floats, indices = n_tris*3 ints, one material for all triangles */
 yafaray_bool_t yafaray_addTriangles(yafaray_interface_t *yi, int n_verts, const float *verts, int n_tris, const int *indices,
@@ -111,6 +114,9 @@ void yafaray_paramsEndList(yafaray_interface_t *yi);                            
 /* RenderEnvironment factories — interface.cc:312-372; dispatch on the "type" string exactly like
  * Material::factory (src/material/material.cc:36-52), Light::factory (src/light/light.cc:36-51),
  * Camera::factory (src/camera/camera.cc:34-44), Integrator::factory (src/integrator/integrator.cc:36-57) */
+/* createLight: arealight, pointlight, directionallight, sunlight and spherelight (light_area.cc, light_point.cc, light_directional.cc,
+ * light_sun.cc, light_sphere.cc factories); every other type, and photon_only lights, are refused with a diagnostic.  A sphere light's
+ * `object` is accepted and changes nothing: the mesh it names renders as the light-material geometry it is. */
 yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name);            /* :92 */
 yafaray_texture_t *yafaray_createTexture(yafaray_interface_t *yi, const char *name);        /* :93: type "image" (TGA, HDR and PNG files; none /
                                                                                                bilinear interpolation); procedural types are refused */

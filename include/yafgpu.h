@@ -31,7 +31,7 @@ extern "C" {
 enum { YAFGPU_MAT_SHINYDIFFUSE = 0, YAFGPU_MAT_GLOSSY = 1, YAFGPU_MAT_LIGHT = 2, YAFGPU_MAT_GLASS = 3, YAFGPU_MAT_MIRROR = 4,
        YAFGPU_MAT_COATED_GLOSSY = 5, /* glossy's fields + mirror_color, mirror_strength, glass_ior = IOR, c_flags[0..2], n_bsdf */
        YAFGPU_MAT_ROUGH_GLASS = 6 /* glass's fields (glass_ior, filter_color, mirror_color, fake_shadow, beer_sigma) + rg_a2: RoughGlassMaterial, material_rough_glass.cc */ };
-enum { YAFGPU_LIGHT_AREA = 0, YAFGPU_LIGHT_POINT = 1 };
+enum { YAFGPU_LIGHT_AREA = 0, YAFGPU_LIGHT_POINT = 1, YAFGPU_LIGHT_DIRECTIONAL = 2, YAFGPU_LIGHT_SUN = 3, YAFGPU_LIGHT_SPHERE = 4 };
 enum { YAFGPU_INTEGRATOR_PATH = 0, YAFGPU_INTEGRATOR_DIRECT = 1 };
 enum { YAFGPU_FILTER_BOX = 0, YAFGPU_FILTER_MITCHELL = 1, YAFGPU_FILTER_GAUSS = 2, YAFGPU_FILTER_LANCZOS = 3 };
 
@@ -133,11 +133,32 @@ typedef struct yafgpu_node
 	float d_u, d_v, bump_str;
 } yafgpu_node;
 
-/* A light after its constructor ran on the host (light_area.cc:34-52, light_point.cc:28-36) */
+/* A light after its constructor ran on the host (light_area.cc:34-52, light_point.cc:28-36, light_directional.cc:31-42,
+ * light_sun.cc:29-42, light_sphere.cc:31-41).  136 bytes whatever the type: the area light's corner block is overlaid by the
+ * fields of the directional, sun and sphere lights.  Which fields each type reads:
+ *   area         samples, corner, c2, c3, c4, to_x, to_y, fnormal, color (col * power * pi), area
+ *   point        position (from), color (col * power)
+ *   directional  direction (normalised), position (from) and radius when infinite == 0, color (col * power); du / dv are filled as the
+ *                ctor does (createCs__ of the direction, light_directional.cc:39) and read by nothing here (photon emission only)
+ *   sun          samples, direction (normalised), du / dv (createCs__ of the direction AS GIVEN, sic light_sun.cc:36), cos_angle,
+ *                invpdf, pdf, col_pdf (color * pdf); color (col * power) is kept for reference only
+ *   sphere       samples, position (center), radius, square_radius, square_radius_epsilon, color (col * power) */
 typedef struct yafgpu_light
 {
-	int32_t type, samples, cast_shadows, pad0;
-	float corner[3], c2[3], c3[3], c4[3], to_x[3], to_y[3], fnormal[3];
+	int32_t type, samples, cast_shadows;
+	int32_t infinite;              /* directional: infinite_ (the shadow ray has no end); 0 for every other type */
+	union
+	{
+		struct { float corner[3], c2[3], c3[3], c4[3], to_x[3], to_y[3], fnormal[3]; };      /* area */
+		struct
+		{	/* directional, sun, sphere */
+			float direction[3], du[3], dv[3];
+			float cos_angle, invpdf, pdf;
+			float col_pdf[3];
+			float radius, square_radius, square_radius_epsilon;
+			float pad2[2];
+		};
+	};
 	float color[3];
 	float area;
 	float position[3];

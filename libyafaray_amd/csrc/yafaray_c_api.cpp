@@ -760,6 +760,98 @@ bool make_pointlight(const ParamMap &p, yafgpu_light &l)
 	return enabled;
 }
 
+inline float host_fsin_poly(float x)   // fSin__ with FAST_TRIG, util_math_optimizations.h:219-244
+{
+	const double k2Pi = 6.28318530717958647692, kPi = 3.14159265358979323846;
+	if((double)x > k2Pi || (double)x < -k2Pi) x -= ((int)(x * (float)0.15915494309189533577)) * (float)k2Pi;
+	if((double)x < -kPi) x += (float)k2Pi;
+	else if((double)x > kPi) x -= (float)k2Pi;
+	x = ((float)1.27323954473516268615 * x) - ((float)0.40528473456935108578 * x * std::fabs(x));
+	const float result = 0.225f * (x * std::fabs(x) - x) + x;
+	if(result <= -1.0f) return -1.0f;
+	if(result >= 1.0f) return 1.0f;
+	return result;
+}
+// Vec3::normalize, vector.h (len = 1.0 / fSqrt__(len) in double, narrowed)
+inline void ref_normalize(float *v)
+{
+	float len = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+	if(len != 0.f) { len = (float)(1.0 / (double)std::sqrt(len)); v[0] *= len; v[1] *= len; v[2] *= len; }
+}
+// createCs__, vector.h:319-337
+inline void ref_create_cs(const float *n, float *u, float *v)
+{
+	if(n[0] == 0.f && n[1] == 0.f)
+	{
+		u[0] = n[2] < 0.f ? -1.f : 1.f; u[1] = 0.f; u[2] = 0.f;
+		v[0] = 0.f; v[1] = 1.f; v[2] = 0.f;
+	}
+	else
+	{
+		const float d = (float)(1.0 / (double)std::sqrt(n[1] * n[1] + n[0] * n[0]));
+		u[0] = n[1] * d; u[1] = -n[0] * d; u[2] = 0.f;
+		cross3(n, u, v);
+	}
+}
+// with_caustic / with_diffuse: photon-mapping settings, read by the reference's factories and dropped here (photon_only is refused by the caller)
+// DirectionalLight::factory + ctor, light_directional.cc:118-158, :31-42: `from` (or the deprecated `position`) and `radius` are only read
+// for a finite light; an infinite one's shadow rays have no end (illuminate, :60-80)
+bool make_directionallight(const ParamMap &p, yafgpu_light &l)
+{
+	float from[3] = {0, 0, 0}, dir[3] = {0, 0, 1}, color[3] = {1, 1, 1};
+	float power = 1.f, rad = 1.f; bool inf = true, enabled = true, cast = true;
+	p.getPoint("direction", dir); p.getColor("color", color); p.get("power", power); p.get("infinite", inf);
+	p.get("light_enabled", enabled); p.get("cast_shadows", cast);
+	if(!inf)
+	{
+		if(!p.getPoint("from", from)) p.getPoint("position", from);
+		p.get("radius", rad);
+	}
+	std::memset(&l, 0, sizeof l);
+	l.type = YAFGPU_LIGHT_DIRECTIONAL; l.samples = 1; l.cast_shadows = cast; l.infinite = inf;
+	for(int k = 0; k < 3; ++k) { l.position[k] = from[k]; l.direction[k] = dir[k]; l.color[k] = color[k] * power; }
+	ref_normalize(l.direction);
+	ref_create_cs(l.direction, l.du, l.dv);
+	l.radius = rad;
+	return enabled;
+}
+// SunLight::factory + ctor, light_sun.cc:96-125, :29-42
+bool make_sunlight(const ParamMap &p, yafgpu_light &l)
+{
+	float dir[3] = {0, 0, 1}, color[3] = {1, 1, 1};
+	float power = 1.f, angle = 0.27f; int samples = 4; bool enabled = true, cast = true;
+	p.getPoint("direction", dir); p.getColor("color", color); p.get("power", power); p.get("angle", angle); p.get("samples", samples);
+	p.get("light_enabled", enabled); p.get("cast_shadows", cast);
+	std::memset(&l, 0, sizeof l);
+	l.type = YAFGPU_LIGHT_SUN; l.samples = samples; l.cast_shadows = cast;
+	for(int k = 0; k < 3; ++k) { l.direction[k] = dir[k]; l.color[k] = color[k] * power; }
+	ref_normalize(l.direction);
+	ref_create_cs(dir, l.du, l.dv);                 // createCs__(dir, ...): the direction as given, not the normalised one (:36)
+	if(angle > 80.f) angle = 80.f;
+	l.cos_angle = host_fsin_poly((float)((double)angle * 0.01745329251994329576922) + (float)1.57079632679489661923);   // fCos__(DEG_TO_RAD(angle))
+	l.invpdf = (float)(6.28318530717958647692 * (double)(1.f - l.cos_angle));                                           // M_2PI * (1 - cos_angle_)
+	l.pdf = (float)(1.0 / (double)l.invpdf);
+	for(int k = 0; k < 3; ++k) l.col_pdf[k] = l.color[k] * l.pdf;
+	return enabled;
+}
+// SphereLight::factory + ctor, light_sphere.cc:165-195, :31-41.  `object` names the mesh the exporter pairs with the light; SphereLight::init
+// (:45-55) only hands that mesh a pointer to the light, for photon mapping.  Here the mesh stays the ordinary (light-material) geometry it is.
+bool make_spherelight(const ParamMap &p, yafgpu_light &l)
+{
+	float from[3] = {0, 0, 0}, color[3] = {1, 1, 1};
+	float power = 1.f, radius = 1.f; int samples = 4, object = 0; bool enabled = true, cast = true;
+	p.getPoint("from", from); p.getColor("color", color); p.get("power", power); p.get("radius", radius); p.get("samples", samples);
+	p.get("object", object); p.get("light_enabled", enabled); p.get("cast_shadows", cast);
+	(void)object;
+	std::memset(&l, 0, sizeof l);
+	l.type = YAFGPU_LIGHT_SPHERE; l.samples = samples; l.cast_shadows = cast;
+	for(int k = 0; k < 3; ++k) { l.position[k] = from[k]; l.color[k] = color[k] * power; }
+	l.radius = radius;
+	l.square_radius = radius * radius;
+	l.square_radius_epsilon = (float)((double)l.square_radius * 1.000003815);    // ~0.2 % larger radius squared
+	return enabled;
+}
+
 // PerspectiveCamera::factory, Camera::Camera, setAxis — camera_perspective.cc:198-243, camera.cc:46-66, :60-74
 bool make_camera(yafaray_interface *yi, const ParamMap &p, yafgpu_camera &c)
 {
@@ -949,18 +1041,6 @@ inline float sin_from_vectors(const float *a, const float *b)   // Vec3::sinFrom
 	if(arg > 1.f) arg = 1.f;
 	return (float)std::asin((double)arg);
 }
-inline float host_fsin_poly(float x)   // fSin__ with FAST_TRIG, util_math_optimizations.h:219-244
-{
-	const double k2Pi = 6.28318530717958647692, kPi = 3.14159265358979323846;
-	if((double)x > k2Pi || (double)x < -k2Pi) x -= ((int)(x * (float)0.15915494309189533577)) * (float)k2Pi;
-	if((double)x < -kPi) x += (float)k2Pi;
-	else if((double)x > kPi) x -= (float)k2Pi;
-	x = ((float)1.27323954473516268615 * x) - ((float)0.40528473456935108578 * x * std::fabs(x));
-	const float result = 0.225f * (x * std::fabs(x) - x) + x;
-	if(result <= -1.0f) return -1.0f;
-	if(result >= 1.0f) return 1.0f;
-	return result;
-}
 }
 yafaray_bool_t yafaray_smoothMesh(yafaray_interface_t *yi, unsigned int id, double angle_d)
 {
@@ -1064,6 +1144,12 @@ yafaray_bool_t yafaray_smoothMesh(yafaray_interface_t *yi, unsigned int id, doub
 	}
 	m.smooth = true;
 	return 1;
+}
+int yafaray_getLights(yafaray_interface_t *yi, void *out, int max_lights)
+{
+	const int n = (int)yi->light_order.size();
+	for(int i = 0; out && i < std::min(n, max_lights); ++i) std::memcpy((char *)out + (size_t)i * sizeof(yafgpu_light), &yi->light_order[(size_t)i]->l, sizeof(yafgpu_light));
+	return n;
 }
 yafaray_bool_t yafaray_getMeshCornerNormals(yafaray_interface_t *yi, unsigned int id, float *out, int n_floats)
 {
@@ -1275,12 +1361,15 @@ yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name)
 	if(!yi->params.get("type", type)) { fail(yi, "createLight: type of light not specified"); return nullptr; }
 	auto l = std::make_unique<yafaray_light>();
 	bool enabled, photon_only = false;
-	// light_area.cc:69, light_point.cc:40,60: a photon-only light gives illumSample / illuminate nothing (and still counts among the lights the
+	// light_area.cc:69, light_point.cc:40,60 (and light_directional.cc:62, light_sun.cc:55, light_sphere.cc:73): a photon-only light gives illumSample / illuminate nothing (and still counts among the lights the
 	// one-light estimator picks from): a photon-mapping setting, not taken over
 	if(yi->params.get("photon_only", photon_only) && photon_only) { fail(yi, "createLight: photon_only lights are outside the GPU path's scope (photon mapping)"); return nullptr; }
 	if(type == "arealight") enabled = make_arealight(yi->params, l->l);
 	else if(type == "pointlight") enabled = make_pointlight(yi->params, l->l);
-	else { fail(yi, "createLight: light type \"" + type + "\" is outside the GPU path's scope (arealight, pointlight)"); return nullptr; }
+	else if(type == "directionallight") enabled = make_directionallight(yi->params, l->l);
+	else if(type == "sunlight") enabled = make_sunlight(yi->params, l->l);
+	else if(type == "spherelight") enabled = make_spherelight(yi->params, l->l);
+	else { fail(yi, "createLight: light type \"" + type + "\" is outside the GPU path's scope (arealight, pointlight, directionallight, sunlight, spherelight)"); return nullptr; }
 	yafaray_light *raw = l.get();
 	if(enabled) yi->light_order.push_back(raw);   // Scene::addLight only sees enabled lights (environment.cc:230-233)
 	yi->lights[name] = std::move(l);

@@ -1094,6 +1094,62 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			o[7] = d1.x; o[8] = d1.y; o[9] = d1.z; o[10] = tcol.r; o[11] = tcol.g; o[12] = tcol.b; o[13] = w1; o[14] = bs.pdf; o[15] = __uint_as_float(bs.sampled);
 			break;
 		}
+		// the directional, sun and sphere lights (ops 17-21): the light is sc.lights[k], k the last input word (a uint's bits); a k that is out of
+		// range or names a light of another type leaves the outputs at zero
+		case 17:
+		{	// DirectionalLight::illuminate: in p.xyz, k -> ok, wi.dir, wi.tmax, col
+			if(n_in < 4) break;
+			const uint32_t k = __float_as_uint(x[3]);
+			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_DIRECTIONAL || n_out < 8) break;
+			Col c = mkc(0.f, 0.f, 0.f); V3 d = mk(0.f, 0.f, 0.f); float tmax = 0.f;
+			const bool ok = directionallight_illuminate(sc.lights[k], mk(x[0], x[1], x[2]), c, d, tmax);
+			o[0] = ok ? 1.f : 0.f;
+			o[1] = ok ? d.x : 0.f; o[2] = ok ? d.y : 0.f; o[3] = ok ? d.z : 0.f; o[4] = ok ? tmax : 0.f; o[5] = ok ? c.r : 0.f; o[6] = ok ? c.g : 0.f; o[7] = ok ? c.b : 0.f;
+			break;
+		}
+		case 18:
+		{	// SunLight::illumSample: in s_1, s_2, k -> ok, wi.dir, wi.tmax, pdf, ls.col
+			if(n_in < 3) break;
+			const uint32_t k = __float_as_uint(x[2]);
+			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_SUN || n_out < 9) break;
+			Col c = mkc(0.f, 0.f, 0.f); V3 d = mk(0.f, 0.f, 0.f); float tmax = 0.f, pdf = 0.f;
+			const bool ok = sunlight_illum_sample(sc.lights[k], x[0], x[1], d, tmax, pdf, c);
+			o[0] = ok ? 1.f : 0.f;
+			o[1] = d.x; o[2] = d.y; o[3] = d.z; o[4] = tmax; o[5] = pdf; o[6] = c.r; o[7] = c.g; o[8] = c.b;
+			break;
+		}
+		case 19:
+		{	// SunLight::intersect: in dir.xyz, k -> ok, t, ipdf, col
+			if(n_in < 4) break;
+			const uint32_t k = __float_as_uint(x[3]);
+			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_SUN || n_out < 6) break;
+			Col c = mkc(0.f, 0.f, 0.f); float t = 0.f, ipdf = 0.f;
+			const bool ok = sunlight_intersect(sc.lights[k], mk(x[0], x[1], x[2]), t, c, ipdf);
+			o[0] = ok ? 1.f : 0.f; o[1] = t; o[2] = ipdf; o[3] = c.r; o[4] = c.g; o[5] = c.b;
+			break;
+		}
+		case 20:
+		{	// SphereLight::illumSample: in p.xyz, s_1, s_2, k -> ok, wi.dir, wi.tmax, pdf, ls.col
+			if(n_in < 6) break;
+			const uint32_t k = __float_as_uint(x[5]);
+			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_SPHERE || n_out < 9) break;
+			Col c = mkc(0.f, 0.f, 0.f); V3 d = mk(0.f, 0.f, 0.f); float tmax = 0.f, pdf = 0.f;
+			const bool ok = spherelight_illum_sample(sc.lights[k], mk(x[0], x[1], x[2]), x[3], x[4], d, tmax, pdf, c);
+			o[0] = ok ? 1.f : 0.f;
+			o[1] = ok ? d.x : 0.f; o[2] = ok ? d.y : 0.f; o[3] = ok ? d.z : 0.f; o[4] = ok ? tmax : 0.f; o[5] = ok ? pdf : 0.f;
+			o[6] = ok ? c.r : 0.f; o[7] = ok ? c.g : 0.f; o[8] = ok ? c.b : 0.f;
+			break;
+		}
+		case 21:
+		{	// sphereIntersect__ against sphere light k's center and squared radius: in from.xyz, dir.xyz, k -> ret, d_1, d_2 (d_2 only on a hit)
+			if(n_in < 7) break;
+			const uint32_t k = __float_as_uint(x[6]);
+			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_SPHERE || n_out < 3) break;
+			float d_1 = 0.f, d_2 = 0.f;
+			const bool ok = sphere_intersect(mk(x[0], x[1], x[2]), mk(x[3], x[4], x[5]), vec3(sc.lights[k].position), sc.lights[k].square_radius, d_1, d_2);
+			o[0] = ok ? 1.f : 0.f; o[1] = d_1; o[2] = ok ? d_2 : 0.f;
+			break;
+		}
 		default: break;
 	}
 }
@@ -1161,6 +1217,7 @@ struct yafgpu_scene
 	int pipe_next = 0, pass_pipelining = -1;      // -1: by size (render_wavefront), 0 / 1: forced (yafgpu_scene_set_pass_pipelining)
 	yafgpu_counters *pipe_counters[kPipeMax] = {};      // a pipelined pass counts here; the sums reach the caller's block on the caller's stream
 	uint32_t mat_mask = 0u;              // bit per YAFGPU_MAT_* present; picks the shading kernel variant
+	uint32_t light_mask = 0u;            // bit per YAFGPU_LIGHT_* present; a variant must have been built for all of them
 	bool has_volumetric = false;
 	int max_add_depth = 0;               // the largest Material::additional_depth_ of the scene: recursion frames beyond raydepth
 	bool has_glossy_two = false;         // rough glass: a glossy trajectory sends two rays (the replay's call count)
@@ -1260,6 +1317,8 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 	}
 	for(int i = 0; i < d->n_tris; ++i)
 		if(d->tri_mat[i] < 0 || d->tri_mat[i] >= d->n_materials) return fail(-3, "triangle material index out of range");
+	for(int i = 0; i < d->n_lights; ++i)
+		if(d->lights[i].type < YAFGPU_LIGHT_AREA || d->lights[i].type > YAFGPU_LIGHT_SPHERE) return fail(-2, "light " + std::to_string(i) + ": unknown type");
 	for(int i = 0; i < d->n_materials; ++i)
 	{
 		// recursiveRaytrace (integrator_montecarlo.cc:782-1028): the perfect specular branch and both cases of the glossy branch (reflect
@@ -1546,6 +1605,7 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 	s->mats.assign(d->materials, d->materials + d->n_materials);
 	s->n_lights = d->n_lights;
 	s->h_lights.assign(d->lights, d->lights + d->n_lights);
+	for(const yafgpu_light &l : s->h_lights) s->light_mask |= 1u << (uint32_t)l.type;
 	s->info.upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
 	(void)t0;
 	*out = s;
@@ -1673,6 +1733,14 @@ static void host_filter_table(int type, float table[256])
 		for(int x = 0; x < 16; ++x) table[y * 16 + x] = host_filter(type, (x + .5f) * scale, (y + .5f) * scale);
 }
 
+// MIS pairs (shadow parks) of one light estimate of light l: one for a Dirac light, else ceil(samples x multiplier)
+// (doLightEstimation, integrator_montecarlo.cc:153)
+static_assert(sizeof(yafgpu_light) == 136, "yafgpu_light: the directional / sun / sphere fields overlay the area light's, the record keeps its size");
+static int light_pairs(const yafgpu_light &l, float aa_light_sample_multiplier)
+{
+	return light_is_dirac(l.type) ? 1 : (int)std::ceil((float)l.samples * aa_light_sample_multiplier);
+}
+
 static int validate(const yafgpu_scene *s, const yafgpu_render_params *rp)
 {
 	if(rp->width <= 0 || rp->height <= 0 || rp->aa_minsamples <= 0 || rp->tile_size <= 0) return fail(-10, "empty image, sample count or tile size");
@@ -1685,8 +1753,8 @@ static int validate(const yafgpu_scene *s, const yafgpu_render_params *rp)
 	// the sample index of a light estimate in flight is packed in 12 bits (pack_dlc); validate() runs for every pass, so a
 	// light-sample multiplier that grows over the passes of an adaptive render is caught when it gets there
 	for(const yafgpu_light &l : s->h_lights)
-		if(l.type != YAFGPU_LIGHT_POINT && std::ceil((float)l.samples * rp->aa_light_sample_multiplier) > 4095.f)
-			return fail(-19, "an area light with more than 4095 samples per estimate (samples x AA light-sample multiplier): the device path counts them in 12 bits");
+		if(!light_is_dirac(l.type) && std::ceil((float)l.samples * rp->aa_light_sample_multiplier) > 4095.f)
+			return fail(-19, "a sampled light (area, sun, sphere) with more than 4095 samples per estimate (samples x AA light-sample multiplier): the device path counts them in 12 bits");
 	return 0;
 }
 
@@ -1714,11 +1782,12 @@ static int wf_grid(const void *kernel, int cus)
 }
 
 // Scene-specialised builds of wf_shade (yafgpu_shade_variant.hip), most specialised first.  A variant serves a scene
-// whose material types are a subset of its mask and which needs recursiveRaytrace only if the variant has it; every
+// whose material types are a subset of its mask, whose light types are a subset of its light mask (not asked of a record
+// pass's program, which has no light code) and which needs recursiveRaytrace only if the variant has it; every
 // other scene takes the general kernel of this unit.  YAFGPU_SHADE_VARIANT=general forces the general kernel.
 extern "C" {
 #define YG_DECLARE_SHADE_VARIANT(name) \
-	void yafgpu_shade_##name##_describe(uint32_t *, int *, int *, int *); const void *yafgpu_shade_##name##_kernel(); \
+	void yafgpu_shade_##name##_describe(uint32_t *, int *, int *, int *, uint32_t *); const void *yafgpu_shade_##name##_kernel(); \
 	int yafgpu_shade_##name##_launch(const void *, size_t, int, hipStream_t);
 YG_DECLARE_SHADE_VARIANT(diffuse)
 YG_DECLARE_SHADE_VARIANT(glossy)
@@ -1732,7 +1801,7 @@ YG_DECLARE_SHADE_VARIANT(full)
 struct ShadeVariant
 {
 	const char *name;
-	void (*describe)(uint32_t *, int *, int *, int *);
+	void (*describe)(uint32_t *, int *, int *, int *, uint32_t *);
 	const void *(*kernel)();
 	int (*launch)(const void *, size_t, int, hipStream_t);
 };
@@ -1755,9 +1824,10 @@ static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, int frames,
 	if(s->has_textures || s->has_aniso) return nullptr;        // the variants are built without shader nodes and without the anisotropic lobe
 	for(const ShadeVariant &v : kShadeVariants)
 	{
-		uint32_t mask = 0u; int recurse = 0, lights = 1, multi = 0;
-		v.describe(&mask, &recurse, &lights, &multi);
+		uint32_t mask = 0u, light_mask = 0u; int recurse = 0, lights = 1, multi = 0;
+		v.describe(&mask, &recurse, &lights, &multi, &light_mask);
 		if((lights == 0) != record_pass) continue;
+		if(lights != 0 && (s->light_mask & ~light_mask) != 0u) continue;
 		if(!record_pass && (multi != 0) != want_multi) continue;
 		if((s->mat_mask & ~mask) == 0u && (recurse || !needs_recurse)) return &v;
 	}
@@ -2087,8 +2157,7 @@ static int render_wavefront(yafgpu_scene *s, RenderArgs &ra, hipStream_t caller,
 		int pairs = 0;
 		for(int i = 0; i < s->n_lights; ++i)
 		{
-			const yafgpu_light &l = s->h_lights[(size_t)i];
-			pairs += l.type == YAFGPU_LIGHT_POINT ? 1 : (int)std::ceil((float)l.samples * rp.aa_light_sample_multiplier);
+			pairs += light_pairs(s->h_lights[(size_t)i], rp.aa_light_sample_multiplier);
 		}
 		want_multi = pairs > 1;
 	}
@@ -2108,8 +2177,7 @@ static int render_wavefront(yafgpu_scene *s, RenderArgs &ra, hipStream_t caller,
 	int r_all = 0, r_one = 0;
 	for(int i = 0; i < s->n_lights; ++i)
 	{
-		const yafgpu_light &l = s->h_lights[(size_t)i];
-		const int r = l.type == YAFGPU_LIGHT_POINT ? 1 : (int)std::ceil((float)l.samples * rp.aa_light_sample_multiplier);   // shadow parks (MIS pairs)
+		const int r = light_pairs(s->h_lights[(size_t)i], rp.aa_light_sample_multiplier);   // shadow parks (MIS pairs)
 		r_all += r; r_one = std::max(r_one, r);
 	}
 	int iters = 1 + r_all;
@@ -2527,6 +2595,8 @@ int yafgpu_render_tiles(yafgpu_scene_t *s, const yafgpu_render_params *rp, float
 		if(rp->transp_shad) return fail(-15, "the one-kernel pipeline has no transparent shadows (transpShad); use the wavefront pipeline");
 		if((s->has_specular || s->has_glossy) && rp->raydepth + s->max_add_depth > 0) return fail(-15, "the one-kernel pipeline has no recursiveRaytrace; use the wavefront pipeline for mirror / transparent / glossy-recursive materials");
 		if(s->has_textures) return fail(-15, "the one-kernel pipeline has no shader nodes / textures; use the wavefront pipeline");
+		if(s->light_mask & ~((1u << YAFGPU_LIGHT_AREA) | (1u << YAFGPU_LIGHT_POINT)))
+			return fail(-15, "the one-kernel pipeline has area and point lights only (no directional, sun or sphere lights); use the wavefront pipeline");
 		if(rp->trace_caustics && (s->has_specular || s->has_glossy)) return fail(-15, "the one-kernel pipeline has no path caustics (caustic_type path with specular / glossy lobes); use the wavefront pipeline");
 		if(rp->serial_replay && rp->integrator == YAFGPU_INTEGRATOR_PATH && (rp->bounces - 1 > rp->rr_min_bounces || s->n_lights > 1))
 			return fail(-15, "the one-kernel pipeline cannot replay the reference's serial state (Russian roulette stream, light counter); use the wavefront pipeline or switch the replay off");

@@ -25,6 +25,29 @@ namespace yafgpu {
 #define YAFGPU_MAT_MASK 0x7fu
 #endif
 #define YG_IS(m, T) ((((YAFGPU_MAT_MASK) >> (T)) & 1u) != 0u && (m).type == (T))
+// Light types this compilation of the light estimate handles (YAFGPU_LIGHT_MASK, one bit per YAFGPU_LIGHT_*), in the same way: the
+// shade variants are built for area and point lights (0x3) and keep the code they had before the other types came; the main unit has all
+#ifndef YAFGPU_LIGHT_MASK
+#define YAFGPU_LIGHT_MASK 0x1fu
+#endif
+#define YG_LIGHT_HAS(T) ((((YAFGPU_LIGHT_MASK) >> (T)) & 1u) != 0u)
+#define YG_LIGHT_IS(l, T) (YG_LIGHT_HAS(T) && (l).type == (T))
+// Light::diracLight (light_point.h, light_directional.h:44): one illuminate() and no samples.
+// Light::canIntersect (light_area.h, light_sun.h:46; light_sphere.h:56 says no): the sampled lights that take the BSDF half of the MIS pair.
+// A build for area | point lights sees exactly the tests it had before these types came (type == point, type != point).
+// The answers hold only for the types inside YAFGPU_LIGHT_MASK: in such a build light_can_intersect(YAFGPU_LIGHT_SPHERE) is true.
+// Code in a masked unit never sees other types (pick_shade_variant does not hand it such a scene); host code asks the main unit's
+// definitions, which know every type.
+#if (YAFGPU_LIGHT_MASK) & 0x4u          /* YAFGPU_LIGHT_DIRECTIONAL */
+__host__ __device__ __forceinline__ bool light_is_dirac(int type) { return type == YAFGPU_LIGHT_POINT || type == YAFGPU_LIGHT_DIRECTIONAL; }
+#else
+__host__ __device__ __forceinline__ bool light_is_dirac(int type) { return type == YAFGPU_LIGHT_POINT; }
+#endif
+#if (YAFGPU_LIGHT_MASK) & 0x10u         /* YAFGPU_LIGHT_SPHERE */
+__host__ __device__ __forceinline__ bool light_can_intersect(int type) { return !light_is_dirac(type) && type != YAFGPU_LIGHT_SPHERE; }
+#else
+__host__ __device__ __forceinline__ bool light_can_intersect(int type) { return !light_is_dirac(type); }
+#endif
 
 enum : uint32_t {
 	kNone = 0, kSpecular = 1, kGlossy = 2, kDiffuse = 4, kDispersive = 8, kReflect = 0x10, kTransmit = 0x20,
@@ -1054,6 +1077,85 @@ YG_DEV bool pointlight_illuminate(const yafgpu_light &l, V3 sp_p, Col &col, V3 &
 	wi_tmax = dist;
 	wi_dir = ldir;
 	col = col3(l.color) * idist_sqr;
+	return true;
+}
+// sampleCone__, util_sample.h:80-86 (M_2PI * s_1 is formed in double and narrowed)
+YG_DEV V3 sample_cone(V3 d, V3 u, V3 v, float max_cos_ang, float s_1, float s_2)
+{
+	const float cos_ang = 1.f - (1.f - max_cos_ang) * s_2;
+	const float sin_ang = f_sqrt(1.f - cos_ang * cos_ang);
+	const float t_1 = (float)(k2Pi * (double)s_1);
+	return (u * f_cos(t_1) + v * f_sin(t_1)) * sin_ang + d * cos_ang;
+}
+// DirectionalLight::illuminate, light_directional.cc:60-80: an infinite light's shadow ray has no end (tmax -1); a finite one lights the
+// cylinder of `radius` around `from` along the direction, up to the plane through `from`
+YG_DEV bool directionallight_illuminate(const yafgpu_light &l, V3 sp_p, Col &col, V3 &wi_dir, float &wi_tmax)
+{
+	if(!l.infinite)
+	{
+		const V3 vec = vec3(l.position) - sp_p;
+		const float dist = length(cross(vec3(l.direction), vec));
+		if(dist > l.radius) return false;
+		wi_tmax = dot(vec, vec3(l.direction));
+		if(wi_tmax <= 0.f) return false;
+	}
+	else wi_tmax = -1.f;
+	wi_dir = vec3(l.direction);
+	col = col3(l.color);
+	return true;
+}
+// SunLight::illumSample, light_sun.cc:53-66: a direction in the cone, an infinite shadow ray, colour col_pdf
+YG_DEV bool sunlight_illum_sample(const yafgpu_light &l, float s_1, float s_2, V3 &wi_dir, float &wi_tmax, float &pdf, Col &col)
+{
+	wi_dir = sample_cone(vec3(l.direction), vec3(l.du), vec3(l.dv), l.cos_angle, s_1, s_2);
+	wi_tmax = -1.f;
+	col = col3(l.col_pdf);
+	pdf = l.pdf;
+	return true;
+}
+// SunLight::intersect, light_sun.cc:68-77 (returns the INVERSE pdf; t = -1: the ray has no end)
+YG_DEV bool sunlight_intersect(const yafgpu_light &l, V3 dir, float &t, Col &col, float &ipdf)
+{
+	const float cosine = dot(dir, vec3(l.direction));
+	if(cosine < l.cos_angle) return false;
+	col = col3(l.col_pdf);
+	t = -1.f;
+	ipdf = l.invpdf;
+	return true;
+}
+// sphereIntersect__, light_sphere.cc:57-69 (the 4.0 and 2.0 make those products double)
+YG_DEV bool sphere_intersect(V3 from, V3 dir, V3 c, float r_2, float &d_1, float &d_2)
+{
+	const V3 vf = from - c;
+	const float ea = dot(dir, dir);
+	const float eb = dot(vf * 2.f, dir);
+	const float ec = dot(vf, vf) - r_2;
+	float osc = (float)((double)(eb * eb) - 4.0 * (double)ea * (double)ec);
+	if(osc < 0.f) { d_1 = f_sqrt(ec / ea); return false; }
+	osc = f_sqrt(osc);
+	d_1 = (float)((double)(-eb - osc) / (2.0 * (double)ea));
+	d_2 = (float)((double)(-eb + osc) / (2.0 * (double)ea));
+	return true;
+}
+// SphereLight::illumSample, light_sphere.cc:71-103: the cone towards the centre, the shadow ray up to the slightly enlarged sphere
+YG_DEV bool spherelight_illum_sample(const yafgpu_light &l, V3 sp_p, float s_1, float s_2, V3 &wi_dir, float &wi_tmax, float &pdf, Col &col)
+{
+	const V3 c = vec3(l.position);
+	V3 cdir = c - sp_p;
+	const float dist_sqr = cdir.x * cdir.x + cdir.y * cdir.y + cdir.z * cdir.z;
+	if(dist_sqr <= l.square_radius) return false;      // only emit light on the outside
+	const float dist = f_sqrt(dist_sqr);
+	const float idist_sqr = 1.f / (dist_sqr);
+	const float cos_alpha = f_sqrt(1.f - l.square_radius * idist_sqr);
+	cdir = cdir * (1.f / dist);
+	V3 du, dv;
+	create_cs(cdir, du, dv);
+	wi_dir = sample_cone(cdir, du, dv, cos_alpha, s_1, s_2);
+	float d_1, d_2;
+	if(!sphere_intersect(sp_p, wi_dir, c, l.square_radius_epsilon, d_1, d_2)) return false;
+	wi_tmax = d_1;
+	pdf = 1.f / (2.f * (1.f - cos_alpha));
+	col = col3(l.color);
 	return true;
 }
 

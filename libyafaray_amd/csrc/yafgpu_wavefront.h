@@ -130,10 +130,11 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 	const uint32_t kMisFlags = kGlossy | kDiffuse | kDispersive | kReflect | kTransmit;
 	r_dir = mk(0.f, 0.f, 0.f); r_tmin = 0.f; r_tmax = -1.f;
 	contrib = mkc(0.f, 0.f, 0.f);
-	if(light.type == YAFGPU_LIGHT_POINT)
+	if(light_is_dirac(light.type))
 	{
 		Col lcol;
-		if(!pointlight_illuminate(light, sp.p, lcol, r_dir, r_tmax)) return false;
+		if(YG_LIGHT_IS(light, YAFGPU_LIGHT_DIRECTIONAL)) { if(!directionallight_illuminate(light, sp.p, lcol, r_dir, r_tmax)) return false; }
+		else if(!pointlight_illuminate(light, sp.p, lcol, r_dir, r_tmax)) return false;
 		r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
 		const float angle = mat.flat ? 1.f : fabsf(dot(sp.n, r_dir));
 		contrib = (mat_eval(mat, dat, sp, wo, r_dir, kAll) * lcol) * angle;
@@ -142,14 +143,23 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 	if(phase == 0)
 	{
 		float ls_pdf;
-		if(!arealight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf)) return false;
+		Col l_col = mkc(0.f, 0.f, 0.f);
+		if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN)) sunlight_illum_sample(light, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col);
+		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPHERE)) { if(!spherelight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col)) return false; }
+		else if(!arealight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf)) return false;
 		r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
 		if(ls_pdf > 1e-6f)
 		{
 			const Col surf_col = mat_eval(mat, dat, sp, wo, r_dir, kAll);
 			const float angle = mat.flat ? 1.f : fabsf(dot(sp.n, r_dir));
+			// the light colour of this half is what illumSample returned (ls.col_, :178-262): col_pdf for the sun, the fixed colour otherwise
+			if(YG_LIGHT_HAS(YAFGPU_LIGHT_SPHERE) && !light_can_intersect(light.type))
+			{	// a light the BSDF half cannot hit takes no MIS weight (:244-258)
+				contrib = ((surf_col * l_col) * angle) / ls_pdf;
+				return true;
+			}
 			const float m_pdf = mat_pdf(mat, dat, sp, wo, r_dir, kMisFlags);
-			const Col ls_col = col3(light.color);
+			const Col ls_col = YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) ? l_col : col3(light.color);
 			if(m_pdf > 1e-6f)
 			{
 				const float l_2 = ls_pdf * ls_pdf, m_2 = m_pdf * m_pdf;
@@ -165,13 +175,17 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 	BsdfSample bs; bs.s_1 = s_1; bs.s_2 = s_2; bs.pdf = 0.f; bs.flags = kMisFlags; bs.sampled = kNone;
 	const Col surf_col = mat_sample(mat, dat, sp, wo, r_dir, bs, W);
 	float light_ipdf;
-	if(!(bs.pdf > 1e-6f && arealight_intersect(light, sp.p, r_dir, r_tmax, light_ipdf))) return false;
+	// Light::intersect: the sun's also returns its colour (lcol = col_pdf) and t = -1, an infinite shadow ray
+	Col l_col = mkc(0.f, 0.f, 0.f);
+	if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN)) { if(!(bs.pdf > 1e-6f && sunlight_intersect(light, r_dir, r_tmax, l_col, light_ipdf))) return false; }
+	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPHERE)) return false;      // (canIntersect() is false: st_dl_eval never asks)
+	else if(!(bs.pdf > 1e-6f && arealight_intersect(light, sp.p, r_dir, r_tmax, light_ipdf))) return false;
 	if(light_ipdf > 1e-6f)
 	{
 		const float l_pdf = 1.f / light_ipdf;
 		const float l_2 = l_pdf * l_pdf, m_2 = bs.pdf * bs.pdf;
 		const float w = m_2 / (l_2 + m_2);
-		contrib = ((surf_col * col3(light.color)) * w) * W;
+		contrib = ((surf_col * (YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) ? l_col : col3(light.color))) * w) * W;
 	}
 	return true;
 }
@@ -628,7 +642,7 @@ YG_DEV int st_after_shadow(const WfArgs &a, uint32_t slot, Hot &h, uint2 verdict
 	const uint32_t w = ubits(r14.w);
 	const int li = (int)(w & 0xffu), l_end = (int)((w >> 8) & 0xffu), mask = second ? mask2 : (int)((w >> 16) & 0x3u), is = (int)(w >> 20);
 	if(second) { const float4 r29 = REC(29); r14.x = r29.x; r14.y = r29.y; r14.z = r29.z; }
-	const bool dirac = sc.lights[li].type == YAFGPU_LIGHT_POINT;
+	const bool dirac = light_is_dirac(sc.lights[li].type);
 	// transparent shadows (integrator_montecarlo.cc:114,182,309): what an unblocked ray picked up on its way scales the
 	// light.  (The reference scales the light colour before forming the contribution, here the parked contribution is
 	// scaled: same product, other rounding order.)
@@ -666,7 +680,7 @@ YG_DEV int st_dl_next(const WfArgs &a, uint32_t slot, Hot &h, int level)
 	while(li < l_end)
 	{
 		const yafgpu_light &light = sc.lights[li];
-		const bool dirac = light.type == YAFGPU_LIGHT_POINT;
+		const bool dirac = light_is_dirac(light.type);
 		const int n = dirac ? 1 : dl_area_samples(ra, light, division);
 		if(is < n)
 		{
@@ -700,7 +714,7 @@ YG_DEV int st_dl_eval(const WfArgs &a, uint32_t slot, Hot &h, const Ctl &c, uint
 	const yafgpu_material &mat = wf_mat_parked(a, slot, c.dl_on_sp0 ? 0 : 1, sp, mat_tmp);
 	BsdfDat dat; mat_init_bsdf(mat, dat);
 	const yafgpu_light &light = sc.lights[li];
-	const bool dirac = light.type == YAFGPU_LIGHT_POINT;
+	const bool dirac = light_is_dirac(light.type), bsdf_half = light_can_intersect(light.type);
 	const bool cast_shadows = light.cast_shadows && mat.receive_shadows;
 	if(second && !cast_shadows) return W_DL_NEXT;      // (its contributions would go straight into the accumulators: out of order before the first pair's)
 	float s_1 = 0.f, s_2 = 0.f;
@@ -715,7 +729,7 @@ YG_DEV int st_dl_eval(const WfArgs &a, uint32_t slot, Hot &h, const Ctl &c, uint
 		else if(dirac) HSET(17, f4(c3(HGET(17)) + contrib, 0.f));
 		else HSET(15, f4(c3(HGET(15)) + contrib, 0.f));
 	}
-	if(!dirac && dl_candidate(ra, light, 1, s_1, s_2, sp, mat, dat, wo, d, tmin, tmax, contrib))
+	if(!dirac && bsdf_half && dl_candidate(ra, light, 1, s_1, s_2, sp, mat, dat, wo, d, tmin, tmax, contrib))
 	{
 		if(cast_shadows) { wf_rec(a, second ? 30 : 20, slot) = f4(d, tmin); wf_rec(a, second ? 31 : 21, slot) = f4(contrib, tmax); mask |= 2; }
 		else HSET(16, f4(c3(HGET(16)) + contrib, 0.f));
@@ -951,7 +965,7 @@ YG_DEV int st_beside(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint32_t pi
 		const int li = (int)(w14 & 0xffu), l_end = (int)((w14 >> 8) & 0xffu), is = (int)(w14 >> 20);
 		if(li + 1 != l_end) return W_PARK_SHADOW;
 		const yafgpu_light &light = sc.lights[li];
-		if(light.type != YAFGPU_LIGHT_POINT && is + 1 != dl_area_samples(ra, light, 1)) return W_PARK_SHADOW;
+		if(!light_is_dirac(light.type) && is + 1 != dl_area_samples(ra, light, 1)) return W_PARK_SHADOW;
 	}
 	if(c.stage == kStPrimary)
 	{	// st_dl_done will go to st_start_path(path_i = 0): :186-216
@@ -1331,7 +1345,7 @@ YG_DEV int wf_advance(const WfArgs &a, uint32_t slot, uint32_t pixel_sample, uin
 						{	// the pair st_dl_next would name after this one: the light's next sample, or the next light's first
 							const int li = (int)(w_last & 0xffu), l_end = (int)((w_last >> 8) & 0xffu), is = (int)(w_last >> 20);
 							const yafgpu_light &light = a.ra.sc.lights[li];
-							const int n = light.type == YAFGPU_LIGHT_POINT ? 1 : dl_area_samples(a.ra, light, wf_div(a, slot, c.level).division);
+							const int n = light_is_dirac(light.type) ? 1 : dl_area_samples(a.ra, light, wf_div(a, slot, c.level).division);
 							const bool same = is + 1 < n;
 							if(same || li + 1 < l_end) { second = true; w2 = pack_dlc(same ? li : li + 1, l_end, 0, same ? is + 1 : 0); where = W_DL_EVAL; }
 						}

@@ -50,7 +50,7 @@ C_API_SYMBOLS = [
     "yafaray_createInterface", "yafaray_destroyInterface", "yafaray_getLastError", "yafaray_getVersion",
     "yafaray_startScene", "yafaray_startGeometry", "yafaray_endGeometry", "yafaray_getNextFreeId",
     "yafaray_startTriMesh", "yafaray_endTriMesh", "yafaray_addVertex", "yafaray_addNormal", "yafaray_addTriangle",
-    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_addTriangles",
+    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_addTriangles",
     "yafaray_startTriMeshPtr", "yafaray_addVertexWithOrco", "yafaray_addUv", "yafaray_addTriangleWithUv",
     "yafaray_startCurveMesh", "yafaray_endCurveMesh", "yafaray_addInstance",
     "yafaray_paramsSetColorArray", "yafaray_paramsSetMatrix", "yafaray_paramsSetMatrixD", "yafaray_setInputColorSpace",
@@ -99,6 +99,7 @@ def load():
         "yafaray_addVertex": (ci, [vp, cd, cd, cd]), "yafaray_addNormal": (None, [vp, cd, cd, cd]),
         "yafaray_addTriangle": (ci, [vp, ci, ci, ci, vp]), "yafaray_smoothMesh": (ci, [vp, C.c_uint, cd]),
         "yafaray_getMeshCornerNormals": (ci, [vp, C.c_uint, C.POINTER(cf), ci]),
+        "yafaray_getLights": (ci, [vp, vp, ci]),
         "yafaray_addTriangles": (ci, [vp, ci, C.POINTER(cf), ci, C.POINTER(ci), vp]),
         "yafaray_startTriMeshPtr": (ci, [vp, C.POINTER(C.c_uint), ci, ci, ci, ci, ci, ci]),
         "yafaray_addVertexWithOrco": (ci, [vp, cd, cd, cd, cd, cd, cd]), "yafaray_addUv": (ci, [vp, cf, cf]),
@@ -316,6 +317,15 @@ class Interface:
     def getMeshCornerNormals(self, id, n_tris):
         out = np.zeros((n_tris, 3, 3), dtype=np.float32)
         self._ok(self._L.yafaray_getMeshCornerNormals(self._h, id, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "getMeshCornerNormals")
+        return out
+
+    def getLights(self):
+        """the scene's enabled lights in Scene::addLight order, as the device gets them: one row of the 34 words of a yafgpu_light
+        (include/yafgpu.h) each, as float32 (the int fields type / samples / cast_shadows / infinite are words 0-3: view them as int32)"""
+        n = self._L.yafaray_getLights(self._h, None, 0)
+        out = np.zeros((max(n, 0), 34), dtype=np.float32)
+        if n > 0:
+            self._L.yafaray_getLights(self._h, out.ctypes.data_as(C.c_void_p), n)
         return out
 
     # -- params
