@@ -356,6 +356,11 @@ yafgpu_kdtree_t *yafgpu_kdtree_build_device(const float *verts, int32_t n_tris);
 yafgpu_kdtree_t *yafgpu_kdtree_build(const float *verts, int32_t n_tris, int32_t threads);
 void yafgpu_kdtree_info(const yafgpu_kdtree_t *tree, yafgpu_tree_info *info);
 void yafgpu_kdtree_get(const yafgpu_kdtree_t *tree, uint32_t *nodes, uint32_t *refs, float bound6[6]);
+/* The treelet layout the traversal kernels walk (kdtree_build.h, TreeletLayout), built from n_nodes nodes as yafgpu_kdtree_get
+ * returns them.  *n_words / *n_leaves: room of words / leaves on entry (either may be NULL to ask for the sizes only), the sizes
+ * on return.  inline_leaves = 0 sends every non-empty leaf to the escape array.  0, or -2 when the tree is too large. */
+int32_t yafgpu_kdtree_treelets(const uint32_t *nodes, uint32_t n_nodes, int32_t inline_leaves, uint32_t *words, uint32_t *n_words,
+                               uint32_t *leaves, uint32_t *n_leaves, uint32_t *root);
 void yafgpu_kdtree_destroy(yafgpu_kdtree_t *tree);
 
 /* kd-tree built on the host, downloadable for inspection/tests: nodes = n_nodes*2 uint32, refs = n_leaf_refs uint32 */

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <future>
 #include <thread>
+#include <utility>
 
 namespace yafgpu {
 namespace {
@@ -356,12 +357,80 @@ void build_kdtree(const float *verts, int n_tris, int depth_cap, int threads, Kd
 	out.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
+int build_treelets(const std::vector<KdNode> &nodes, bool inline_leaves, TreeletLayout &out)
+{
+	out.words.clear(); out.leaves.clear(); out.root = kLinkEmpty;
+	if(nodes.empty()) return 0;
+	bool overflow = false;
+	auto leaf_link = [&](const KdNode &nd) -> uint32_t {
+		const uint32_t np = nd.b >> 2;
+		if(np == 0u) return kLinkEmpty;
+		if(inline_leaves && np <= kLinkCountMax && nd.a < (1u << kLinkFirstBits)) return kLinkLeaf | (np << kLinkFirstBits) | nd.a;
+		const size_t e = out.leaves.size() / 2;
+		if(e > kLinkIndex) overflow = true;
+		out.leaves.push_back(nd.a); out.leaves.push_back(np);
+		return kLinkLeaf | kLinkEscape | (uint32_t)(e & kLinkIndex);
+	};
+	// depth-first over treelet roots: a treelet's record is written when it is taken off the list, and its grandchildren's
+	// treelets are numbered then, the near (left) ones first
+	std::vector<std::pair<uint32_t, uint32_t>> todo;      // (node index of a treelet root, its treelet)
+	auto link_of = [&](uint32_t g) -> uint32_t {
+		if((nodes[g].b & 3u) == 3u) return leaf_link(nodes[g]);
+		const size_t t = out.words.size() / 8;
+		if(t > (kLinkIndex >> 2)) overflow = true;
+		out.words.resize(out.words.size() + 8, 0u);
+		todo.emplace_back(g, (uint32_t)t);
+		return (uint32_t)t << 2;
+	};
+	out.root = link_of(0u);
+	while(!todo.empty() && !overflow)
+	{
+		const auto [g, t] = todo.back(); todo.pop_back();
+		uint32_t w[8] = {nodes[g].a, 0u, 0u, nodes[g].b & 3u, 0u, 0u, 0u, 0u};
+		const uint32_t child[2] = {g + 1u, nodes[g].b >> 2};
+		uint32_t grand[4] = {0u, 0u, 0u, 0u}; bool interior[2];
+		for(int k = 0; k < 2; ++k)
+		{
+			const KdNode &c = nodes[child[k]];
+			interior[k] = (c.b & 3u) != 3u;
+			w[1 + k] = interior[k] ? c.a : 0u;
+			w[3] |= (interior[k] ? (c.b & 3u) : 3u) << (2 * (k + 1));
+			if(interior[k]) { grand[2 * k] = child[k] + 1u; grand[2 * k + 1] = c.b >> 2; }
+		}
+		// number the right child's grandchildren after the left child's, and push them first so that the left ones are written first
+		uint32_t links[4] = {0u, 0u, 0u, 0u};
+		const size_t mark = todo.size();
+		for(int k = 0; k < 2; ++k)
+		{
+			if(!interior[k]) { links[2 * k] = leaf_link(nodes[child[k]]); continue; }
+			links[2 * k] = link_of(grand[2 * k]);
+			links[2 * k + 1] = link_of(grand[2 * k + 1]);
+		}
+		std::reverse(todo.begin() + (std::ptrdiff_t)mark, todo.end());
+		for(int k = 0; k < 4; ++k) w[4 + k] = links[k];
+		std::memcpy(&out.words[(size_t)t * 8], w, sizeof w);
+	}
+	return overflow ? -2 : 0;
+}
+
 } // namespace yafgpu
 
 // ---- host-only C entry points (include/yafgpu.h) ----
 #include "../../include/yafgpu.h"
 struct yafgpu_kdtree { yafgpu::KdTree t; int n_tris; };
 extern "C" {
+int32_t yafgpu_kdtree_treelets(const uint32_t *nodes, uint32_t n_nodes, int32_t inline_leaves, uint32_t *words, uint32_t *n_words,
+                                uint32_t *leaves, uint32_t *n_leaves, uint32_t *root)
+{
+	std::vector<yafgpu::KdNode> tn(n_nodes);
+	if(n_nodes) std::memcpy(tn.data(), nodes, (size_t)n_nodes * sizeof(yafgpu::KdNode));
+	yafgpu::TreeletLayout tl;
+	if(const int rc = yafgpu::build_treelets(tn, inline_leaves != 0, tl)) return rc;
+	if(words && tl.words.size() <= *n_words && !tl.words.empty()) std::memcpy(words, tl.words.data(), tl.words.size() * 4);
+	if(leaves && tl.leaves.size() <= *n_leaves && !tl.leaves.empty()) std::memcpy(leaves, tl.leaves.data(), tl.leaves.size() * 4);
+	*n_words = (uint32_t)tl.words.size(); *n_leaves = (uint32_t)tl.leaves.size(); *root = tl.root;
+	return 0;
+}
 yafgpu_kdtree_t *yafgpu_kdtree_build(const float *verts, int32_t n_tris, int32_t threads)
 {
 	auto *k = new yafgpu_kdtree();

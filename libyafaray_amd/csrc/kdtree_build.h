@@ -36,4 +36,27 @@ int build_kdtree_device(const float *verts, int n_tris, int depth_cap, KdTree &o
 // the same with more room on -2 (1, 4, 16), for callers that want a device-built tree or an error
 int build_kdtree_device_retry(const float *verts, int n_tris, int depth_cap, KdTree &out, std::string *err);
 
+// The treelet layout of the same tree, the one the traversal kernels (wf_trace) walk: an interior node and its two children in
+// one 32-byte record, read as two uint4, so that one fetch brings two levels of the walk.
+//   words 0-3: split of the root, split of the left child, split of the right child (float bits, as in KdNode), header =
+//              axis of the root | axis of the left child << 2 | axis of the right child << 4, where axis 3 marks a leaf child
+//   words 4-7: links — [4], [5] the left child's two children, or [4] the left child itself when it is a leaf (then [5] is 0);
+//              [6], [7] the same for the right child
+// A link names the place of a walk:
+//   bit 31 clear      a node of a treelet: treelet << 2 | slot (0 root, 1 left child, 2 right child)
+//   bits 31:30 = 10   a leaf inline: first reference in bits 23:0, reference count in bits 29:24 (kLinkEmpty: an empty leaf)
+//   bits 31:30 = 11   a leaf whose numbers do not fit inline: (first reference, count) at leaves[2 * (link & kLinkIndex)]
+// The (up to four) treelets below a treelet take consecutive numbers, and subtrees are numbered left first.
+constexpr uint32_t kLinkLeaf = 0x80000000u, kLinkEscape = 0x40000000u, kLinkIndex = 0x3fffffffu, kLinkEmpty = kLinkLeaf;
+constexpr uint32_t kLinkFirstBits = 24u, kLinkCountMax = 63u;
+struct TreeletLayout
+{
+	std::vector<uint32_t> words;      // 8 per treelet
+	std::vector<uint32_t> leaves;     // 2 per escaped leaf
+	uint32_t root = kLinkEmpty;       // where every walk starts: treelet 0, or the root leaf of a tree without interior nodes
+};
+// inline_leaves false sends every non-empty leaf to the escape array (a test aid).  Returns 0, or -2 when the tree has too many
+// treelets or escaped leaves for the link's index bits.
+int build_treelets(const std::vector<KdNode> &nodes, bool inline_leaves, TreeletLayout &out);
+
 } // namespace yafgpu

@@ -49,16 +49,6 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 #define YAFGPU_WAVES 4                // __launch_bounds__ min waves/SIMD of the render kernel (C2 measured: 1:368 2:667 3:781 4:793 Mrays/s)
 #endif
 constexpr int kStack = YAFGPU_STACK;  // per-lane LDS stack slots (power of two)
-// Top of the tree apart (north_star: "LDS-staged node tiles"; measured in profiles/r03_ab_toptree.txt).  0: off.  1: the first kTopDepth levels
-// are walked in a heap-ordered copy (DevScene::top) that stays resident in the vector L1.  2: that copy is staged into LDS by every workgroup.
-#ifndef YAFGPU_TRACE_TOP
-#define YAFGPU_TRACE_TOP 0
-#endif
-#ifndef YAFGPU_TOP_DEPTH
-#define YAFGPU_TOP_DEPTH 10
-#endif
-constexpr int kTopDepth = YAFGPU_TOP_DEPTH, kTopN = (1 << kTopDepth) - 1, kTopBottom = (1 << (kTopDepth - 1)) - 1;      // entries; first entry of the last level
-constexpr uint32_t kTopTag = 0x80000000u;      // a node id with this bit is a heap index into the top copy
 constexpr int kDepthCap = 48;         // host tree depth cap; deeper pending lists restart
 constexpr int kQueues = 8;            // one per XCD
 constexpr float kMinRayDist = (float)0.00005;   // MIN_RAYDIST, CMakeLists.txt:46-48
@@ -69,12 +59,9 @@ constexpr float kShadowBias = (float)0.0005;    // YAF_SHADOW_BIAS, CMakeLists.t
 struct DevScene
 {
 	const uint2 *nodes;          // 8-byte kd nodes (kdtree_build.h)
-	const uint4 *nodes2;         // (node i, a copy of its right child): the pair layout of the traversal kernels (YAFGPU_TRACE_PAIR), or nullptr
-	const uint2 *nodes_blk;      // the same tree in 64-B blocks of three levels (YAFGPU_TRACE_BLOCKS): node id = block * 8 + slot, slot s < 3 has its
-	                             // children in slots 2s + 1, 2s + 2; a node in slots 3..6 keeps (in the child field) the block of its left child, the right
-	                             // child's block is the next one; both children sit in their blocks' slot 0.  Or nullptr.
-	const uint4 *top;            // YAFGPU_TRACE_TOP: the tree's first kTopDepth levels in heap order (children of entry h at 2h + 1, 2h + 2):
-	                             // (split, flags as in `nodes`, the node's own index in `nodes`, 0); entries no node maps to are empty leaves.  Or nullptr.
+	const uint4 *treelets;       // the treelet layout of the same tree (kdtree_build.h, TreeletLayout): 2 x uint4 per treelet, walked by wf_trace
+	const uint2 *tl_leaves;      // (first reference, count) of the leaves whose links escape (kLinkEscape)
+	uint32_t tl_root;            // the link every walk of wf_trace starts at
 	const uint32_t *refs;        // leaf references
 	const float4 *tri;           // 3 x float4 per triangle: (a, eps) (e1, mat|vis<<30) (e2, 0)
 	const float4 *tri_ng;        // geometric normal + smooth flag
@@ -1433,88 +1420,15 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 	}
 	int rc = 0;
 	DevScene &dv = s->dev;
-	const uint2 *nodes = nullptr;
-	{	// the traversal kernels fetch a window of 8 nodes starting at the current one: pad the array so the last window stays in bounds
-		std::vector<KdNode> padded(s->tree.nodes);
-		padded.resize(padded.size() + 8, KdNode{0u, 3u});
-		if((rc = upload(s, (const uint2 *)padded.data(), padded.size(), &nodes))) { yafgpu_scene_destroy(s); return rc; }
+	if((rc = upload(s, (const uint2 *)s->tree.nodes.data(), s->tree.nodes.size(), &dv.nodes))) { yafgpu_scene_destroy(s); return rc; }
+	{	// the treelet layout for wf_trace; YAFGPU_TREELET_INLINE=0 sends every non-empty leaf through the escape array (a test aid)
+		const char *e = std::getenv("YAFGPU_TREELET_INLINE");
+		TreeletLayout tl;
+		if(build_treelets(s->tree.nodes, !(e && std::atoi(e) == 0), tl)) { yafgpu_scene_destroy(s); return fail(-2, "kd-tree too large for the treelet layout"); }
+		dv.tl_root = tl.root;
+		if((rc = upload(s, (const uint4 *)tl.words.data(), tl.words.size() / 4, &dv.treelets))) { yafgpu_scene_destroy(s); return rc; }
+		if((rc = upload(s, (const uint2 *)tl.leaves.data(), tl.leaves.size() / 2, &dv.tl_leaves))) { yafgpu_scene_destroy(s); return rc; }
 	}
-	dv.nodes = nodes;
-	dv.nodes2 = nullptr;
-#if YAFGPU_TRACE_PAIR
-	{
-		const std::vector<KdNode> &tn = s->tree.nodes;
-		std::vector<uint4> pairs(tn.size() + 8, make_uint4(0u, 3u, 0u, 3u));
-		for(size_t i = 0; i < tn.size(); ++i)
-		{
-			const uint2 nd = *(const uint2 *)&tn[i];
-			uint4 pr = make_uint4(nd.x, nd.y, 0u, 3u);
-			if((nd.y & 3u) != 3u) { const uint2 r = *(const uint2 *)&tn[nd.y >> 2]; pr.z = r.x; pr.w = r.y; }
-			pairs[i] = pr;
-		}
-		const uint4 *d_pairs = nullptr;
-		if((rc = upload(s, pairs.data(), pairs.size(), &d_pairs))) { yafgpu_scene_destroy(s); return rc; }
-		dv.nodes2 = d_pairs;
-	}
-#endif
-	dv.top = nullptr;
-#if YAFGPU_TRACE_TOP
-	if(!s->tree.nodes.empty())
-	{	// the top of the tree once more, in heap order: every ray's first steps touch these few nodes (a breadth-first prefix is 128
-		// cache lines at depth 10; in the depth-first array the same nodes are spread over as many lines as there are left spines)
-		const std::vector<KdNode> &tn = s->tree.nodes;
-		std::vector<uint4> top((size_t)kTopN, make_uint4(0u, 3u, 0u, 0u));
-		std::vector<std::pair<uint32_t, uint32_t>> todo;      // (index in the depth-first array, heap index)
-		todo.emplace_back(0u, 0u);
-		while(!todo.empty())
-		{
-			const auto [g, h] = todo.back(); todo.pop_back();
-			const uint2 nd = *(const uint2 *)&tn[g];
-			top[h] = make_uint4(nd.x, nd.y, g, 0u);
-			if((nd.y & 3u) != 3u && 2u * h + 2u < (uint32_t)kTopN) { todo.emplace_back(nd.y >> 2, 2u * h + 2u); todo.emplace_back(g + 1u, 2u * h + 1u); }
-		}
-		if(tn.size() >= kTopTag) { yafgpu_scene_destroy(s); return fail(-2, "kd-tree too large for tagged node indices"); }
-		if((rc = upload(s, top.data(), top.size(), &dv.top))) { yafgpu_scene_destroy(s); return rc; }
-	}
-#endif
-	dv.nodes_blk = nullptr;
-#if YAFGPU_TRACE_BLOCKS
-	if(!s->tree.nodes.empty())
-	{	// the depth-first array (left child = next node, right child in the node) laid out again in blocks of three levels
-		const std::vector<KdNode> &tn = s->tree.nodes;
-		std::vector<uint2> blk(8, make_uint2(0u, 3u));
-		std::vector<std::pair<uint32_t, uint32_t>> todo;      // (depth-first index of a subtree's root, its block)
-		todo.emplace_back(0u, 0u);
-		while(!todo.empty())
-		{
-			const auto [root, b] = todo.back(); todo.pop_back();
-			uint32_t at[7]; bool have[7] = {true, false, false, false, false, false, false};
-			at[0] = root;
-			for(int sl = 0; sl < 7; ++sl)
-			{
-				if(!have[sl]) continue;
-				const uint2 nd = *(const uint2 *)&tn[at[sl]];
-				uint2 out = nd;
-				if((nd.y & 3u) != 3u)
-				{
-					const uint32_t left = at[sl] + 1u, right = nd.y >> 2;
-					if(sl < 3) { at[2 * sl + 1] = left; at[2 * sl + 2] = right; have[2 * sl + 1] = have[2 * sl + 2] = true; out.y = nd.y & 3u; }
-					else
-					{
-						const uint32_t bl = (uint32_t)(blk.size() / 8);
-						blk.resize(blk.size() + 16, make_uint2(0u, 3u));
-						out.y = (nd.y & 3u) | (bl << 2);
-						todo.emplace_back(right, bl + 1u);
-						todo.emplace_back(left, bl);
-					}
-				}
-				blk[(size_t)b * 8 + (size_t)sl] = out;
-			}
-		}
-		if(blk.size() / 8 >= (1u << 27)) { yafgpu_scene_destroy(s); return fail(-2, "kd-tree too large for the block layout"); }
-		if((rc = upload(s, blk.data(), blk.size(), &dv.nodes_blk))) { yafgpu_scene_destroy(s); return rc; }
-	}
-#endif
 	if((rc = upload(s, s->tree.refs.data(), s->tree.refs.size(), &dv.refs))) { yafgpu_scene_destroy(s); return rc; }
 	if((rc = upload(s, rec.data(), rec.size(), &dv.tri))) { yafgpu_scene_destroy(s); return rc; }
 	if((rc = upload(s, ng.data(), ng.size(), &dv.tri_ng))) { yafgpu_scene_destroy(s); return rc; }

@@ -1501,9 +1501,6 @@ __global__ __launch_bounds__(kBlock) void wf_generate(const WfArgs a)
 // queue with one atomic (ballot + prefix rank) and the freed lanes start them while the others carry
 // on.  Traversal state (current node, [tmin,tmax], best hit, short stack in LDS) is per lane, so lanes
 // of one wave can be at any point of any ray.  The walk itself is kd_trace's, cut at leaf granularity.
-#ifndef YAFGPU_NODE_WINDOW
-#define YAFGPU_NODE_WINDOW 1   // C2 sweep: 1 -> 22.1, 2 -> 23.7, 4 -> 27.2, 8 -> 37.0 ms of traversal per pass: extra node fetches cost more than the latency they hide
-#endif
 #ifndef YAFGPU_VOTE_NUM
 #define YAFGPU_VOTE_NUM 1      // triangle round when n_tri * NUM >= n_node * DEN
 #endif
@@ -1511,7 +1508,7 @@ __global__ __launch_bounds__(kBlock) void wf_generate(const WfArgs a)
 #define YAFGPU_VOTE_DEN 1
 #endif
 #ifndef YAFGPU_NODE_BURST
-#define YAFGPU_NODE_BURST 4    // node steps per vote
+#define YAFGPU_NODE_BURST 2    // treelet fetches per vote, each good for up to two node steps (K sweep: profiles/r04_ab_treelet.txt)
 #endif
 #ifndef YAFGPU_TRACE_BATCH
 #define YAFGPU_TRACE_BATCH 512
@@ -1532,46 +1529,17 @@ constexpr int kTraceBatch = YAFGPU_TRACE_BATCH;
 #ifndef YAFGPU_TRACE_POSTPONE
 #define YAFGPU_TRACE_POSTPONE 1
 #endif
-#ifndef YAFGPU_TRACE_FUSED
-#define YAFGPU_TRACE_FUSED 0
-#endif
 #ifndef YAFGPU_TRACE_BELOW_MASKS
 #define YAFGPU_TRACE_BELOW_MASKS 1
 #endif
-#ifndef YAFGPU_TRACE_TRIPF
-#define YAFGPU_TRACE_TRIPF 0     // measured, off: the pending leaf's next triangle record fetched a round ahead (10 more VGPRs, loads for tests that never run, a wait for the reference where the fetch is issued): 2035 against 2245 Mrays/s on the 1 M-triangle scene
-#endif
-#ifndef YAFGPU_TRACE_PAIR
-#define YAFGPU_TRACE_PAIR 1      // closest-hit launches -6.5 % on the 1 M-triangle scenes, -4.5 % on the 100 k one (pair4 in profiles/r02_ab_pair.txt)
-#endif
-#ifndef YAFGPU_TRACE_BLOCKS
-#define YAFGPU_TRACE_BLOCKS 0    // measured, off: 1 = the any-hit launches walk the block layout of the tree (DevScene::nodes_blk): +4 %; 2 = the closest-hit ones too, instead of the pair array: +10 % (profiles/r02_ab_blocks.txt)
-#endif
-// Leaves apart.  A node burst used to handle a leaf the moment a lane fetched one: the empty-leaf pop (21 vector instructions) and
-// the non-empty leaf's note-and-go-on (30) sat as divergent branches inside EVERY node step, entered by the 15 % of the walking
-// lanes that stood at a leaf — with 35 lanes walking some lane nearly always does, so a step cost 28 + 21 + 30 instructions for
-// 28 useful ones.  Now a lane that fetches a leaf stands still for the rest of the burst (kAtLeaf) and all leaves of a burst are
-// handled together after it, once.  Per ray the steps and their order are what they were.  0: the old placement (comparison build).
-#ifndef YAFGPU_TRACE_LEAF_APART
-#define YAFGPU_TRACE_LEAF_APART 0      // measured (profiles/r03_ab_leaf.txt): fewer instructions, fewer lanes per step — closest-hit launches +6 %, any-hit launches equal
-#endif
-// Triangle records (48 MB at 1 M triangles, each read a few times per pass by unrelated rays) loaded with the non-temporal hint, so that
-// they do not push the node lines out of the 32 KB L1 / 4 MB L2 (measured: profiles/r03_ab_toptree.txt).
-#ifndef YAFGPU_TRACE_NT
-#define YAFGPU_TRACE_NT 0
-#endif
-typedef float yg_f4v __attribute__((ext_vector_type(4)));
-YG_DEV float4 ld_tri(const float4 *p)
-{
-#if YAFGPU_TRACE_NT
-	const yg_f4v v = __builtin_nontemporal_load((const yg_f4v *)p);
-	return make_float4(v.x, v.y, v.z, v.w);
-#else
-	return *p;
-#endif
-}
+// Treelets.  The walk reads the tree in the treelet layout (DevScene::treelets, kdtree_build.h): one 32-byte fetch brings an interior
+// node, its two children and the links below them, so a fetch is good for up to two node steps, and a leaf is reached through a link
+// that carries its numbers — an empty leaf or an inline one costs no fetch at all.  The lane state and the stack entries are links.
+// Per ray the node steps, the leaves and their order are kd_trace's; only where a step's operands come from differs.  (The closed
+// alternatives — pair fetch, 64-byte blocks, the tree's top in L1 or LDS, fused rounds, triangle prefetch, leaves apart, non-temporal
+// triangle loads, node windows — are measured in profiles/r02_ab_*.txt and profiles/r03_ab_*.txt.)
 #ifndef YAFGPU_TRACE_WAVES
-#define YAFGPU_TRACE_WAVES 7     // waves per SIMD the register allocation must leave room for (22.5 KB of LDS per block allow 7): 70 / 68 VGPRs; without the bound the any-hit kernel took 81 (5 waves)
+#define YAFGPU_TRACE_WAVES 7     // waves per SIMD the register allocation must leave room for (22.5 KB of LDS per block allow 7): 72 / 70 VGPRs (closest / any); without the bound the any-hit kernel once took 81 (5 waves)
 #endif
 template<bool kAny, bool kStats>
 __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfArgs a)
@@ -1582,16 +1550,7 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 	__shared__ float2 s_axis[kWavesPerBlock][3][kWave];
 	const int lane = (int)(threadIdx.x & (kWave - 1)), wave = (int)(threadIdx.x >> 6);
 	const DevScene &sc = a.ra.sc;
-#if YAFGPU_TRACE_TOP == 2
-	__shared__ uint4 s_top[kTopN];
-	for(int i = (int)threadIdx.x; i < kTopN; i += (int)blockDim.x) s_top[i] = sc.top[i];
-	__syncthreads();
-#endif
-#ifdef YAFGPU_TRACE_LDS_PAD      // (A/B aid: the LDS the staged top would take, without it — the occupancy alone)
-	__shared__ uint32_t s_pad[YAFGPU_TRACE_LDS_PAD / 4];
-	if(a.cap == 0xffffffffu) s_pad[threadIdx.x] = 1u;
-#endif
-	constexpr uint32_t kRoot = YAFGPU_TRACE_TOP ? kTopTag : 0u;
+	const uint32_t root = sc.tl_root;
 	LaneStack stk;
 	stk.col = &s_stack[wave][0][lane];
 	float2 *const axis_col = &s_axis[wave][0][lane];      // axis k at axis_col[k * kWave]
@@ -1601,7 +1560,7 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 	const uint32_t *q = kAny ? a.q_shadow_in : a.q_closest_in;
 	const size_t c = a.cap;
 	bool exhausted = (n == 0u);
-	uint32_t slot = 0u, node = 0u, which = 0u, pair = 0u, qi = 0u;      // qi: the ray's position in the queue (where a closest-hit answer goes)
+	uint32_t slot = 0u, link = 0u, which = 0u, pair = 0u, qi = 0u;      // link: where the walk stands (kdtree_build.h)      // qi: the ray's position in the queue (where a closest-hit answer goes)
 	uint32_t w_next = 0u, w_end = 0u;      // this wave's reserved queue range (wave-uniform)
 	// reservation size: large enough to keep the counter word off the critical path, small enough that a short queue still spreads over all waves
 	const uint32_t batch = min((uint32_t)kTraceBatch, max((uint32_t)kWave, (n / (gridDim.x * (uint32_t)kWavesPerBlock * 2u)) & ~63u));
@@ -1616,18 +1575,12 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 		const uint32_t bit = 4u * slot + 2u * pair + which;
 		if(occluded) atomicOr(&a.verdict[bit >> 5], 1u << (bit & 31u));
 	};
-	// the walk: at a node | at a non-empty leaf, waiting for the pending slot | no node left | no ray
-	enum : uint32_t { kWalk = 0u, kBlocked = 1u, kWalkEnd = 2u, kNoRay = 3u, kAtLeaf = 4u };
-	uint32_t lf_first = 0u, lf_np = 0u;              // the leaf a lane in kAtLeaf stands at: first reference, reference count
+	// the walk: at a node or a leaf | at a non-empty leaf, waiting for the pending slot | no node left | no ray
+	enum : uint32_t { kWalk = 0u, kBlocked = 1u, kWalkEnd = 2u, kNoRay = 3u };
 	constexpr int kVoteNum = YAFGPU_VOTE_NUM, kVoteDen = YAFGPU_VOTE_DEN, kNodeBurst = YAFGPU_NODE_BURST;
-	constexpr bool kBlk = (YAFGPU_TRACE_BLOCKS == 2) || (YAFGPU_TRACE_BLOCKS == 1 && kAny);
 	uint32_t ws = kNoRay;
 	uint32_t p_cur = 0u, p_end = 0u, ti = 0u;       // pending leaf: references [p_cur, p_end) still to test, ti = refs[p_cur] (in flight)
 	float p_tmax = 0.f;                              // exit distance of the pending leaf's cell
-#if YAFGPU_TRACE_TRIPF
-	float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0, q2 = q0;      // record of triangle `ti`, fetched ahead of its test
-	bool q_ok = false;
-#endif
 	bool done = false;
 	uint32_t spec = 0u;                              // kStats: node steps + leaves of the walk ahead of the pending leaf
 	uint32_t spec_leaves = 0u;
@@ -1706,7 +1659,7 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 					axis_col[kWave] = make_float2(from.y, inv_dir.y);
 					axis_col[2 * kWave] = make_float2(from.z, inv_dir.z);
 					dneg = (dir.x <= 0.f ? 1u : 0u) | (dir.y <= 0.f ? 2u : 0u) | (dir.z <= 0.f ? 4u : 0u);
-					t_exit = eb; tmin = smax(ea, 0.f); tmax = t_exit; node = kRoot; ws = kWalk;
+					t_exit = eb; tmin = smax(ea, 0.f); tmax = t_exit; link = root; ws = kWalk;
 					stk.reset();
 				}
 				else
@@ -1735,7 +1688,7 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 			const bool restart = emp && stk.lost() && !(tmax >= t_exit);
 			if(kStats && restart && !hit_here) ++cn.restarts;
 			tmin = restart ? restart_from(tmin, tmax) : tmax;                          // see restart_from: progress on degenerate trees
-			node = emp ? kRoot : top.x;
+			link = emp ? root : top.x;
 			tmax = emp ? t_exit : __uint_as_float(top.y);
 			stk.sp = emp ? 0 : stk.sp - 1;
 			stk.lo = emp ? 0 : stk.lo;
@@ -1775,134 +1728,59 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 				else if(!done) leaf_end();                  // (comparison build) the lane stood at the leaf: go on from it
 			}
 		};
-		// one step of the walk on the fetched node
-		auto node_step = [&](const uint2 nd, const uint32_t left_c, const uint32_t right_c) {
-			if((nd.y & 3u) != 3u)
-			{
-				const uint32_t axis = nd.y & 3u;
-				const float split = __uint_as_float(nd.x);
-				const float2 oi = axis_col[axis * kWave];
-				const float o = oi.x;
-				const float tplane = (split - o) * oi.y;
-				// (o < split) || (o == split && d <= 0), kdtree_triangle.cc:725-760, without the short-circuit branches
-				const bool dn = ((dneg >> axis) & 1u) != 0u;
+		// one node step of the walk, on the fetched treelet (t0: the three splits and the header, t1: the links): the node in slot
+		// link & 3 of it
+		auto node_step = [&](const uint4 t0, const uint4 t1) {
+			const uint32_t sl = link & 3u;
+			const uint32_t axis = (t0.w >> (2u * sl)) & 3u;
+			const float split = __uint_as_float(sl == 0u ? t0.x : (sl == 1u ? t0.y : t0.z));
+			const float2 oi = axis_col[axis * kWave];
+			const float o = oi.x;
+			const float tplane = (split - o) * oi.y;
+			// (o < split) || (o == split && d <= 0), kdtree_triangle.cc:725-760, without the short-circuit branches
+			const bool dn = ((dneg >> axis) & 1u) != 0u;
 #if YAFGPU_TRACE_BELOW_MASKS
-				// the same predicate as lane-mask logic: three compares, combined on the scalar unit (the kernel is VALU-bound)
-				const bool below = __builtin_amdgcn_inverse_ballot_w64(__ballot(o < split) | (__ballot(o == split) & __ballot(dn)));
+			// the same predicate as lane-mask logic: three compares, combined on the scalar unit (the kernel is VALU-bound)
+			const bool below = __builtin_amdgcn_inverse_ballot_w64(__ballot(o < split) | (__ballot(o == split) & __ballot(dn)));
 #else
-				const bool below = dn ? (o <= split) : (o < split);
+			const bool below = dn ? (o <= split) : (o < split);
 #endif
-				uint32_t left = left_c, right = right_c;
-				if(kBlk)
-				{	// block layout: children inside the block for slots 0..2, the roots of the two child blocks for slots 3..6
-					const uint32_t sl = node & 7u;
-					const bool inside = sl < 3u;
-					left = inside ? node + sl + 1u : (nd.y >> 2) << 3;
-					right = inside ? left + 1u : left + 8u;
-				}
-				const uint32_t near_c = below ? left : right, far_c = below ? right : left;
-				if(kStats) { ++cn.interior; if(p_cur < p_end) ++spec; }
-				const bool near_only = !(tplane <= tmax) || tplane <= 0.f;        // plane beyond the cell or behind the origin (also NaN)
-				const bool far_only = !near_only && tplane < tmin;
-				const bool both = !near_only && !far_only;
-				// the slot above the top is always free (at most kStack-1 live entries), so the far child is written
-				// unconditionally and only the stack pointer says whether it was a push
-				stk.col[(stk.sp & (kStack - 1)) * kWave] = make_uint2(far_c, __float_as_uint(tmax));
-				stk.sp += both ? 1 : 0;
-				stk.lo = max(stk.lo, stk.sp - (kStack - 1));
-				node = far_only ? far_c : near_c;
-				tmax = both ? tplane : tmax;
-			}
-			else if(YAFGPU_TRACE_LEAF_APART) { lf_first = nd.x; lf_np = nd.y >> 2; ws = kAtLeaf; }      // handled after the burst (leaf_visit)
-			else
-			{
-				const uint32_t np = nd.y >> 2;
-				if(np == 0u) { if(kStats) { ++cn.leaves; if(p_cur < p_end) ++spec_leaves; } leaf_end(); }
-				else if(!YAFGPU_TRACE_POSTPONE)
-				{	// (comparison build) stop at every non-empty leaf until its tests are through
-					if(kStats) ++cn.leaves;
-					p_cur = nd.x; p_end = nd.x + np; p_tmax = tmax; ti = sc.refs[nd.x]; ws = kBlocked;
-				}
-				else if(p_cur < p_end) ws = kBlocked;          // a second non-empty leaf: wait for the pending one (the node is read again then)
-				else
-				{
-					if(kStats) ++cn.leaves;
-					p_cur = nd.x; p_end = nd.x + np; p_tmax = tmax;
-					ti = sc.refs[nd.x];                           // in flight while the lane walks on
-					leaf_end();
-				}
-			}
+			// the root's children are nodes of this treelet, or leaves whose links stand in t1.x / t1.z; a child's children are links
+			const bool l_in = sl == 0u && ((t0.w >> 2) & 3u) != 3u, r_in = sl == 0u && ((t0.w >> 4) & 3u) != 3u;
+			const uint32_t left = l_in ? (link | 1u) : (sl == 2u ? t1.z : t1.x);
+			const uint32_t right = r_in ? (link | 2u) : (sl == 0u ? t1.z : (sl == 1u ? t1.y : t1.w));
+			const uint32_t near_c = below ? left : right, far_c = below ? right : left;
+			if(kStats) { ++cn.interior; if(p_cur < p_end) ++spec; }
+			const bool near_only = !(tplane <= tmax) || tplane <= 0.f;        // plane beyond the cell or behind the origin (also NaN)
+			const bool far_only = !near_only && tplane < tmin;
+			const bool both = !near_only && !far_only;
+			// the slot above the top is always free (at most kStack-1 live entries), so the far child is written
+			// unconditionally and only the stack pointer says whether it was a push
+			stk.col[(stk.sp & (kStack - 1)) * kWave] = make_uint2(far_c, __float_as_uint(tmax));
+			stk.sp += both ? 1 : 0;
+			stk.lo = max(stk.lo, stk.sp - (kStack - 1));
+			link = far_only ? far_c : near_c;
+			tmax = both ? tplane : tmax;
 		};
-		// one step on the heap-ordered copy of the tree's top (YAFGPU_TRACE_TOP): children by index arithmetic, and by the node's own
-		// place in the depth-first array on the copy's last level, below which the walk goes on in `nodes`
-		auto top_step = [&]() {
-#if YAFGPU_TRACE_TOP
-			const uint32_t hh = node & ~kTopTag;
-#if YAFGPU_TRACE_TOP == 2
-			const uint4 e = s_top[hh];
-#else
-			const uint4 e = sc.top[hh];
-#endif
-			const bool bottom = hh >= (uint32_t)kTopBottom;
-			node_step(make_uint2(e.x, e.y), bottom ? e.z + 1u : (kTopTag | (2u * hh + 1u)), bottom ? (e.y >> 2) : (kTopTag | (2u * hh + 2u)));
-#endif
-		};
-		// the leaves of a burst, together (YAFGPU_TRACE_LEAF_APART): an empty leaf is left at once, a non-empty one becomes the pending
-		// leaf (its first reference in flight while the lane walks on) — or the lane waits at it while another leaf is pending
-		auto leaf_visit = [&]() {
-			const bool empty = lf_np == 0u, pend = p_cur < p_end;
-			if(!YAFGPU_TRACE_POSTPONE && !empty)
+		// the leaf the walk stands at (a leaf link): its numbers are in the link, or in the escape array
+		auto leaf_step = [&]() {
+			uint32_t first = link & ((1u << kLinkFirstBits) - 1u), np = (link >> kLinkFirstBits) & kLinkCountMax;
+			if(link & kLinkEscape) { const uint2 e = sc.tl_leaves[link & kLinkIndex]; first = e.x; np = e.y; }
+			if(np == 0u) { if(kStats) { ++cn.leaves; if(p_cur < p_end) ++spec_leaves; } leaf_end(); }
+			else if(!YAFGPU_TRACE_POSTPONE)
 			{	// (comparison build) stop at every non-empty leaf until its tests are through
 				if(kStats) ++cn.leaves;
-				p_cur = lf_first; p_end = lf_first + lf_np; p_tmax = tmax; ti = sc.refs[lf_first]; ws = kBlocked;
+				p_cur = first; p_end = first + np; p_tmax = tmax; ti = sc.refs[first]; ws = kBlocked;
 			}
-			else if(!empty && pend) ws = kBlocked;           // the node is read again when the pending leaf is through
+			else if(p_cur < p_end) ws = kBlocked;          // a second non-empty leaf: wait for the pending one (the link stays)
 			else
 			{
-				if(kStats) { ++cn.leaves; if(empty && pend) ++spec_leaves; }
-				if(!empty)
-				{
-					p_cur = lf_first; p_end = lf_first + lf_np; p_tmax = tmax;
-					ti = sc.refs[lf_first];
-				}
+				if(kStats) ++cn.leaves;
+				p_cur = first; p_end = first + np; p_tmax = tmax;
+				ti = sc.refs[first];                          // in flight while the lane walks on
 				leaf_end();
 			}
 		};
-#if YAFGPU_TRACE_TOP
-		// lanes that stand in the top copy (new rays; a far child popped off the stack) walk down it first, together: these steps wait for
-		// the L1 or LDS only, and afterwards the node rounds below find (nearly) every lane in the depth-first array
-#pragma unroll 1
-		for(int s = 0; s < kTopDepth + 2; ++s)
-		{
-			if(__ballot(ws == kWalk && (node & kTopTag)) == 0ull) break;
-			if(ws == kWalk && (node & kTopTag)) top_step();
-			if(YAFGPU_TRACE_LEAF_APART && ws == kAtLeaf) leaf_visit();
-		}
-#endif
-#if YAFGPU_TRACE_FUSED
-		// Fused rounds: every lane fetches what it can use — the node its walk stands at AND the next triangle of its pending
-		// leaf — the wave waits once, then runs the node section and the triangle section one after the other.  More
-		// instructions per round than a voted round (both sections are always issued), half as many memory round trips per
-		// ray: the better trade when the tree does not fit the L2s and waves spend most of their time in s_waitcnt
-		// (1M triangles: PMC SQ_WAIT_ANY 65 % of wave cycles, L2 hit rate 75-83 %).
-		{
-			const bool walking = ws == kWalk;
-			uint2 nd = make_uint2(0u, 3u);
-			float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
-			uint32_t ref_v = 0u;
-			if(walking) nd = sc.nodes[node];
-			if(has_pend)
-			{
-				if(p_cur + 1u < p_end) ref_v = sc.refs[p_cur + 1u];
-				r0 = sc.tri[3u * ti]; r1 = sc.tri[3u * ti + 1u]; r2 = sc.tri[3u * ti + 2u];
-			}
-			if(kStats) { ++rounds_node; ++rounds_tri; }
-			if(walking) node_step(nd, node + 1u, nd.y >> 2);
-			if(YAFGPU_TRACE_LEAF_APART && ws == kAtLeaf) leaf_visit();
-			if(has_pend) tri_step(r0, r1, r2, ref_v);
-			(void)n_tri; (void)n_node;
-		}
-#else
 		if(n_tri * kVoteNum >= n_node * kVoteDen && n_tri > 0)
 		{
 			if(kStats) ++rounds_tri;
@@ -1910,69 +1788,34 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 			{
 				uint32_t ref_v = 0u;
 				if(p_cur + 1u < p_end) ref_v = sc.refs[p_cur + 1u];
-#if YAFGPU_TRACE_TRIPF
-				if(!q_ok) { q0 = sc.tri[3u * ti]; q1 = sc.tri[3u * ti + 1u]; q2 = sc.tri[3u * ti + 2u]; }
-				tri_step(q0, q1, q2, ref_v);
-				// the next triangle of the leaf (its reference has arrived meanwhile): its record is in flight until the next
-				// triangle round — behind whatever the wave waits for in between
-				q_ok = p_cur < p_end;
-				if(q_ok) { q0 = sc.tri[3u * ti]; q1 = sc.tri[3u * ti + 1u]; q2 = sc.tri[3u * ti + 2u]; }
-#else
-				const float4 r0 = ld_tri(&sc.tri[3u * ti]), r1 = ld_tri(&sc.tri[3u * ti + 1u]), r2 = ld_tri(&sc.tri[3u * ti + 2u]);
+				const float4 r0 = sc.tri[3u * ti], r1 = sc.tri[3u * ti + 1u], r2 = sc.tri[3u * ti + 2u];
 				tri_step(r0, r1, r2, ref_v);
-#endif
 			}
 		}
 		else
 		{
-#if YAFGPU_TRACE_PAIR
-			// Two node steps per memory round trip: nodes2[i] holds node i and a copy of its right child, the left child is node
-			// i + 1, so one 32-byte fetch at i brings both children along and the step after an interior node needs no fetch.
-			// Closest-hit rays only: the doubled node footprint costs the any-hit rays (L2 hit rate 75 %) more than the saved
-			// round trips give them (1 M triangles: closest-hit launches -7 %, any-hit launches +8.5 %).
+			// kNodeBurst treelet rounds: a leaf the walk stands at is taken first (a far child popped at the end of the last round,
+			// the leaf a lane waited at, a tree that is one leaf), then one fetch and two node steps from the registers, with the
+			// leaf the first step may reach between them; a far child popped there that lies in the same treelet is stepped into at once
 #pragma unroll 1
-			for(int s = 0; s < ((kAny || kBlk) ? 0 : kNodeBurst / 2); ++s)
+			for(int s = 0; s < kNodeBurst; ++s)
 			{
 				if(kStats && __ballot(ws == kWalk) != 0ull) ++rounds_node;
-#if YAFGPU_TRACE_TRIPF
-				if(p_cur < p_end && !q_ok) { q0 = sc.tri[3u * ti]; q1 = sc.tri[3u * ti + 1u]; q2 = sc.tri[3u * ti + 2u]; q_ok = true; }
-#endif
-				if(YAFGPU_TRACE_TOP && ws == kWalk && (node & kTopTag)) { top_step(); if(ws == kWalk && (node & kTopTag)) top_step(); }
-				else if(ws == kWalk)
-				{
-					const uint32_t n0 = node;
-					const uint4 a0 = sc.nodes2[n0], a1 = sc.nodes2[n0 + 1u];
-					node_step(make_uint2(a0.x, a0.y), n0 + 1u, a0.y >> 2);
-					if((a0.y & 3u) != 3u)          // an interior node hands the walk to one of its two children
-					{
-						const bool to_left = node == n0 + 1u;
-						const uint2 n1 = to_left ? make_uint2(a1.x, a1.y) : make_uint2(a0.z, a0.w);
-						node_step(n1, node + 1u, n1.y >> 2);
-					}
-				}
+				if(ws == kWalk && (link & kLinkLeaf)) leaf_step();
+				const bool fetch = ws == kWalk && !(link & kLinkLeaf);
+				const uint32_t at = link >> 2;
+				uint4 t0 = make_uint4(0u, 0u, 0u, 0u), t1 = t0;
+				if(fetch) { t0 = sc.treelets[2u * at]; t1 = sc.treelets[2u * at + 1u]; }
+				if(fetch) node_step(t0, t1);
+				if(ws == kWalk && (link & kLinkLeaf)) leaf_step();
+				if(fetch && ws == kWalk && (link >> 2) == at) node_step(t0, t1);
 			}
-#endif
-#pragma unroll 1
-			for(int s = 0; s < ((YAFGPU_TRACE_PAIR && !kAny && !kBlk) ? 0 : kNodeBurst); ++s)
-			{
-				if(kStats && __ballot(ws == kWalk) != 0ull) ++rounds_node;
-#if YAFGPU_TRACE_TRIPF
-				if(p_cur < p_end && !q_ok) { q0 = sc.tri[3u * ti]; q1 = sc.tri[3u * ti + 1u]; q2 = sc.tri[3u * ti + 2u]; q_ok = true; }
-#endif
-				if(YAFGPU_TRACE_TOP && ws == kWalk && (node & kTopTag)) top_step();
-				else if(ws == kWalk) { const uint2 nd = kBlk ? sc.nodes_blk[node] : sc.nodes[node]; node_step(nd, node + 1u, nd.y >> 2); }
-			}
-			if(YAFGPU_TRACE_LEAF_APART && ws == kAtLeaf) leaf_visit();
 		}
-#endif
 		if(done || (ws == kWalkEnd && p_cur >= p_end))
 		{
 			if(kAny) answer_any(hit);
 			else a.state[2 * c + qi] = make_float4(fbits((uint32_t)(hit ? tri : -1)), z, bu, bv);
 			ws = kNoRay; done = false; p_cur = p_end = 0u;
-#if YAFGPU_TRACE_TRIPF
-			q_ok = false;
-#endif
 		}
 	}
 	if(a.ra.counters != nullptr)
@@ -2004,16 +1847,6 @@ __global__ __launch_bounds__(kBlock) void wf_trace_ts(const WfArgs a)
 	__shared__ uint32_t s_seen[kWavesPerBlock][kTsMaxDepth + 1][kWave];
 	const int lane = (int)(threadIdx.x & (kWave - 1)), wave = (int)(threadIdx.x >> 6);
 	const DevScene &sc = a.ra.sc;
-#if YAFGPU_TRACE_TOP == 2
-	__shared__ uint4 s_top[kTopN];
-	for(int i = (int)threadIdx.x; i < kTopN; i += (int)blockDim.x) s_top[i] = sc.top[i];
-	__syncthreads();
-#endif
-#ifdef YAFGPU_TRACE_LDS_PAD      // (A/B aid: the LDS the staged top would take, without it — the occupancy alone)
-	__shared__ uint32_t s_pad[YAFGPU_TRACE_LDS_PAD / 4];
-	if(a.cap == 0xffffffffu) s_pad[threadIdx.x] = 1u;
-#endif
-	constexpr uint32_t kRoot = YAFGPU_TRACE_TOP ? kTopTag : 0u;
 	LaneStack stk;
 	stk.col = &s_stack[wave][0][lane];
 	uint32_t *seen = &s_seen[wave][0][lane];

@@ -74,7 +74,7 @@ GPU_ABI_SYMBOLS = [
     "yafgpu_last_error", "yafgpu_device_count", "yafgpu_set_device", "yafgpu_scene_create", "yafgpu_scene_destroy",
     "yafgpu_scene_info", "yafgpu_planes_bytes", "yafgpu_render_tiles", "yafgpu_film_combine", "yafgpu_render_to_host", "yafgpu_render_passes_to_host",
     "yafgpu_trace_closest", "yafgpu_trace_shadow", "yafgpu_scene_get_tree", "yafgpu_probe",
-    "yafgpu_kdtree_build", "yafgpu_kdtree_build_device", "yafgpu_kdtree_info", "yafgpu_kdtree_get", "yafgpu_kdtree_destroy",
+    "yafgpu_kdtree_build", "yafgpu_kdtree_build_device", "yafgpu_kdtree_info", "yafgpu_kdtree_get", "yafgpu_kdtree_destroy", "yafgpu_kdtree_treelets",
     "yafgpu_set_profiling", "yafgpu_scene_set_pass_pipelining", "yafgpu_get_profile", "yafgpu_scene_set_abort_flag", "yafgpu_scene_set_exchange", "yafgpu_glibc_rand",
 ]
 
@@ -569,6 +569,26 @@ def build_kdtree(verts, threads=0, device=False):
     L.yafgpu_kdtree_get(h, nodes.ctypes.data_as(up), refs.ctypes.data_as(up), bound.ctypes.data_as(C.POINTER(C.c_float)))
     L.yafgpu_kdtree_destroy(h)
     return nodes[:info.n_nodes], refs[:info.n_leaf_refs], bound, info
+
+
+def build_treelets(nodes, inline_leaves=True):
+    """The treelet layout the traversal kernels walk, built from a flattened tree as build_kdtree returns it
+    -> (treelets (n,8) u32, escaped leaves (m,2) u32, root link).  See libyafaray_amd/csrc/kdtree_build.h."""
+    L = load()
+    up = C.POINTER(C.c_uint32)
+    L.yafgpu_kdtree_treelets.argtypes = [up, C.c_uint32, C.c_int32, up, up, up, up, up]
+    nd = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1, 2)
+    nw, nl, root = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    rc = L.yafgpu_kdtree_treelets(nd.ctypes.data_as(up), nd.shape[0], int(bool(inline_leaves)), None, C.byref(nw), None, C.byref(nl), C.byref(root))
+    if rc:
+        raise YafaRayError(f"treelet layout: {rc}")
+    words = np.zeros(max(nw.value, 1), np.uint32)
+    leaves = np.zeros(max(nl.value, 1), np.uint32)
+    rc = L.yafgpu_kdtree_treelets(nd.ctypes.data_as(up), nd.shape[0], int(bool(inline_leaves)), words.ctypes.data_as(up), C.byref(nw),
+                                  leaves.ctypes.data_as(up), C.byref(nl), C.byref(root))
+    if rc:
+        raise YafaRayError(f"treelet layout: {rc}")
+    return words[:nw.value].reshape(-1, 8), leaves[:nl.value].reshape(-1, 2), root.value
 
 
 def planes_bytes(width, height):
