@@ -1,5 +1,5 @@
 // MI355X (gfx950) path-tracing core: flattened kd-tree traversal, surface shading with MIS direct
-// lighting, and deterministic film accumulation — hand-written HIP, one persistent launch per pass.
+// lighting, and deterministic film accumulation — hand-written HIP.
 //
 // Reference path: TiledIntegrator::renderTile (integrator_tiled.cc:309-521) ->
 // PathIntegrator::integrate (integrator_path_tracer.cc:112-347) -> Scene::intersect / isShadowed
@@ -7,17 +7,11 @@
 // Triangle::intersect (triangle.h:223-259), MonteCarloIntegrator::doLightEstimation
 // (integrator_montecarlo.cc:78-345), ImageFilm::addSample (imagefilm.cc:925-1015).
 //
-// Execution model (DESIGN.md has the full picture):
-//   * one lane = one camera sample; a wave owns P pixels x L lanes (L = min(spp,64)) and walks their
-//     samples in index order, so each pixel's film sum is a sequential sum in sample order with no
-//     atomics (ImageFilm::addSample's order for a single-threaded reference render);
-//   * persistent waves pull "units" (pixel groups of one tile) from 8 queues, one per XCD, and
-//     steal from the others when their own runs dry, so the waves of one XCD share an image region
-//     and hence a kd-tree working set in that XCD's L2;
-//   * integrate() is an explicit state machine with exactly one closest-hit trace site and one
-//     any-hit trace site, so the traversal loops exist once in the instruction stream;
-//   * traversal keeps a short per-lane stack in LDS ([slot][lane], conflict-free), with the
-//     classic kd-restart fallback when more than kStack far-children are pending.
+// This unit holds the device scene, the pieces of traversal and shading the kernels share, the host side
+// of the narrow ABI, and (through yafgpu_wavefront.h) the wavefront pass: a path runs as a coroutine that
+// parks its state in HBM at every kd-tree query, and traversal kernels answer the queries in queues
+// (DESIGN.md §4.1 has the full picture).  Traversal keeps a short per-lane stack in LDS ([slot][lane],
+// conflict-free), with the classic kd-restart fallback when more than kStack far-children are pending.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,12 +39,8 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 #ifndef YAFGPU_STACK
 #define YAFGPU_STACK 8                // 8 slots: 8 waves/SIMD for the traversal kernels, 0.8 % of rays restart (C2)
 #endif
-#ifndef YAFGPU_WAVES
-#define YAFGPU_WAVES 4                // __launch_bounds__ min waves/SIMD of the render kernel (C2 measured: 1:368 2:667 3:781 4:793 Mrays/s)
-#endif
 constexpr int kStack = YAFGPU_STACK;  // per-lane LDS stack slots (power of two)
 constexpr int kDepthCap = 48;         // host tree depth cap; deeper pending lists restart
-constexpr int kQueues = 8;            // one per XCD
 constexpr float kMinRayDist = (float)0.00005;   // MIN_RAYDIST, CMakeLists.txt:46-48
 constexpr float kShadowBias = (float)0.0005;    // YAF_SHADOW_BIAS, CMakeLists.txt:50-52
 
@@ -85,12 +75,8 @@ struct RenderArgs
 	float shadow_bias, ray_min_dist, filterw;
 	float table_scale; int wide_filter;   // wide_filter: footprint beyond the 2x2 box case -> table weights + atomics (wavefront accumulate)
 	const float *filter_table;            // 16x16 reconstruction-filter table (ImageFilm ctor, imagefilm.cc:152-176)
-	int lanes_per_pixel, pixels_per_wave, iters;
-	int n_tiles; uint32_t n_units;
+	int n_tiles;
 	const int4 *tile_rect;         // x0,y0,w,h per tile of this shard
-	const uint32_t *unit_prefix;   // n_tiles+1
-	uint32_t *queue_next;          // kQueues counters, 32 words apart
-	uint32_t queue_begin[kQueues + 1];
 	float *planes;
 	yafgpu_counters *counters;
 };
@@ -227,84 +213,6 @@ YG_DEV float restart_from(float tmin, float tmax)
 	return (tmax > tmin) ? tmax : tmax + fmaxf(fabsf(tmax) * 1.2e-7f, 1e-30f);
 }
 
-// Closest hit (kAny == false): TriKdTree::intersect, kdtree_triangle.cc:684-837 — the nearest
-//   triangle with ray_tmin <= t < dist whose material is visible to camera rays (:786).
-// Any hit (kAny == true): TriKdTree::intersectS, :840-977 — any triangle with 0 <= t < dist whose
-//   material casts shadows (:938).
-// Both walk [t_enter, t_exit] of the ray against the tree bound front to back; a triangle is
-// referenced by every leaf its bounds overlap, so the result does not depend on tree topology.
-template<bool kAny, bool kStats>
-YG_DEV bool kd_trace(const DevScene &sc, LaneStack &stk, V3 from, V3 dir, float ray_tmin, float dist,
-                     int &tri_out, float &t_out, float &bu, float &bv, LaneCounters &cn)
-{
-	float a, b;
-	if(sc.n_nodes == 0u) return false;
-	const V3 inv_dir = mk(1.f / dir.x, 1.f / dir.y, 1.f / dir.z);
-	if(!bound_cross(sc, from, dir, inv_dir, dist, a, b)) return false;
-	const float t_exit = b;
-	float tmin = smax(a, 0.f), tmax = t_exit;
-	float z = dist;
-	bool hit = false;
-	uint32_t node = 0u;
-	stk.reset();
-	for(;;)
-	{
-		if(z < tmin) break;       // kdtree_triangle.cc:717 (dist < entry distance)
-		uint2 nd = sc.nodes[node];
-		while((nd.y & 3u) != 3u)
-		{
-			const int axis = (int)(nd.y & 3u);
-			const float split = __uint_as_float(nd.x);
-			const float o = comp(from, axis), d = comp(dir, axis);
-			const float tplane = (split - o) * comp(inv_dir, axis);
-			const bool below = (o < split) || (o == split && d <= 0.f);
-			const uint32_t left = node + 1u, right = nd.y >> 2;
-			const uint32_t near_c = below ? left : right, far_c = below ? right : left;
-			if(kStats) ++cn.interior;
-			if(!(tplane <= tmax) || tplane <= 0.f) node = near_c;       // plane beyond the cell or behind the origin (also NaN)
-			else if(tplane < tmin) node = far_c;
-			else { stk.push(far_c, tmax); node = near_c; tmax = tplane; }
-			nd = sc.nodes[node];
-		}
-		{
-			const uint32_t np = nd.y >> 2, first = nd.x;
-			if(kStats) ++cn.leaves;
-			for(uint32_t i = 0; i < np; ++i)
-			{
-				const uint32_t ti = sc.refs[first + i];
-				const float4 r0 = sc.tri[3u * ti], r1 = sc.tri[3u * ti + 1u], r2 = sc.tri[3u * ti + 2u];
-				float t, u, v;
-				if(kStats) ++cn.tests;
-				if(tri_test(r0, r1, r2, from, dir, t, u, v))
-				{
-					const uint32_t vis = __float_as_uint(r1.w) >> 30;
-					if(kAny)
-					{
-						if(t < dist && t >= 0.f && (vis == 0u || vis == 2u)) return true;
-					}
-					else if(t < z && t >= ray_tmin && (vis == 0u || vis == 1u))
-					{
-						z = t; tri_out = (int)ti; bu = u; bv = v; hit = true;
-					}
-				}
-			}
-		}
-		if(!kAny && hit && z <= tmax) break;   // :822
-		if(stk.empty())
-		{
-			if(!stk.lost() || tmax >= t_exit) break;
-			// kd-restart: pending far-children were lost to the short stack; resume at the cell exit
-			tmin = restart_from(tmin, tmax); tmax = t_exit; node = 0u; stk.reset();
-			if(kStats) ++cn.restarts;
-			continue;
-		}
-		tmin = tmax;
-		stk.pop(node, tmax);
-	}
-	t_out = z;
-	return hit;
-}
-
 // Triangle::getSurface, src/common/triangle.cc:30-133 (no UV / orco)
 YG_DEV void get_surface(const DevScene &sc, int ti, V3 hitp, float bu, float bv, SurfPt &sp)
 {
@@ -397,320 +305,11 @@ YG_DEV bool kd_trace_ts(const DevScene &sc, LaneStack &stk, uint32_t *seen /* [k
 	return false;
 }
 
-// ------------------------------------------------------------------------------------------------
-// direct lighting: MonteCarloIntegrator::doLightEstimation, integrator_montecarlo.cc:78-345,
-// over lights [l_begin, l_end).  One any-hit trace site serves the Dirac branch (:94-148), the
-// light-sampling half (:161-262) and the BSDF-sampling half (:285-333) of the area-light MIS.
-template<bool kStats>
-YG_DEV Col direct_light(const RenderArgs &ra, LaneStack &stk, const SurfPt &sp, const yafgpu_material &mat, const BsdfDat &dat, V3 wo,
-                        int l_begin, int l_end, uint32_t pixel_sample, uint32_t sampling_offs, LaneCounters &cn)
-{
-	const DevScene &sc = ra.sc;
-	Col total = mkc(0.f, 0.f, 0.f);
-	const uint32_t kMisFlags = kGlossy | kDiffuse | kDispersive | kReflect | kTransmit;
-	for(int li = l_begin; li < l_end; ++li)
-	{
-		const yafgpu_light &light = sc.lights[li];
-		const bool cast_shadows = light.cast_shadows && mat.receive_shadows;
-		const bool dirac = light.type == YAFGPU_LIGHT_POINT;
-		const int n = dirac ? 1 : (int)ceilf((float)light.samples * ra.rp.aa_light_sample_multiplier);
-		const float inv_ns = 1.f / (float)n;
-		const uint32_t offs = (uint32_t)n * pixel_sample + sampling_offs + (uint32_t)li * 4567u; // LOFFS_DELTA :45
-		Col ccol = mkc(0.f, 0.f, 0.f), ccol_2 = mkc(0.f, 0.f, 0.f), col_dirac = mkc(0.f, 0.f, 0.f);
-		Halton hal_2, hal_3;
-		hal_2.init(2u); hal_3.init(3u);
-		const int n_phase = dirac ? 1 : 2;
-		for(int phase = 0; phase < n_phase; ++phase)
-		{
-			hal_2.set_start(offs - 1u);
-			hal_3.set_start(offs - 1u);
-			for(int i = 0; i < n; ++i)
-			{
-				V3 r_dir = mk(0.f, 0.f, 0.f);
-				float r_tmin = 0.f, r_tmax = -1.f;
-				Col contrib = mkc(0.f, 0.f, 0.f);
-				bool want = false;
-				if(dirac)
-				{
-					Col lcol;
-					if(pointlight_illuminate(light, sp.p, lcol, r_dir, r_tmax))
-					{
-						r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
-						const float angle = mat.flat ? 1.f : fabsf(dot(sp.n, r_dir));
-						contrib = (mat_eval(mat, dat, sp, wo, r_dir, kAll) * lcol) * angle;
-						want = true;
-					}
-				}
-				else
-				{
-					const float s_1 = hal_2.next(), s_2 = hal_3.next();
-					if(phase == 0)
-					{
-						float ls_pdf;
-						if(arealight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf))
-						{
-							r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
-							if(ls_pdf > 1e-6f)
-							{
-								const Col surf_col = mat_eval(mat, dat, sp, wo, r_dir, kAll);
-								const float angle = mat.flat ? 1.f : fabsf(dot(sp.n, r_dir));
-								const float m_pdf = mat_pdf(mat, dat, sp, wo, r_dir, kMisFlags);
-								const Col ls_col = col3(light.color);
-								if(m_pdf > 1e-6f)
-								{
-									const float l_2 = ls_pdf * ls_pdf, m_2 = m_pdf * m_pdf;
-									const float w = l_2 / (l_2 + m_2);
-									contrib = (((surf_col * ls_col) * angle) * w) / ls_pdf;
-								}
-								else contrib = ((surf_col * ls_col) * angle) / ls_pdf;
-							}
-							// the reference traces the shadow ray before it looks at the pdf (:170-179)
-							want = true;
-						}
-					}
-					else
-					{
-						r_tmin = ra.rp.min_raydist_auto ? ra.ray_min_dist * smax(1.f, length(sp.p)) : ra.ray_min_dist;
-						float W = 0.f;
-						BsdfSample bs; bs.s_1 = s_1; bs.s_2 = s_2; bs.pdf = 0.f; bs.flags = kMisFlags; bs.sampled = kNone;
-						const Col surf_col = mat_sample(mat, dat, sp, wo, r_dir, bs, W);
-						float light_ipdf;
-						if(bs.pdf > 1e-6f && arealight_intersect(light, sp.p, r_dir, r_tmax, light_ipdf))
-						{
-							if(light_ipdf > 1e-6f)
-							{
-								const float l_pdf = 1.f / light_ipdf;
-								const float l_2 = l_pdf * l_pdf, m_2 = bs.pdf * bs.pdf;
-								const float w = m_2 / (l_2 + m_2);
-								contrib = ((surf_col * col3(light.color)) * w) * W;
-							}
-							want = true;
-						}
-					}
-				}
-				if(want)
-				{
-					bool shadowed = false;
-					if(cast_shadows)
-					{	// Scene::isShadowed, scene.cc:962-994
-						const V3 sfrom = sp.p + r_dir * r_tmin;
-						const float dis = (r_tmax < 0.f) ? INFINITY : r_tmax - 2.f * r_tmin;
-						int ti; float tt, uu, vv;
-						++cn.shadow;
-						shadowed = kd_trace<true, kStats>(sc, stk, sfrom, r_dir, 0.f, dis, ti, tt, uu, vv, cn);
-					}
-					if(!shadowed)
-					{
-						if(dirac) col_dirac = col_dirac + contrib;
-						else if(phase == 0) ccol = ccol + contrib;
-						else ccol_2 = ccol_2 + contrib;
-					}
-				}
-			}
-		}
-		Col col = mkc(0.f, 0.f, 0.f);
-		if(dirac) col = col + col_dirac;
-		else { col = col + ccol * inv_ns; col = col + ccol_2 * inv_ns; }
-		total = total + col;
-	}
-	return total;
-}
-
-// ------------------------------------------------------------------------------------------------
-// PathIntegrator::integrate, integrator_path_tracer.cc:112-347, as a per-lane state machine.
-// Supported lobes: diffuse/translucent shinydiffuse, glossy(as_diffuse), light_mat — the host
-// rejects materials that would need recursiveRaytrace (integrator_montecarlo.cc:782-1028).
+// stage of PathIntegrator::integrate (integrator_path_tracer.cc:112-347) a path's closest-hit query belongs to:
+// the camera ray, a path sample's first segment from the camera hit, a later segment
 enum : int { kStPrimary = 0, kStFirst = 1, kStDepth = 2 };
 
-template<bool kStats>
-YG_DEV void integrate(const RenderArgs &ra, LaneStack &stk, V3 from, V3 dir, float tmin, float tmax,
-                      uint32_t pixel_sample, uint32_t sampling_offs, uint32_t sample_ordinal, float out[4], LaneCounters &cn)
-{
-	const DevScene &sc = ra.sc;
-	const yafgpu_render_params &rp = ra.rp;
-	Col col = mkc(0.f, 0.f, 0.f);
-	float alpha = rp.bg_transp ? 0.f : 1.f;
-
-	int stage = kStPrimary;
-	SurfPt sp0, hit;                   // camera hit, current path vertex
-	BsdfDat dat0, dat_n;
-	V3 wo0 = mk(0.f, 0.f, 0.f), pwo = mk(0.f, 0.f, 0.f);
-	int mat0 = 0;
-	uint32_t bsdfs0 = 0u;
-	Col path_col = mkc(0.f, 0.f, 0.f), throughput = mkc(1.f, 1.f, 1.f);
-	int path_i = 0, depth = 0;
-	float last_w = 0.f;          // integrate()'s `w`: Material::sample may leave it untouched (see st_extend)
-	const int n_paths = rp.path_samples > 1 ? rp.path_samples : 1;
-	uint32_t offs = 0u;
-	uint32_t sampled_flags = kNone;
-	uint32_t one_light_calls = 0u;
-	Mwc rr; rr.init(fnv32a(sample_ordinal) + 123u);   // see DESIGN.md: Russian-roulette stream (row N4)
-
-	V3 r_from = from, r_dir = dir;
-	float r_tmin = tmin, r_tmax = tmax;
-	bool running = true;
-	while(running)
-	{
-		// ---- the one closest-hit trace site: Scene::intersect, scene.cc:896-927
-		int ti = -1; float z = 0.f, bu = 0.f, bv = 0.f;
-		const float dis = (r_tmax < 0.f) ? INFINITY : r_tmax;
-		++cn.closest;
-		const bool got = kd_trace<false, kStats>(sc, stk, r_from, r_dir, r_tmin, dis, ti, z, bu, bv, cn);
-		bool start_path = false;     // begin path sample `path_i` from the camera hit
-		bool extend = false;         // sample the current vertex and continue the path
-		if(stage == kStPrimary)
-		{
-			if(!got)
-			{
-				if(rp.has_background && !rp.bg_transp_refract) col = col + mkc(rp.background[0], rp.background[1], rp.background[2]);
-				break;
-			}
-			get_surface(sc, ti, r_from + r_dir * z, bu, bv, sp0);
-			const yafgpu_material &m = sc.mats[sp0.mat];
-			mat0 = sp0.mat;
-			bsdfs0 = mat_init_bsdf(m, dat0);
-			wo0 = -r_dir;
-			if(bsdfs0 & kEmit) col = col + mat_emit(m, sp0, wo0, true);                     // :152, include_lights_ = true (:133)
-			if(bsdfs0 & kDiffuse) col = col + direct_light<kStats>(ra, stk, sp0, m, dat0, wo0, 0, sc.n_lights, pixel_sample, sampling_offs, cn); // :156
-			alpha = 1.f;
-			if(rp.bg_transp_refract)
-			{
-				const float m_alpha = mat_alpha(m, dat0, sp0, wo0);
-				alpha = m_alpha + (1.f - m_alpha) * (rp.bg_transp ? 0.f : 1.f);
-			}
-			const uint32_t path_flags = rp.no_recursive ? (uint32_t)kAll : (uint32_t)kDiffuse;
-			if(rp.integrator != YAFGPU_INTEGRATOR_PATH || !(bsdfs0 & path_flags)) break;
-			path_i = 0;
-			start_path = true;
-		}
-		else if(stage == kStFirst)
-		{
-			if(!got) { ++path_i; start_path = true; }                                        // :218 `continue`
-			else
-			{
-				get_surface(sc, ti, r_from + r_dir * z, bu, bv, hit);
-				const yafgpu_material &pm = sc.mats[hit.mat];
-				const uint32_t mb = mat_init_bsdf(pm, dat_n);
-				if(sampled_flags != kNone) pwo = -r_dir;                                      // :224
-				Col lcol = mkc(0.f, 0.f, 0.f);
-				if(sc.n_lights > 0)
-				{	// estimateOneDirectLight, integrator_montecarlo.cc:62-76
-					int lnum = 0;
-					if(sc.n_lights > 1)
-					{
-						Halton h2; h2.init(2u);
-						h2.set_start(rp.base_sampling_offset + (sample_ordinal * 16u + one_light_calls) - 1u);
-						lnum = min((int)(h2.next() * (float)sc.n_lights), sc.n_lights - 1);
-					}
-					++one_light_calls;
-					lcol = direct_light<kStats>(ra, stk, hit, pm, dat_n, pwo, lnum, lnum + 1, pixel_sample, sampling_offs, cn) * (float)sc.n_lights;
-				}
-				if(mb & kEmit) lcol = lcol + mat_emit(pm, hit, pwo, false);                   // :226
-				path_col = path_col + lcol * throughput;                                       // :228
-				depth = 1;
-				if(depth < rp.bounces) extend = true;
-				else { ++path_i; start_path = true; }
-			}
-		}
-		else
-		{
-			if(!got) { ++path_i; start_path = true; }                                        // :259-266 `break`
-			else
-			{
-				get_surface(sc, ti, r_from + r_dir * z, bu, bv, hit);
-				const yafgpu_material &pm = sc.mats[hit.mat];
-				const uint32_t mb = mat_init_bsdf(pm, dat_n);
-				pwo = -r_dir;                                                                  // :271
-				Col lcol = mkc(0.f, 0.f, 0.f);
-				if((mb & kDiffuse) && sc.n_lights > 0)
-				{
-					int lnum = 0;
-					if(sc.n_lights > 1)
-					{
-						Halton h2; h2.init(2u);
-						h2.set_start(rp.base_sampling_offset + (sample_ordinal * 16u + one_light_calls) - 1u);
-						lnum = min((int)(h2.next() * (float)sc.n_lights), sc.n_lights - 1);
-					}
-					++one_light_calls;
-					lcol = direct_light<kStats>(ra, stk, hit, pm, dat_n, pwo, lnum, lnum + 1, pixel_sample, sampling_offs, cn) * (float)sc.n_lights;
-				}
-				bool alive = true;
-				if(depth > rp.rr_min_bounces)
-				{	// Russian roulette :282-288
-					const float random_value = (float)rr.next();
-					const float probability = smax(throughput.r, smax(throughput.g, throughput.b));
-					if(probability <= 0.f || probability < random_value) alive = false;
-					else throughput = throughput * (1.f / probability);
-				}
-				if(alive)
-				{
-					path_col = path_col + lcol * throughput;                                   // :292
-					++depth;
-					if(depth < rp.bounces) extend = true;
-					else { ++path_i; start_path = true; }
-				}
-				else { ++path_i; start_path = true; }
-			}
-		}
-
-		if(extend)
-		{
-			// next segment from the current vertex, :232-257
-			const yafgpu_material &pm = sc.mats[hit.mat];
-			const int d_4 = 4 * depth;
-			BsdfSample bs;
-			bs.s_1 = (float)scr_halton(sc, d_4 + 3, offs);
-			bs.s_2 = (float)scr_halton(sc, d_4 + 4, offs);
-			bs.pdf = 0.f; bs.sampled = kNone; bs.flags = kAll;
-			float w = last_w;
-			V3 p_dir = r_dir;
-			const Col scol = mat_sample(pm, dat_n, hit, pwo, p_dir, bs, w) * w;
-			last_w = w;
-			if(is_black(scol)) { ++path_i; start_path = true; }                               // :249 `break`
-			else
-			{
-				throughput = throughput * scol;
-				r_from = hit.p; r_dir = p_dir; r_tmin = ra.ray_min_dist; r_tmax = -1.f;
-				stage = kStDepth;
-			}
-		}
-		if(start_path)
-		{
-			if(path_i >= n_paths) { col = col + path_col / (float)n_paths; break; }           // :297
-			// first segment from the camera hit, :186-216
-			const yafgpu_material &m = sc.mats[mat0];
-			offs = (uint32_t)rp.path_samples * pixel_sample + sampling_offs + (uint32_t)path_i;
-			BsdfSample bs;
-			bs.s_1 = ri_vdc(offs, 0u);
-			bs.s_2 = (float)scr_halton(sc, 2, offs);
-			bs.pdf = 0.f; bs.sampled = kNone;
-			bs.flags = (rp.no_recursive ? (uint32_t)kAll : (uint32_t)kDiffuse) | kDiffuse | kReflect | kTransmit;
-			float w = last_w;
-			V3 p_dir = mk(0.f, 0.f, 0.f);
-			pwo = wo0;
-			const Col scol = mat_sample(m, dat0, sp0, pwo, p_dir, bs, w) * w;
-			last_w = w;
-			throughput = scol;
-			sampled_flags = bs.sampled;
-			r_from = sp0.p; r_dir = p_dir; r_tmin = ra.ray_min_dist; r_tmax = -1.f;
-			stage = kStFirst;
-		}
-	}
-	// EmptyVolumeIntegrator (integrator_empty_volume.cc:32-38): transmittance 1, in-scatter 0
-	if(rp.bg_transp) alpha = smax(alpha, 0.f);
-	out[0] = col.r; out[1] = col.g; out[2] = col.b; out[3] = alpha;
-}
-
 YG_DEV int round2int(double v) { return (int)(v + (.5 - 1.4e-11)); } // util_math.h:34-43
-
-YG_DEV uint32_t read_xcc_id()
-{
-	uint32_t v;
-	asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(v));
-	return v & 7u;
-}
-
-template<typename T> YG_DEV T wave_bcast(T v, int src) { return __shfl(v, src, kWave); }
 
 YG_DEV uint32_t wave_sum(uint32_t v)
 {
@@ -718,134 +317,6 @@ YG_DEV uint32_t wave_sum(uint32_t v)
 	for(int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
 	return v;
 }
-
-#ifndef YAFGPU_VARIANT_TU      // the one-kernel pipeline belongs to the main unit
-// ------------------------------------------------------------------------------------------------
-// The render pass: TiledIntegrator::renderTile (integrator_tiled.cc:309-521) for every tile of the
-// shard + ImageFilm::addSample (imagefilm.cc:925-1015) for the box filter of width <= 1.002 px
-// (filterw = 0.501 after the clamp at :165): a sample lands on its own pixel and, when dx (dy)
-// >= 0.999, also on the right (lower) neighbour, weight 1 each.
-template<bool kStats>
-__global__ __launch_bounds__(kBlock, YAFGPU_WAVES) void render_kernel(const RenderArgs ra)
-{
-	__shared__ uint2 s_stack[kWavesPerBlock][kStack][kWave];
-	const int lane = (int)(threadIdx.x & (kWave - 1)), wave = (int)(threadIdx.x >> 6);
-	LaneStack stk;
-	stk.col = &s_stack[wave][0][lane];
-	LaneCounters cn = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
-	const yafgpu_render_params &rp = ra.rp;
-	const int L = ra.lanes_per_pixel, P = ra.pixels_per_wave;
-	const int group = lane / L, lane_in_pixel = lane - group * L;
-	const int n_samples = rp.aa_minsamples;
-	const float d_1 = (float)(1.0 / (double)(float)n_samples);    // integrator_tiled.cc:316
-	const int cx0 = rp.xstart, cy0 = rp.ystart, cx1 = rp.xstart + rp.width, cy1 = rp.ystart + rp.height;
-	const size_t plane_stride = (size_t)rp.width * (size_t)rp.height * YAFGPU_FILM_CHANNELS;
-	const uint32_t my_queue = read_xcc_id();
-
-	for(int qi = 0; qi < kQueues; ++qi)
-	{
-		const uint32_t q = (my_queue + (uint32_t)qi) & (kQueues - 1);
-		const uint32_t q_begin = ra.queue_begin[q], q_end = ra.queue_begin[q + 1];
-		for(;;)
-		{
-			uint32_t u = 0u;
-			if(lane == 0) u = atomicAdd(&ra.queue_next[q * 32u], 1u);
-			u = (uint32_t)__builtin_amdgcn_readfirstlane((int)u) + q_begin;
-			if(u >= q_end) break;
-			// tile of this unit (wave-uniform binary search over the prefix sums)
-			int lo = 0, hi = ra.n_tiles;
-			while(hi - lo > 1) { const int mid = (lo + hi) >> 1; if(ra.unit_prefix[mid] <= u) lo = mid; else hi = mid; }
-			const int4 rect = ra.tile_rect[lo];
-			const int k = (int)(u - ra.unit_prefix[lo]);
-			const int qpix = k * P + group;
-			const bool pix_ok = (group < P) && (qpix < rect.z * rect.w);
-			const int px = rect.x + (pix_ok ? qpix % rect.z : 0), py = rect.y + (pix_ok ? qpix / rect.z : 0);
-			const uint32_t sampling_offs = fnv32a((uint32_t)py * fnv32a((uint32_t)px));       // :379
-			float acc[YAFGPU_FILM_PLANES][YAFGPU_FILM_CHANNELS];
-#pragma unroll
-			for(int a = 0; a < YAFGPU_FILM_PLANES; ++a)
-#pragma unroll
-				for(int c = 0; c < YAFGPU_FILM_CHANNELS; ++c) acc[a][c] = 0.f;
-
-			for(int it = 0; it < ra.iters; ++it)
-			{
-				const int sample = it * L + lane_in_pixel;
-				const bool active = pix_ok && sample < n_samples;
-				float c4[4] = {0.f, 0.f, 0.f, 0.f};
-				uint32_t flag = 0u;
-				if(active)
-				{
-					float dx = 0.5f, dy = 0.5f;
-					if(n_samples > 1)
-					{	// :399-403 (single pass)
-						dx = (float)((0.5 + (double)(float)sample) * (double)d_1);
-						dy = ri_lp((uint32_t)sample + sampling_offs, 0u);
-					}
-					V3 from, dir; float tmin, tmax;
-					camera_shoot(ra.sc.cam, (float)px + dx, (float)py + dy, from, dir, tmin, tmax);   // :410
-					++cn.samples;
-					const uint32_t pixel_sample = rp.base_sampling_offset + (uint32_t)sample;          // :389
-					const uint32_t ordinal = ((uint32_t)(py - cy0) * (uint32_t)rp.width + (uint32_t)(px - cx0)) * (uint32_t)n_samples + (uint32_t)sample;
-					integrate<kStats>(ra, stk, from, dir, tmin, tmax, pixel_sample, sampling_offs, ordinal, c4, cn);
-					if(c4[3] > 1.f) c4[3] = 1.f;                                                     // :459
-					// footprint, imagefilm.cc:933-936 with filterw = 0.501
-					const int dx_1 = min(cx1 - px - 1, round2int((double)dx + (double)ra.filterw - 1.0));
-					const int dy_1 = min(cy1 - py - 1, round2int((double)dy + (double)ra.filterw - 1.0));
-					flag = 1u | (dx_1 >= 1 ? 2u : 0u) | (dy_1 >= 1 ? 4u : 0u);
-				}
-				// sequential per-pixel sums in sample order; every lane of a group replays its group
-				const int base = group * L;
-				for(int s = 0; s < L; ++s)
-				{
-					const int src = (base + s) & (kWave - 1);
-					const uint32_t f = wave_bcast(flag, src);
-					const float r = wave_bcast(c4[0], src), g = wave_bcast(c4[1], src), b = wave_bcast(c4[2], src), al = wave_bcast(c4[3], src);
-					if(f & 1u)
-					{
-						acc[0][0] += r; acc[0][1] += g; acc[0][2] += b; acc[0][3] += al; acc[0][4] += 1.f;
-						if(f & 2u) { acc[1][0] += r; acc[1][1] += g; acc[1][2] += b; acc[1][3] += al; acc[1][4] += 1.f; }
-						if(f & 4u) { acc[2][0] += r; acc[2][1] += g; acc[2][2] += b; acc[2][3] += al; acc[2][4] += 1.f; }
-						if((f & 6u) == 6u) { acc[3][0] += r; acc[3][1] += g; acc[3][2] += b; acc[3][3] += al; acc[3][4] += 1.f; }
-					}
-				}
-			}
-			if(pix_ok && lane_in_pixel == 0)
-			{
-				const size_t pix = ((size_t)(py - cy0) * (size_t)rp.width + (size_t)(px - cx0)) * YAFGPU_FILM_CHANNELS;
-#pragma unroll
-				for(int a = 0; a < YAFGPU_FILM_PLANES; ++a)
-				{
-					if(a == 0 || acc[a][4] != 0.f)
-					{
-						float *dst = ra.planes + (size_t)a * plane_stride + pix;
-#pragma unroll
-						for(int c = 0; c < YAFGPU_FILM_CHANNELS; ++c) dst[c] = acc[a][c];
-					}
-				}
-			}
-		}
-	}
-	if(ra.counters != nullptr)
-	{
-		const uint32_t v0 = wave_sum(cn.closest), v1 = wave_sum(cn.shadow), v2 = wave_sum(cn.interior), v3 = wave_sum(cn.leaves),
-		               v4 = wave_sum(cn.tests), v5 = wave_sum(cn.samples), v6 = wave_sum(cn.restarts);
-		if(lane == 0)
-		{
-			atomicAdd((unsigned long long *)&ra.counters->rays_closest, (unsigned long long)v0);
-			atomicAdd((unsigned long long *)&ra.counters->rays_shadow, (unsigned long long)v1);
-			atomicAdd((unsigned long long *)&ra.counters->camera_samples, (unsigned long long)v5);
-			if(kStats)
-			{
-				atomicAdd((unsigned long long *)&ra.counters->interior_steps, (unsigned long long)v2);
-				atomicAdd((unsigned long long *)&ra.counters->leaves, (unsigned long long)v3);
-				atomicAdd((unsigned long long *)&ra.counters->tri_tests, (unsigned long long)v4);
-				atomicAdd((unsigned long long *)&ra.counters->restarts, (unsigned long long)v6);
-			}
-		}
-	}
-}
-
-#endif // YAFGPU_VARIANT_TU
 
 } // namespace yafgpu
 #include "yafgpu_wavefront.h"
@@ -868,37 +339,6 @@ __global__ __launch_bounds__(kBlock) void combine_kernel(const float *planes, fl
 			if(y > 0) v += planes[2 * stride + (i - (size_t)w) * YAFGPU_FILM_CHANNELS + c];
 			if(x > 0 && y > 0) v += planes[3 * stride + (i - (size_t)w - 1) * YAFGPU_FILM_CHANNELS + c];
 			film[i * YAFGPU_FILM_CHANNELS + c] = v;
-		}
-	}
-}
-
-// ray batches: Scene::intersect / Scene::isShadowed on arrays (tests and kernel-level measurements)
-template<bool kAny>
-__global__ __launch_bounds__(kBlock) void trace_kernel(const DevScene sc, int n, const float *rays, int *tri, float *t, float *bary, int *shadowed)
-{
-	__shared__ uint2 s_stack[kWavesPerBlock][kStack][kWave];
-	const int lane = (int)(threadIdx.x & (kWave - 1)), wave = (int)(threadIdx.x >> 6);
-	LaneStack stk;
-	stk.col = &s_stack[wave][0][lane];
-	LaneCounters cn = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
-	for(int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < n; i += (int)(gridDim.x * blockDim.x))
-	{
-		const float *r = rays + 8 * (size_t)i;
-		const V3 from = mk(r[0], r[1], r[2]), dir = mk(r[3], r[4], r[5]);
-		const float tmin = r[6], tmax = r[7];
-		int ti = -1; float z = 0.f, bu = 0.f, bv = 0.f;
-		if(kAny)
-		{
-			const V3 sfrom = from + dir * tmin;
-			const float dis = (tmax < 0.f) ? INFINITY : tmax - 2.f * tmin;
-			shadowed[i] = kd_trace<true, false>(sc, stk, sfrom, dir, 0.f, dis, ti, z, bu, bv, cn) ? 1 : 0;
-		}
-		else
-		{
-			const float dis = (tmax < 0.f) ? INFINITY : tmax;
-			const bool h = kd_trace<false, false>(sc, stk, from, dir, tmin, dis, ti, z, bu, bv, cn);
-			tri[i] = h ? ti : -1; t[i] = h ? z : 0.f;
-			bary[3 * i] = h ? 1.f - bu - bv : 0.f; bary[3 * i + 1] = h ? bu : 0.f; bary[3 * i + 2] = h ? bv : 0.f;
 		}
 	}
 }
@@ -1178,10 +618,10 @@ struct yafgpu_scene
 	std::vector<yafgpu_light> h_lights;
 	int n_lights = 0;
 	// per-render scratch, grown on demand
-	int4 *d_tiles = nullptr; uint32_t *d_prefix = nullptr; uint32_t *d_queue = nullptr; size_t tiles_cap = 0;
+	int4 *d_tiles = nullptr; size_t tiles_cap = 0;
 	// the tile list of the last launch stays resident; it is re-uploaded only when its key changes
-	std::vector<int4> h_tiles; std::vector<uint32_t> h_prefix;
-	int tile_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+	std::vector<int4> h_tiles;
+	int tile_key[7] = {-1, -1, -1, -1, -1, -1, -1};
 	// wavefront workspace (allocated on first use, sized for kWfMaxPaths paths or the whole frame)
 	std::vector<uint32_t> h_pix_prefix; uint32_t *d_pix_prefix = nullptr; size_t pix_prefix_cap = 0;
 	float4 *wf_state = nullptr, *wf_results = nullptr; uint32_t *wf_queues = nullptr, *wf_counts = nullptr, *wf_verdict = nullptr, *wf_pix_xy = nullptr; uint32_t wf_cap = 0;
@@ -1531,8 +971,6 @@ void yafgpu_scene_destroy(yafgpu_scene_t *s)
 	if(!s) return;
 	for(void *p : s->allocs) (void)hipFree(p);
 	if(s->d_tiles) (void)hipFree(s->d_tiles);
-	if(s->d_prefix) (void)hipFree(s->d_prefix);
-	if(s->d_queue) (void)hipFree(s->d_queue);
 	if(s->d_pix_prefix) (void)hipFree(s->d_pix_prefix);
 	if(s->wf_state) (void)hipFree(s->wf_state);
 	if(s->wf_results) (void)hipFree(s->wf_results);
@@ -1674,6 +1112,17 @@ static int validate(const yafgpu_scene *s, const yafgpu_render_params *rp)
 
 // ---- wavefront pass -------------------------------------------------------------------------
 static constexpr uint32_t kWfMaxPaths = 32u << 20;   // paths in flight per chunk: 32 Mi x 304 B = 9.5 GiB of parked state
+
+// compute units of the scene's device (s->n_cus), asked once
+static int device_cus(yafgpu_scene *s)
+{
+	if(s->n_cus > 0) return 0;
+	int dev = 0; hipDeviceProp_t prop;
+	HIP_OK(hipGetDevice(&dev));
+	HIP_OK(hipGetDeviceProperties(&prop, dev));
+	s->n_cus = prop.multiProcessorCount;
+	return 0;
+}
 
 static int wf_grid(const void *kernel, int cus)
 {
@@ -1826,7 +1275,7 @@ static int render_wavefront(yafgpu_scene *s, RenderArgs &ra, hipStream_t caller,
 	hipStream_t stream = caller;
 	const yafgpu_render_params &rp = ra.rp;
 	const uint32_t spp = (uint32_t)rp.aa_minsamples;
-	// per-tile pixel prefix (same tile list as the unit prefix)
+	// per-tile pixel prefix of the shard's tile list
 	std::vector<uint32_t> &pp = s->h_pix_prefix;
 	pp.assign(1, 0u);
 	for(const int4 &r : s->h_tiles) pp.push_back(pp.back() + (uint32_t)(r.z * r.w));
@@ -1863,7 +1312,7 @@ static int render_wavefront(yafgpu_scene *s, RenderArgs &ra, hipStream_t caller,
 		uint32_t mp = kWfMaxPaths;
 		if(const char *e = std::getenv("YAFGPU_WF_CHUNK")) mp = std::max(256u, (uint32_t)std::strtoul(e, nullptr, 10));
 		const ReplayPlan pl = replay_plan(s, rp);
-		pass_piped = want && !masked && !stats && !s->profiling && !pl.replay && pl.frames == 0 && (uint64_t)n_pixels_total * spp <= mp && !std::getenv("YAFGPU_CHUNK_PIPELINE");
+		pass_piped = want && !masked && !stats && !s->profiling && !pl.replay && pl.frames == 0 && (uint64_t)n_pixels_total * spp <= mp;
 		if(pass_piped)
 		{
 			int depth = 2;      // (a third pass in flight adds nothing: two chains already keep a launch beside every tail, profiles/r03_ab_pipeline.txt)
@@ -2051,14 +1500,8 @@ static int render_wavefront(yafgpu_scene *s, RenderArgs &ra, hipStream_t caller,
 		HIP_OK(hipMalloc((void **)&s->wf_filt, (size_t)2 * s->wf_cap * sizeof(float4)));
 		s->wf_filt_cap = s->wf_cap;
 	}
-	if(!s->wf_counts) HIP_OK(hipMalloc((void **)&s->wf_counts, 128 * sizeof(uint32_t)));      // two sets of 2 x 32 (chunk pipelining)
-	if(s->n_cus <= 0)
-	{
-		int dev = 0; hipDeviceProp_t prop;
-		HIP_OK(hipGetDevice(&dev));
-		HIP_OK(hipGetDeviceProperties(&prop, dev));
-		s->n_cus = prop.multiProcessorCount;
-	}
+	if(!s->wf_counts) HIP_OK(hipMalloc((void **)&s->wf_counts, 64 * sizeof(uint32_t)));      // two sets of 32 (in / out)
+	if(const int e = device_cus(s)) return e;
 	const int cus = s->n_cus;
 	const int g_trace_c = stats ? wf_grid((const void *)wf_trace<false, true>, cus) : wf_grid((const void *)wf_trace<false, false>, cus);
 	const int g_trace_s = stats ? wf_grid((const void *)wf_trace<true, true>, cus) : wf_grid((const void *)wf_trace<true, false>, cus);
@@ -2293,102 +1736,6 @@ static int render_wavefront(yafgpu_scene *s, RenderArgs &ra, hipStream_t caller,
 		return 0;
 	};
 	int rc = 0;
-	// Chunk pipelining.  The launches of a pass form a chain (trace -> shade -> trace ...), and a persistent traversal launch ends in a
-	// tail as long as one ray's walk (~0.3 ms at 1 M triangles) during which the GPU drains: four exposed tails per pass, 5 % of the
-	// metric pass and a third of an eighth-of-the-frame shard's.  Two halves of the pass's pixels, each with its own state, queues
-	// and stream, run the same chain side by side: one's tail is filled by the other's launches.  The film planes are added to by
-	// one accumulate launch at a time, after both.  (Not with the serial-state replay, recursion polling, a resample mask or per-kernel
-	// profiling, which keep the sequential path below.)
-	// MEASURED, OFF (opt in with YAFGPU_CHUNK_PIPELINE=1): the two streams' persistent launches mostly take turns instead of filling
-	// each other's tails, and every half pays the full tail — 25.5 / 13.8 / 8.0 / 5.5 ms per pass at 1, 1/2, 1/4, 1/8 of the metric frame
-	// against 25.5 / 13.9 / 7.9 / 4.75 ms with the closest-hit / any-hit overlap alone.
-	bool pipelined = false;
-	if(const char *e = std::getenv("YAFGPU_CHUNK_PIPELINE"))
-		pipelined = std::atoi(e) != 0 && !replay && frames == 0 && !masked && !s->profiling && !stats && (uint64_t)n_pixels_total * spp >= (1u << 16);
-	if(pipelined)
-	{
-		if(!s->side_stream)
-		{
-			HIP_OK(hipStreamCreateWithFlags(&s->side_stream, hipStreamNonBlocking));
-			HIP_OK(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-			HIP_OK(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
-		}
-		struct Ctx { WfArgs a; uint32_t *qset[2][3]; uint32_t *cnt[2]; hipStream_t st; uint32_t g_gen; int cur; };
-		// halves of every chunk, two at a time (a chunk already fits the allocated capacity: its halves fit side by side)
-		for(const Chunk &ch : chunks)
-		{
-			if(s->aborted()) return fail(-30, "aborted");
-			const uint32_t px_a = (ch.n_pixels + 1u) / 2u, px_b = ch.n_pixels - px_a;
-			Ctx cx[2];
-			const int n_ctx = px_b > 0 ? 2 : 1;
-			size_t slot_off = 0;
-			for(int k = 0; k < n_ctx; ++k)
-			{
-				Ctx &c = cx[k];
-				const uint32_t px = k == 0 ? px_a : px_b, px_begin = ch.pixel_begin + (k == 0 ? 0u : px_a);
-				const size_t np = (size_t)px * spp;
-				c.a = WfArgs{};
-				c.a.ra = ra;
-				c.a.state = s->wf_state + slot_off; c.a.cap = s->wf_cap; c.a.results = s->wf_results + slot_off;
-				c.a.frames = 0; c.a.frame_recs = frame_recs; c.a.has_glossy = s->has_glossy ? 1 : 0;
-				c.a.pixel_begin = px_begin; c.a.n_pixels = px; c.a.n_paths = (uint32_t)np;
-				c.a.pix_prefix = s->d_pix_prefix; c.a.pix_xy = s->wf_pix_xy + (k == 0 ? 0u : px_a); c.a.pix_listed = 0;
-				c.a.ev_m = 1;
-				uint32_t *qb = s->wf_queues + 12 * slot_off;
-				c.qset[0][0] = qb; c.qset[0][1] = qb + np; c.qset[0][2] = qb + 5 * np;
-				c.qset[1][0] = qb + 6 * np; c.qset[1][1] = qb + 7 * np; c.qset[1][2] = qb + 11 * np;
-				c.cnt[0] = s->wf_counts + 64 * k; c.cnt[1] = s->wf_counts + 64 * k + 32;
-				c.a.verdict = s->wf_verdict + (4 * slot_off + 31) / 32 + (k ? 1 : 0);
-				c.a.shadow_filt = transp ? s->wf_filt + 2 * slot_off : nullptr;
-				c.st = k == 0 ? stream : s->side_stream;
-				c.g_gen = std::min<uint32_t>((uint32_t)((np + kBlock - 1) / kBlock), (uint32_t)cus * 8u);
-				c.cur = 0;
-				slot_off += np;
-			}
-			// fork: what the caller's stream holds so far (the previous pass, the prefix upload) precedes both halves
-			HIP_OK(hipEventRecord(s->ev_fork, stream));
-			HIP_OK(hipStreamWaitEvent(s->side_stream, s->ev_fork, 0));
-			for(int k = 0; k < n_ctx; ++k)
-			{
-				Ctx &c = cx[k];
-				c.a.cnt_in = c.cnt[0]; c.a.cnt_out = c.cnt[1];
-				c.a.q_closest_in = nullptr; c.a.q_shadow_in = c.qset[0][1]; c.a.q_resume_in = c.qset[0][2];
-				c.a.q_closest_out = c.qset[1][0]; c.a.q_shadow_out = c.qset[1][1]; c.a.q_resume_out = c.qset[1][2];
-				hipLaunchKernelGGL(wf_generate, dim3(c.g_gen), dim3(kBlock), 0, c.st, c.a);
-			}
-			HIP_OK(hipGetLastError());
-			for(int it = 0; it < iters; ++it)
-				for(int k = 0; k < n_ctx; ++k)
-				{
-					Ctx &c = cx[k];
-					HIP_OK(hipMemsetAsync(c.a.cnt_out, 0, 8 * sizeof(uint32_t), c.st));
-					hipLaunchKernelGGL((wf_trace<false, false>), dim3(g_trace_c), dim3(kBlock), 0, c.st, c.a);
-					if(it > 0)
-					{
-						HIP_OK(hipMemsetAsync(c.a.verdict, 0, ((size_t)4 * c.a.n_paths + 31) / 32 * sizeof(uint32_t), c.st));
-						if(transp) hipLaunchKernelGGL(wf_trace_ts, dim3(cus * 8), dim3(kBlock), 0, c.st, c.a);
-						else hipLaunchKernelGGL((wf_trace<true, false>), dim3(g_trace_s), dim3(kBlock), 0, c.st, c.a);
-					}
-					if(shade_variant) { if(shade_variant->launch(&c.a, sizeof c.a, g_shade, c.st)) return fail(-21, "shading kernel variant and main unit disagree on the argument layout"); }
-					else hipLaunchKernelGGL(wf_shade, dim3(g_shade), dim3(kBlock), 0, c.st, c.a);
-					HIP_OK(hipGetLastError());
-					c.cur ^= 1;
-					c.a.cnt_in = c.cnt[c.cur]; c.a.cnt_out = c.cnt[c.cur ^ 1];
-					c.a.q_closest_in = c.qset[c.cur][0]; c.a.q_shadow_in = c.qset[c.cur][1]; c.a.q_resume_in = c.qset[c.cur][2];
-					c.a.q_closest_out = c.qset[c.cur ^ 1][0]; c.a.q_shadow_out = c.qset[c.cur ^ 1][1]; c.a.q_resume_out = c.qset[c.cur ^ 1][2];
-				}
-			// join, then the film: one accumulate launch at a time
-			HIP_OK(hipEventRecord(s->ev_join, s->side_stream));
-			HIP_OK(hipStreamWaitEvent(stream, s->ev_join, 0));
-			for(int k = 0; k < n_ctx; ++k)
-			{
-				const uint32_t g_acc = std::min<uint32_t>((cx[k].a.n_pixels + kBlock - 1) / kBlock, (uint32_t)cus * 8u);
-				hipLaunchKernelGGL(wf_accumulate, dim3(g_acc), dim3(kBlock), 0, stream, cx[k].a);
-			}
-			HIP_OK(hipGetLastError());
-		}
-		return 0;
-	}
 	if(lc_sharded)
 	{
 		size_t seg_off = 0;
@@ -2442,19 +1789,14 @@ int yafgpu_render_tiles(yafgpu_scene_t *s, const yafgpu_render_params *rp, float
 			ra.filter_table = s->d_filter_table;
 		}
 	}
-	const int spp = rp->aa_minsamples;
-	ra.lanes_per_pixel = std::min(spp, kWave);
-	ra.pixels_per_wave = kWave / ra.lanes_per_pixel;
-	ra.iters = (spp + ra.lanes_per_pixel - 1) / ra.lanes_per_pixel;
 	// tiles of this shard, row-major (ImageSplitter linear order, imagesplitter.cc:30-60)
-	const int key[8] = {rp->width, rp->height, rp->xstart, rp->ystart, rp->tile_size, rp->shard_index, rp->shard_count, ra.pixels_per_wave};
+	const int key[7] = {rp->width, rp->height, rp->xstart, rp->ystart, rp->tile_size, rp->shard_index, rp->shard_count};
 	const bool same = std::memcmp(key, s->tile_key, sizeof key) == 0;
 	if(!same)
 	{
 		const int ntx = (rp->width + rp->tile_size - 1) / rp->tile_size, nty = (rp->height + rp->tile_size - 1) / rp->tile_size;
-		std::vector<int4> &tiles = s->h_tiles; std::vector<uint32_t> &prefix = s->h_prefix;
-		tiles.clear(); prefix.clear();
-		prefix.push_back(0u);
+		std::vector<int4> &tiles = s->h_tiles;
+		tiles.clear();
 		for(int t = 0; t < ntx * nty; ++t)
 		{
 			if(t % rp->shard_count != rp->shard_index) continue;
@@ -2463,72 +1805,30 @@ int yafgpu_render_tiles(yafgpu_scene_t *s, const yafgpu_render_params *rp, float
 			r.x = rp->xstart + tx * rp->tile_size; r.y = rp->ystart + ty * rp->tile_size;
 			r.z = std::min(rp->tile_size, rp->xstart + rp->width - r.x); r.w = std::min(rp->tile_size, rp->ystart + rp->height - r.y);
 			tiles.push_back(r);
-			const uint32_t units = (uint32_t)((r.z * r.w + ra.pixels_per_wave - 1) / ra.pixels_per_wave);
-			prefix.push_back(prefix.back() + units);
 		}
 	}
 	ra.n_tiles = (int)s->h_tiles.size();
-	ra.n_units = s->h_prefix.back();
 	if(!rp->accumulate) HIP_OK(hipMemsetAsync(d_planes, 0, yafgpu_planes_bytes(rp->width, rp->height), stream));
-	if(ra.n_tiles == 0)
-	{	// a rank without tiles still owes the others its (empty) share of the light-counter exchange
-		const char *pl = std::getenv("YAFGPU_PIPELINE");
-		const bool mega = pl && std::strcmp(pl, "megakernel") == 0;
-		return (!mega && replay_plan(s, *rp).lc_sharded) ? lc_exchange_counts(s, *rp, {}, nullptr) : 0;
-	}
-	if(!s->d_queue) HIP_OK(hipMalloc((void **)&s->d_queue, kQueues * 32 * sizeof(uint32_t)));
+	if(ra.n_tiles == 0)      // a rank without tiles still owes the others its (empty) share of the light-counter exchange
+		return replay_plan(s, *rp).lc_sharded ? lc_exchange_counts(s, *rp, {}, nullptr) : 0;
 	if(!same)
 	{
 		if(s->h_tiles.size() > s->tiles_cap)
 		{
 			HIP_OK(hipStreamSynchronize(stream));      // the previous pass may still read the old arrays
 			if(s->d_tiles) (void)hipFree(s->d_tiles);
-			if(s->d_prefix) (void)hipFree(s->d_prefix);
 			s->tiles_cap = s->h_tiles.size();
 			HIP_OK(hipMalloc((void **)&s->d_tiles, s->tiles_cap * sizeof(int4)));
-			HIP_OK(hipMalloc((void **)&s->d_prefix, (s->tiles_cap + 1) * sizeof(uint32_t)));
 		}
 		HIP_OK(hipMemcpyAsync(s->d_tiles, s->h_tiles.data(), s->h_tiles.size() * sizeof(int4), hipMemcpyHostToDevice, stream));
-		HIP_OK(hipMemcpyAsync(s->d_prefix, s->h_prefix.data(), s->h_prefix.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
 		std::memcpy(s->tile_key, key, sizeof key);
 		s->pipe_prev = false;      // (pipelined passes: the new tile arrays precede the internal streams' next launches)
 	}
-	HIP_OK(hipMemsetAsync(s->d_queue, 0, kQueues * 32 * sizeof(uint32_t), stream));
-	ra.tile_rect = s->d_tiles; ra.unit_prefix = s->d_prefix; ra.queue_next = s->d_queue;
-	for(int q = 0; q <= kQueues; ++q) ra.queue_begin[q] = (uint32_t)(((uint64_t)ra.n_units * (uint64_t)q) / kQueues);
+	ra.tile_rect = s->d_tiles;
 	ra.planes = d_planes;
 	ra.counters = d_counters;
 	const bool stats = d_counters != nullptr && std::getenv("YAFGPU_STATS") != nullptr;
-	{
-		const char *pl = std::getenv("YAFGPU_PIPELINE");
-		const bool mega = pl && std::strcmp(pl, "megakernel") == 0;
-		if(!mega) return render_wavefront(s, ra, stream, stats);
-		if(ra.wide_filter) return fail(-15, "the one-kernel pipeline implements the box filter of width <= 1.002 only; use the wavefront pipeline");
-		if(s->dev.cam.aperture != 0.f) return fail(-15, "the one-kernel pipeline has the pinhole camera only; use the wavefront pipeline");
-		// transpShad changes which hits occlude even without a transparent material (intersectTs skips hits before tmin_)
-		if(rp->transp_shad) return fail(-15, "the one-kernel pipeline has no transparent shadows (transpShad); use the wavefront pipeline");
-		if((s->has_specular || s->has_glossy) && rp->raydepth + s->max_add_depth > 0) return fail(-15, "the one-kernel pipeline has no recursiveRaytrace; use the wavefront pipeline for mirror / transparent / glossy-recursive materials");
-		if(s->has_textures) return fail(-15, "the one-kernel pipeline has no shader nodes / textures; use the wavefront pipeline");
-		if(s->light_mask & ~((1u << YAFGPU_LIGHT_AREA) | (1u << YAFGPU_LIGHT_POINT)))
-			return fail(-15, "the one-kernel pipeline has area and point lights only (no directional, sun or sphere lights); use the wavefront pipeline");
-		if(rp->trace_caustics && (s->has_specular || s->has_glossy)) return fail(-15, "the one-kernel pipeline has no path caustics (caustic_type path with specular / glossy lobes); use the wavefront pipeline");
-		if(rp->serial_replay && rp->integrator == YAFGPU_INTEGRATOR_PATH && (rp->bounces - 1 > rp->rr_min_bounces || s->n_lights > 1))
-			return fail(-15, "the one-kernel pipeline cannot replay the reference's serial state (Russian roulette stream, light counter); use the wavefront pipeline or switch the replay off");
-		if(rp->multi_pass || rp->accumulate || rp->resample_mask || rp->aa_clamp_samples != 0.f || rp->pass_offset != 0u)
-			return fail(-15, "the one-kernel pipeline renders single-pass films only; use the wavefront pipeline");
-	}
-	int dev = 0; hipDeviceProp_t prop;
-	HIP_OK(hipGetDevice(&dev));
-	HIP_OK(hipGetDeviceProperties(&prop, dev));
-	int blocks_per_cu = 0;
-	HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, render_kernel<false>, kBlock, 0));
-	blocks_per_cu = std::max(1, std::min(blocks_per_cu, 8));
-	const uint32_t want = (ra.n_units + kWavesPerBlock - 1) / kWavesPerBlock;
-	const uint32_t grid = std::max(1u, std::min(want, (uint32_t)(prop.multiProcessorCount * blocks_per_cu)));
-	if(stats) hipLaunchKernelGGL(render_kernel<true>, dim3(grid), dim3(kBlock), 0, stream, ra);
-	else hipLaunchKernelGGL(render_kernel<false>, dim3(grid), dim3(kBlock), 0, stream, ra);
-	HIP_OK(hipGetLastError());
-	return 0;
+	return render_wavefront(s, ra, stream, stats);
 }
 
 int yafgpu_film_combine(const float *d_planes, float *d_film, int32_t width, int32_t height, void *stream_)
@@ -2839,28 +2139,65 @@ int yafgpu_render_passes_to_host(yafgpu_scene_t *s, const yafgpu_render_params *
 	return rc;
 }
 
+// Ray batches (tests and kernel-level measurements): Scene::intersect / Scene::isShadowed on arrays, answered by the traversal
+// kernel of the wavefront pass.  Ray i is path slot i of a pass without queues (the identity): record 0 holds (from, tmin),
+// record 1 (dir, tmax); a closest hit is answered in record 2, an occluded ray sets verdict bit 4 i.  wf_trace reads the top two
+// bits of a queue entry as tags, so the rays go in chunks of kWfMaxPaths at most.  No counters and no transparent shadows
+// (rp.transp_shad = 0): the any-hit ray is intersectS from 0.
 static int trace_batch(yafgpu_scene_t *s, int32_t n, const float *rays, int32_t *tri, float *t, float *bary, int32_t *shadowed, bool any)
 {
 	if(!s || !rays || n < 0) return fail(-1, "bad argument");
 	if(n == 0) return 0;
-	DevMem<float> d_rays, d_t, d_b; DevMem<int> d_tri, d_sh;
-	HIP_OK(d_rays.alloc((size_t)n * 8));
-	HIP_OK(hipMemcpy(d_rays, rays, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice));
-	HIP_OK(d_tri.alloc((size_t)n));
-	HIP_OK(d_t.alloc((size_t)n));
-	HIP_OK(d_b.alloc((size_t)n * 3));
-	HIP_OK(d_sh.alloc((size_t)n));
-	const uint32_t grid = (uint32_t)std::min((n + kBlock - 1) / kBlock, 4096);
-	if(any) hipLaunchKernelGGL(trace_kernel<true>, dim3(grid), dim3(kBlock), 0, nullptr, s->dev, n, d_rays.p, d_tri.p, d_t.p, d_b.p, d_sh.p);
-	else hipLaunchKernelGGL(trace_kernel<false>, dim3(grid), dim3(kBlock), 0, nullptr, s->dev, n, d_rays.p, d_tri.p, d_t.p, d_b.p, d_sh.p);
-	HIP_OK(hipGetLastError());
-	HIP_OK(hipDeviceSynchronize());
-	if(any) HIP_OK(hipMemcpy(shadowed, d_sh, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-	else
+	int rc = device_cus(s);
+	if(rc) return rc;
+	const uint32_t cap = std::min((uint32_t)n, kWfMaxPaths);
+	DevMem<float4> d_state; DevMem<uint32_t> d_cnt, d_verdict;
+	HIP_OK(d_state.alloc((size_t)3 * cap));
+	HIP_OK(d_cnt.alloc(5));
+	HIP_OK(d_verdict.alloc(((size_t)4 * cap + 31) / 32));
+	std::vector<float4> h((size_t)2 * cap);
+	std::vector<uint32_t> h_verdict;
+	WfArgs a{};
+	a.ra.sc = s->dev;
+	a.state = d_state; a.cap = cap;
+	a.cnt_in = d_cnt; a.verdict = d_verdict;
+	const void *kernel = any ? (const void *)wf_trace<true, false> : (const void *)wf_trace<false, false>;
+	const int grid = wf_grid(kernel, s->n_cus);
+	for(uint32_t o = 0; o < (uint32_t)n; o += cap)
 	{
-		HIP_OK(hipMemcpy(tri, d_tri, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-		HIP_OK(hipMemcpy(t, d_t, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-		HIP_OK(hipMemcpy(bary, d_b, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+		const uint32_t m = std::min(cap, (uint32_t)n - o);
+		for(uint32_t i = 0; i < m; ++i)
+		{
+			const float *r = rays + 8 * (size_t)(o + i);
+			h[i] = make_float4(r[0], r[1], r[2], r[6]);
+			h[cap + i] = make_float4(r[3], r[4], r[5], r[7]);
+		}
+		HIP_OK(hipMemcpy(d_state, h.data(), h.size() * sizeof(float4), hipMemcpyHostToDevice));
+		const uint32_t cnt[5] = {m, m, 0u, 0u, 0u};
+		HIP_OK(hipMemcpy(d_cnt, cnt, sizeof cnt, hipMemcpyHostToDevice));
+		const size_t words = ((size_t)4 * m + 31) / 32;
+		if(any) HIP_OK(hipMemset(d_verdict, 0, words * sizeof(uint32_t)));
+		if(any) hipLaunchKernelGGL((wf_trace<true, false>), dim3(grid), dim3(kBlock), 0, nullptr, a);
+		else hipLaunchKernelGGL((wf_trace<false, false>), dim3(grid), dim3(kBlock), 0, nullptr, a);
+		HIP_OK(hipGetLastError());
+		HIP_OK(hipDeviceSynchronize());
+		if(any)
+		{
+			h_verdict.resize(words);
+			HIP_OK(hipMemcpy(h_verdict.data(), d_verdict, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+			for(uint32_t i = 0; i < m; ++i) shadowed[o + i] = (int32_t)((h_verdict[i >> 3] >> (4u * (i & 7u))) & 1u);
+			continue;
+		}
+		HIP_OK(hipMemcpy(h.data(), d_state + (size_t)2 * cap, m * sizeof(float4), hipMemcpyDeviceToHost));
+		for(uint32_t i = 0; i < m; ++i)
+		{	// (tri, t, u, v); tri -1: a miss
+			const float4 ans = h[i];
+			int32_t ti; std::memcpy(&ti, &ans.x, sizeof ti);
+			const bool hit = ti >= 0;
+			const size_t k = o + i;
+			tri[k] = hit ? ti : -1; t[k] = hit ? ans.y : 0.f;
+			bary[3 * k] = hit ? 1.f - ans.z - ans.w : 0.f; bary[3 * k + 1] = hit ? ans.z : 0.f; bary[3 * k + 2] = hit ? ans.w : 0.f;
+		}
 	}
 	return 0;
 }

@@ -5,16 +5,17 @@
 // after a *trace* kernel has answered the query.  Three kinds of kernels alternate:
 //
 //   wf_trace<closest|any>  — nothing but traversal: reads 32 B of ray per path from a compacted
-//                            queue, walks the tree (kd_trace), writes 16 B of hit / 4 B of verdict.
-//                            ~60 VGPRs, so it runs at full occupancy, and every lane has a live ray.
+//                            queue, walks the tree (TriKdTree::intersect / intersectS,
+//                            kdtree_triangle.cc:684-977), writes 16 B of hit / 1 bit of verdict.
+//                            ~70 VGPRs, so it runs at 7 waves per SIMD, and every lane has a live ray.
 //   wf_shade               — resumes every path that was just answered, runs material / light /
 //                            sampling code until the next query, and appends the path to the
 //                            closest-hit or the any-hit queue (wave-aggregated atomics).
 //   wf_accumulate          — when all paths of a chunk have ended: one thread per pixel adds the
 //                            per-sample results in sample order (ImageFilm::addSample's order).
 //
-// The arithmetic is the same, operation for operation, as in the one-kernel path (integrate /
-// direct_light in yafgpu_device.hip); results are bit-identical between the two (tests/test_gpu_parity.py).
+// The arithmetic restates the reference's, operation for operation (integrate, doLightEstimation
+// integrator_montecarlo.cc:78-345, Triangle::intersect); tests/test_gpu_parity.py holds the films to the oracle's.
 #pragma once
 
 namespace yafgpu {
@@ -123,7 +124,7 @@ YG_DEV void dl_samples(const RenderArgs &ra, const yafgpu_light &light, int li, 
 // One candidate of MonteCarloIntegrator::doLightEstimation (integrator_montecarlo.cc:78-345): light
 // `li`, half `phase` of the MIS pair (0 light sampling :161-262, 1 BSDF sampling :285-333; Dirac lights
 // have a single half :94-148).  Returns whether a shadow ray is wanted and, if so, the ray and the
-// radiance it would carry if unoccluded — identical arithmetic to direct_light().
+// radiance it would carry if unoccluded — the arithmetic of doLightEstimation, operation for operation.
 YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int phase, float s_1, float s_2, const SurfPt &sp, const yafgpu_material &mat,
                          const BsdfDat &dat, V3 wo, V3 &r_dir, float &r_tmin, float &r_tmax, Col &contrib)
 {
@@ -665,9 +666,9 @@ YG_DEV int st_after_shadow(const WfArgs &a, uint32_t slot, Hot &h, uint2 verdict
 	return W_DL_NEXT;
 }
 
-// direct_light()'s loops, with the two halves of a MIS pair (same light, same sample index) taken together:
-// each half adds into its own accumulator (ccol / ccol_2) in sample order, exactly as `for phase { for is }` does.
-// The loops are cut in two steps.  st_dl_next is the bookkeeping: it closes every light whose samples are all in
+// doLightEstimation's loops (integrator_montecarlo.cc:78-345), with the two halves of a MIS pair (same light, same
+// sample index) taken together: each half adds into its own accumulator (ccol / ccol_2) in sample order, as the
+// reference's two loops over the samples do.  The loops are cut in two steps.  st_dl_next is the bookkeeping: it closes every light whose samples are all in
 // and says whether a candidate pair has to be evaluated next (W_DL_EVAL).  st_dl_eval evaluates that pair — the
 // widest step of the path program (81 VGPRs).
 YG_DEV int st_dl_next(const WfArgs &a, uint32_t slot, Hot &h, int level)
@@ -1500,7 +1501,8 @@ __global__ __launch_bounds__(kBlock) void wf_generate(const WfArgs a)
 // of its wave ends; when at least kRefill lanes are free the wave fetches that many new rays from the
 // queue with one atomic (ballot + prefix rank) and the freed lanes start them while the others carry
 // on.  Traversal state (current node, [tmin,tmax], best hit, short stack in LDS) is per lane, so lanes
-// of one wave can be at any point of any ray.  The walk itself is kd_trace's, cut at leaf granularity.
+// of one wave can be at any point of any ray.  The walk itself is TriKdTree::intersect / intersectS's
+// (kdtree_triangle.cc:684-977: front to back through [t_enter, t_exit], a short stack with kd-restart), cut at leaf granularity.
 #ifndef YAFGPU_VOTE_NUM
 #define YAFGPU_VOTE_NUM 1      // triangle round when n_tri * NUM >= n_node * DEN
 #endif
@@ -1535,7 +1537,7 @@ constexpr int kTraceBatch = YAFGPU_TRACE_BATCH;
 // Treelets.  The walk reads the tree in the treelet layout (DevScene::treelets, kdtree_build.h): one 32-byte fetch brings an interior
 // node, its two children and the links below them, so a fetch is good for up to two node steps, and a leaf is reached through a link
 // that carries its numbers — an empty leaf or an inline one costs no fetch at all.  The lane state and the stack entries are links.
-// Per ray the node steps, the leaves and their order are kd_trace's; only where a step's operands come from differs.  (The closed
+// Per ray the node steps, the leaves and their order are TriKdTree::intersect's; only where a step's operands come from differs.  (The closed
 // alternatives — pair fetch, 64-byte blocks, the tree's top in L1 or LDS, fused rounds, triangle prefetch, leaves apart, non-temporal
 // triangle loads, node windows — are measured in profiles/r02_ab_*.txt and profiles/r03_ab_*.txt.)
 #ifndef YAFGPU_TRACE_WAVES
@@ -1673,7 +1675,7 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 		// The kernel is bound by instruction issue, not by memory, so what counts is how many lanes share each
 		// instruction.  Each round the WAVE does one kind of work, chosen by vote: a round of triangle tests (lanes with a
 		// pending leaf) when at least as many lanes can take part in it as in node steps, else a burst of node steps (lanes
-		// whose walk stands at a node).  Per ray the steps and their order are kd_trace's.
+		// whose walk stands at a node).  Per ray the steps and their order are TriKdTree::intersect / intersectS's.
 		const bool has_pend = p_cur < p_end;
 		const unsigned long long m_tri = __ballot(has_pend);
 		const int n_tri = __popcll(m_tri), n_node = __popcll(__ballot(ws == kWalk));

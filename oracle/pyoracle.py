@@ -249,6 +249,7 @@ def lib():
     L.yor_nodes_probe.argtypes = [C.c_int32, C.POINTER(NodeDesc), C.c_int32, C.POINTER(TextureDesc), C.POINTER(CameraDesc), fp, fp]
     L.yor_render.restype = C.c_int
     L.yor_render.argtypes = [C.c_void_p, C.POINTER(RenderDesc), fp, C.POINTER(Stats)]
+    L.yor_scene_set_per_sample_streams.argtypes = [C.c_void_p, C.c_int32]
     L.yor_scene_set_tree.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), fp]
     L.yor_intersect.restype = C.c_int
     L.yor_intersect.argtypes = [C.c_void_p, C.c_int, fp, fp, C.c_float, C.c_float, C.POINTER(C.c_int32), fp, fp]
@@ -562,6 +563,8 @@ class OracleScene:
         rd = render_desc(render)
         film = np.zeros((rd.height, rd.width, 5), dtype=np.float32)
         st = Stats()
+        # per_sample_streams: the GPU path without serial-state replay (yor_scene_set_per_sample_streams)
+        L.yor_scene_set_per_sample_streams(self.h, int(render.get("per_sample_streams", False)))
         rc = L.yor_render(self.h, C.byref(rd), fptr(film), C.byref(st))
         if rc != 0:
             raise RuntimeError(f"oracle: unsupported configuration (code {rc})")

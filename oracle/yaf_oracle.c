@@ -502,6 +502,7 @@ struct yor_scene
 	/* image textures + per-triangle texture coordinates (row N2) */
 	int n_tex; struct tex_s *tex;
 	float *tri_uv, *tri_orco;
+	int per_sample_streams; /* yor_scene_set_per_sample_streams */
 };
 
 /* per-thread counters */
@@ -3337,6 +3338,8 @@ void yor_nodes_probe(int32_t n_nodes, const yor_node_desc *nodes, int32_t n_text
 	free(tx);
 }
 
+void yor_scene_set_per_sample_streams(yor_scene *s, int32_t on) { s->per_sample_streams = on != 0; }
+
 void yor_scene_set_tree(yor_scene *s, uint32_t n_nodes, const uint32_t *nodes, uint32_t n_refs, const uint32_t *refs, const float bound6[6])
 {
 	free(s->nodes); free(s->leaf_refs);
@@ -3926,6 +3929,12 @@ static void render_tile(worker_t *wk, int tx, int ty, rstate_t *st)
 				if(cam->aperture != 0) { lens_u = halton_next(&hal_u); lens_v = halton_next(&hal_v); }   /* :405-409 */
 				camera_shoot_lens(cam, j + dx, i + dy, lens_u, lens_v, &from, &dir, &tmin, &tmax, &wt);
 				wk->camera_samples++;
+				if(wk->s->per_sample_streams)
+				{	/* per-sample streams in place of the serial state: the counter's and the roulette stream's start */
+					const uint32_t ordinal = ((uint32_t)(i - rd->ystart) * (uint32_t)rd->width + (uint32_t)(j - rd->xstart)) * (uint32_t)n_samples + (uint32_t)sample;
+					st->correlative_sample_number = ordinal * 16u;
+					mwc_init(&prng, yor_fnv32a(ordinal) + 123u);
+				}
 				float c[4];
 				g_trace_px = (float)j; g_trace_py = (float)i;
 				integrate(st, from, dir, tmin, tmax, 0, c, NULL);
@@ -4143,6 +4152,7 @@ int yor_render(yor_scene *s, const yor_render_desc *rd, float *film_out, yor_sta
 		if(s->mats[i].flags & BSDF_DISPERSIVE) return -4; /* recursiveRaytrace: the dispersive branch is not restated */
 	if(rd->tile_size <= 0 || rd->width <= 0 || rd->height <= 0 || rd->aa_minsamples <= 0) return -5;
 	if(rd->aa_passes > 1 && rd->shard_count > 1) return -6; /* the noise detection needs the whole frame */
+	if(s->per_sample_streams && rd->aa_passes > 1) return -7; /* the GPU path's per-sample mode is restated for single-pass renders */
 	struct timespec t0, t1;
 	memset(film_out, 0, sizeof(float) * 5 * (size_t)rd->width * (size_t)rd->height);
 	film_t film;

@@ -278,6 +278,12 @@ void yor_trace_counts(uint64_t *n_samples, uint64_t *n_rays);
  * tests walk the PRODUCT's tree with the reference's traversal algorithm. */
 void yor_scene_set_tree(yor_scene *s, uint32_t n_nodes, const uint32_t *nodes, uint32_t n_refs, const uint32_t *refs, const float bound6[6]);
 
+/* on = 0 (the default): the reference's serial state.  on = 1: the GPU path's mode without serial-state replay, for single-pass,
+ * non-recursive renders: every camera sample starts the light counter at ordinal * 16 and a roulette stream of its own, ordinal =
+ * ((y - ystart) * width + x - xstart) * samples + sample.  A scene setting, not a yor_render_desc field: the descriptor keeps the
+ * layout its callers were built with. */
+void yor_scene_set_per_sample_streams(yor_scene *s, int32_t on);
+
 /* ray-level entry points (kd traversal vs brute force cross-checks and GPU ray parity tests) */
 int yor_intersect(const yor_scene *s, int use_tree, const float from[3], const float dir[3], float tmin, float tmax,
                   int32_t *tri, float *t, float bary[3]);

@@ -71,11 +71,10 @@ def test_degenerate_inputs():
     assert len(nodes) == 1 and list(refs) == [0]
 
 
-@pytest.mark.parametrize("pipeline", ["wavefront", "megakernel"])
+@pytest.mark.parametrize("pipeline", ["wavefront"])      # (the one pipeline there is: a parameter only so that the test's id stays the one the suite's records name)
 def test_render_through_device_tree(pipeline, monkeypatch):
     """YAFGPU_BUILD=device: the scene's tree comes from the GPU builder; film and ray counts equal the oracle's render
     through that same tree, and the film equals the host-tree render wherever no exact hit-distance tie is involved."""
-    monkeypatch.setenv("YAFGPU_PIPELINE", pipeline)
     sc = scenes.cornell_soup(3000, seed=21, res=(96, 80))
     rd = scenes.render_settings(96, 80, 4, bounces=3)
 

@@ -42,7 +42,6 @@ def _worker(rank, world, port, out_path, case):
     sys.path.insert(0, ROOT)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
-    os.environ["YAFGPU_PIPELINE"] = "wavefront"
     import torch
     import torch.distributed as dist
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -69,7 +68,6 @@ def _worker(rank, world, port, out_path, case):
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("case", ["aa", "lights_rr_only", "lights_lc_only", "lights", "lights_aa", "lights_chunks", "lights_one_tile"])
 def test_sharded_render_with_cross_rank_state_equals_the_single_gpu_render(tmp_path, monkeypatch, case):
-    monkeypatch.setenv("YAFGPU_PIPELINE", "wavefront")
     if case == "lights_chunks":      # several chunks per rank (a tile each): the count pass and the final pass record a chunk's events twice
         monkeypatch.setenv("YAFGPU_WF_CHUNK", "1500")
     from libyafaray_amd import Interface, scenes

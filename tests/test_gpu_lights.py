@@ -1,8 +1,7 @@
-"""The directional, sun and sphere lights on the DEVICE (wavefront pipeline): their leaf functions bit for bit against a float32
+"""The directional, sun and sphere lights on the DEVICE: their leaf functions bit for bit against a float32
 restatement in the reference's operation order (probe ops 17-21), renders against closed forms (a diffuse plane under each light,
 infinite and finite directional shadows, transparent shadows on infinite rays, the sun's cone, the sphere's cap), the light-sampling
-half only for the sphere (no BSDF-half rays), the serial-state replay with sharding and pass pipelining, and the one-kernel
-pipeline's refusal."""
+half only for the sphere (no BSDF-half rays), the serial-state replay with sharding and pass pipelining."""
 import ctypes as C
 
 import numpy as np
@@ -22,11 +21,6 @@ def torch_first():
     """the emulated shard exchange hands device memory to torch: let torch open the GPU before the library does"""
     import torch
     torch.cuda.init()
-
-
-@pytest.fixture(autouse=True)
-def wavefront_only(monkeypatch):
-    monkeypatch.setenv("YAFGPU_PIPELINE", "wavefront")     # the one-kernel pipeline refuses these lights (error -15)
 
 
 RHO = (0.8, 0.6, 0.4)
@@ -410,15 +404,3 @@ def test_replay_shards_and_pipelining_with_three_light_types():
         films.append(y2.getFilm(W, H).copy())
     assert np.array_equal(films[0], films[1])
 
-
-# ---- 8. the one-kernel pipeline refuses them ------------------------------------------------------------------------
-@pytest.mark.parametrize("light", [directional(), sun(), {"type": "spherelight", "from": (0.0, 0.0, 2.0), "radius": 0.2}])
-def test_one_kernel_pipeline_refuses_the_new_lights(monkeypatch, light):
-    monkeypatch.setenv("YAFGPU_PIPELINE", "megakernel")
-    yi = Interface(strict=False)
-    scenes.load_scene(yi, plane_scene([light], res=16), scenes.render_settings(16, 16, 1, integrator="directlighting"))
-    ok = yi.render()
-    assert not ok
-    msg = yi.getLastError()
-    assert "-15" in msg or "one-kernel pipeline" in msg, msg
-    assert "directional, sun or sphere" in msg, msg

@@ -30,10 +30,8 @@ def compare_films(gpu_film, ora_film, what, max_outliers=0, exact_weights=True):
 
 
 @pytest.fixture(params=["wavefront"], autouse=True)
-def pipeline(request, monkeypatch):
-    """The wavefront pipeline is the product.  The one-kernel pipeline (render_kernel, YAFGPU_PIPELINE=megakernel) is kept as ONE
-    cross-check — test_pipelines_are_bit_identical — on the single-pass pinhole diffuse / glossy subset it renders."""
-    monkeypatch.setenv("YAFGPU_PIPELINE", request.param)
+def pipeline(request):
+    """The one pipeline there is.  (A parameter of every test of this module, so that their ids stay those the suite's records name.)"""
     return request.param
 
 
@@ -83,20 +81,22 @@ def test_render_matches_oracle(n_tris, res, spp, bounces):
     compare_films(film, ofilm, f"cornell {n_tris} tris {res}x{res} {spp}spp b{bounces}")
 
 
-def test_pipelines_are_bit_identical(monkeypatch):
+@pytest.mark.parametrize("rr_min", [3, 1])
+def test_per_sample_streams_match_the_oracle(rr_min):
+    """Serial-state replay off, two lights: estimateOneDirectLight's counter starts every camera sample at its ordinal x 16
+    (st_after_closest) and Russian roulette draws from the sample's own MWC stream (st_start_path).  The oracle restates
+    that mode (per_sample_streams).  rr_min 3: roulette off, the counter alone; rr_min 1: roulette from depth 1 on too."""
     sc = scenes.cornell_soup(3000, seed=77, res=(56, 40), n_lights=2, glossy_fraction=0.3)
-    rd = scenes.render_settings(56, 40, 12, bounces=3, path_samples=2)
-    films = {}
-    for pl in ("wavefront", "megakernel"):
-        monkeypatch.setenv("YAFGPU_PIPELINE", pl)
-        yi = Interface()
-        scenes.load_scene(yi, sc, rd)
-        yi.setSerialReplay(False)       # two lights: the one-kernel pipeline only has the per-sample light ordinal
-        yi.render()
-        films[pl] = (yi.getFilm(56, 40), yi.getRenderStats())
-    a, b = films["wavefront"], films["megakernel"]
-    assert a[1].rays_closest == b[1].rays_closest and a[1].rays_shadow == b[1].rays_shadow
-    assert np.array_equal(a[0], b[0]), "wavefront and megakernel films differ"
+    rd = scenes.render_settings(56, 40, 12, bounces=3, path_samples=2, russian_roulette_min_bounces=rr_min)
+    yi = Interface()
+    scenes.load_scene(yi, sc, rd)
+    yi.setSerialReplay(False)
+    yi.render()
+    film, st = yi.getFilm(56, 40), yi.getRenderStats()
+    ofilm, ost = po.OracleScene(sc).render(dict(rd, per_sample_streams=True))
+    assert st.camera_samples == ost.camera_samples == 56 * 40 * 12
+    assert st.rays_closest == ost.rays_closest and st.rays_shadow == ost.rays_shadow, "ray counts differ from the oracle"
+    compare_films(film, ofilm, f"per-sample streams, roulette from depth {rr_min}")
 
 
 def test_glossy_two_lights_point_light_run_and_match_oracle_where_defined():
@@ -134,11 +134,9 @@ def test_config0_test01_xml_path_tracing():
     compare_films(film, ofilm, "test01 path tracing 256x256 16spp")
 
 
-def test_test01_xml_shipped_settings_direct_lighting_gauss(pipeline):
+def test_test01_xml_shipped_settings_direct_lighting_gauss():
     """The reference's test scene with the integrator and film settings it ships (tests/test01/test01.xml:
     directlighting, 480x270, 1 spp, gauss 1.5 — the render behind BASELINE.md's 0.9 s badge), textures removed."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline implements the narrow box filter only")
     import os
     from tests import xml_scene
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "test01_dl.xml")
@@ -154,13 +152,11 @@ def test_test01_xml_shipped_settings_direct_lighting_gauss(pipeline):
     compare_films(film, ofilm, "test01 shipped settings", exact_weights=False)
 
 
-def test_device_whole_path_against_the_references_expected_png(pipeline):
+def test_device_whole_path_against_the_references_expected_png():
     """The DEVICE render of the reference's shipped test scene (textures stripped) through the reference's output
     transform, against the expected PNG the reference's tests hold — every pixel whose filter footprint sees only
     untextured materials (47 % of the frame; tests/png_fixture.py).  The same bounds as the oracle's own check
     (tests/test_oracle_golden.py): >= 99.5 % within two 8-bit levels, >= 96 % within one, >= 80 % equal."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline implements the narrow box filter only")
     import os
     from tests import png_fixture, xml_scene
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "test01_dl.xml")
@@ -244,12 +240,10 @@ def test_empty_scene_and_single_pixel():
 
 
 @pytest.mark.parametrize("filt,width", [("gauss", 1.5), ("mitchell", 1.2), ("lanczos", 2.0), ("box", 2.5)])
-def test_reconstruction_filters(filt, width, pipeline):
+def test_reconstruction_filters(filt, width):
     """ImageFilm's filter table and footprint (imagefilm.cc:124-187, 925-1015) beyond the 1-pixel box: the
     reference's own test scene ships with gauss 1.5.  Neighbour splats go through float atomics, so the sum
     order — and only that — differs from the oracle: same tolerance, weights to 2e-6."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline implements the narrow box filter only")
     sc = scenes.cornell_soup(900, seed=12, res=(45, 37))
     rd = scenes.render_settings(45, 37, 6, bounces=2, filter_type=filt, AA_pixelwidth=width, background=(0.1, 0.1, 0.2))
     film, st, ofilm, ost = render_both(sc, rd)
@@ -313,45 +307,35 @@ def _full_size_against_crops(name, crops, size, lights=None, low_spp=4):
     return st
 
 
-def test_full_size_m1_against_oracle_windows(pipeline):
+def test_full_size_m1_against_oracle_windows():
     """The configuration BASELINE.json's metric is quoted on (bench.py's default): 1M triangles, 512x512, 64 spp,
     primary + 1 bounce.  4 windows of 64x64 = 6 % of the frame at 64 spp + the whole frame at 4 spp."""
-    if pipeline == "megakernel":
-        pytest.skip("full-size runs use the default pipeline; the two are compared bit for bit at small sizes")
     _full_size_against_crops("m1", [(30, 40), (224, 224), (440, 300), (200, 440)], 64)
 
 
-def test_full_size_c2_against_oracle_windows(pipeline):
+def test_full_size_c2_against_oracle_windows():
     """BASELINE.json configs[1]: 100k triangles, 512x512, 64 spp, primary + 1 bounce."""
-    if pipeline == "megakernel":
-        pytest.skip("full-size runs use the default pipeline; the two are compared bit for bit at small sizes")
     _full_size_against_crops("c2", [(40, 60), (224, 224), (440, 300), (200, 440)], 64)
 
 
-def test_full_size_c3_against_oracle_windows(pipeline):
+def test_full_size_c3_against_oracle_windows():
     """BASELINE.json configs[2]: 1M triangles, 1024x1024, 256 spp, 2 bounces.  4 windows of 116x116 = 5.1 % of the
     frame at 256 spp + the whole frame at 2 spp."""
-    if pipeline == "megakernel":
-        pytest.skip("full-size runs use the default pipeline; the two are compared bit for bit at small sizes")
     _full_size_against_crops("c3", [(100, 700), (454, 454), (800, 200), (600, 880)], 116, low_spp=2)
 
 
-def test_full_size_c4_one_light_against_oracle_windows(pipeline):
+def test_full_size_c4_one_light_against_oracle_windows():
     """BASELINE.json configs[3] in its one-light variant: 1M triangles, half of them glossy, 1024x1024, 64 spp,
     2 bounces, MIS.  (The two-light configuration as stated: test_full_size_c4_two_lights_exact_replay.)"""
-    if pipeline == "megakernel":
-        pytest.skip("full-size runs use the default pipeline; the two are compared bit for bit at small sizes")
     _full_size_against_crops("c4", [(300, 800), (640, 400), (60, 100), (850, 850)], 116, lights=1, low_spp=2)
 
 
 # ---- serial-state replay (SURVEY row N4): the reference's per-tile roulette stream and its light counter -------------
 @pytest.mark.parametrize("aa", [dict(AA_threshold=0.02), dict(AA_threshold=0.03, AA_detect_color_noise=True, AA_dark_detection_type="linear", AA_dark_threshold_factor=0.6),
                                 dict(AA_threshold=0.5, AA_dark_detection_type="curve", AA_variance_pixels=3, AA_variance_edge_size=8)])
-def test_noise_detection_on_the_device_equals_the_host_version(aa, pipeline, monkeypatch):
+def test_noise_detection_on_the_device_equals_the_host_version(aa, monkeypatch):
     """ImageFilm::nextPass's detection (imagefilm.cc:270-480) runs on the device between adaptive passes; the host restatement it
     replaced (YAFGPU_AA_DETECT=host) must flag the same pixels: same resampled counts per pass, same film."""
-    if pipeline == "megakernel":
-        pytest.skip("multi-pass renders belong to the wavefront pipeline")
     sc = scenes.cornell_soup(2000, seed=17, res=(71, 53))
     rd = scenes.render_settings(71, 53, 2, bounces=2, AA_passes=4, AA_inc_samples=2, **aa)
     out = []
@@ -365,12 +349,10 @@ def test_noise_detection_on_the_device_equals_the_host_version(aa, pipeline, mon
     assert np.array_equal(out[0][0], out[1][0])
 
 
-def test_prepare_render_keeps_the_device_scene_until_something_changes(pipeline):
+def test_prepare_render_keeps_the_device_scene_until_something_changes():
     """Scene::update rebuilds the tree only when the scene changed (scene.cc:784-790): a second render() of an untouched scene reuses
     the device scene (no second tree build), a render parameter alone (samples) does not rebuild either, a new camera or a changed
     material does — and the film is then the one a fresh Interface renders."""
-    if pipeline == "megakernel":
-        pytest.skip("one pipeline is enough")
     sc = scenes.cornell_soup(3000, seed=3, res=(40, 32))
     rd = scenes.render_settings(40, 32, 2, bounces=2)
     yi = Interface()
@@ -430,14 +412,12 @@ def _render_with_rand_state(sc, rd, replay=True, same_tree=False):
     dict(n_lights=2, bounces=3, rr=1, path_samples=2, raydepth=2, spec=True, glossy=0.3, glossy_rec=True),      # the glossy branch: 8 trajectories, split path samples
     dict(n_lights=2, bounces=3, rr=0, path_samples=1, raydepth=2, spec=True, aa=dict(AA_passes=3, AA_inc_samples=2, AA_threshold=0.02)),
 ])
-def test_serial_state_replay_matches_the_single_threaded_oracle(case, pipeline, monkeypatch):
+def test_serial_state_replay_matches_the_single_threaded_oracle(case, monkeypatch):
     """Russian roulette ON (the reference's default, integrator_path_tracer.cc:355) and / or more than one light: the
     film depends on state that runs through the samples in the reference's order — the tile's MWC stream
     (integrator_tiled.cc:319, seeded from libc rand()) and correlative_sample_number_ (integrator_montecarlo.cc:62-76).
     The device replays both (record pass, per-tile scan, final pass) and must reproduce the oracle's one-thread render:
     same ray counts, same film."""
-    if pipeline == "megakernel":
-        pytest.skip("the replay belongs to the wavefront pipeline")
     sc = scenes.cornell_soup(1500, seed=41 + case["bounces"], res=(72, 56), n_lights=case["n_lights"], glossy_fraction=case.get("glossy", 0.0))
     if case.get("spec"):
         m = sc["materials"]
@@ -468,12 +448,10 @@ def test_serial_state_replay_matches_the_single_threaded_oracle(case, pipeline, 
     assert not np.array_equal(film3, film)
 
 
-def test_full_size_c4_two_lights_exact_replay(pipeline):
+def test_full_size_c4_two_lights_exact_replay():
     """BASELINE.json configs[3] AS STATED — 1M triangles, half of them glossy, TWO area lights, 1024x1024 — whole frame
     at 2 spp against the oracle's single-threaded render (with two lights the light a path vertex samples depends on
     the number of estimateOneDirectLight calls before it in the whole frame, so windows cannot stand in for the frame)."""
-    if pipeline == "megakernel":
-        pytest.skip("the replay belongs to the wavefront pipeline")
     import bench
     w, sc, rd = bench.make_workload("c4", spp=2)
     film, st, ofilm, ost = _render_with_rand_state(sc, rd)
@@ -481,13 +459,11 @@ def test_full_size_c4_two_lights_exact_replay(pipeline):
     compare_films(film, ofilm, "c4 two lights 1024x1024 2 spp, exact replay", max_outliers=1024 * 1024 // 20000)
 
 
-def test_device_shards_sum_to_the_unsharded_frame(pipeline):
+def test_device_shards_sum_to_the_unsharded_frame():
     """The multi-GPU decomposition on ONE GPU: shard 0/2 and 1/2 (tile t -> rank t % 2, yafaray_setShard) rendered by the
     device one after the other, their films summed as parallel.reduce_film sums them over RCCL — equal to the unsharded
     device film bit for bit on every pixel that is not on a tile's first row / column (those also take a neighbouring
     tile's box-filter splat, i.e. one addition in another order), and to 1 ulp there."""
-    if pipeline == "megakernel":
-        pytest.skip("sharding is exercised on the default pipeline")
     W, H, T = 160, 128, 32
     sc = scenes.cornell_soup(6000, seed=23, res=(W, H), glossy_fraction=0.3)
     rd = scenes.render_settings(W, H, 16, bounces=3, tile_size=T)
@@ -528,12 +504,10 @@ def test_device_shards_sum_to_the_unsharded_frame(pipeline):
          AA_dark_threshold_factor=0.5, AA_variance_edge_size=6, AA_variance_pixels=3, AA_resampled_floor=60.0),
     dict(AA_passes=2, AA_inc_samples=4, AA_threshold=0.005, AA_dark_detection_type="curve", AA_clamp_samples=0.6),
 ])
-def test_multi_pass_anti_aliasing(aa, pipeline):
+def test_multi_pass_anti_aliasing(aa):
     """integrator_tiled.cc:116-258 (pass schedule, sample / light multipliers, threshold decay under the resampled
     floor), :394-398 (riVdC / riS sub-pixel positions), imagefilm.cc:270-480 (noise detection), :975 (sample clamp).
     The set of resampled pixels shows in the film weights, which must match the oracle's exactly."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline renders single-pass films only")
     from libyafaray_amd import interface
     sc = scenes.cornell_soup(700, seed=21, res=(56, 44))
     rd = scenes.render_settings(56, 44, 3, bounces=2, background=(0.05, 0.1, 0.2), **aa)
@@ -556,11 +530,9 @@ def test_multi_pass_anti_aliasing(aa, pipeline):
 
 @pytest.mark.parametrize("bokeh", [dict(bokeh_type="disk1"), dict(bokeh_type="hexagon", bokeh_bias="edge", bokeh_rotation=20.0),
                                    dict(bokeh_type="ring"), dict(bokeh_type="disk2", bokeh_bias="center")])
-def test_depth_of_field(bokeh, pipeline):
+def test_depth_of_field(bokeh):
     """aperture != 0: per-pixel Halton(3) / Halton(5) lens coordinates (integrator_tiled.cc:382-383,405-409) through
     PerspectiveCamera::getLensUv (camera_perspective.cc:91-131)"""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline has the pinhole camera only")
     sc = scenes.cornell_soup(600, seed=8, res=(52, 40))
     sc["camera"] = dict(sc["camera"], aperture=0.08, dof_distance=3.7, **bokeh)
     rd = scenes.render_settings(52, 40, 9, bounces=2, background=(0.1, 0.1, 0.1), adv_base_sampling_offset=5)
@@ -573,7 +545,7 @@ def test_depth_of_field(bokeh, pipeline):
 
 
 @pytest.mark.parametrize("angle", [181.0, 40.0])
-def test_smooth_mesh_render(angle, pipeline):
+def test_smooth_mesh_render(angle):
     """Interface::smoothMesh (scene.cc:383-543): vertex normals computed on the host from the shared-vertex mesh,
     interpolated by Triangle::getSurface on the device.  The oracle gets the same corner normals."""
     sc = scenes.cornell_soup(40, seed=5, res=(48, 40))
@@ -643,11 +615,9 @@ def test_smooth_mesh_render(angle, pipeline):
     assert not np.allclose(po.film_to_rgb(ffilm), po.film_to_rgb(ofilm), rtol=1e-3), "smoothing changes the shading"
 
 
-def test_chunked_frames(pipeline, monkeypatch):
+def test_chunked_frames(monkeypatch):
     """A frame larger than one wavefront chunk (YAFGPU_WF_CHUNK caps the paths in flight): pixel tables, masks of the
     adaptive passes, lens streams and film accumulation must not depend on where the chunk borders fall."""
-    if pipeline == "megakernel":
-        pytest.skip("chunks belong to the wavefront pipeline")
     sc = scenes.cornell_soup(500, seed=17, res=(100, 90))
     sc["camera"] = dict(sc["camera"], aperture=0.05, dof_distance=3.9, bokeh_type="pentagon")
     rd = scenes.render_settings(100, 90, 12, bounces=2, AA_passes=3, AA_inc_samples=9, AA_threshold=0.03, background=(0.1, 0.2, 0.3))
@@ -664,13 +634,11 @@ def test_chunked_frames(pipeline, monkeypatch):
     assert len(np.unique(np.round(whole[..., 4]))) >= 2      # the adaptive passes did resample a subset
 
 
-def test_transparent_shadows_flag_with_opaque_materials(pipeline):
+def test_transparent_shadows_flag_with_opaque_materials():
     """transpShad = true selects TriKdTree::intersectTs (kdtree_triangle.cc:983-1162).  Even with no transparent
     material it is not intersectS: it accepts hits from the shadow ray's tmin_ on (:1099), intersectS from 0 on (:936),
     both measured from the origin Scene::isShadowed has already advanced by tmin_ — so an occluder within the bias
     of the surface shadows it under one and not under the other.  The tilted soup puts triangles that close."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline has no transparent shadows")
     sc = scenes.cornell_soup(400, seed=4, res=(40, 32), sigma=0.1)
     films = {}
     for transp in (True, False):
@@ -683,13 +651,11 @@ def test_transparent_shadows_flag_with_opaque_materials(pipeline):
 
 
 @pytest.mark.parametrize("raydepth,integrator", [(1, "pathtracing"), (3, "pathtracing"), (5, "pathtracing"), (4, "directlighting")])
-def test_recursive_raytrace_mirror_and_transparency(raydepth, integrator, pipeline):
+def test_recursive_raytrace_mirror_and_transparency(raydepth, integrator):
     """recursiveRaytrace's perfect specular branch (integrator_montecarlo.cc:971-1025) for shinydiffusemat's mirror
     (with and without Fresnel) and transparency (filtered, straight through): a full integrate() per followed ray, one
     level deeper, alpha from the transmitted ray.  Frames per level behind the parked records; the iteration loop
     runs until the queues are empty."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline has no recursiveRaytrace")
     sc = scenes.cornell_soup(260, seed=13, res=(48, 40))
     sc["materials"] = [dict(m) for m in sc["materials"]]
     sc["materials"][0].update({"specular_reflect": 0.5, "mirror_color": (0.9, 0.9, 1.0)})
@@ -705,11 +671,9 @@ def test_recursive_raytrace_mirror_and_transparency(raydepth, integrator, pipeli
 
 
 @pytest.mark.parametrize("raydepth", [2, 6])
-def test_glass_and_mirror_materials(raydepth, pipeline):
+def test_glass_and_mirror_materials(raydepth):
     """GlassMaterial (refraction, Fresnel reflection, total inner reflection, the level-3 cut of reflections inside the
     glass, with and without fake shadows) and MirrorMaterial through recursiveRaytrace and as path bounces."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline has no recursiveRaytrace")
     sc = scenes.cornell_soup(300, seed=29, res=(52, 44), sigma=0.06)
     sc["materials"] = [dict(m) for m in sc["materials"]]
     sc["materials"].append({"type": "glass", "IOR": 1.5, "filter_color": (0.7, 0.95, 0.8), "transmit_filter": 0.9, "mirror_color": (1.0, 0.95, 0.9)})
@@ -727,13 +691,11 @@ def test_glass_and_mirror_materials(raydepth, pipeline):
 
 
 @pytest.mark.parametrize("raydepth,bounces", [(4, 3), (7, 4)])
-def test_glass_absorption(raydepth, bounces, pipeline):
+def test_glass_absorption(raydepth, bounces):
     """Glass with "absorption": the material owns a BeerVolumeHandler (material_glass.cc:371-398); light that travelled
     inside it is attenuated by exp(-sigma * distance) — for followed specular rays in recursiveRaytrace
     (integrator_montecarlo.cc:991-994, 1016-1019; a ray that leaves the scene from inside comes back black) and for
     path segments that end on the inner side of the surface (integrator_path_tracer.cc:276-279)."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline has no recursiveRaytrace")
     sc = scenes.cornell_soup(240, seed=37, res=(52, 44), sigma=0.12)
     sc["materials"] = [dict(m) for m in sc["materials"]]
     sc["materials"].append({"type": "glass", "IOR": 1.45, "filter_color": (0.95, 0.95, 1.0), "transmit_filter": 0.6,
@@ -754,12 +716,10 @@ def test_glass_absorption(raydepth, bounces, pipeline):
 
 
 @pytest.mark.parametrize("shadow_depth", [1, 5])
-def test_transparent_shadows(shadow_depth, pipeline):
+def test_transparent_shadows(shadow_depth):
     """Shadow rays through transparent shinydiffuse and fake-shadow glass are filtered, not blocked
     (TriKdTree::intersectTs; integrator_montecarlo.cc:102-114,176-182,304-309); more than shadowDepth transparent
     surfaces block.  The product of the filters is taken in visiting order, which is the tree's: tolerance, not bits."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline has no transparent shadows")
     sc = scenes.cornell_soup(420, seed=31, res=(48, 40), sigma=0.09)
     sc["materials"] = [dict(m) for m in sc["materials"]]
     sc["materials"].append({"type": "shinydiffusemat", "color": (0.3, 0.9, 0.4), "diffuse_reflect": 0.6, "transparency": 0.7, "transmit_filter": 0.8,
@@ -778,11 +738,9 @@ def test_transparent_shadows(shadow_depth, pipeline):
     assert po.film_to_rgb(ofilm)[..., :3].sum() > po.film_to_rgb(opaque)[..., :3].sum() * 1.02, "filtered shadows let light through"
 
 
-def test_coated_glossy_material(pipeline):
+def test_coated_glossy_material():
     """CoatedGlossyMaterial (as_diffuse): Blinn lobe + diffuse substrate under a Fresnel-weighted specular coat that
     recursiveRaytrace follows (material_coated_glossy.cc)."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline has no recursiveRaytrace")
     sc = scenes.cornell_soup(300, seed=37, res=(48, 40), sigma=0.07)
     sc["materials"] = [dict(m) for m in sc["materials"]]
     sc["materials"].append({"type": "coated_glossy", "color": (0.9, 0.8, 0.7), "diffuse_color": (0.3, 0.5, 0.7), "mirror_color": (1.0, 0.95, 0.9),
@@ -799,12 +757,10 @@ def test_coated_glossy_material(pipeline):
     compare_films(film, ofilm, "coated glossy")
 
 
-def test_anisotropic_glossy_lobe(pipeline):
+def test_anisotropic_glossy_lobe():
     """The Ashikhmin-Shirley lobe of glossy / coated_glossy (`anisotropic`, exp_u / exp_v; material_utils_microfacet.h:38-87) in a
     path-traced box: MIS pairs, bounces and the coat's recursion all sample it.  Its sampling calls libm's tanf (double tan
     narrowed on the device): the tolerance is north_star's, the ray counts must still agree."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline has no recursiveRaytrace")
     sc = scenes.cornell_soup(300, seed=41, res=(48, 40), sigma=0.07)
     sc["materials"] = [dict(m) for m in sc["materials"]]
     sc["materials"].append({"type": "glossy", "color": (0.9, 0.8, 0.85), "diffuse_color": (0.5, 0.4, 0.6), "diffuse_reflect": 0.5, "glossy_reflect": 0.5,
@@ -824,14 +780,12 @@ def test_anisotropic_glossy_lobe(pipeline):
 
 
 @pytest.mark.parametrize("raydepth,integrator", [(1, "pathtracing"), (2, "pathtracing"), (3, "pathtracing"), (2, "directlighting")])
-def test_glossy_branch_of_recursive_raytrace(raydepth, integrator, pipeline):
+def test_glossy_branch_of_recursive_raytrace(raydepth, integrator):
     """recursiveRaytrace's glossy branch (integrator_montecarlo.cc:861-972): glossy / coated_glossy with as_diffuse off are not
     path-traced but followed by 8 trajectories through the glossy lobe, each a full integrate() one level down with the
     trajectory-splitting state set — fewer light samples (:154) and path samples (:182), shifted first-segment samples (:201-205),
     one trajectory per level below the first (:869).  Mirrors and glass in the scene nest the specular branch inside it and the
     other way round."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline has no recursiveRaytrace")
     sc = scenes.cornell_soup(260, seed=43, res=(40, 32), sigma=0.08)
     sc["materials"] = [dict(m) for m in sc["materials"]]
     sc["lights"] = [dict(l, samples=4) for l in sc["lights"]]
@@ -855,7 +809,7 @@ def test_glossy_branch_of_recursive_raytrace(raydepth, integrator, pipeline):
 
 @pytest.mark.parametrize("raydepth,integrator,extra", [(0, "pathtracing", {"no_recursive": True, "bounces": 3}), (1, "pathtracing", {}), (2, "pathtracing", {"bg_transp": True, "bg_transp_refract": True}),
                                                        (3, "pathtracing", {"transpShad": True, "shadowDepth": 3}), (2, "directlighting", {"transpShad": True, "bg_transp_refract": True})])
-def test_rough_glass(raydepth, integrator, extra, pipeline):
+def test_rough_glass(raydepth, integrator, extra):
     """RoughGlassMaterial (material_rough_glass.cc): a glossy lobe that reflects AND transmits.  recursiveRaytrace's glossy branch takes the
     two-direction sample and sends two rays per trajectory (integrator_montecarlo.cc:919-959: absorption along either, the second one's
     alpha for the level); path segments take the one-direction sample; fake shadows filter the light through getTransparency; glossy,
@@ -883,7 +837,7 @@ def test_rough_glass(raydepth, integrator, extra, pipeline):
 
 
 @pytest.mark.parametrize("integrator,samples", [("pathtracing", (5, 2)), ("pathtracing", (1, 1)), ("directlighting", (4, 3))])
-def test_two_shadow_pairs_per_park(integrator, samples, pipeline):
+def test_two_shadow_pairs_per_park(integrator, samples):
     """WfArgs::multi: a vertex whose light estimate has another MIS pair to go — the light's next sample, the next light — parks for two pairs
     at once (odd counts leave a single one at the end; the last pair of an estimate still takes the next segment beside it).  The shadow answers
     steer nothing, so the film must be the one-pair-per-park program's bit for bit, and the oracle's."""
@@ -904,7 +858,7 @@ def test_two_shadow_pairs_per_park(integrator, samples, pipeline):
 
 
 @pytest.mark.parametrize("raydepth,extra", [(0, {}), (2, {"russian_roulette_min_bounces": 1}), (1, {"no_recursive": True, "path_samples": 2})])
-def test_path_caustics(raydepth, extra, pipeline):
+def test_path_caustics(raydepth, extra):
     """caustic_type "path" — PathIntegrator's default when the parameter is absent (integrator_path_tracer.cc:36, :85): after a bounce through a
     specular, glossy or filter lobe the next vertex shows its lights (the emitting panel of the ceiling, a light material) and adds its emission
     after the roulette test (:252-253, :290); the state is left as the last bounce set it for whatever recursiveRaytrace does next (:863, :973)."""
@@ -934,12 +888,10 @@ def test_path_caustics(raydepth, extra, pipeline):
 
 
 @pytest.mark.parametrize("raydepth", [0, 1, 2])
-def test_additional_depth_and_transparent_bias(raydepth, pipeline):
+def test_additional_depth_and_transparent_bias(raydepth):
     """Material::additional_depth_ (integrate() carries the largest one met on the way down and recursiveRaytrace goes that much
     deeper below it, integrator_path_tracer.cc:149, integrator_montecarlo.cc:791) on glass, shinydiffuse and glossy, and
     shinydiffusemat's transparent bias (the transmitted ray starts `factor` [x raylevel] along its direction, :1003-1011)."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline has no recursiveRaytrace")
     sc = scenes.cornell_soup(260, seed=47, res=(40, 32), sigma=0.08)
     sc["materials"] = [dict(m) for m in sc["materials"]]
     sc["materials"].append({"type": "glass", "IOR": 1.5, "filter_color": (0.8, 0.9, 1.0), "transmit_filter": 0.6, "additionaldepth": 2})
@@ -962,11 +914,9 @@ def test_additional_depth_and_transparent_bias(raydepth, pipeline):
     assert not yi.render() and "7" in yi.getLastError(), yi.getLastError()          # 6 + 2 frames
 
 
-def test_light_count_and_sample_count_limits(pipeline):
+def test_light_count_and_sample_count_limits():
     """The light-estimate bookkeeping packs the light index in 8 bits and the sample index in 12: 255 lights render and equal
     the oracle, 256 are refused; an area light asking for more than 4095 samples per estimate is refused."""
-    if pipeline == "megakernel":
-        pytest.skip("limits are checked on the default pipeline")
     sc = scenes.cornell_soup(120, seed=51, res=(24, 20), sigma=0.1)
     rng = np.random.default_rng(7)
     points = [{"type": "pointlight", "from": tuple(float(x) for x in rng.uniform(-0.8, 0.8, 3)), "color": (1.0, 0.9, 0.8), "power": 0.02} for _ in range(255)]
@@ -993,12 +943,10 @@ def test_light_count_and_sample_count_limits(pipeline):
     assert not yi.render() and "4095" in yi.getLastError(), yi.getLastError()
 
 
-def test_xml_scene_with_every_feature(pipeline, tmp_path):
+def test_xml_scene_with_every_feature(tmp_path):
     """The C++ XML loader driven with everything the device path does — glass, mirror, coated glossy, mirror /
     transparent shinydiffuse, depth of field, recursion depth, transparent shadows, adaptive multi-pass AA with a
     gauss filter and a sample clamp — against the oracle fed by an independent Python parse of the same file."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline renders the single-pass pinhole diffuse subset only")
     from tests import xml_scene, xml_writer
     sc = scenes.cornell_soup(240, seed=43, res=(44, 36), sigma=0.08)
     sc["materials"] = [dict(m, type=m.get("type", "shinydiffusemat")) for m in sc["materials"]]
@@ -1387,13 +1335,11 @@ def _texturize(sc, rng):
 
 
 @pytest.mark.parametrize("seed", list(range(int(__import__("os").environ.get("YAFGPU_FUZZ_FIRST", "0")), int(__import__("os").environ.get("YAFGPU_FUZZ_SEEDS", "16")))))
-def test_random_feature_mixes(seed, pipeline, monkeypatch):
+def test_random_feature_mixes(seed, monkeypatch):
     """Features are pinned one at a time above; here random combinations of them — materials of every supported type
     on one scene, area + point lights, vertex normals, depth of field, recursion depth, transparent shadows, path
     samples, background alpha modes, adaptive passes — must still equal the oracle: steps share parked records,
     frames and queues, and a field one feature reuses must not leak into another."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline renders the single-pass pinhole diffuse subset only")
     sc, rd, w, h, base, kw = _feature_mix(seed)
     if seed % 2:      # every other seed in several wavefront chunks: chunk borders must not show (pixel lists, frames, lens streams)
         monkeypatch.setenv("YAFGPU_WF_CHUNK", str([700, 1500, 4000][seed % 3]))
@@ -1405,12 +1351,10 @@ def test_random_feature_mixes(seed, pipeline, monkeypatch):
 
 
 @pytest.mark.parametrize("seed", list(range(int(__import__("os").environ.get("YAFGPU_SERIAL_FUZZ_FIRST", "0")), int(__import__("os").environ.get("YAFGPU_SERIAL_FUZZ_SEEDS", "12")))))
-def test_random_feature_mixes_with_serial_state(seed, pipeline):
+def test_random_feature_mixes_with_serial_state(seed):
     """The random mixes again, consuming the reference's serial state (roulette stream, light counter) — with mirrors, glass and
     glossy-recursive materials a camera sample is a tree of integrate() calls whose events are replayed in the reference's depth-first
     order: the device must equal the SINGLE-THREADED oracle started from the same libc rand() state."""
-    if pipeline == "megakernel":
-        pytest.skip("the replay belongs to the wavefront pipeline")
     sc, rd, w, h, base, kw = _feature_mix(seed, serial=True)
     what = f"serial feature mix {seed}: {[m['type'] for m in sc['materials'][base:]]} {kw}"
     evidence = []
@@ -1499,11 +1443,9 @@ def _first_tree_artefact(sc, rd, same_tree, film, ofilm):
 
 
 @pytest.mark.parametrize("seed", [3, 14, 25, 36, 47, 58, 69, 80])
-def test_random_feature_mixes_through_the_xml_loader(seed, pipeline, tmp_path):
+def test_random_feature_mixes_through_the_xml_loader(seed, tmp_path):
     """The same random scenes written as scene XML and read by the C++ loader (yafaray_xml.cpp): parameter parsing,
     defaults and list order of the loader against the direct Interface calls of the test above."""
-    if pipeline == "megakernel":
-        pytest.skip("the one-kernel pipeline renders the single-pass pinhole diffuse subset only")
     from tests import xml_writer
     sc, rd, w, h, base, kw = _feature_mix(seed, textures=False)      # (texels in memory have no place in a scene file)
     sc = dict(sc, vnormals=None)                     # the writer emits positions and faces only
@@ -1526,12 +1468,10 @@ def test_random_feature_mixes_through_the_xml_loader(seed, pipeline, tmp_path):
 
 @pytest.mark.timeout(180)
 @pytest.mark.parametrize("kind", ["needles", "cluster", "scales", "sheets", "duplicates", "grid"])
-def test_render_odd_geometry(kind, pipeline):
+def test_render_odd_geometry(kind):
     """A frame of geometry that stresses builder and traversal (tests/test_gpu_device_build.py), lit and path traced:
     the wavefront traversal with its short stack and restarts, leaves of hundreds of coincident triangles, hit-distance
     ties between duplicates."""
-    if pipeline == "megakernel":
-        pytest.skip("one pipeline is enough here")
     from tests.test_gpu_device_build import _odd_geometry
     rng = np.random.default_rng(11)
     verts = _odd_geometry(kind, rng, 3000)

@@ -18,11 +18,6 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-@pytest.fixture(autouse=True)
-def wavefront_only(monkeypatch):
-    monkeypatch.setenv("YAFGPU_PIPELINE", "wavefront")     # the one-kernel pipeline refuses shader nodes (error -15)
-
-
 def _one_triangle_scene(yi, mat_handle, cam):
     yi.paramsClearAll()
     yi.paramsSet({"type": "pointlight", "from": (0.0, 0.0, 3.0), "color": ("color", 1.0, 1.0, 1.0), "power": 1.0})

@@ -1,6 +1,5 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ["YAFGPU_PIPELINE"] = "wavefront"
 import numpy as np
 from libyafaray_amd import Interface, scenes, interface
 from oracle import pyoracle as po

@@ -1,7 +1,6 @@
 """diagnostic (GPU): feature mix N against the oracle, with features switched off one at a time"""
 import os, sys, copy
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ["YAFGPU_PIPELINE"] = "wavefront"
 import numpy as np
 from libyafaray_amd import Interface, scenes, interface
 from oracle import pyoracle as po

@@ -2,7 +2,6 @@
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ["YAFGPU_PIPELINE"] = "wavefront"
 from tests import test_gpu_parity as T
 
 seed = int(sys.argv[1])

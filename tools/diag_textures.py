@@ -1,7 +1,6 @@
 """diagnostic (GPU): where do textured renders differ from the oracle in the last bits?"""
 import os, sys, copy
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ["YAFGPU_PIPELINE"] = "wavefront"
 import numpy as np
 from libyafaray_amd import Interface, scenes
 from oracle import pyoracle as po

@@ -1,6 +1,6 @@
 """GPU-box probe: what ray ORDER is worth to the traversal.  Random rays in the metric scene (origins uniform in the box, directions uniform)
 through yafaray_intersectRays / shadowRays, once in random order, once sorted by the Morton code of their origin cell at several grid sizes.
-Run under `rocprofv3 --kernel-trace --stats`: the trace_kernel launches appear in call order (one closest-hit + one any-hit per ordering)."""
+Run under `rocprofv3 --kernel-trace --stats`: the wf_trace launches appear in call order (one closest-hit + one any-hit per ordering)."""
 import sys
 import time
 
