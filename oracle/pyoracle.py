@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "liboracle.so")
 
 MAT_SHINYDIFFUSE, MAT_GLOSSY, MAT_LIGHT = 0, 1, 2
-LIGHT_AREA, LIGHT_POINT = 0, 1
+LIGHT_AREA, LIGHT_POINT, LIGHT_DIRECTIONAL, LIGHT_SUN, LIGHT_SPHERE = 0, 1, 2, 3, 4
 INTEGRATOR_PATH, INTEGRATOR_DIRECT = 0, 1
 FILTER_BOX, FILTER_MITCHELL, FILTER_GAUSS, FILTER_LANCZOS = 0, 1, 2, 3
 
@@ -283,6 +283,14 @@ def lib():
     L.yor_arealight_intersect.argtypes = [C.POINTER(LightDesc), fp, fp, fp]
     L.yor_pointlight_illuminate.restype = C.c_int
     L.yor_pointlight_illuminate.argtypes = [C.POINTER(LightDesc), fp, fp]
+    L.yor_directional_illuminate.restype = C.c_int
+    L.yor_directional_illuminate.argtypes = [C.POINTER(LightDesc), fp, fp]
+    L.yor_sun_illum_sample.restype = C.c_int
+    L.yor_sun_illum_sample.argtypes = [C.POINTER(LightDesc), C.c_float, C.c_float, fp]
+    L.yor_sun_intersect.restype = C.c_int
+    L.yor_sun_intersect.argtypes = [C.POINTER(LightDesc), fp, fp]
+    L.yor_sphere_illum_sample.restype = C.c_int
+    L.yor_sphere_illum_sample.argtypes = [C.POINTER(LightDesc), fp, C.c_float, C.c_float, fp]
     L.yor_material_transparency.argtypes = [C.POINTER(MaterialDesc), fp, fp]
     L.yor_material_specular.argtypes = [C.POINTER(MaterialDesc), fp, C.c_int32, C.POINTER(C.c_int32), fp, C.POINTER(C.c_float)]
     L.yor_material_probe.argtypes = [C.POINTER(MaterialDesc), fp, C.c_int32, C.POINTER(C.c_int32), fp, fp,
@@ -418,6 +426,23 @@ def light_desc(l):
     elif l["type"] == "pointlight":
         d.type = LIGHT_POINT
         d.corner = f3(*l.get("from", (0, 0, 0)))
+    elif l["type"] == "directionallight":
+        # the overlay of yor_light_desc (yaf_oracle.h): pad0 = infinite, point1 = direction, corner = from, pad1[0] = radius
+        d.type = LIGHT_DIRECTIONAL
+        d.point1 = f3(*l.get("direction", (0, 0, 1)))
+        d.pad0 = int(l.get("infinite", True))
+        d.corner = f3(*l.get("from", l.get("position", (0, 0, 0))))
+        d.pad1 = f3(l.get("radius", 1.0), 0.0, 0.0)
+    elif l["type"] == "sunlight":
+        d.type = LIGHT_SUN
+        d.samples = l.get("samples", 4)
+        d.point1 = f3(*l.get("direction", (0, 0, 1)))
+        d.pad1 = f3(0.0, l.get("angle", 0.27), 0.0)
+    elif l["type"] == "spherelight":
+        d.type = LIGHT_SPHERE
+        d.samples = l.get("samples", 4)
+        d.corner = f3(*l.get("from", (0, 0, 0)))
+        d.pad1 = f3(l.get("radius", 1.0), 0.0, 0.0)
     else:
         raise ValueError(l["type"])
     return d

@@ -44,6 +44,15 @@
 // camera, QMC and PRNG — produce these per-sample colours, in this order, with these ray queries.  Rows K1/K2/G1/G2/S1
 // (traversal, triangle test, getSurface, scene wrappers) and F1 (the film filter) stay pinned only as DESIGN.md §2 says.
 //
+// `ref_integrator lights` emits a SECOND document instead: the same room, film and tile size with six cases on the directional, sun
+// and sphere lights (light_directional.cc, light_sun.cc, light_sphere.cc, linked like the other two light sources), stored as
+// ref_integrator_lights_{fast,ieee}.json.gz.  None of the paths these cases run calls Scene::getSceneBound (only the lights' init()
+// does, for photon emission), so the harness gives it no body.  Each of these cases also carries `lit_share`, one number per light:
+// of the light samples doLightEstimation asked that light for (illuminate / illumSample calls), the share that the light took, that
+// arrived on the side of the surface the viewer is on, and whose shadow query found nothing in the way — counted in a second render
+// of the case with every light wrapped in a forwarding proxy, which must reproduce the first render's samples bit for bit.  The
+// driver refuses to emit a case in which a light does not reach the scene (see check_lit_share).
+//
 // Output: one JSON document on stdout: the scene (reference parameter names, so that tests can hand the same
 // description to the oracle and to the device through the C API) and per case the recorded samples and the first
 // ray queries as IEEE-754 bit patterns.  tests/golden/make_golden.py stores it as ref_integrator_{fast,ieee}.json.gz.
@@ -83,6 +92,9 @@
 #include "material/material_rough_glass.h"
 #include "light/light_area.h"
 #include "light/light_point.h"
+#include "light/light_directional.h"
+#include "light/light_sun.h"
+#include "light/light_sphere.h"
 #include "volume/volumehandler_beer.h"
 #include "common/environment.h"
 
@@ -109,6 +121,18 @@ struct RayRec { float from[3], dir[3], tmin, tmax_in; int tri; float t; };
 static std::vector<RayRec> g_ray_log;
 static size_t g_ray_log_cap = 0;
 static uint64_t g_n_closest = 0, g_n_shadow = 0;
+
+// lit_share bookkeeping (see the header): the direction of the last closest-hit query that found something, the light sample that
+// waits for its shadow query, and per light the samples asked for / lit
+static Vec3 g_last_hit_dir(0.f);
+static int g_pending_light = -1;
+static std::vector<uint64_t> g_light_asked, g_light_lit;
+static inline void shadow_verdict(bool shadowed)
+{
+	if(g_pending_light < 0) return;
+	if(!shadowed) ++g_light_lit[(size_t)g_pending_light];
+	g_pending_light = -1;
+}
 
 // arithmetic of Triangle::intersect (include/common/triangle.h:223-259), on the harness's own triangle record
 static inline bool tri_hit(const HTri &tr, const Ray &ray, float &t, float &u, float &v)
@@ -182,6 +206,7 @@ static bool closest_hit(const Ray &ray, SurfacePoint &sp)
 		g_ray_log.push_back(r);
 	}
 	if(hit_tri < 0) return false;
+	g_last_hit_dir = ray.dir_;
 	Point3 h = ray.from_ + z * ray.dir_;
 	fill_sp(sp, hit_tri, h, hu, hv);
 	sp.origin_ = nullptr;
@@ -252,9 +277,10 @@ bool Scene::isShadowed(RenderState &state, const Ray &ray, float &obj_index, flo
 		if(t < dis && t >= 0.f)
 		{
 			const Visibility vis = g_tris[i].mat->getVisibility();
-			if(vis == NormalVisible || vis == InvisibleShadowsOnly) return true;
+			if(vis == NormalVisible || vis == InvisibleShadowsOnly) { shadow_verdict(true); return true; }
 		}
 	}
+	shadow_verdict(false);
 	return false;
 }
 
@@ -295,6 +321,7 @@ bool Scene::isShadowed(RenderState &state, const Ray &ray, int max_depth, Rgb &f
 		}
 	}
 	state.userdata_ = odat;
+	shadow_verdict(isect);
 	return isect;
 }
 
@@ -366,7 +393,7 @@ static P pf(const char *n, double v) { P p; p.kind = P::F; p.name = n; p.f = v; 
 static P ps(const char *n, const char *v) { P p; p.kind = P::S; p.name = n; p.s = v; return p; }
 static P pv(const char *n, double x, double y, double z) { P p; p.kind = P::V3; p.name = n; p.v[0] = x; p.v[1] = y; p.v[2] = z; return p; }
 
-static bool is_point_key(const std::string &k) { return k == "from" || k == "to" || k == "up" || k == "corner" || k == "point1" || k == "point2"; }
+static bool is_point_key(const std::string &k) { return k == "from" || k == "to" || k == "up" || k == "corner" || k == "point1" || k == "point2" || k == "direction"; }
 
 static ParamMap to_map(const Params &ps_)
 {
@@ -442,9 +469,60 @@ static Light *make_light(const Params &ps_)
 	const std::string t = find(ps_, "type")->s;
 	if(t == "arealight") return AreaLight::factory(m, fake_env());
 	if(t == "pointlight") return PointLight::factory(m, fake_env());
+	if(t == "directionallight") return DirectionalLight::factory(m, fake_env());
+	if(t == "sunlight") return SunLight::factory(m, fake_env());
+	if(t == "spherelight") return SphereLight::factory(m, fake_env());
 	fprintf(stderr, "unknown light type %s\n", t.c_str());
 	exit(2);
 }
+
+// A light that forwards every call doLightEstimation makes to the reference's light and counts (lit_share, see the header).  Only the
+// second, counting render of a `lights` case uses it; the fixture's samples come from the first render, on the lights themselves.
+class CountingLight final : public Light
+{
+	public:
+		CountingLight(const Light *inner, int index): Light(inner->getFlags()), inner_(inner), index_(index)
+		{
+			light_enabled_ = inner->lightEnabled(); cast_shadows_ = inner->castShadows(); shoot_caustic_ = inner->shootsCausticP();
+			shoot_diffuse_ = inner->shootsDiffuseP(); photon_only_ = inner->photonOnly();
+		}
+		Rgb totalEnergy() const override { return inner_->totalEnergy(); }
+		Rgb emitPhoton(float s_1, float s_2, float s_3, float s_4, Ray &ray, float &ipdf) const override { return inner_->emitPhoton(s_1, s_2, s_3, s_4, ray, ipdf); }
+		bool diracLight() const override { return inner_->diracLight(); }
+		bool canIntersect() const override { return inner_->canIntersect(); }
+		int nSamples() const override { return inner_->nSamples(); }
+		bool illumSample(const SurfacePoint &sp, LSample &s, Ray &wi) const override
+		{
+			const bool ok = inner_->illumSample(sp, s, wi);
+			asked(sp, wi, ok && s.pdf_ > 1e-6f && !s.col_.isBlack());
+			return ok;
+		}
+		bool illuminate(const SurfacePoint &sp, Rgb &col, Ray &wi) const override
+		{
+			const bool ok = inner_->illuminate(sp, col, wi);
+			asked(sp, wi, ok && !col.isBlack());
+			return ok;
+		}
+		bool intersect(const Ray &ray, float &t, Rgb &col, float &ipdf) const override
+		{
+			g_pending_light = -1;          // the BSDF half's shadow query is no light sample
+			return inner_->intersect(ray, t, col, ipdf);
+		}
+	private:
+		void asked(const SurfacePoint &sp, const Ray &wi, bool taken) const
+		{
+			++g_light_asked[(size_t)index_];
+			g_pending_light = -1;
+			if(!taken) return;
+			// on the viewer's side of the surface: wo = -(the ray that found sp)
+			const float cos_wo = -(sp.ng_ * g_last_hit_dir), cos_wi = sp.ng_ * wi.dir_;
+			if(cos_wo * cos_wi <= 0.f) return;
+			if(cast_shadows_ && sp.material_->getReceiveShadows()) g_pending_light = index_;      // the shadow query follows (integrator_montecarlo.cc:102, :176)
+			else ++g_light_lit[(size_t)index_];
+		}
+		const Light *inner_;
+		int index_;
+};
 
 // ---------------------------------------------------------------- the scene
 // A Cornell-style room [-1,1]^3 open toward -y with four objects (slots A-D) whose materials a case chooses, two quad
@@ -565,6 +643,8 @@ struct Case
 	Params render;                     // AA_* etc. by their reference names
 	int srand_seed;                    // srand() before render(): the libc state integrator_tiled.cc:319 draws tile seeds from
 	double background[3];
+	bool count_lit = false;            // the `lights` document: a second, counting render and lit_share (see the header)
+	int partial_light = -1;            // position in `lights` of the light that must reach only part of the scene
 };
 
 static const int W = 20, H = 16, TILE = 8;
@@ -593,11 +673,12 @@ static int pint(const Params &p, const char *n, int def) { const P *q = find(p, 
 static double pflt(const Params &p, const char *n, double def) { const P *q = find(p, n); return q ? q->f : def; }
 static bool pbool(const Params &p, const char *n, bool def) { const P *q = find(p, n); return q ? q->b : def; }
 
-static void run_case(Emit &out, const Case &cs, bool first)
+// one render of a case on the reference's integrators; counting: every light wrapped in a CountingLight
+static void render_case(const Case &cs, bool counting, std::vector<int> &tri_mat, std::vector<Params> &lights, Params &cam)
 {
 	// geometry with the case's slot materials
 	g_tris.clear();
-	std::vector<int> tri_mat;
+	tri_mat.clear(); lights.clear();
 	for(const Quad &q : g_quads)
 	{
 		const int mat = q.slot < 0 ? -q.slot - 1 : cs.slot_mat[q.slot];
@@ -624,7 +705,7 @@ static void run_case(Emit &out, const Case &cs, bool first)
 	scene.ray_min_dist_ = scene.ray_min_dist_auto_ ? (float)H_MIN_RAYDIST : (float)pflt(cs.render, "adv_min_raydist_value", H_MIN_RAYDIST);   // scene.cc:826
 
 	// lights
-	std::vector<Params> lights;
+	std::vector<Light *> made;
 	for(int li : cs.lights)
 	{
 		Params lp = g_light_params[li];
@@ -638,11 +719,14 @@ static void run_case(Emit &out, const Case &cs, bool first)
 			if(!done) { P r = o; r.name = key; lp.push_back(r); }
 		}
 		lights.push_back(lp);
-		scene.lights_.push_back(make_light(lp));
+		made.push_back(make_light(lp));
+		if(counting) made.push_back(new CountingLight(made.back(), (int)scene.lights_.size()));
+		scene.lights_.push_back(made.back());
 	}
+	g_light_asked.assign(scene.lights_.size(), 0); g_light_lit.assign(scene.lights_.size(), 0); g_pending_light = -1;
 
 	// camera
-	Params cam = {ps("type", "perspective"), pv("from", 0.13, -3.8, 0.21), pv("to", 0.02, 0.0, -0.06), pv("up", 0.13, -3.8, 1.21), pi("resx", W), pi("resy", H), pf("focal", 1.35)};
+	cam = {ps("type", "perspective"), pv("from", 0.13, -3.8, 0.21), pv("to", 0.02, 0.0, -0.06), pv("up", 0.13, -3.8, 1.21), pi("resx", W), pi("resy", H), pf("focal", 1.35)};
 	for(const P &p : cs.camera) cam.push_back(p);
 	ParamMap cam_map = to_map(cam);
 	Camera *camera = PerspectiveCamera::factory(cam_map, fake_env());
@@ -685,6 +769,40 @@ static void run_case(Emit &out, const Case &cs, bool first)
 	srand((unsigned)cs.srand_seed);
 	surf->render(0, &film);
 
+	delete camera;
+	for(Light *l : made) delete l;
+}
+
+// every light of a `lights` case must reach the scene: at least 15 % of its samples lit, the one with the partial cylinder 5 % to 80 %
+static void check_lit_share(const Case &cs, const std::vector<double> &share)
+{
+	for(size_t i = 0; i < share.size(); ++i)
+	{
+		const bool partial = (int)i == cs.partial_light;
+		const bool ok = partial ? (share[i] >= 0.05 && share[i] <= 0.8) : share[i] >= 0.15;
+		if(!ok) { fprintf(stderr, "ref_integrator: case %s: light %zu has lit_share %.4f\n", cs.name, i, share[i]); exit(2); }
+	}
+}
+
+static void run_case(Emit &out, const Case &cs, bool first)
+{
+	std::vector<int> tri_mat; std::vector<Params> lights; Params cam;
+	render_case(cs, false, tri_mat, lights, cam);
+	std::vector<double> lit_share;
+	if(cs.count_lit)
+	{
+		const std::vector<SampleRec> samples = g_samples; const std::vector<int> tile_log = g_tile_log; const std::vector<RayRec> ray_log = g_ray_log;
+		const uint64_t n_closest = g_n_closest, n_shadow = g_n_shadow;
+		render_case(cs, true, tri_mat, lights, cam);
+		bool same = g_samples.size() == samples.size() && g_n_closest == n_closest && g_n_shadow == n_shadow;
+		for(size_t i = 0; same && i < samples.size(); ++i) same = memcmp(&samples[i], &g_samples[i], sizeof(SampleRec)) == 0;
+		if(!same) { fprintf(stderr, "ref_integrator: case %s: the counting render differs from the render on the lights themselves\n", cs.name); exit(2); }
+		for(size_t i = 0; i < g_light_asked.size(); ++i) lit_share.push_back(g_light_asked[i] ? (double)g_light_lit[i] / (double)g_light_asked[i] : 0.0);
+		for(size_t i = 0; i < lit_share.size(); ++i) fprintf(stderr, "case %-26s light %zu: asked %8llu lit_share %.4f\n", cs.name, i, (unsigned long long)g_light_asked[i], lit_share[i]);
+		check_lit_share(cs, lit_share);
+		g_samples = samples; g_tile_log = tile_log; g_ray_log = ray_log;
+	}
+
 	// ---- emit
 	char b[256];
 	if(!first) out.raw(",\n");
@@ -698,6 +816,12 @@ static void run_case(Emit &out, const Case &cs, bool first)
 	snprintf(b, sizeof b, ",\n\"background\": [%.17g, %.17g, %.17g],\n\"srand\": %d, \"n_closest\": %llu, \"n_shadow\": %llu,\n",
 	         cs.background[0], cs.background[1], cs.background[2], cs.srand_seed, (unsigned long long)g_n_closest, (unsigned long long)g_n_shadow);
 	out.raw(b);
+	if(cs.count_lit)
+	{
+		out.raw("\"lit_share\": [");
+		for(size_t i = 0; i < lit_share.size(); ++i) { snprintf(b, sizeof b, "%s%.6f", i ? ", " : "", lit_share[i]); out.raw(b); }
+		out.raw("],\n");
+	}
 	out.arr_i32("tiles4", g_tile_log); out.raw(",\n");
 	std::vector<int> xy; std::vector<uint32_t> sm;
 	for(const SampleRec &r : g_samples)
@@ -721,18 +845,22 @@ static void run_case(Emit &out, const Case &cs, bool first)
 	out.raw("}");
 	fprintf(stderr, "case %-22s samples %6zu  closest %8llu  shadow %8llu\n", cs.name, g_samples.size(), (unsigned long long)g_n_closest, (unsigned long long)g_n_shadow);
 
-	delete camera;
-	for(Light *l : scene.lights_) delete l;
 }
 
-int main()
+static void light_cases(std::vector<Case> &cases);
+
+int main(int argc, char **argv)
 {
+	const bool lights_doc = argc > 1 && std::string(argv[1]) == "lights";
 	logger__.setConsoleMasterVerbosity("mute");
 	logger__.setLogMasterVerbosity("mute");
 	g_passes = new RenderPasses();
 	build_catalogue();
 
 	std::vector<Case> cases;
+	if(lights_doc) light_cases(cases);
+	else
+	{
 	{	// path samples > 1, four bounces (QMC dimensions up to 4*3+4 = 16), one area light with two samples: light- and BSDF-sampling halves of the MIS estimate
 		// on diffuse, Oren-Nayar and glossy (as_diffuse) surfaces; an emitting shinydiffuse sheet; roulette off
 		Case c; c.name = "pt_mis_paths";
@@ -903,6 +1031,7 @@ int main()
 		c.srand_seed = 23; c.background[0] = 0.3; c.background[1] = 0.2; c.background[2] = 0.1;
 		cases.push_back(c);
 	}
+	}
 
 	Emit out;
 	out.raw("{\n\"width\": "); out.raw(std::to_string(W)); out.raw(", \"height\": "); out.raw(std::to_string(H)); out.raw(", \"tile_size\": "); out.raw(std::to_string(TILE));
@@ -921,4 +1050,78 @@ int main()
 	out.raw("\n]\n}\n");
 	fwrite(out.s.data(), 1, out.s.size(), stdout);
 	return 0;
+}
+
+// ---------------------------------------------------------------- the `lights` document
+// Light parameters 3 .. 8 of the catalogue and six cases on them.  Directions point at the light (wi.dir_ = direction_) and leave the room
+// through its open side (-y); the sphere and finite lights sit inside the room.
+static void light_cases(std::vector<Case> &cases)
+{
+	enum { L_AREA = 0, L_POINT = 2, L_DIR_INF, L_SUN, L_SPHERE, L_DIR_FIN, L_SUN_NOSHADOW, L_SPHERE_BIG };
+	g_light_params.push_back({ps("type", "directionallight"), pv("direction", 0.25, -0.9, 0.35), pv("color", 1.0, 0.95, 0.85), pf("power", 0.8)});
+	g_light_params.push_back({ps("type", "sunlight"), pv("direction", -0.3, -0.85, 0.45), pv("color", 1.0, 0.9, 0.75), pf("power", 1.2), pf("angle", 6.0), pi("samples", 2)});
+	g_light_params.push_back({ps("type", "spherelight"), pv("from", 0.4, -0.45, 0.3), pf("radius", 0.1), pv("color", 0.8, 0.9, 1.0), pf("power", 40.0), pi("samples", 2)});
+	// a cylinder of radius 0.45 that comes down on the right half of the floor's front and ends at `from`, below the ceiling
+	g_light_params.push_back({ps("type", "directionallight"), pv("direction", 0.05, -0.1, 1.0), pv("color", 0.9, 1.0, 0.8), pf("power", 1.5), pb("infinite", false),
+	                          pv("from", 0.45, -0.55, 0.8), pf("radius", 0.45)});
+	g_light_params.push_back({ps("type", "sunlight"), pv("direction", 0.5, -0.7, 0.3), pv("color", 0.7, 0.8, 1.0), pf("power", 0.6), pf("angle", 2.0), pi("samples", 1), pb("cast_shadows", false)});
+	// two vertices of the slot C sheet, (0.47, -0.05, -0.18) and (-0.22, -0.27, -0.14), lie inside this one: illumSample refuses the points in it
+	g_light_params.push_back({ps("type", "spherelight"), pv("from", 0.125, -0.16, -0.16), pf("radius", 0.4), pv("color", 1.0, 0.95, 0.9), pf("power", 6.0), pi("samples", 3)});
+
+	{	// estimateAllDirectLight over five light types (five l_offs values) under the direct-lighting integrator, recursion through a mirror sheet
+		Case c; c.name = "dl_all_light_types"; c.count_lit = true;
+		c.slot_mat[SLOT_A] = M_GLOSSY; c.slot_mat[SLOT_B] = M_GREEN_ON; c.slot_mat[SLOT_C] = M_MIRROR; c.slot_mat[SLOT_D] = M_WHITE;
+		c.lights = {L_AREA, L_POINT, L_DIR_INF, L_SUN, L_SPHERE};
+		c.light_override = {pi("4:samples", 3)};
+		c.integrator = {ps("type", "directlighting"), pi("raydepth", 2), pb("caustics", false), pb("do_AO", false)};
+		c.render = {pi("AA_passes", 1), pi("AA_minsamples", 2)};
+		c.srand_seed = 31; c.background[0] = 0.02; c.background[1] = 0.03; c.background[2] = 0.05;
+		cases.push_back(c);
+	}
+	{	// the sun alone: both halves of the MIS pair (SunLight::illumSample and ::intersect) on glossy, Oren-Nayar and mirror materials; one light, roulette off
+		Case c; c.name = "pt_sun_mis"; c.count_lit = true;
+		c.slot_mat[SLOT_A] = M_GLOSSY; c.slot_mat[SLOT_B] = M_GREEN_ON; c.slot_mat[SLOT_C] = M_MIRROR; c.slot_mat[SLOT_D] = M_WHITE;
+		c.lights = {L_SUN};
+		c.integrator = {ps("type", "pathtracing"), pi("path_samples", 2), pi("bounces", 3), pi("russian_roulette_min_bounces", 3), pi("raydepth", 2), ps("caustic_type", "none")};
+		c.render = {pi("AA_passes", 1), pi("AA_minsamples", 2)};
+		c.srand_seed = 32; c.background[0] = 0.05; c.background[1] = 0.06; c.background[2] = 0.08;
+		cases.push_back(c);
+	}
+	{	// the sphere alone: canIntersect() is false, so the light half carries no MIS weight and there is no BSDF half; points inside the sphere get nothing
+		Case c; c.name = "pt_sphere_only"; c.count_lit = true;
+		c.slot_mat[SLOT_A] = M_GLOSSY; c.slot_mat[SLOT_B] = M_WHITE; c.slot_mat[SLOT_C] = M_RED; c.slot_mat[SLOT_D] = M_GREEN_ON;
+		c.lights = {L_SPHERE_BIG};
+		c.integrator = {ps("type", "pathtracing"), pi("path_samples", 1), pi("bounces", 3), pi("russian_roulette_min_bounces", 3), pi("raydepth", 2), ps("caustic_type", "none")};
+		c.render = {pi("AA_passes", 1), pi("AA_minsamples", 2)};
+		c.srand_seed = 33; c.background[0] = 0.0; c.background[1] = 0.0; c.background[2] = 0.0;
+		cases.push_back(c);
+	}
+	{	// the one-light counter over five types with the roulette stream and a base sampling offset; the finite directional light reaches part of the floor only
+		Case c; c.name = "pt_five_types_rr"; c.count_lit = true; c.partial_light = 2;
+		c.slot_mat[SLOT_A] = M_GLOSSY; c.slot_mat[SLOT_B] = M_RED; c.slot_mat[SLOT_C] = M_GREEN_ON; c.slot_mat[SLOT_D] = M_WHITE;
+		c.lights = {L_AREA, L_POINT, L_DIR_FIN, L_SUN, L_SPHERE};
+		c.integrator = {ps("type", "pathtracing"), pi("path_samples", 1), pi("bounces", 4), pi("russian_roulette_min_bounces", 1), pi("raydepth", 2), ps("caustic_type", "none")};
+		c.render = {pi("AA_passes", 1), pi("AA_minsamples", 3), pi("adv_base_sampling_offset", 53)};
+		c.srand_seed = 34; c.background[0] = 0.0; c.background[1] = 0.0; c.background[2] = 0.0;
+		cases.push_back(c);
+	}
+	{	// endless shadow rays (tmax = -1) of an infinite directional light and a sun through the transparent sheet of slot D; a second sun that casts no shadows
+		Case c; c.name = "pt_lights_transp_shadows"; c.count_lit = true;
+		c.slot_mat[SLOT_A] = M_WHITE; c.slot_mat[SLOT_B] = M_GLOSSY; c.slot_mat[SLOT_C] = M_RED; c.slot_mat[SLOT_D] = M_SD_TRANSP;
+		c.lights = {L_DIR_INF, L_SUN, L_SUN_NOSHADOW};
+		c.integrator = {ps("type", "pathtracing"), pi("path_samples", 1), pi("bounces", 2), pi("russian_roulette_min_bounces", 2), pi("raydepth", 2), ps("caustic_type", "none"),
+		                pb("transpShad", true), pi("shadowDepth", 2)};
+		c.render = {pi("AA_passes", 1), pi("AA_minsamples", 2)};
+		c.srand_seed = 35; c.background[0] = 0.0; c.background[1] = 0.0; c.background[2] = 0.0;
+		cases.push_back(c);
+	}
+	{	// three passes with a light-sample multiplier of 1.5: ceil(samples * multiplier) grows over the passes for the sun (2 samples) and the sphere
+		Case c; c.name = "pt_sun_multipass"; c.count_lit = true;
+		c.slot_mat[SLOT_A] = M_GLOSSY; c.slot_mat[SLOT_B] = M_WHITE; c.slot_mat[SLOT_C] = M_RED; c.slot_mat[SLOT_D] = M_GREEN_ON;
+		c.lights = {L_SUN, L_SPHERE};
+		c.integrator = {ps("type", "pathtracing"), pi("path_samples", 1), pi("bounces", 3), pi("russian_roulette_min_bounces", 2), pi("raydepth", 2), ps("caustic_type", "none")};
+		c.render = {pi("AA_passes", 3), pi("AA_minsamples", 2), pi("AA_inc_samples", 2), pf("AA_threshold", 0.0), pf("AA_light_sample_multiplier_factor", 1.5)};
+		c.srand_seed = 36; c.background[0] = 0.0; c.background[1] = 0.0; c.background[2] = 0.0;
+		cases.push_back(c);
+	}
 }

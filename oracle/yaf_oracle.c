@@ -472,9 +472,19 @@ typedef struct
 	v3 corner, c2, c3, c4, to_x, to_y, normal, fnormal;
 	rgb color;
 	float area, inv_area;
-	/* point, light_point.cc:28-36 */
+	/* point, light_point.cc:28-36; directional: position_; sphere: center_ */
 	v3 position;
+	/* directional (light_directional.cc:31-42), sun (light_sun.cc:29-42), sphere (light_sphere.cc:31-41) */
+	int infinite;
+	v3 direction, du, dv;
+	float radius, cos_angle, invpdf, pdf;
+	rgb col_pdf;
+	float square_radius, square_radius_epsilon;
 } light_t;
+/* Light::diracLight() (light_point.h, light_directional.h) and Light::canIntersect() (light_area.h, light_sun.h; the sphere light keeps the
+ * base class's false, light.h:77) */
+static inline int light_is_dirac(const light_t *l) { return l->type == YOR_LIGHT_POINT || l->type == YOR_LIGHT_DIRECTIONAL; }
+static inline int light_can_intersect(const light_t *l) { return l->type == YOR_LIGHT_AREA || l->type == YOR_LIGHT_SUN; }
 
 typedef struct
 {
@@ -3011,6 +3021,36 @@ static void light_configure(light_t *l, const yor_light_desc *d)
 		l->c3 = vadd(l->corner, vadd(l->to_x, l->to_y));
 		l->c4 = vadd(l->corner, l->to_y);
 	}
+	else if(d->type == YOR_LIGHT_DIRECTIONAL)
+	{	/* factory light_directional.cc:118-158 (from and radius are read for a finite light only), ctor :31-42 */
+		l->infinite = d->pad0 != 0;
+		l->position = l->infinite ? V(0, 0, 0) : V(d->corner[0], d->corner[1], d->corner[2]);
+		l->radius = l->infinite ? 1.f : d->pad1[0];
+		l->color = cscale(col, d->power);
+		l->direction = vnormalize(V(d->point1[0], d->point1[1], d->point1[2]));
+		create_cs(l->direction, &l->du, &l->dv);
+	}
+	else if(d->type == YOR_LIGHT_SUN)
+	{	/* light_sun.cc:29-42: the frame is built from the direction AS GIVEN (:36), the angle is clamped to 80 degrees */
+		v3 dir = V(d->point1[0], d->point1[1], d->point1[2]);
+		l->color = cscale(col, d->power);
+		l->direction = vnormalize(dir);
+		create_cs(dir, &l->du, &l->dv);
+		float angle = d->pad1[1];
+		if(angle > 80.f) angle = 80.f;
+		l->cos_angle = yor_fcos((float)((double)angle * 0.01745329251994329576922)); /* DEG_TO_RAD, util_math_optimizations.h:94 */
+		l->invpdf = (float)(Y_M_2PI * (double)(1.f - l->cos_angle));
+		l->pdf = (float)(1.0 / (double)l->invpdf);
+		l->col_pdf = cscale(l->color, l->pdf);
+	}
+	else if(d->type == YOR_LIGHT_SPHERE)
+	{	/* light_sphere.cc:31-41 */
+		l->position = V(d->corner[0], d->corner[1], d->corner[2]);
+		l->radius = d->pad1[0];
+		l->color = cscale(col, d->power);
+		l->square_radius = l->radius * l->radius;
+		l->square_radius_epsilon = (float)((double)l->square_radius * 1.000003815);
+	}
 	else
 	{	/* light_point.cc:28-36 */
 		l->position = V(d->corner[0], d->corner[1], d->corner[2]);
@@ -3085,6 +3125,102 @@ static int pointlight_illuminate(const light_t *l, v3 sp_p, rgb *col, v3 *wi_dir
 	*wi_dir = ldir;
 	*col = cscale(l->color, (float)idist_sqr);
 	return 1;
+}
+
+/* DirectionalLight::illuminate, light_directional.cc:60-81 */
+static int directional_illuminate(const light_t *l, v3 sp_p, rgb *col, v3 *wi_dir, float *wi_tmax)
+{
+	if(!l->infinite)
+	{
+		v3 vec = vsub(l->position, sp_p);
+		float dist = vlength(vcross(l->direction, vec));
+		if(dist > l->radius) return 0;
+		*wi_tmax = vdot(vec, l->direction);
+		if(*wi_tmax <= 0.0) return 0;
+	}
+	else *wi_tmax = -1.f;
+	*wi_dir = l->direction;
+	*col = l->color;
+	return 1;
+}
+/* sampleCone__, util_sample.h:80-86 */
+static v3 sample_cone(v3 d, v3 u, v3 v, float max_cos_ang, float s_1, float s_2)
+{
+	float cos_ang = 1.f - (1.f - max_cos_ang) * s_2;
+	float sin_ang = yor_fsqrt(1.f - cos_ang * cos_ang);
+	float t_1 = (float)(Y_M_2PI * (double)s_1);
+	return vadd(vmul(vadd(vmul(u, yor_fcos(t_1)), vmul(v, yor_fsin(t_1))), sin_ang), vmul(d, cos_ang));
+}
+/* SunLight::illumSample, light_sun.cc:53-66 */
+static int sun_illum_sample(const light_t *l, float s_1, float s_2, v3 *wi_dir, float *wi_tmax, float *pdf, rgb *col)
+{
+	*wi_dir = sample_cone(l->direction, l->du, l->dv, l->cos_angle, s_1, s_2);
+	*wi_tmax = -1.f;
+	*col = l->col_pdf;
+	*pdf = l->pdf;
+	return 1;
+}
+/* SunLight::intersect, light_sun.cc:68-76 */
+static int sun_intersect(const light_t *l, v3 dir, float *t, rgb *col, float *ipdf)
+{
+	float cosine = vdot(dir, l->direction);
+	if(cosine < l->cos_angle) return 0;
+	*col = l->col_pdf;
+	*t = -1.f;
+	*ipdf = l->invpdf;
+	return 1;
+}
+/* sphereIntersect__, light_sphere.cc:57-69: the literals 2.0 and 4.0 make those products double */
+static int sphere_intersect(v3 from, v3 dir, v3 c, float r_2, float *d_1, float *d_2)
+{
+	v3 vf = vsub(from, c);
+	float ea = vdot(dir, dir);
+	float eb = vdot(vmul(vf, (float)2.0), dir);   /* 2.0 * vf is Vec3 operator*(float, Vec3): the factor narrows to float first */
+	float ec = vdot(vf, vf) - r_2;
+	float osc = (float)((double)(eb * eb) - 4.0 * (double)ea * (double)ec);
+	if(osc < 0) { *d_1 = yor_fsqrt(ec / ea); return 0; }
+	osc = yor_fsqrt(osc);
+	*d_1 = (float)((double)(-eb - osc) / (2.0 * (double)ea));
+	*d_2 = (float)((double)(-eb + osc) / (2.0 * (double)ea));
+	return 1;
+}
+/* SphereLight::illumSample, light_sphere.cc:71-103 */
+static int sphere_illum_sample(const light_t *l, v3 sp_p, float s_1, float s_2, v3 *wi_dir, float *wi_tmax, float *pdf, rgb *col)
+{
+	v3 cdir = vsub(l->position, sp_p);
+	float dist_sqr = cdir.x * cdir.x + cdir.y * cdir.y + cdir.z * cdir.z;
+	if(dist_sqr <= l->square_radius) return 0;
+	float dist = yor_fsqrt(dist_sqr);
+	float idist_sqr = 1.f / (dist_sqr);
+	float cos_alpha = yor_fsqrt(1.f - l->square_radius * idist_sqr);
+	cdir = vmul(cdir, 1.f / dist);
+	v3 du, dv;
+	create_cs(cdir, &du, &dv);
+	v3 dir = sample_cone(cdir, du, dv, cos_alpha, s_1, s_2);
+	*wi_dir = dir;                                  /* written before the test below: the ray keeps it when the sample is refused */
+	float d_1, d_2;
+	if(!sphere_intersect(sp_p, dir, l->position, l->square_radius_epsilon, &d_1, &d_2)) return 0;
+	*wi_tmax = d_1;
+	*pdf = 1.f / (2.f * (1.f - cos_alpha));
+	*col = l->color;
+	return 1;
+}
+/* Light::illumSample / Light::intersect of a light that is not Dirac, by type */
+static int light_illum_sample(const light_t *l, v3 sp_p, float s_1, float s_2, v3 *wi_dir, float *wi_tmax, float *pdf, rgb *col)
+{
+	if(l->type == YOR_LIGHT_SUN) return sun_illum_sample(l, s_1, s_2, wi_dir, wi_tmax, pdf, col);
+	if(l->type == YOR_LIGHT_SPHERE) return sphere_illum_sample(l, sp_p, s_1, s_2, wi_dir, wi_tmax, pdf, col);
+	return arealight_illum_sample(l, sp_p, s_1, s_2, wi_dir, wi_tmax, pdf, col);
+}
+static int light_intersect(const light_t *l, v3 from, v3 dir, float *t, rgb *col, float *ipdf)
+{
+	if(l->type == YOR_LIGHT_SUN) return sun_intersect(l, dir, t, col, ipdf);
+	return arealight_intersect(l, from, dir, t, col, ipdf);
+}
+static int light_illuminate(const light_t *l, v3 sp_p, rgb *col, v3 *wi_dir, float *wi_tmax)
+{
+	if(l->type == YOR_LIGHT_DIRECTIONAL) return directional_illuminate(l, sp_p, col, wi_dir, wi_tmax);
+	return pointlight_illuminate(l, sp_p, col, wi_dir, wi_tmax);
 }
 
 /* ------------------------------------------------------------------ camera
@@ -3381,9 +3517,9 @@ static rgb do_light_estimation(rstate_t *st, const light_t *light, const sp_t *s
 	v3 lr_dir = V(0, 0, 0); float lr_tmin = 0.f, lr_tmax = -1.f;
 	rgb lcol = C(0, 0, 0);
 	int cast_shadows = light->cast_shadows && material->receive_shadows;
-	if(light->type == YOR_LIGHT_POINT)
+	if(light_is_dirac(light))
 	{	/* :94-148 */
-		if(pointlight_illuminate(light, sp->p, &lcol, &lr_dir, &lr_tmax))
+		if(light_illuminate(light, sp->p, &lcol, &lr_dir, &lr_tmax))
 		{
 			if(st->rd->shadow_bias_auto) lr_tmin = st->shadow_bias * fmaxf_(1.f, vlength(sp->p));
 			else lr_tmin = st->shadow_bias;
@@ -3409,6 +3545,7 @@ static rgb do_light_estimation(rstate_t *st, const light_t *light, const sp_t *s
 		if(st->ray_division > 1) { n = n / st->ray_division; if(n < 1) n = 1; }      /* :154 */
 		float inv_ns = 1.f / (float)n;
 		unsigned offs = (unsigned)n * st->pixel_sample + st->sampling_offs + l_offs;
+		const int can_intersect = light_can_intersect(light);                         /* :157 */
 		rgb ccol = C(0, 0, 0);
 		halton_set_start(&hal_2, offs - 1);
 		halton_set_start(&hal_3, offs - 1);
@@ -3417,7 +3554,7 @@ static rgb do_light_estimation(rstate_t *st, const light_t *light, const sp_t *s
 			float ls_s1 = halton_next(&hal_2);
 			float ls_s2 = halton_next(&hal_3);
 			float ls_pdf; rgb ls_col;
-			if(arealight_illum_sample(light, sp->p, ls_s1, ls_s2, &lr_dir, &lr_tmax, &ls_pdf, &ls_col))
+			if(light_illum_sample(light, sp->p, ls_s1, ls_s2, &lr_dir, &lr_tmax, &ls_pdf, &ls_col))
 			{
 				if(st->rd->shadow_bias_auto) lr_tmin = st->shadow_bias * fmaxf_(1.f, vlength(sp->p));
 				else lr_tmin = st->shadow_bias;
@@ -3431,9 +3568,9 @@ static rgb do_light_estimation(rstate_t *st, const light_t *light, const sp_t *s
 					if(tr_shad && cast_shadows) ls_col = cmul(ls_col, scol);          /* :182 */
 					rgb surf_col = mat_eval(material, dat, sp, wo, lr_dir, BSDF_ALL);
 					float angle_light_normal = (material->flat ? 1.f : fabsf(vdot(sp->n, lr_dir)));
-					/* canIntersect() is true for area lights (light_area.h) */
-					float m_pdf = mat_pdf(material, dat, sp, wo, lr_dir, BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_DISPERSIVE | BSDF_REFLECT | BSDF_TRANSMIT);
-					if(m_pdf > 1e-6f)
+					/* :191-248: a light that cannot be intersected takes the unweighted estimate and never asks for the material's pdf */
+					float m_pdf = can_intersect ? mat_pdf(material, dat, sp, wo, lr_dir, BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_DISPERSIVE | BSDF_REFLECT | BSDF_TRANSMIT) : 0.f;
+					if(can_intersect && m_pdf > 1e-6f)
 					{
 						float l_2 = ls_pdf * ls_pdf;
 						float m_2 = m_pdf * m_pdf;
@@ -3448,7 +3585,8 @@ static rgb do_light_estimation(rstate_t *st, const light_t *light, const sp_t *s
 			}
 		}
 		col = cadd(col, cscale(ccol, inv_ns));
-		{	/* BSDF-sampling half of MIS :285-333 */
+		if(can_intersect)
+		{	/* BSDF-sampling half of MIS :273-341 */
 			rgb ccol_2 = C(0, 0, 0);
 			halton_set_start(&hal_2, offs - 1);
 			halton_set_start(&hal_3, offs - 1);
@@ -3464,7 +3602,7 @@ static rgb do_light_estimation(rstate_t *st, const light_t *light, const sp_t *s
 				sm.flags = BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_DISPERSIVE | BSDF_REFLECT | BSDF_TRANSMIT;
 				rgb surf_col = mat_sample(material, dat, sp, wo, &b_dir, &sm, &W);
 				float light_pdf;
-				if(sm.pdf > 1e-6f && arealight_intersect(light, sp->p, b_dir, &b_tmax, &lcol, &light_pdf))
+				if(sm.pdf > 1e-6f && light_intersect(light, sp->p, b_dir, &b_tmax, &lcol, &light_pdf))
 				{
 					rgb scol = C(1.f, 1.f, 1.f);
 					const int tr_shad = st->rd->transp_shad;
@@ -4312,6 +4450,40 @@ int yor_arealight_intersect(const yor_light_desc *ld, const float from[3], const
 	int ok = arealight_intersect(&l, V(from[0], from[1], from[2]), V(dir[0], dir[1], dir[2]), &t, &col, &ipdf);
 	if(!ok) { t = 0; ipdf = 0; col = C(0, 0, 0); }
 	out5[0] = t; out5[1] = ipdf; out5[2] = col.r; out5[3] = col.g; out5[4] = col.b;
+	return ok;
+}
+int yor_directional_illuminate(const yor_light_desc *ld, const float p[3], float out7[7])
+{
+	light_t l; light_configure(&l, ld);
+	v3 dir = V(0, 0, 0); float tmax = 0.f; rgb col = C(0, 0, 0);
+	int ok = directional_illuminate(&l, V(p[0], p[1], p[2]), &col, &dir, &tmax);
+	if(!ok) { dir = V(0, 0, 0); tmax = 0.f; }
+	out7[0] = dir.x; out7[1] = dir.y; out7[2] = dir.z; out7[3] = tmax; out7[4] = col.r; out7[5] = col.g; out7[6] = col.b;
+	return ok;
+}
+int yor_sun_illum_sample(const yor_light_desc *ld, float s1, float s2, float out8[8])
+{
+	light_t l; light_configure(&l, ld);
+	v3 dir = V(0, 0, 0); float tmax = 0.f, pdf = 0.f; rgb col = C(0, 0, 0);
+	int ok = sun_illum_sample(&l, s1, s2, &dir, &tmax, &pdf, &col);
+	out8[0] = dir.x; out8[1] = dir.y; out8[2] = dir.z; out8[3] = tmax; out8[4] = pdf; out8[5] = col.r; out8[6] = col.g; out8[7] = col.b;
+	return ok;
+}
+int yor_sun_intersect(const yor_light_desc *ld, const float dir[3], float out5[5])
+{
+	light_t l; light_configure(&l, ld);
+	float t = 0.f, ipdf = 0.f; rgb col = C(0, 0, 0);
+	int ok = sun_intersect(&l, V(dir[0], dir[1], dir[2]), &t, &col, &ipdf);
+	out5[0] = t; out5[1] = ipdf; out5[2] = col.r; out5[3] = col.g; out5[4] = col.b;
+	return ok;
+}
+int yor_sphere_illum_sample(const yor_light_desc *ld, const float p[3], float s1, float s2, float out8[8])
+{
+	light_t l; light_configure(&l, ld);
+	v3 dir = V(0, 0, 0); float tmax = 0.f, pdf = 0.f; rgb col = C(0, 0, 0);
+	int ok = sphere_illum_sample(&l, V(p[0], p[1], p[2]), s1, s2, &dir, &tmax, &pdf, &col);
+	if(!ok) { dir = V(0, 0, 0); tmax = 0.f; pdf = 0.f; col = C(0, 0, 0); }
+	out8[0] = dir.x; out8[1] = dir.y; out8[2] = dir.z; out8[3] = tmax; out8[4] = pdf; out8[5] = col.r; out8[6] = col.g; out8[7] = col.b;
 	return ok;
 }
 int yor_pointlight_illuminate(const yor_light_desc *ld, const float p[3], float out7[7])

@@ -6,7 +6,7 @@
  *
  * Pinning status:
  *   - fast-math, QMC, createCs/sampleCosHemisphere, Bound::cross, perspective camera (pinhole and
- *     depth of field), area/point lights, shinydiffuse/glossy/coated-glossy/glass/rough-glass/mirror/light
+ *     depth of field), area/point/directional/sun/sphere lights, shinydiffuse/glossy/coated-glossy/glass/rough-glass/mirror/light
  *     materials (eval, pdf, sample — rough glass also its two-direction sample —, getSpecular, getAlpha,
  *     getTransparency), BeerVolumeHandler (glass absorption), image textures, shader nodes and image decoders
  *     are pinned bit-for-bit against the reference's own sources compiled here (oracle/_ref, IEEE build) and
@@ -38,7 +38,7 @@ enum { YOR_MAT_SHINYDIFFUSE = 0, YOR_MAT_GLOSSY = 1, YOR_MAT_LIGHT = 2,
        YOR_MAT_MIRROR = 4,  /* color, specular_reflect = reflect */
        YOR_MAT_COATED_GLOSSY = 5, /* glossy's fields + mirror_color, specular_reflect = mirror strength, ior = IOR */
        YOR_MAT_ROUGH_GLASS = 6 /* color = filter_color, mirror_color, ior = IOR, transmit_filter (float), fresnel_effect = fake_shadows, rough_alpha = alpha, absorption */ };
-enum { YOR_LIGHT_AREA = 0, YOR_LIGHT_POINT = 1 };
+enum { YOR_LIGHT_AREA = 0, YOR_LIGHT_POINT = 1, YOR_LIGHT_DIRECTIONAL = 2, YOR_LIGHT_SUN = 3, YOR_LIGHT_SPHERE = 4 };
 enum { YOR_INTEGRATOR_PATH = 0, YOR_INTEGRATOR_DIRECT = 1 };
 enum { YOR_FILTER_BOX = 0, YOR_FILTER_MITCHELL = 1, YOR_FILTER_GAUSS = 2, YOR_FILTER_LANCZOS = 3 };
 
@@ -150,18 +150,24 @@ typedef struct yor_node_desc
 	float bump_strength;       /* texture_mapper "bump_strength" (factory default 1) */
 } yor_node_desc;
 
+/* Parameter-level light description.  The directional, sun and sphere lights overlay the fields the area light does not need
+ * (the struct keeps its size and layout, tests/test_abi.py):
+ *   directional (light_directional.cc:118-158): pad0 = infinite, point1 = direction, corner = from, pad1[0] = radius
+ *   sun         (light_sun.cc:96-125):          point1 = direction, pad1[1] = angle in degrees, samples
+ *   sphere      (light_sphere.cc:165-195):      corner = from, pad1[0] = radius, samples
+ * colour, power and cast_shadows mean the same for every type; a directional light ignores samples. */
 typedef struct yor_light_desc
 {
 	int32_t type;
 	int32_t samples;
 	int32_t cast_shadows;
-	int32_t pad0;
-	float corner[3];   /* area: corner; point: position */
-	float point1[3];
+	int32_t pad0;      /* directional: infinite */
+	float corner[3];   /* area: corner; point: position; directional, sphere: from */
+	float point1[3];   /* area: point1; directional, sun: direction */
 	float point2[3];
 	float color[3];
 	float power;
-	float pad1[3];
+	float pad1[3];     /* [0] directional, sphere: radius; [1] sun: angle */
 } yor_light_desc;
 
 typedef struct yor_camera_desc
@@ -315,6 +321,11 @@ void yor_camera_shoot_lens(const yor_camera_desc *cam, float px, float py, float
 int yor_arealight_illum_sample(const yor_light_desc *l, const float p[3], float s1, float s2, float out8[8]);
 int yor_arealight_intersect(const yor_light_desc *l, const float from[3], const float dir[3], float out5[5]);
 int yor_pointlight_illuminate(const yor_light_desc *l, const float p[3], float out7[7]);
+/* out7 = wi.dir_, wi.tmax_, colour; out8 = wi.dir_, wi.tmax_, s.pdf_, s.col_; out5 = t, ipdf, colour */
+int yor_directional_illuminate(const yor_light_desc *l, const float p[3], float out7[7]);
+int yor_sun_illum_sample(const yor_light_desc *l, float s1, float s2, float out8[8]);
+int yor_sun_intersect(const yor_light_desc *l, const float dir[3], float out5[5]);
+int yor_sphere_illum_sample(const yor_light_desc *l, const float p[3], float s1, float s2, float out8[8]);
 /* in14 = n, ng, wo, wl, s1, s2 ; outputs as in the harness */
 /* Material::getTransparency(sp, wo) */
 void yor_material_transparency(const yor_material_desc *m, const float in14[14], float out3[3]);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Regenerate tests/golden/ref_components_{fast,ieee}.json.gz (and their textures / integrator siblings, and
+"""Regenerate tests/golden/ref_components_{fast,ieee}.json.gz (and their textures / lights / integrator siblings, and
 faure_tables.json.gz).
 
 Runs ONLY in the build container (needs /root/reference).  It builds the component-level
@@ -27,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 def main():
     if not os.path.isdir("/root/reference"):
         sys.exit("reference tree not present; fixtures can only be regenerated in the build container")
-    which = sys.argv[1:] or ["components", "textures", "integrator", "faure"]
+    which = sys.argv[1:] or ["components", "textures", "lights", "integrator", "integrator_lights", "faure"]
     if "faure" in which:
         which.remove("faure")
         faure()
@@ -35,8 +35,9 @@ def main():
         subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True, timeout=900)
     for name in which:          # textures: image textures + shader nodes, oracle/ref_harness/ref_textures.cc
         for variant in ("fast", "ieee"):
-            exe = os.path.join(ROOT, "oracle", "_ref", f"ref_{name}_{variant}")
-            out = subprocess.run([exe], check=True, capture_output=True, timeout=120).stdout
+            # integrator_lights: the integrator harness's second document (`ref_integrator lights`: the directional, sun and sphere light cases)
+            exe, *args = (f"ref_{name}_{variant}",) if name != "integrator_lights" else (f"ref_integrator_{variant}", "lights")
+            out = subprocess.run([os.path.join(ROOT, "oracle", "_ref", exe), *args], check=True, capture_output=True, timeout=120).stdout
             out = out[out.index(b"{\n"):]          # the reference's handlers log to stdout before the document starts
             path = os.path.join(HERE, f"ref_{name}_{variant}.json.gz")
             with gzip.GzipFile(path, "wb", mtime=0) as f:

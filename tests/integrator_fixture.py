@@ -1,4 +1,4 @@
-"""Reader of tests/golden/ref_integrator_{ieee,fast}.json.gz — what the reference's own TiledIntegrator::render /
+"""Reader of tests/golden/ref_integrator_{ieee,fast}.json.gz and ref_integrator_lights_{ieee,fast}.json.gz — what the reference's own TiledIntegrator::render /
 renderTile / PathIntegrator::integrate / doLightEstimation / recursiveRaytrace (compiled from /root/reference by
 oracle/Makefile, driver oracle/ref_harness/ref_integrator.cc) produced on the harness's scenes: every sample handed to
 ImageFilm::addSample in call order, the first closest-hit queries, the ray counts.  The geometry query and the film are
@@ -16,8 +16,11 @@ def u2f(a):
     return np.asarray(a, dtype=np.uint32).view(np.float32)
 
 
-def load(variant):
-    with gzip.open(os.path.join(HERE, "golden", f"ref_integrator_{variant}.json.gz"), "rt") as f:
+def load(variant, document="integrator"):
+    """document: "integrator" (the sixteen cases on area and point lights) or "integrator_lights" (six cases on the directional, sun and
+    sphere lights: the harness's second document, same room, film and tile size; each case also holds lit_share, per light the share of
+    its samples that reached the scene)"""
+    with gzip.open(os.path.join(HERE, "golden", f"ref_{document}_{variant}.json.gz"), "rt") as f:
         return json.load(f)
 
 

@@ -29,6 +29,11 @@ def _scene(case):
     if case == "aa":
         sc = scenes.cornell_soup(900, seed=29, res=(W, H))
         rd = scenes.render_settings(W, H, 3, bounces=2, tile_size=T, background=(0.05, 0.1, 0.2), **AA)
+    elif case == "lights_five_types":
+        # one light of each type (area, point, directional, sun, sphere): the counter picks among five, roulette from the first bounce on
+        from tests.lights_fixture import five_light_scene
+        sc = five_light_scene(900, seed=31, res=(W, H))
+        rd = scenes.render_settings(W, H, 3, bounces=4, tile_size=T, background=(0.05, 0.1, 0.2), russian_roulette_min_bounces=1)
     else:
         # two area lights (the light counter picks one per estimate) and Russian roulette from the first bounce on (the per-tile
         # stream decides which paths make further estimates); "lights_aa" carries the counter over adaptive passes as well
@@ -66,7 +71,7 @@ def _worker(rank, world, port, out_path, case):
 
 
 @pytest.mark.timeout(600)
-@pytest.mark.parametrize("case", ["aa", "lights_rr_only", "lights_lc_only", "lights", "lights_aa", "lights_chunks", "lights_one_tile"])
+@pytest.mark.parametrize("case", ["aa", "lights_rr_only", "lights_lc_only", "lights", "lights_aa", "lights_chunks", "lights_one_tile", "lights_five_types"])
 def test_sharded_render_with_cross_rank_state_equals_the_single_gpu_render(tmp_path, monkeypatch, case):
     if case == "lights_chunks":      # several chunks per rank (a tile each): the count pass and the final pass record a chunk's events twice
         monkeypatch.setenv("YAFGPU_WF_CHUNK", "1500")

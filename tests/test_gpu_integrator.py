@@ -1,4 +1,5 @@
-"""The device path against the reference's OWN integrators (tests/golden/ref_integrator_ieee.json.gz: the reference's
+"""The device path against the reference's OWN integrators (tests/golden/ref_integrator_ieee.json.gz and
+ref_integrator_lights_ieee.json.gz — the latter: six cases on the directional, sun and sphere lights —: the reference's
 TiledIntegrator::render / renderTile / PathIntegrator::integrate / doLightEstimation / recursiveRaytrace compiled from
 /root/reference and run on the harness's scenes — see tests/integrator_fixture.py and oracle/ref_harness/ref_integrator.cc).
 
@@ -19,13 +20,30 @@ CASES = ["pt_mis_paths", "pt_three_lights_rr", "pt_recursive", "pt_multipass", "
          "pt_caustics_default", "pt_caustics_path_no_recursive", "dl_rough_glass"]
 
 
+LIGHT_CASES = ["dl_all_light_types", "pt_sun_mis", "pt_sphere_only", "pt_five_types_rr", "pt_lights_transp_shadows", "pt_sun_multipass"]
+
+
 @pytest.fixture(scope="module")
 def doc():
     return load("ieee")
 
 
+@pytest.fixture(scope="module")
+def lights_doc():
+    return load("ieee", "integrator_lights")
+
+
 @pytest.mark.parametrize("name", CASES)
 def test_device_equals_the_reference_integrators(doc, name):
+    device_equals_the_reference(doc, name)
+
+
+@pytest.mark.parametrize("name", LIGHT_CASES)
+def test_device_equals_the_reference_integrators_on_directional_sun_sphere_lights(lights_doc, name):
+    device_equals_the_reference(lights_doc, name)
+
+
+def device_equals_the_reference(doc, name):
     cs = next(c for c in doc["cases"] if c["name"] == name)
     sc, rd = case_scene(doc, cs)
     yi = Interface()

@@ -1,5 +1,6 @@
-"""The directional, sun and sphere lights on the DEVICE: their leaf functions bit for bit against a float32
-restatement in the reference's operation order (probe ops 17-21), renders against closed forms (a diffuse plane under each light,
+"""The directional, sun and sphere lights on the DEVICE: their leaf functions bit for bit against the reference's own light sources
+(tests/golden/ref_lights_ieee, probe ops 17-20) and against a float32 restatement in the reference's operation order (probe ops 17-21:
+the static sphereIntersect__ has no fixture), a scene with all five light types against the oracle, renders against closed forms (a diffuse plane under each light,
 infinite and finite directional shadows, transparent shadows on infinite rays, the sun's cone, the sphere's cap), the light-sampling
 half only for the sphere (no BSDF-half rays), the serial-state replay with sharding and pass pipelining."""
 import ctypes as C
@@ -8,10 +9,11 @@ import numpy as np
 import pytest
 
 from libyafaray_amd import Interface, scenes
-from oracle import pyoracle as po          # film_to_rgb and the material probe only: the oracle does not take these lights
+from oracle import pyoracle as po
+from tests import lights_fixture
 from tests.test_gpu_components import exact
 from tests.test_lights_host import (F, W_COLOR, W_COLPDF, W_COS, W_DIR, W_DU, W_DV, W_INVPDF, W_PDF, W_POS, W_RAD, W_RAD2, W_RAD2EPS,
-                                    create_cs, cross, dot, fsqrt, sample_cone)
+                                    create_cs, cross, dot, fsqrt, sample_cone, sphere_consts, sphere_intersect, sun_consts)
 
 pytestmark = pytest.mark.gpu
 
@@ -163,20 +165,61 @@ def test_leaf_functions_bit_for_bit():
     exact(o, want.view(np.uint32), "sphereIntersect__")
 
 
-def sphere_intersect(frm, d, c, r2):
-    """sphereIntersect__, light_sphere.cc:57-69: the 4.0 and 2.0 make those products double"""
-    vf = frm - c
-    ea = dot(d, d)
-    eb = dot(vf * F(2), d)
-    ec = dot(vf, vf) - F(r2)
-    osc = (eb * eb).astype(np.float64) - 4.0 * ea.astype(np.float64) * ec.astype(np.float64)
-    osc = osc.astype(np.float32)
-    hit = ~(osc < 0)
-    so = fsqrt(np.where(hit, osc, F(0)))
-    d1 = ((-eb - so).astype(np.float64) / (2.0 * ea.astype(np.float64))).astype(np.float32)
-    d2 = ((-eb + so).astype(np.float64) / (2.0 * ea.astype(np.float64))).astype(np.float32)
-    d1 = np.where(hit, d1, fsqrt(ec / ea))
-    return hit, d1, d2
+@pytest.fixture(scope="module")
+def gold():
+    return lights_fixture.load("ieee")
+
+
+def test_leaf_functions_match_the_reference(gold):
+    """Probe ops 17-20 on the inputs of tests/golden/ref_lights_ieee (the reference's own light sources, every light made by its factory):
+    each parameter set goes through the C ABI as a light of one scene, the outputs are compared bit for bit.  The getLights() records
+    hold what the constructors compute: checked against the fixture's outputs where those carry the value (direction, colour, pdf,
+    inverse pdf, colour times pdf) and against the restated constructors otherwise (cosine, squared radius and its epsilon —
+    tests/test_lights_host.py holds those restatements to the same fixture), the cosine also against the directions SunLight::intersect
+    took and refused."""
+    doc = gold
+    names = doc["sets"]
+    sc = plane_scene([lights_fixture.light(doc, n) for n in names], res=8)
+    yi = Interface()
+    scenes.load_scene(yi, sc, scenes.render_settings(8, 8, 1, integrator="directlighting"))
+    yi.prepareRender()
+    rec = yi.getLights()
+    assert rec.shape[0] == len(names)
+    bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)
+    for k, name in enumerate(names):
+        p = lights_fixture.light(doc, name)
+        L = rec[k]
+        kb = lambda n: np.full((n, 1), np.uint32(k)).view(np.float32)
+        dirac, can_intersect, n_samples = doc[name + "_flags3"]
+        if p["type"] == "directionallight":
+            inp, want = lights_fixture.leaf(doc, name, "illuminate")
+            exact(yi.probe(17, np.hstack([inp, kb(len(inp))]), 8), want, f"{name} illuminate")
+            ok = want[:, 0] != 0
+            assert dirac == 1 and int(L[:4].view(np.int32)[3]) == int(p.get("infinite", True))
+            assert np.array_equal(bits(L[W_DIR:W_DIR + 3]), want[ok][0, 1:4]) and np.array_equal(bits(L[W_COLOR:W_COLOR + 3]), want[ok][0, 5:8])
+        elif p["type"] == "sunlight":
+            inp, want = lights_fixture.leaf(doc, name, "illum_sample")
+            exact(yi.probe(18, np.hstack([inp, kb(len(inp))]), 9), want, f"{name} illumSample")
+            assert bits(L[W_PDF]) == want[0, 5] and np.array_equal(bits(L[W_COLPDF:W_COLPDF + 3]), want[0, 6:9])
+            inp, want = lights_fixture.leaf(doc, name, "intersect")
+            exact(yi.probe(19, np.hstack([inp, kb(len(inp))]), 6), want, f"{name} intersect")
+            ok = want[:, 0] != 0
+            assert bits(L[W_INVPDF]) == want[ok][0, 2] and np.array_equal(bits(L[W_COLPDF:W_COLPDF + 3]), want[ok][0, 3:6])
+            c = sun_consts(p["direction"], p["color"], p["power"], p["angle"])
+            cosine = dot(inp, np.broadcast_to(c["direction"], inp.shape))
+            assert cosine[~ok].max() < L[W_COS] <= cosine[ok].min()
+            assert bits(L[W_COS]) == bits(c["cos_angle"])
+            for w, key in ((W_DIR, "direction"), (W_DU, "du"), (W_DV, "dv")):
+                assert np.array_equal(bits(L[w:w + 3]), bits(c[key])), (name, key)
+            assert (dirac, can_intersect) == (0, 1) and int(L[:4].view(np.int32)[1]) == n_samples
+        else:
+            inp, want = lights_fixture.leaf(doc, name, "illum_sample")
+            exact(yi.probe(20, np.hstack([inp, kb(len(inp))]), 9), want, f"{name} illumSample")
+            ok = want[:, 0] != 0
+            assert np.array_equal(bits(L[W_COLOR:W_COLOR + 3]), want[ok][0, 6:9])
+            r2, r2eps = sphere_consts(p["radius"])
+            assert bits(L[W_RAD2]) == bits(r2) and bits(L[W_RAD2EPS]) == bits(r2eps)
+            assert (dirac, can_intersect) == (0, 0) and int(L[:4].view(np.int32)[1]) == n_samples
 
 
 # ---- 2.-4. directional lights --------------------------------------------------------------------------------------
@@ -404,3 +447,27 @@ def test_replay_shards_and_pipelining_with_three_light_types():
         films.append(y2.getFilm(W, H).copy())
     assert np.array_equal(films[0], films[1])
 
+
+
+# ---- 8. every light type in one scene, against the oracle --------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["directlighting", "pathtracing", "pathtracing_three_passes"])
+def test_render_matches_oracle_with_every_light_type(mode):
+    """One light of each of the five types in the soup's room, against the oracle (which tests/test_integrator_golden.py holds to the
+    reference's own integrators on these light types): every pixel within the parity tolerance, no outliers, the oracle's ray counts.
+    With five lights the path tracer's light choice is the reference's serial counter: the device replays it, the oracle renders
+    single-threaded from the same libc state."""
+    from tests.test_gpu_parity import _render_with_rand_state, compare_films, render_both
+    W, H = 48, 40
+    sc = lights_fixture.five_light_scene(800, seed=43, res=(W, H))
+    if mode == "directlighting":
+        rd = scenes.render_settings(W, H, 2, integrator="directlighting", raydepth=2, tile_size=16)
+        film, st, ofilm, ost = render_both(sc, rd)
+    else:
+        aa = dict(AA_passes=3, AA_inc_samples=2, AA_threshold=0.02, AA_light_sample_multiplier_factor=1.5) if mode.endswith("passes") else {}
+        rd = scenes.render_settings(W, H, 4, bounces=3, tile_size=16, **aa)          # roulette off (render_settings' default)
+        # (adaptive passes: the oracle walks the product's tree — a camera ray on a pixel's diagonal can run into the edge two walls share,
+        # a tie that the tree's topology resolves: see tests.test_gpu_parity._render_with_rand_state)
+        film, st, ofilm, ost = _render_with_rand_state(sc, rd, same_tree=bool(aa))
+    assert film[..., :3].sum() > 0
+    assert (st.camera_samples, st.rays_closest, st.rays_shadow) == (ost.camera_samples, ost.rays_closest, ost.rays_shadow)
+    compare_films(film, ofilm, f"five light types, {mode}")

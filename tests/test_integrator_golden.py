@@ -26,13 +26,22 @@ from tests.integrator_fixture import case_scene, closest_rays, film_from_samples
 CASES = ["pt_mis_paths", "pt_three_lights_rr", "pt_recursive", "pt_multipass", "pt_dof", "directlighting",
          "pt_transparent_shadows", "pt_no_recursive", "pt_absorption_aniso", "pt_depth_bias_visibility", "dl_fake_shadows_flat", "pt_degenerate_lobes_clip", "pt_rough_glass",
          "pt_caustics_default", "pt_caustics_path_no_recursive", "dl_rough_glass"]
+# the second document (tests/golden/ref_integrator_lights_*): the directional, sun and sphere lights, alone and mixed with the other two
+LIGHT_CASES = ["dl_all_light_types", "pt_sun_mis", "pt_sphere_only", "pt_five_types_rr", "pt_lights_transp_shadows", "pt_sun_multipass"]
 # one light and roulette off: every sample is a pure function of (pixel, sample index)
-NO_SERIAL_STATE = {"pt_mis_paths", "pt_dof"}
+NO_SERIAL_STATE = {"pt_mis_paths", "pt_dof", "pt_sun_mis", "pt_sphere_only"}
+ALL_CASES = CASES + LIGHT_CASES
 
 
 @pytest.fixture(scope="module")
 def docs():
-    return {v: load(v) for v in ("ieee", "fast")}
+    """variant -> both documents merged: the scene they share and the cases of both"""
+    out = {}
+    for v in ("ieee", "fast"):
+        a, b = load(v), load(v, "integrator_lights")
+        assert all(a[k] == b[k] for k in ("width", "height", "tile_size", "materials", "verts"))
+        out[v] = dict(a, cases=a["cases"] + b["cases"], n_first=len(a["cases"]))
+    return out
 
 
 def _case(doc, name):
@@ -51,10 +60,30 @@ def _run(doc, cs, **override):
 
 def test_fixture_holds_every_case(docs):
     for v in ("ieee", "fast"):
-        assert [c["name"] for c in docs[v]["cases"]] == CASES
+        assert [c["name"] for c in docs[v]["cases"][:docs[v]["n_first"]]] == CASES
 
 
-@pytest.mark.parametrize("name", CASES)
+def test_lights_fixture_holds_every_case(docs):
+    """... and every light of every case reaches the scene: lit_share is, per light, the share of the light samples the reference asked it
+    for that arrived unshadowed on the viewer's side of the surface (counted by the harness); 0.15 at least, and 0.05 to 0.8 for the
+    finite directional light whose cylinder covers part of the floor only"""
+    for v in ("ieee", "fast"):
+        cases = docs[v]["cases"][docs[v]["n_first"]:]
+        assert [c["name"] for c in cases] == LIGHT_CASES
+        for c in cases:
+            assert len(c["lit_share"]) == len(c["lights"])
+            for light, share in zip(c["lights"], c["lit_share"]):
+                if light["type"] == "directionallight" and not light.get("infinite", True):
+                    assert 0.05 <= share <= 0.8, (c["name"], light)
+                else:
+                    assert share >= 0.15, (c["name"], light)
+    types = lambda name: [l["type"] for l in _case(docs["ieee"], name)["lights"]]
+    five = ["arealight", "pointlight", "directionallight", "sunlight", "spherelight"]
+    assert types("dl_all_light_types") == five and types("pt_five_types_rr") == five
+    assert types("pt_sun_mis") == ["sunlight"] and types("pt_sphere_only") == ["spherelight"]
+
+
+@pytest.mark.parametrize("name", ALL_CASES)
 def test_oracle_equals_the_reference_integrators_bit_for_bit(docs, name):
     doc = docs["ieee"]
     cs = _case(doc, name)
@@ -90,7 +119,7 @@ def test_tiles_are_handed_out_in_linear_order(docs):
         assert [tuple(r) for r in t] == one * n_pass
 
 
-@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("name", ALL_CASES)
 def test_oracle_against_the_release_flag_build(docs, name):
     doc = docs["fast"]
     cs = _case(doc, name)
@@ -126,3 +155,21 @@ def test_the_fixture_sees_the_serial_state(docs):
     _, _, smp, _, _ = _run(doc, cs, AA_light_sample_multiplier_factor=1.0)
     n0 = doc["width"] * doc["height"] * cs["render"]["AA_minsamples"]
     assert np.array_equal(smp[:n0, 4:], rgba[:n0]) and (smp[n0:, 4:] != rgba[n0:]).any(), "later passes take more light samples"
+
+
+def test_the_fixture_sees_can_intersect(docs):
+    """negative control: pt_sphere_only has no BSDF half because SphereLight::canIntersect() is false (light.h:77).  With an area light of
+    similar size in the sphere's place the BSDF-half shadow rays appear, and the fixture's shadow-ray count no longer holds"""
+    doc = docs["ieee"]
+    cs = _case(doc, "pt_sphere_only")
+    (sphere,) = cs["lights"]
+    c, r = np.array(sphere["from"]), sphere["radius"]
+    area = {"type": "arealight", "corner": tuple(c + (-r, -r, 0)), "point1": tuple(c + (-r, r, 0)), "point2": tuple(c + (r, -r, 0)),
+            "color": sphere["color"], "power": sphere["power"], "samples": sphere["samples"]}
+    swapped = dict(cs, lights=[area])
+    _, st, _, _, _ = _run(doc, swapped)
+    _, st_sphere, _, _, _ = _run(doc, cs)
+    assert st_sphere.rays_shadow == cs["n_shadow"]
+    assert st.rays_shadow != cs["n_shadow"], "an area light takes the BSDF half too"
+    # every light sample of the sphere is at most one shadow ray; no more than samples x (camera hits + bounce hits)
+    assert cs["n_shadow"] <= cs["n_closest"] * sphere["samples"]

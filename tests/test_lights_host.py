@@ -11,6 +11,7 @@ import pytest
 
 from libyafaray_amd import Interface
 from oracle import pyoracle as po
+from tests import lights_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -106,6 +107,118 @@ def sun_consts(direction, color, power, angle):
             "color": col, "col_pdf": col * pdf}
 
 
+def sphere_intersect(frm, d, c, r2):
+    """sphereIntersect__, light_sphere.cc:57-69: the 4.0 and 2.0 make those products double"""
+    vf = frm - c
+    ea = dot(d, d)
+    eb = dot(vf * F(2), d)
+    ec = dot(vf, vf) - F(r2)
+    osc = (eb * eb).astype(np.float64) - 4.0 * ea.astype(np.float64) * ec.astype(np.float64)
+    osc = osc.astype(np.float32)
+    hit = ~(osc < 0)
+    so = fsqrt(np.where(hit, osc, F(0)))
+    d1 = ((-eb - so).astype(np.float64) / (2.0 * ea.astype(np.float64))).astype(np.float32)
+    d2 = ((-eb + so).astype(np.float64) / (2.0 * ea.astype(np.float64))).astype(np.float32)
+    d1 = np.where(hit, d1, fsqrt(ec / ea))
+    return hit, d1, d2
+
+
+def directional_illuminate(direction, position, radius, infinite, color, p):
+    """DirectionalLight::illuminate, light_directional.cc:60-81 -> (n, 8): ok, wi.dir_, wi.tmax_, colour (zeros where refused)"""
+    n = p.shape[0]
+    d = np.broadcast_to(np.asarray(direction, np.float32), (n, 3))
+    if infinite:
+        ok = np.ones(n, bool); tmax = np.full(n, -1, np.float32)
+    else:
+        vec = np.asarray(position, np.float32) - p
+        cr = cross(d, vec)
+        dist = fsqrt(dot(cr, cr))
+        tmax = dot(vec, d)
+        ok = ~(dist > F(radius)) & ~(tmax <= 0)
+    out = np.zeros((n, 8), np.float32)
+    out[:, 0] = ok
+    out[ok, 1:4] = d[ok]; out[ok, 4] = tmax[ok]; out[ok, 5:8] = np.asarray(color, np.float32)
+    return out
+
+
+def sun_illum_sample(k, s):
+    """SunLight::illumSample, light_sun.cc:53-66, with the constructor's values k (sun_consts) -> (n, 9)"""
+    n = s.shape[0]
+    out = np.zeros((n, 9), np.float32)
+    out[:, 0] = 1
+    out[:, 1:4] = sample_cone(*(np.broadcast_to(k[w], (n, 3)) for w in ("direction", "du", "dv")), np.full(n, k["cos_angle"], np.float32), s[:, 0], s[:, 1])
+    out[:, 4] = -1; out[:, 5] = k["pdf"]; out[:, 6:9] = k["col_pdf"]
+    return out
+
+
+def sun_intersect(k, dirs):
+    """SunLight::intersect, light_sun.cc:68-76 -> (n, 6): ok, t, ipdf, colour"""
+    n = dirs.shape[0]
+    ok = ~(dot(dirs, np.broadcast_to(k["direction"], (n, 3))) < k["cos_angle"])
+    out = np.zeros((n, 6), np.float32)
+    out[:, 0] = ok; out[ok, 1] = -1; out[ok, 2] = k["invpdf"]; out[ok, 3:6] = k["col_pdf"]
+    return out
+
+
+def sphere_consts(radius):
+    """SphereLight ctor, light_sphere.cc:37-38 -> square_radius_, square_radius_epsilon_"""
+    r2 = F(radius) * F(radius)
+    return r2, np.float32(np.float64(r2) * 1.000003815)
+
+
+def sphere_illum_sample(center, r2, r2eps, color, p, s):
+    """SphereLight::illumSample, light_sphere.cc:71-103 -> (n, 9): ok, wi.dir_, wi.tmax_, s.pdf_, s.col_"""
+    n = p.shape[0]
+    c = np.asarray(center, np.float32)
+    cdir = c - p
+    dist_sqr = dot(cdir, cdir)
+    outside = ~(dist_sqr <= F(r2))
+    with np.errstate(all="ignore"):
+        dist = fsqrt(dist_sqr)
+        cos_alpha = fsqrt(F(1) - F(r2) * (F(1) / dist_sqr))
+        cdir = cdir * (F(1) / dist)[:, None]
+        cu, cv = create_cs(cdir)
+        wdir = sample_cone(cdir, cu, cv, cos_alpha, s[:, 0], s[:, 1])
+        hit, d1, _ = sphere_intersect(p, wdir, c, r2eps)
+        pdf = F(1) / (F(2) * (F(1) - cos_alpha))
+    ok = outside & hit
+    out = np.zeros((n, 9), np.float32)
+    out[:, 0] = ok; out[ok, 1:4] = wdir[ok]; out[ok, 4] = d1[ok]; out[ok, 5] = pdf[ok]; out[ok, 6:9] = np.asarray(color, np.float32)
+    return out
+
+
+def test_restatements_reproduce_the_reference_bit_for_bit():
+    """The float32 restatements above (tests/test_gpu_lights.py holds the device to them where the reference exports nothing:
+    sphereIntersect__ alone, probe op 21) on the inputs of tests/golden/ref_lights_ieee: the reference's own light sources, IEEE build."""
+    doc = lights_fixture.load("ieee")
+
+    def same(got, want, what):
+        got = np.ascontiguousarray(got, dtype=np.float32).view(np.uint32)
+        bad = (got != want) & ~(((got | want) & 0x7fffffff) == 0)          # +0 / -0 are not distinguished
+        assert not bad.any(), f"{what}: {bad.sum()} of {bad.size} words differ, first row {np.nonzero(bad.any(axis=1))[0][0]}"
+
+    for name in lights_fixture.sets(doc, "directionallight"):
+        p = lights_fixture.light(doc, name)
+        inp, want = lights_fixture.leaf(doc, name, "illuminate")
+        inf = p.get("infinite", True)
+        col = np.array(p["color"], np.float32) * F(p["power"])
+        got = directional_illuminate(normalize(p["direction"]), (0, 0, 0) if inf else p["from"], 1.0 if inf else p["radius"], inf, col, inp)
+        same(got, want, name)
+    for name in lights_fixture.sets(doc, "sunlight"):
+        p = lights_fixture.light(doc, name)
+        k = sun_consts(p["direction"], p["color"], p["power"], p["angle"])
+        inp, want = lights_fixture.leaf(doc, name, "illum_sample")
+        same(sun_illum_sample(k, inp), want, name + " illumSample")
+        inp, want = lights_fixture.leaf(doc, name, "intersect")
+        same(sun_intersect(k, inp), want, name + " intersect")
+    for name in lights_fixture.sets(doc, "spherelight"):
+        p = lights_fixture.light(doc, name)
+        r2, r2eps = sphere_consts(p["radius"])
+        col = np.array(p["color"], np.float32) * F(p["power"])
+        inp, want = lights_fixture.leaf(doc, name, "illum_sample")
+        same(sphere_illum_sample(p["from"], r2, r2eps, col, inp[:, :3], inp[:, 3:5]), want, name)
+
+
 # ---- the factories through the C API ----
 def light_of(params, name="l"):
     yi = Interface(strict=False)
@@ -118,6 +231,38 @@ def light_of(params, name="l"):
 
 def color(*c):
     return ("color", float(c[0]), float(c[1]), float(c[2]), 1.0)
+
+
+def test_factories_through_the_c_api_match_the_reference():
+    """every parameter set of the fixture through createLight: the getLights() record holds what the reference's factory + constructor
+    computed, as far as the fixture's outputs carry it (direction, colour x power, pdf, inverse pdf, colour x pdf, the flags)"""
+    doc = lights_fixture.load("ieee")
+    for name in doc["sets"]:
+        p = lights_fixture.light(doc, name)
+        yi, h = light_of({k: (color(*v) if k == "color" else v) for k, v in p.items()})
+        assert h, yi.getLastError()
+        r = yi.getLights()[0]
+        dirac, can_intersect, n_samples = doc[name + "_flags3"]
+        if p["type"] == "directionallight":
+            _, want = lights_fixture.leaf(doc, name, "illuminate")
+            first = want[want[:, 0] != 0][0]
+            assert np.array_equal(bits(r[W_DIR:W_DIR + 3]), first[1:4]) and np.array_equal(bits(r[W_COLOR:W_COLOR + 3]), first[5:8]), name
+            assert ints(r)[3] == int(p.get("infinite", True)) and ints(r)[2] == int(p.get("cast_shadows", True))
+        elif p["type"] == "sunlight":
+            _, want = lights_fixture.leaf(doc, name, "illum_sample")
+            assert bits(r[W_PDF]) == want[0, 5] and np.array_equal(bits(r[W_COLPDF:W_COLPDF + 3]), want[0, 6:9]), name
+            inp, want = lights_fixture.leaf(doc, name, "intersect")
+            ok = want[:, 0] != 0
+            assert bits(r[W_INVPDF]) == want[ok][0, 2], name
+            cosine = dot(inp, np.broadcast_to(r[W_DIR:W_DIR + 3], inp.shape))
+            assert cosine[~ok].max() < r[W_COS] <= cosine[ok].min(), name
+            assert ints(r)[1] == n_samples
+        else:
+            _, want = lights_fixture.leaf(doc, name, "illum_sample")
+            assert np.array_equal(bits(r[W_COLOR:W_COLOR + 3]), want[want[:, 0] != 0][0, 6:9]), name
+            r2, r2eps = sphere_consts(p["radius"])
+            assert bits(r[W_RAD2]) == bits(r2) and bits(r[W_RAD2EPS]) == bits(r2eps), name
+            assert ints(r)[1] == n_samples
 
 
 @pytest.mark.parametrize("t", ["directionallight", "sunlight", "spherelight"])

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle as po
+from tests import lights_fixture
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FAST_RTOL = 2e-3   # fPow at exponent 500 amplifies 1-ulp input noise to ~4e-4 between the two reference builds
@@ -233,6 +234,47 @@ def test_lights(gold):
         L.yor_pointlight_illuminate(C.byref(pl), po.fptr(inp[i].copy()), po.fptr(out))
         got.extend(out.tolist())
     check(variant, got, g["pl_out7"], "PointLight::illuminate")
+
+
+def test_directional_sun_sphere_lights(gold):
+    """DirectionalLight::illuminate, SunLight::illumSample / ::intersect, SphereLight::illumSample and the three factories + constructors
+    against the reference's own (tests/golden/ref_lights_*, oracle/ref_harness/ref_lights.cc): every parameter set goes through
+    pyoracle.light_desc, the dict form a scene uses"""
+    variant = gold[0]
+    doc = lights_fixture.load(variant)
+    L = po.lib()
+    assert len(lights_fixture.sets(doc, "directionallight")) >= 4 and len(lights_fixture.sets(doc, "sunlight")) >= 3
+    assert len(lights_fixture.sets(doc, "spherelight")) >= 3
+
+    def run(name, fn, call, n_out):
+        ld = po.light_desc(lights_fixture.light(doc, name))
+        inp, want = lights_fixture.leaf(doc, name, fn)
+        assert inp.shape[0] == 2000
+        out = np.zeros(n_out, np.float32)
+        got = np.zeros((inp.shape[0], 1 + n_out), np.float32)
+        for i in range(inp.shape[0]):
+            out[:] = 0
+            got[i, 0] = call(ld, inp[i].copy(), out)
+            got[i, 1:] = out if got[i, 0] else 0            # a refused call's outputs are not read by the integrators
+        want_ok = f32(want[:, 0])
+        if variant == "ieee":
+            assert np.array_equal(got[:, 0], want_ok), f"{name} {fn}: accepted"
+            check(variant, got, want, f"{name} {fn}")
+        else:
+            same = got[:, 0] == want_ok
+            assert same.mean() > 0.98, f"{name} {fn}"      # a point on the edge may flip under -ffast-math
+            check(variant, got[same], want[same], f"{name} {fn}")
+
+    for name in lights_fixture.sets(doc, "directionallight"):
+        run(name, "illuminate", lambda ld, x, o: L.yor_directional_illuminate(C.byref(ld), po.fptr(x), po.fptr(o)), 7)
+        assert doc[name + "_flags3"][:2] == [1, 0]
+    for name in lights_fixture.sets(doc, "sunlight"):
+        run(name, "illum_sample", lambda ld, x, o: L.yor_sun_illum_sample(C.byref(ld), x[0], x[1], po.fptr(o)), 8)
+        run(name, "intersect", lambda ld, x, o: L.yor_sun_intersect(C.byref(ld), po.fptr(x), po.fptr(o)), 5)
+        assert doc[name + "_flags3"] == [0, 1, doc[name + "_params"]["samples"]]
+    for name in lights_fixture.sets(doc, "spherelight"):
+        run(name, "illum_sample", lambda ld, x, o: L.yor_sphere_illum_sample(C.byref(ld), po.fptr(x[:3].copy()), x[3], x[4], po.fptr(o)), 8)
+        assert doc[name + "_flags3"] == [0, 0, doc[name + "_params"]["samples"]]      # canIntersect() is false: light.h:77
 
 
 # RenderState::raylevel_ when the golden getSpecular calls were made (GlassMaterial::getSpecular depends on it)

@@ -10,8 +10,10 @@ from libyafaray_amd import Interface, scenes          # noqa: E402
 from oracle import pyoracle as po                     # noqa: E402
 from tests.integrator_fixture import case_scene, load      # noqa: E402
 
-doc = load("ieee")
 name = sys.argv[1]
+doc = load("ieee")
+if not any(c["name"] == name for c in doc["cases"]):      # a case of the second document (directional, sun and sphere lights)
+    doc = load("ieee", "integrator_lights")
 cs = next(c for c in doc["cases"] if c["name"] == name)
 
 
