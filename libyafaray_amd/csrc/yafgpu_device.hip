@@ -592,20 +592,65 @@ static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #define HIP_OK(expr) do { hipError_t e_ = (expr); if(e_ != hipSuccess) return fail(-100, std::string(#expr) + ": " + hipGetErrorString(e_)); } while(0)
 
-// device allocation released on every exit path of the host entry points
+// Owning handles of the host side: what a scene or an entry point holds is released when it goes, on every exit path.
+// DevMem: a device array.  alloc() is for the temporaries of an entry point; reserve() makes a long-lived buffer large enough and
+// never shrinks it.
 template<typename T> struct DevMem
 {
-	T *p = nullptr;
+	T *p = nullptr; size_t cap = 0;      // cap: elements reserve() has made room for
 	DevMem() = default;
 	DevMem(const DevMem &) = delete; DevMem &operator=(const DevMem &) = delete;
 	~DevMem() { if(p) (void)hipFree(p); }
 	hipError_t alloc(size_t count) { return hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T)); }
+	// room for `count` elements; the contents are not kept.  Work enqueued on `stream` may still use the old array: it is waited for
+	// before the array is freed.  After a failed allocation the buffer is empty (p == nullptr, cap == 0).
+	hipError_t reserve(size_t count, hipStream_t stream)
+	{
+		if(p && count <= cap) return hipSuccess;
+		hipError_t e = hipStreamSynchronize(stream);
+		if(e != hipSuccess) return e;
+		if(p) (void)hipFree(p);
+		p = nullptr; cap = 0;
+		if((e = alloc(count)) != hipSuccess) { p = nullptr; return e; }
+		cap = count;
+		return hipSuccess;
+	}
 	operator T *() const { return p; }
 };
-struct EventPair
+struct Stream      // a non-blocking stream, created on first use
 {
-	hipEvent_t e[2] = {nullptr, nullptr};
-	~EventPair() { for(hipEvent_t x : e) if(x) (void)hipEventDestroy(x); }
+	hipStream_t s = nullptr;
+	Stream() = default;
+	Stream(const Stream &) = delete; Stream &operator=(const Stream &) = delete;
+	~Stream() { if(s) (void)hipStreamDestroy(s); }
+	hipError_t create() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+	operator hipStream_t() const { return s; }
+};
+struct Event       // an event, created on first use: for ordering only unless asked to time
+{
+	hipEvent_t e = nullptr;
+	Event() = default;
+	Event(const Event &) = delete; Event &operator=(const Event &) = delete;
+	~Event() { if(e) (void)hipEventDestroy(e); }
+	hipError_t create(unsigned flags = hipEventDisableTiming) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+	operator hipEvent_t() const { return e; }
+};
+
+// Everything one pass in flight owns: the wavefront workspace, the side stream of its any-hit launches and — for pass pipelining
+// (begin_piped_pass) — the internal stream its path work runs on.  Passes that are not pipelined use set 0 on the caller's stream.
+struct WfSet
+{
+	DevMem<uint32_t> pix_prefix;                     // per-tile pixel prefix of the shard's tile list
+	DevMem<float4> state, results;                   // parked path records (recursiveRaytrace frames behind the working records), rgba per path
+	DevMem<uint32_t> queues, counts, verdict, pix_xy;
+	DevMem<float4> filt;                             // transparent shadows: the filter products of the shadow rays
+	uint32_t cap = 0; int frame_recs = 0;            // paths and frame records per path the first five are laid out for (WfArgs::cap is the record stride)
+	Stream side; Event fork, join;                   // the any-hit launch of an iteration runs beside the closest-hit one
+	Stream stream; Event done, acc; bool acc_set = false;      // pipelining: path work done / film added (recorded on the caller's stream; acc_set: ever)
+	DevMem<yafgpu_counters> counters;                // a pipelined pass counts here; the sums reach the caller's block on the caller's stream
+	// a set that a pass outgrows is laid out anew for exactly what that pass asks (reserve_workspace); cap_for: `cap` after that
+	bool outgrown(uint32_t paths, int recs) const { return paths > cap || recs > frame_recs; }
+	uint32_t cap_for(uint32_t paths, int recs) const { return outgrown(paths, recs) ? paths : cap; }
 };
 
 struct yafgpu_scene
@@ -617,32 +662,18 @@ struct yafgpu_scene
 	std::vector<yafgpu_material> mats;
 	std::vector<yafgpu_light> h_lights;
 	int n_lights = 0;
-	// per-render scratch, grown on demand
-	int4 *d_tiles = nullptr; size_t tiles_cap = 0;
 	// the tile list of the last launch stays resident; it is re-uploaded only when its key changes
+	DevMem<int4> d_tiles;
 	std::vector<int4> h_tiles;
 	int tile_key[7] = {-1, -1, -1, -1, -1, -1, -1};
-	// wavefront workspace (allocated on first use, sized for kWfMaxPaths paths or the whole frame)
-	std::vector<uint32_t> h_pix_prefix; uint32_t *d_pix_prefix = nullptr; size_t pix_prefix_cap = 0;
-	float4 *wf_state = nullptr, *wf_results = nullptr; uint32_t *wf_queues = nullptr, *wf_counts = nullptr, *wf_verdict = nullptr, *wf_pix_xy = nullptr; uint32_t wf_cap = 0;
-	hipStream_t side_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;      // the any-hit launch of an iteration runs beside the closest-hit one
+	std::vector<uint32_t> h_pix_prefix;
 	// Pass pipelining (render_wavefront): consecutive passes that do not depend on each other's film take turns on two internal streams, each
 	// with its own set of the wavefront buffers, so that one pass's launch tails are filled by the other's launches; the film is added to
-	// on the caller's stream, in call order.  `alt[]` are the sets that are not in the members above at the moment.
-	struct WfSet
-	{
-		uint32_t *d_pix_prefix = nullptr; size_t pix_prefix_cap = 0;
-		float4 *wf_state = nullptr, *wf_results = nullptr, *wf_filt = nullptr;
-		uint32_t *wf_queues = nullptr, *wf_counts = nullptr, *wf_verdict = nullptr, *wf_pix_xy = nullptr;
-		uint32_t wf_cap = 0, wf_filt_cap = 0; int wf_frames = 0;
-		hipStream_t side_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-	} alt[2];
-	static constexpr int kPipeMax = 3;      // passes in flight at most (buffer sets: the members above + alt[])
-	hipStream_t pipe_stream[kPipeMax] = {};
-	hipEvent_t pipe_done[kPipeMax] = {}, pipe_acc[kPipeMax] = {}, pipe_sync = nullptr;
-	bool pipe_acc_set[kPipeMax] = {}, pipe_prev = false;
-	int pipe_next = 0, pass_pipelining = -1;      // -1: by size (render_wavefront), 0 / 1: forced (yafgpu_scene_set_pass_pipelining)
-	yafgpu_counters *pipe_counters[kPipeMax] = {};      // a pipelined pass counts here; the sums reach the caller's block on the caller's stream
+	// on the caller's stream, in call order.
+	static constexpr int kPipeMax = 2;      // passes in flight at most
+	WfSet sets[kPipeMax];
+	Event pipe_sync; bool pipe_prev = false;
+	int pipe_next = 0, pass_pipelining = -1;      // -1: by size (plan_pass), 0 / 1: forced (yafgpu_scene_set_pass_pipelining)
 	uint32_t mat_mask = 0u;              // bit per YAFGPU_MAT_* present; picks the shading kernel variant
 	uint32_t light_mask = 0u;            // bit per YAFGPU_LIGHT_* present; a variant must have been built for all of them
 	bool has_volumetric = false;
@@ -652,17 +683,17 @@ struct yafgpu_scene
 	bool has_aniso = false;              // some material has the anisotropic glossy lobe: the general shading kernel
 	bool has_bump = false;               // some material has a bump shader: the shading frame is parked per vertex (records 24 / 25, frame record 12)
 	bool has_textures = false;           // some material in use has shader nodes: the general shading kernel, texture coordinates parked per path
-	bool has_specular = false, has_transparent = false; int wf_frames = 0; float4 *wf_filt = nullptr; uint32_t wf_filt_cap = 0;      // recursiveRaytrace frames allocated behind the working records
-	float *d_filter_table = nullptr;
-	// serial-state replay tables (WfArgs::replay)
-	uint32_t *rp_flags = nullptr; float *rp_p = nullptr; uint8_t *rp_kill = nullptr, *rp_calls = nullptr; uint32_t *rp_base = nullptr; size_t rp_ents = 0; uint32_t rp_prob = 0;
-	uint32_t *rp_seg_begin = nullptr, *rp_seg_seed = nullptr, *rp_seg_total = nullptr, *rp_seg_base = nullptr, *rp_counter = nullptr; size_t rp_segs = 0;
+	bool has_specular = false, has_transparent = false;
+	DevMem<float> d_filter_table;
+	// serial-state replay tables (WfArgs::replay), per scene: a pass that replays is never pipelined
+	DevMem<uint32_t> rp_flags; DevMem<float> rp_p; DevMem<uint8_t> rp_kill, rp_calls; DevMem<uint32_t> rp_base;
+	DevMem<uint32_t> rp_seg_begin, rp_seg_seed, rp_seg_total, rp_seg_base, rp_counter;
+	DevMem<float4> rp_hits;              // closest-hit answers of the record pass (WfArgs::hit_cache)
 	// render targets of the host-film entry points, kept between calls (allocating and freeing 100 MB per render cost up to half a
 	// second a call on this runtime — ten times the pass itself at 1024x1024)
-	float *rt_planes = nullptr, *rt_film = nullptr; yafgpu_counters *rt_cnt = nullptr; size_t rt_planes_n = 0, rt_film_n = 0;
+	DevMem<float> rt_planes, rt_film; DevMem<yafgpu_counters> rt_cnt;
+	DevMem<uint8_t> rt_flags;            // resample flags of the detection step between adaptive passes
 	int n_cus = 0;                                            // compute units of the device the scene lives on
-	uint8_t *rt_flags = nullptr; size_t rt_flags_n = 0;       // resample flags of the detection step between adaptive passes
-	float4 *rp_hits = nullptr; size_t rp_hits_cap = 0;       // closest-hit answers of the record pass (WfArgs::hit_cache)
 	uint32_t lc_host_counter = 0;                        // correlative_sample_number_ of a sharded render: the same value on every rank (lc_exchange_counts)
 	std::vector<uint32_t> h_seg_base;
 	std::vector<uint32_t> h_listed;                      // pixels of a masked (adaptive) pass, in tile order
@@ -970,39 +1001,7 @@ void yafgpu_scene_destroy(yafgpu_scene_t *s)
 {
 	if(!s) return;
 	for(void *p : s->allocs) (void)hipFree(p);
-	if(s->d_tiles) (void)hipFree(s->d_tiles);
-	if(s->d_pix_prefix) (void)hipFree(s->d_pix_prefix);
-	if(s->wf_state) (void)hipFree(s->wf_state);
-	if(s->wf_results) (void)hipFree(s->wf_results);
-	if(s->wf_queues) (void)hipFree(s->wf_queues);
-	if(s->wf_counts) (void)hipFree(s->wf_counts);
-	if(s->wf_verdict) (void)hipFree(s->wf_verdict);
-	if(s->wf_pix_xy) (void)hipFree(s->wf_pix_xy);
-	if(s->wf_filt) (void)hipFree(s->wf_filt);
-	for(yafgpu_scene::WfSet &o : s->alt)
-	{
-		for(void *q : {(void *)o.d_pix_prefix, (void *)o.wf_state, (void *)o.wf_results, (void *)o.wf_filt, (void *)o.wf_queues, (void *)o.wf_counts, (void *)o.wf_verdict, (void *)o.wf_pix_xy})
-			if(q) (void)hipFree(q);
-		if(o.side_stream) (void)hipStreamDestroy(o.side_stream);
-		if(o.ev_fork) (void)hipEventDestroy(o.ev_fork);
-		if(o.ev_join) (void)hipEventDestroy(o.ev_join);
-	}
-	for(int k = 0; k < yafgpu_scene::kPipeMax; ++k)
-	{
-		if(s->pipe_stream[k]) (void)hipStreamDestroy(s->pipe_stream[k]);
-		if(s->pipe_done[k]) (void)hipEventDestroy(s->pipe_done[k]);
-		if(s->pipe_acc[k]) (void)hipEventDestroy(s->pipe_acc[k]);
-	}
-	if(s->pipe_sync) (void)hipEventDestroy(s->pipe_sync);
-	for(int k = 0; k < yafgpu_scene::kPipeMax; ++k) if(s->pipe_counters[k]) (void)hipFree(s->pipe_counters[k]);
-	if(s->side_stream) (void)hipStreamDestroy(s->side_stream);
-	if(s->ev_fork) (void)hipEventDestroy(s->ev_fork);
-	if(s->ev_join) (void)hipEventDestroy(s->ev_join);
-	if(s->d_filter_table) (void)hipFree(s->d_filter_table);
-	for(void *q : {(void *)s->rp_flags, (void *)s->rp_p, (void *)s->rp_kill, (void *)s->rp_calls, (void *)s->rp_base, (void *)s->rp_seg_begin,
-	               (void *)s->rp_seg_seed, (void *)s->rp_seg_total, (void *)s->rp_seg_base, (void *)s->rp_counter, (void *)s->rp_hits,
-	               (void *)s->rt_planes, (void *)s->rt_film, (void *)s->rt_cnt, (void *)s->rt_flags}) if(q) (void)hipFree(q);
-	delete s;
+	delete s;      // (buffers, streams and events go with their owners)
 }
 
 int yafgpu_scene_info(const yafgpu_scene_t *s, yafgpu_tree_info *info)
@@ -1110,8 +1109,55 @@ static int validate(const yafgpu_scene *s, const yafgpu_render_params *rp)
 	return 0;
 }
 
+// a pipelined pass's counters into the caller's block (accumulate_chunk)
+__global__ void add_counters(yafgpu_counters *dst, const yafgpu_counters *src)
+{
+	const unsigned i = threadIdx.x;
+	if(i < sizeof(yafgpu_counters) / sizeof(uint64_t)) ((uint64_t *)dst)[i] += ((const uint64_t *)src)[i];
+}
+
+} // extern "C": the pass driver below is internal, and `timed` is a template
+
 // ---- wavefront pass -------------------------------------------------------------------------
 static constexpr uint32_t kWfMaxPaths = 32u << 20;   // paths in flight per chunk: 32 Mi x 304 B = 9.5 GiB of parked state
+
+// The environment switches of the render path.  Read at the top of every render call and never kept between
+// calls: tests and A/B runs change them between the renders of one process.
+struct Switches
+{
+	uint32_t wf_chunk = kWfMaxPaths;           // YAFGPU_WF_CHUNK: cap on the paths in flight per chunk, at least 256 (tests chunk tiny frames)
+	int pass_pipeline = -1, overlap = -1;      // YAFGPU_PASS_PIPELINE, YAFGPU_OVERLAP: 0 / 1 force either; -1: unset, the pass decides (plan_pass)
+	bool speculate = true;                     // YAFGPU_SPECULATE=0: the sequential phases (WfArgs::speculate)
+	bool multi_pair = true;                    // YAFGPU_MULTI_PAIR=0: one MIS pair per park
+	bool hit_cache = true;                     // YAFGPU_HIT_CACHE=0: the final pass of a replay traces its closest hits again
+	bool serial_replay = true;                 // YAFGPU_SERIAL_REPLAY=0: per-sample streams instead of the replay
+	bool general_shade = false;                // YAFGPU_SHADE_VARIANT=general: the general shading kernel
+	bool record_variant = true;                // YAFGPU_RECORD_VARIANT=0: the record pass on the pass's own kernel (A/B)
+	int blocks_per_cu = 8;                     // YAFGPU_BLOCKS_PER_CU: resident workgroups per CU of the persistent kernels (occupancy experiments)
+	bool stats = false, verbose = false;       // YAFGPU_STATS, YAFGPU_VERBOSE: set at all
+};
+static int env_flag(const char *name)      // 1 / 0: set to a number that is / is not zero; -1: unset
+{
+	const char *e = std::getenv(name);
+	return e ? (std::atoi(e) != 0 ? 1 : 0) : -1;
+}
+static Switches read_switches()
+{
+	Switches sw;
+	if(const char *e = std::getenv("YAFGPU_WF_CHUNK")) sw.wf_chunk = std::max(256u, (uint32_t)std::strtoul(e, nullptr, 10));
+	sw.pass_pipeline = env_flag("YAFGPU_PASS_PIPELINE");
+	sw.overlap = env_flag("YAFGPU_OVERLAP");
+	sw.speculate = env_flag("YAFGPU_SPECULATE") != 0;
+	sw.multi_pair = env_flag("YAFGPU_MULTI_PAIR") != 0;
+	sw.hit_cache = env_flag("YAFGPU_HIT_CACHE") != 0;
+	sw.serial_replay = env_flag("YAFGPU_SERIAL_REPLAY") != 0;
+	if(const char *e = std::getenv("YAFGPU_SHADE_VARIANT")) sw.general_shade = std::strcmp(e, "general") == 0;
+	sw.record_variant = env_flag("YAFGPU_RECORD_VARIANT") != 0;
+	if(const char *e = std::getenv("YAFGPU_BLOCKS_PER_CU")) sw.blocks_per_cu = std::max(1, std::atoi(e));
+	sw.stats = std::getenv("YAFGPU_STATS") != nullptr;
+	sw.verbose = std::getenv("YAFGPU_VERBOSE") != nullptr;
+	return sw;
+}
 
 // compute units of the scene's device (s->n_cus), asked once
 static int device_cus(yafgpu_scene *s)
@@ -1124,7 +1170,7 @@ static int device_cus(yafgpu_scene *s)
 	return 0;
 }
 
-static int wf_grid(const void *kernel, int cus)
+static int wf_grid(const void *kernel, int cus, const Switches &sw)
 {
 	// (the occupancy of a kernel does not change between passes: asked once per kernel)
 	static std::mutex mu; static std::map<const void *, int> known;
@@ -1139,9 +1185,7 @@ static int wf_grid(const void *kernel, int cus)
 			known[kernel] = per_cu;
 		}
 	}
-	int cap = 8;
-	if(const char *e = std::getenv("YAFGPU_BLOCKS_PER_CU")) cap = std::max(1, std::atoi(e));   // occupancy experiments
-	return cus * std::min(per_cu, cap);
+	return cus * std::min(per_cu, sw.blocks_per_cu);
 }
 
 // Scene-specialised builds of wf_shade (yafgpu_shade_variant.hip), most specialised first.  A variant serves a scene
@@ -1179,10 +1223,9 @@ static const ShadeVariant kShadeVariants[] = {
 	{"glossy_rec", yafgpu_shade_glossy_rec_describe, yafgpu_shade_glossy_rec_kernel, yafgpu_shade_glossy_rec_launch},
 	{"full", yafgpu_shade_full_describe, yafgpu_shade_full_kernel, yafgpu_shade_full_launch},      // everything but shader nodes
 };
-static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, int frames, bool record_pass = false, bool want_multi = false)
+static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, const Switches &sw, int frames, bool record_pass, bool want_multi)
 {
-	if(const char *e = std::getenv("YAFGPU_SHADE_VARIANT")) if(std::strcmp(e, "general") == 0) return nullptr;
-	if(record_pass) if(const char *e = std::getenv("YAFGPU_RECORD_VARIANT")) if(std::atoi(e) == 0) return nullptr;      // (A/B: the record pass on the pass's own kernel)
+	if(sw.general_shade || (record_pass && !sw.record_variant)) return nullptr;
 	const bool needs_recurse = frames > 0 || s->has_volumetric;
 	if(s->has_textures || s->has_aniso) return nullptr;        // the variants are built without shader nodes and without the anisotropic lobe
 	for(const ShadeVariant &v : kShadeVariants)
@@ -1204,7 +1247,7 @@ static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, int frames,
 // starts with the sum over all tiles before it): with an exchange function attached the ranks share them (lc_sharded),
 // without one the per-sample ordinals stand in for the counter.
 struct ReplayPlan { int frames; bool need_rr, need_lc, replay, replay_lights, lc_sharded; int ev_m; };
-static ReplayPlan replay_plan(const yafgpu_scene *s, const yafgpu_render_params &rp)
+static ReplayPlan replay_plan(const yafgpu_scene *s, const yafgpu_render_params &rp, const Switches &sw)
 {
 	ReplayPlan p{};
 	p.frames = ((s->has_specular || s->has_glossy) && rp.raydepth + s->max_add_depth > 0) ? rp.raydepth + s->max_add_depth : 0;
@@ -1220,8 +1263,7 @@ static ReplayPlan replay_plan(const yafgpu_scene *s, const yafgpu_render_params 
 		for(int k = 0; k < p.frames; ++k) { const long long t2 = s->has_glossy ? 1 + 8 * per_traj * g + 2 * t : 1 + 2 * t; g = 1 + 3 * g; t = std::min<long long>(t2, 1 << 20); }
 		p.ev_m = (int)t;
 	}
-	p.replay = rp.serial_replay != 0 && p.ev_m <= 255 && (p.need_rr || p.need_lc);
-	if(const char *e = std::getenv("YAFGPU_SERIAL_REPLAY")) if(std::atoi(e) == 0) p.replay = false;
+	p.replay = rp.serial_replay != 0 && p.ev_m <= 255 && (p.need_rr || p.need_lc) && sw.serial_replay;
 	p.lc_sharded = p.replay && p.need_lc && rp.shard_count > 1 && s->exchange != nullptr;
 	p.replay_lights = p.replay && p.need_lc && (rp.shard_count == 1 || p.lc_sharded);
 	if(p.replay && !p.need_rr && !p.replay_lights) p.replay = false;
@@ -1255,511 +1297,493 @@ static int lc_exchange_counts(yafgpu_scene *s, const yafgpu_render_params &rp, c
 	return 0;
 }
 
-__global__ void add_counters(yafgpu_counters *dst, const yafgpu_counters *src)
+
+// a tile's index among the tiles of the whole frame, row-major (the reference's tile order)
+static int tile_global_index(const yafgpu_render_params &rp, const int4 &r)
 {
-	const unsigned i = threadIdx.x;
-	if(i < sizeof(yafgpu_counters) / sizeof(uint64_t)) ((uint64_t *)dst)[i] += ((const uint64_t *)src)[i];
-}
-static void swap_wf_sets(yafgpu_scene *s, int which)
-{
-	yafgpu_scene::WfSet &o = s->alt[which];
-	std::swap(s->d_pix_prefix, o.d_pix_prefix); std::swap(s->pix_prefix_cap, o.pix_prefix_cap);
-	std::swap(s->wf_state, o.wf_state); std::swap(s->wf_results, o.wf_results); std::swap(s->wf_filt, o.wf_filt);
-	std::swap(s->wf_queues, o.wf_queues); std::swap(s->wf_counts, o.wf_counts); std::swap(s->wf_verdict, o.wf_verdict); std::swap(s->wf_pix_xy, o.wf_pix_xy);
-	std::swap(s->wf_cap, o.wf_cap); std::swap(s->wf_filt_cap, o.wf_filt_cap); std::swap(s->wf_frames, o.wf_frames);
-	std::swap(s->side_stream, o.side_stream); std::swap(s->ev_fork, o.ev_fork); std::swap(s->ev_join, o.ev_join);
+	const int ntx = (rp.width + rp.tile_size - 1) / rp.tile_size;
+	return ((r.y - rp.ystart) / rp.tile_size) * ntx + (r.x - rp.xstart) / rp.tile_size;
 }
 
-static int render_wavefront(yafgpu_scene *s, RenderArgs &ra, hipStream_t caller, bool stats)
+// chunks: runs of pixels whose paths are in flight together (tile_begin, tile_end: with the replay, the tiles it is made of)
+struct Chunk { uint32_t pixel_begin, n_pixels, tile_begin, tile_end; };
+
+// What a pass is going to do, decided before anything is enqueued (plan_pass)
+struct PassPlan
 {
-	hipStream_t stream = caller;
-	const yafgpu_render_params &rp = ra.rp;
-	const uint32_t spp = (uint32_t)rp.aa_minsamples;
+	ReplayPlan rpl{};
+	bool stats = false;                        // the counting variant of the traversal kernels
+	bool masked = false;                       // a resample mask picks the pixels (adaptive pass)
+	std::vector<uint32_t> tile_px;             // pixels of the pass before every tile of the shard
+	std::vector<Chunk> chunks;                 // none: the mask picked no pixel of this shard's tiles
+	uint32_t spp = 0, cap = 0;                 // cap: paths of the largest chunk
+	int frames = 0, frame_recs = 0;            // recursiveRaytrace: a frame of frame_recs records per level a camera hit may recurse to
+	uint32_t ev_m = 1, n_ps = 1, n_prob = 1;   // replay: calls per camera sample, path samples per call, roulette probabilities per path sample
+	uint32_t hit_k = 0; bool use_hits = false; // the record pass's closest-hit answers per camera sample; kept for the final pass (WfArgs::hit_cache)
+	bool want_multi = false, transp = false, overlap = false, piped = false;
+	const ShadeVariant *shade = nullptr, *record = nullptr;      // nullptr: the general kernel / the pass's own kernel
+	int iters = 0, iters_record = 0;           // upper bound of kd-tree queries per path = iterations needed (every path advances one query per iteration)
+};
+
+// The chunks of a pass.  With the replay a chunk is a run of whole tiles (a tile's stream is walked in one go); without it any run
+// of at most max_paths / spp pixels.
+static void plan_chunks(size_t n_tiles, uint32_t max_paths, PassPlan &p)
+{
+	const uint32_t spp = p.spp, n_pixels_total = p.tile_px.back();
+	if(p.rpl.replay)
+	{
+		const uint32_t n_t = (uint32_t)n_tiles;
+		for(uint32_t t0 = 0; t0 < n_t;)
+		{
+			uint32_t t1 = t0 + 1;
+			while(t1 < n_t && (uint64_t)(p.tile_px[t1 + 1] - p.tile_px[t0]) * spp <= max_paths) ++t1;
+			p.chunks.push_back({p.tile_px[t0], p.tile_px[t1] - p.tile_px[t0], t0, t1});
+			t0 = t1;
+		}
+		return;
+	}
+	const uint32_t chunk_pixels = std::max(1u, std::min(n_pixels_total, std::max(1u, max_paths / spp)));
+	for(uint32_t pb = 0; pb < n_pixels_total; pb += chunk_pixels) p.chunks.push_back({pb, std::min(chunk_pixels, n_pixels_total - pb), 0u, 0u});
+}
+
+// Host arithmetic only: nothing is enqueued, allocated or waited for.  (The pixel tables it fills are the scene's because async copies
+// read them later.)  The refusals of a pass the device path cannot hold come from here.
+static int plan_pass(yafgpu_scene *s, const yafgpu_render_params &rp, const Switches &sw, const ReplayPlan &rpl, bool stats, PassPlan &p)
+{
+	p.rpl = rpl; p.stats = stats;
+	const uint32_t spp = p.spp = (uint32_t)rp.aa_minsamples;
 	// per-tile pixel prefix of the shard's tile list
 	std::vector<uint32_t> &pp = s->h_pix_prefix;
 	pp.assign(1, 0u);
 	for(const int4 &r : s->h_tiles) pp.push_back(pp.back() + (uint32_t)(r.z * r.w));
-	// a resample mask (adaptive pass): the pixels of this shard's tiles that are flagged, in tile order
-	std::vector<uint32_t> &listed = s->h_listed;        // scene-owned: uploaded per chunk with async copies
-	std::vector<uint32_t> listed_prefix(1, 0u);
-	const bool masked = rp.resample_mask != nullptr;
-	if(masked)
-	{
-		HIP_OK(hipStreamSynchronize(stream));             // the previous pass's uploads of the list have been read
+	p.masked = rp.resample_mask != nullptr;
+	if(p.masked)
+	{	// a resample mask (adaptive pass): the pixels of this shard's tiles that are flagged, in tile order
+		std::vector<uint32_t> &listed = s->h_listed;
 		listed.clear();
+		p.tile_px.assign(1, 0u);
 		for(const int4 &r : s->h_tiles)
 		{
 			for(int y = r.y; y < r.y + r.w; ++y)
 				for(int x = r.x; x < r.x + r.z; ++x)
 					if(rp.resample_mask[(size_t)(y - rp.ystart) * (size_t)rp.width + (size_t)(x - rp.xstart)]) listed.push_back((uint32_t)x | ((uint32_t)y << 16));
-			listed_prefix.push_back((uint32_t)listed.size());
+			p.tile_px.push_back((uint32_t)listed.size());
 		}
-		if(listed.empty()) return replay_plan(s, rp).lc_sharded ? lc_exchange_counts(s, rp, {}, nullptr) : 0;      // (the other ranks wait for this one's counts)
+		if(listed.empty()) return 0;      // (no chunks: nothing to render)
 	}
-	const std::vector<uint32_t> &tile_px = masked ? listed_prefix : pp;      // pixels of the pass before every tile of the shard
-	const uint32_t n_pixels_total = tile_px.back();
-	// Pass pipelining: this pass's path work goes to one of two internal streams with its own buffer set and does NOT wait for what the
-	// caller's stream holds (the previous pass, its film combine, a reduce); only the film accumulation is put on the caller's stream, after
-	// the path work.  Eligible: one chunk, no serial-state replay (its tables are per scene), no recursion polling, no resample mask (the
-	// host reads the film between such passes anyway), no per-kernel profiling.
-	bool pass_piped = false; int pipe_k = 0;
-	struct SwapBack { yafgpu_scene *s; int which; ~SwapBack() { if(which >= 0) swap_wf_sets(s, which); } } swap_back{s, -1};
-	{
+	else p.tile_px = pp;
+	const uint32_t n_pixels_total = p.tile_px.back();
+	{	// Pass pipelining: the pass's path work goes to one of two internal streams with its own buffer set and does NOT wait for what the
+		// caller's stream holds (the previous pass, its film combine, a reduce); only the film accumulation is put on the caller's stream, after
+		// the path work.  Eligible: one chunk, no serial-state replay (its tables are per scene), no recursion polling, no resample mask (the
+		// host reads the film between such passes anyway), no per-kernel profiling.
 		// measured (profiles/r03_ab_pipeline.txt): +18 % at an eighth of the metric frame, +10 % at a quarter, +4 % at half, -3 % at the whole
 		// frame (two full-size passes only compete) -- on by size, like the two traversal launches side by side
 		bool want = s->pass_pipelining < 0 ? (uint64_t)n_pixels_total * spp <= (12ull << 20) : s->pass_pipelining != 0;
-		if(const char *e = std::getenv("YAFGPU_PASS_PIPELINE")) want = std::atoi(e) != 0;
-		uint32_t mp = kWfMaxPaths;
-		if(const char *e = std::getenv("YAFGPU_WF_CHUNK")) mp = std::max(256u, (uint32_t)std::strtoul(e, nullptr, 10));
-		const ReplayPlan pl = replay_plan(s, rp);
-		pass_piped = want && !masked && !stats && !s->profiling && !pl.replay && pl.frames == 0 && (uint64_t)n_pixels_total * spp <= mp;
-		if(pass_piped)
-		{
-			int depth = 2;      // (a third pass in flight adds nothing: two chains already keep a launch beside every tail, profiles/r03_ab_pipeline.txt)
-			if(const char *e = std::getenv("YAFGPU_PASS_PIPELINE_DEPTH")) depth = std::min(std::max(std::atoi(e), 2), (int)yafgpu_scene::kPipeMax);
-			for(int k = 0; k < depth; ++k) if(!s->pipe_stream[k])
-			{
-				HIP_OK(hipStreamCreateWithFlags(&s->pipe_stream[k], hipStreamNonBlocking));
-				HIP_OK(hipEventCreateWithFlags(&s->pipe_done[k], hipEventDisableTiming));
-				HIP_OK(hipEventCreateWithFlags(&s->pipe_acc[k], hipEventDisableTiming));
-			}
-			if(!s->pipe_sync) HIP_OK(hipEventCreateWithFlags(&s->pipe_sync, hipEventDisableTiming));
-			if(!s->pipe_prev)
-			{	// the first of a run (or new tile arrays): what the caller's stream holds so far precedes both internal streams, once
-				HIP_OK(hipEventRecord(s->pipe_sync, caller));
-				for(int k = 0; k < depth; ++k) HIP_OK(hipStreamWaitEvent(s->pipe_stream[k], s->pipe_sync, 0));
-			}
-			if(s->pipe_next >= depth) s->pipe_next = 0;
-			pipe_k = s->pipe_next; s->pipe_next = (s->pipe_next + 1) % depth;
-			if(pipe_k > 0) { swap_wf_sets(s, pipe_k - 1); swap_back.which = pipe_k - 1; }
-			stream = s->pipe_stream[pipe_k];
-			// the set's previous pass has been added to the film (its results and pixel list are free again)
-			if(s->pipe_acc_set[pipe_k]) HIP_OK(hipStreamWaitEvent(stream, s->pipe_acc[pipe_k], 0));
-			if(ra.counters)
-			{
-				if(!s->pipe_counters[pipe_k]) HIP_OK(hipMalloc((void **)&s->pipe_counters[pipe_k], sizeof(yafgpu_counters)));
-				HIP_OK(hipMemsetAsync(s->pipe_counters[pipe_k], 0, sizeof(yafgpu_counters), stream));
-			}
-		}
-		s->pipe_prev = pass_piped;
+		if(sw.pass_pipeline >= 0) want = sw.pass_pipeline != 0;
+		p.piped = want && !p.masked && !stats && !s->profiling && !rpl.replay && rpl.frames == 0 && (uint64_t)n_pixels_total * spp <= sw.wf_chunk;
 	}
-	yafgpu_counters *const caller_counters = ra.counters;
-	if(pass_piped && ra.counters) ra.counters = s->pipe_counters[pipe_k];
-	if(pp.size() > s->pix_prefix_cap)
-	{
-		HIP_OK(hipStreamSynchronize(stream));
-		if(s->d_pix_prefix) (void)hipFree(s->d_pix_prefix);
-		s->pix_prefix_cap = pp.size();
-		HIP_OK(hipMalloc((void **)&s->d_pix_prefix, s->pix_prefix_cap * sizeof(uint32_t)));
-	}
-	// on `stream`: kernels of the previous pass may still be reading the table (a null-stream copy does not order against a
-	// non-blocking stream); the source is pageable, so the call returns once it has been staged
-	HIP_OK(hipMemcpyAsync(s->d_pix_prefix, pp.data(), pp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-	uint32_t max_paths = kWfMaxPaths;
-	if(const char *e = std::getenv("YAFGPU_WF_CHUNK")) max_paths = std::max(256u, (uint32_t)std::strtoul(e, nullptr, 10));     // tests chunk tiny frames
-	// recursiveRaytrace: a frame of 5 records per level a camera hit may recurse to
-	const ReplayPlan plan = replay_plan(s, rp);
-	const int frames = plan.frames;
-	const int frame_recs = s->has_glossy ? (s->has_bump ? 13 : 12) : 5;
-	if(frames > 7) return fail(-17, "raydepth + additionaldepth > 7 with mirror / transparent / glossy-recursive materials: the device path keeps at most 7 recursion frames per sample");
+	p.frames = rpl.frames;
+	p.frame_recs = s->has_glossy ? (s->has_bump ? 13 : 12) : 5;
+	if(p.frames > 7) return fail(-17, "raydepth + additionaldepth > 7 with mirror / transparent / glossy-recursive materials: the device path keeps at most 7 recursion frames per sample");
 	const bool path = rp.integrator == YAFGPU_INTEGRATOR_PATH;
-	const bool need_rr = plan.need_rr, replay = plan.replay, replay_lights = plan.replay_lights, lc_sharded = plan.lc_sharded;
-	const uint32_t n_ps = (uint32_t)std::max(rp.path_samples, 1), n_prob = (uint32_t)std::max(rp.bounces - 1, 1);
-	const uint32_t ev_m = replay ? (uint32_t)plan.ev_m : 1u;
-	if(replay && ev_m > 1)
+	p.n_ps = (uint32_t)std::max(rp.path_samples, 1); p.n_prob = (uint32_t)std::max(rp.bounces - 1, 1);
+	p.ev_m = rpl.replay ? (uint32_t)rpl.ev_m : 1u;
+	uint32_t max_paths = sw.wf_chunk;
+	if(rpl.replay && p.ev_m > 1)
 	{	// the event tables grow with the calls a sample can make: keep a chunk's tables within 12 GB
-		const uint64_t per_slot = (uint64_t)ev_m * n_ps * (4 + 4 * n_prob + 2) + 4;
+		const uint64_t per_slot = (uint64_t)p.ev_m * p.n_ps * (4 + 4 * p.n_prob + 2) + 4;
 		max_paths = (uint32_t)std::min<uint64_t>(max_paths, std::max<uint64_t>((12ull << 30) / per_slot, 4096));
 	}
-	// chunks: runs of pixels whose paths are in flight together.  With the replay a chunk is a run of whole tiles (a tile's
-	// stream is walked in one go); without it any run of at most max_paths / spp pixels.
-	struct Chunk { uint32_t pixel_begin, n_pixels, tile_begin, tile_end; };
-	std::vector<Chunk> chunks;
-	if(replay)
-	{
-		const uint32_t n_t = (uint32_t)s->h_tiles.size();
-		for(uint32_t t0 = 0; t0 < n_t;)
-		{
-			uint32_t t1 = t0 + 1;
-			while(t1 < n_t && (uint64_t)(tile_px[t1 + 1] - tile_px[t0]) * spp <= max_paths) ++t1;
-			chunks.push_back({tile_px[t0], tile_px[t1] - tile_px[t0], t0, t1});
-			t0 = t1;
-		}
-	}
-	else
-	{
-		const uint32_t chunk_pixels = std::max(1u, std::min(n_pixels_total, std::max(1u, max_paths / spp)));
-		for(uint32_t pb = 0; pb < n_pixels_total; pb += chunk_pixels) chunks.push_back({pb, std::min(chunk_pixels, n_pixels_total - pb), 0u, 0u});
-	}
+	plan_chunks(s->h_tiles.size(), max_paths, p);
 	uint32_t cap_pixels = 1u;
-	for(const Chunk &ch : chunks) cap_pixels = std::max(cap_pixels, ch.n_pixels);
+	for(const Chunk &ch : p.chunks) cap_pixels = std::max(cap_pixels, ch.n_pixels);
 	if((uint64_t)cap_pixels * spp > (1ull << 27)) return fail(-23, "one tile's samples exceed the 2^27 paths a wavefront chunk can hold: reduce tile_size or the samples per pass");
-	const uint32_t cap = cap_pixels * spp;
-	if(cap > s->wf_cap || frames * frame_recs > s->wf_frames)
-	{
-		HIP_OK(hipStreamSynchronize(stream));
-		if(s->wf_state) (void)hipFree(s->wf_state);
-		if(s->wf_results) (void)hipFree(s->wf_results);
-		if(s->wf_queues) (void)hipFree(s->wf_queues);
-		if(s->wf_verdict) (void)hipFree(s->wf_verdict);
-		if(s->wf_pix_xy) (void)hipFree(s->wf_pix_xy);
-		s->wf_state = nullptr; s->wf_results = nullptr; s->wf_queues = nullptr; s->wf_verdict = nullptr; s->wf_pix_xy = nullptr; s->wf_cap = 0;
-		HIP_OK(hipMalloc((void **)&s->wf_state, (size_t)(kWfRecs + frame_recs * frames) * cap * sizeof(float4)));
-		s->wf_frames = frames * frame_recs;      // frame records allocated per path
-		HIP_OK(hipMalloc((void **)&s->wf_results, (size_t)cap * sizeof(float4)));
-		// per buffer set: closest (cap), shadow rays (4*cap: up to two MIS pairs per park), resume (cap)
-		HIP_OK(hipMalloc((void **)&s->wf_queues, (size_t)12 * cap * sizeof(uint32_t)));
-		HIP_OK(hipMalloc((void **)&s->wf_verdict, ((size_t)4 * cap + 31) / 32 * sizeof(uint32_t) + 64));      // one bit per shadow ray
-		HIP_OK(hipMalloc((void **)&s->wf_pix_xy, (size_t)cap * sizeof(uint32_t)));     // pixels of a chunk <= paths of a chunk
-		s->wf_cap = cap;
-	}
-	uint32_t hit_k = 0; bool use_hits = false;
-	if(replay)
-	{	// event tables of the record pass, per path sample; segment tables per tile
-		const size_t ents = (size_t)s->wf_cap * ev_m * n_ps;
-		if(ents > s->rp_ents || n_prob > s->rp_prob)
-		{
-			HIP_OK(hipStreamSynchronize(stream));
-			for(void *q : {(void *)s->rp_flags, (void *)s->rp_p, (void *)s->rp_kill, (void *)s->rp_calls, (void *)s->rp_base}) if(q) (void)hipFree(q);
-			s->rp_flags = nullptr; s->rp_p = nullptr; s->rp_kill = nullptr; s->rp_calls = nullptr; s->rp_base = nullptr; s->rp_ents = 0;
-			HIP_OK(hipMalloc((void **)&s->rp_flags, ents * sizeof(uint32_t)));
-			HIP_OK(hipMalloc((void **)&s->rp_p, ents * n_prob * sizeof(float)));
-			HIP_OK(hipMalloc((void **)&s->rp_kill, ents));
-			HIP_OK(hipMalloc((void **)&s->rp_calls, ents));
-			HIP_OK(hipMalloc((void **)&s->rp_base, (size_t)s->wf_cap * sizeof(uint32_t)));
-			s->rp_ents = ents; s->rp_prob = n_prob;
-		}
-		// the record pass's closest-hit answers, one per (call, path sample, segment): kept when a camera sample's fit in 1 KB (the
-		// final pass then looks its closest hits up instead of tracing them again); never in a stats pass, whose per-ray traversal
-		// counts are the point
-		hit_k = ev_m * n_ps * ((uint32_t)std::max(rp.bounces, 1) + 1u);
-		use_hits = !stats && (size_t)hit_k * sizeof(float4) <= 1024 && (uint64_t)s->wf_cap * hit_k < (1ull << 32);      // (wf_hit_key is a 32-bit index)
-		if(const char *e = std::getenv("YAFGPU_HIT_CACHE")) use_hits = use_hits && std::atoi(e) != 0;
-		if(use_hits && (size_t)s->wf_cap * hit_k > s->rp_hits_cap)
-		{
-			HIP_OK(hipStreamSynchronize(stream));
-			if(s->rp_hits) (void)hipFree(s->rp_hits);
-			s->rp_hits = nullptr; s->rp_hits_cap = 0;
-			HIP_OK(hipMalloc((void **)&s->rp_hits, (size_t)s->wf_cap * hit_k * sizeof(float4)));
-			s->rp_hits_cap = (size_t)s->wf_cap * hit_k;
-		}
-		// every chunk's tiles as segments — first pixel of each (chunk-local) and the seed of its Random:
-		// rand() + offset * (resx * tile.y + tile.x) + 123 (integrator_tiled.cc:319), offset = pass offset + base sampling
-		// offset (:203,263).  One table for the whole pass, uploaded once: chunk k reads its slice [seg_off[k], ...).
-		HIP_OK(hipStreamSynchronize(stream));        // the previous pass's upload of the table has been read
-		s->h_seg_begin.clear(); s->h_seg_seed.clear();
-		{
-			const int ntx = (rp.width + rp.tile_size - 1) / rp.tile_size;
-			const uint32_t offset = rp.pass_offset + rp.base_sampling_offset;
-			for(const Chunk &ch : chunks)
-			{
-				for(uint32_t t = ch.tile_begin; t <= ch.tile_end; ++t) s->h_seg_begin.push_back(tile_px[t] - ch.pixel_begin);
-				for(uint32_t t = ch.tile_begin; t < ch.tile_end; ++t)
-				{
-					const int4 &r = s->h_tiles[t];
-					const int t_global = ((r.y - rp.ystart) / rp.tile_size) * ntx + (r.x - rp.xstart) / rp.tile_size;
-					const uint32_t rnd = rp.tile_rand ? (uint32_t)rp.tile_rand[t_global] : 0u;
-					s->h_seg_seed.push_back(rnd + offset * ((uint32_t)s->dev.cam.resx * (uint32_t)r.y + (uint32_t)r.x) + 123u);
-				}
-				s->h_seg_seed.push_back(0u);           // keeps the two tables aligned (n + 1 entries per chunk)
-			}
-		}
-		if(std::getenv("YAFGPU_VERBOSE"))
-		{
-			std::fprintf(stderr, "[yafgpu] replay pass_offset %u accumulate %d spp %u: seeds", rp.pass_offset, rp.accumulate, spp);
-			for(size_t k = 0; k < std::min<size_t>(s->h_seg_seed.size(), 6); ++k) std::fprintf(stderr, " %u", s->h_seg_seed[k]);
-			std::fprintf(stderr, " ... entries/tile");
-			for(size_t k = 0; k + 1 < std::min<size_t>(s->h_seg_begin.size(), 7); ++k) std::fprintf(stderr, " %u", s->h_seg_begin[k + 1] - s->h_seg_begin[k]);
-			std::fprintf(stderr, "\n");
-		}
-		const size_t segs = s->h_seg_begin.size();
-		if(segs > s->rp_segs)
-		{
-			HIP_OK(hipStreamSynchronize(stream));
-			for(void *q : {(void *)s->rp_seg_begin, (void *)s->rp_seg_seed, (void *)s->rp_seg_total, (void *)s->rp_seg_base}) if(q) (void)hipFree(q);
-			s->rp_seg_begin = nullptr; s->rp_seg_seed = nullptr; s->rp_seg_total = nullptr; s->rp_seg_base = nullptr; s->rp_segs = 0;
-			HIP_OK(hipMalloc((void **)&s->rp_seg_begin, segs * sizeof(uint32_t)));
-			HIP_OK(hipMalloc((void **)&s->rp_seg_seed, segs * sizeof(uint32_t)));
-			HIP_OK(hipMalloc((void **)&s->rp_seg_total, segs * sizeof(uint32_t)));
-			HIP_OK(hipMalloc((void **)&s->rp_seg_base, segs * sizeof(uint32_t)));
-			s->rp_segs = segs;
-		}
-		HIP_OK(hipMemcpyAsync(s->rp_seg_begin, s->h_seg_begin.data(), segs * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-		HIP_OK(hipMemcpyAsync(s->rp_seg_seed, s->h_seg_seed.data(), segs * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-		if(!s->rp_counter) HIP_OK(hipMalloc((void **)&s->rp_counter, sizeof(uint32_t)));
-		// correlative_sample_number_ is zeroed once per render, before its first pass (integrator_tiled.cc:192-194)
-		if(!rp.accumulate) HIP_OK(hipMemsetAsync(s->rp_counter, 0, sizeof(uint32_t), stream));
-	}
+	p.cap = cap_pixels * spp;
 	// transparent shadows only cost anything when a material can be transparent to a shadow ray
-	const bool transp = rp.transp_shad != 0 && s->has_transparent;
-	if(transp && rp.shadow_depth > kTsMaxDepth) return fail(-18, "shadowDepth > 8 with transparent shadows: the device path remembers at most 9 filtered triangles per shadow ray");
-	if(transp && s->wf_cap > s->wf_filt_cap)
-	{
-		if(s->wf_filt) (void)hipFree(s->wf_filt);
-		s->wf_filt = nullptr; s->wf_filt_cap = 0;
-		HIP_OK(hipMalloc((void **)&s->wf_filt, (size_t)2 * s->wf_cap * sizeof(float4)));
-		s->wf_filt_cap = s->wf_cap;
+	p.transp = rp.transp_shad != 0 && s->has_transparent;
+	if(p.transp && rp.shadow_depth > kTsMaxDepth) return fail(-18, "shadowDepth > 8 with transparent shadows: the device path remembers at most 9 filtered triangles per shadow ray");
+	if(rpl.replay)
+	{	// the record pass's closest-hit answers, one per (call, path sample, segment): kept when a camera sample's fit in 1 KB (the
+		// final pass then looks its closest hits up instead of tracing them again); never in a stats pass, whose per-ray traversal
+		// counts are the point.  (A pass that replays runs on set 0; wf_hit_key is a 32-bit index.)
+		p.hit_k = p.ev_m * p.n_ps * ((uint32_t)std::max(rp.bounces, 1) + 1u);
+		const uint32_t set_cap = s->sets[0].cap_for(p.cap, p.frames * p.frame_recs);
+		p.use_hits = !stats && (size_t)p.hit_k * sizeof(float4) <= 1024 && (uint64_t)set_cap * p.hit_k < (1ull << 32) && sw.hit_cache;
 	}
-	if(!s->wf_counts) HIP_OK(hipMalloc((void **)&s->wf_counts, 64 * sizeof(uint32_t)));      // two sets of 32 (in / out)
-	if(const int e = device_cus(s)) return e;
-	const int cus = s->n_cus;
-	const int g_trace_c = stats ? wf_grid((const void *)wf_trace<false, true>, cus) : wf_grid((const void *)wf_trace<false, false>, cus);
-	const int g_trace_s = stats ? wf_grid((const void *)wf_trace<true, true>, cus) : wf_grid((const void *)wf_trace<true, false>, cus);
-	// two MIS pairs per park (WfArgs::multi): not with transparent shadows (their filter products are kept per pair), not with recursion frames —
-	// and only where a light estimate can have a second pair at all: the kernels that carry it are a little slower on the first
-	bool want_multi = !(rp.transp_shad != 0 && s->has_transparent) && frames == 0;
-	if(const char *e = std::getenv("YAFGPU_MULTI_PAIR")) if(std::atoi(e) == 0) want_multi = false;
-	if(want_multi)
-	{
-		int pairs = 0;
-		for(int i = 0; i < s->n_lights; ++i)
-		{
-			pairs += light_pairs(s->h_lights[(size_t)i], rp.aa_light_sample_multiplier);
-		}
-		want_multi = pairs > 1;
-	}
-	const ShadeVariant *shade_variant = pick_shade_variant(s, frames, false, want_multi);
-	if(!shade_variant && want_multi)
-	{	// no kernel with the second pair for these materials: the one without it rather than the general kernel
-		shade_variant = pick_shade_variant(s, frames, false, false);
-		if(shade_variant) want_multi = false;
-	}
-	if(std::getenv("YAFGPU_VERBOSE")) std::fprintf(stderr, "[yafgpu] shading kernel: %s (materials 0x%x, frames %d), serial replay: %s\n", shade_variant ? shade_variant->name : "general", s->mat_mask, frames,
-	                                               replay ? (replay_lights ? (need_rr ? "roulette + light counter" : "light counter") : "roulette") : "off");
-	const int g_shade = wf_grid(shade_variant ? shade_variant->kernel() : (const void *)wf_shade, cus);
-	// a record pass runs its own, smaller program where one was built for the scene's materials (else the pass's kernel, which branches on WfArgs::replay)
-	const ShadeVariant *record_variant = replay ? pick_shade_variant(s, frames, true) : nullptr;
-	const int g_shade_rec = record_variant ? wf_grid(record_variant->kernel(), cus) : g_shade;
-	// upper bound of kd-tree queries per path = iterations needed (every path advances one query per iteration)
+	// shadow parks (MIS pairs) of the light estimates: all lights of estimateAllDirectLight, the largest of estimateOneDirectLight
 	int r_all = 0, r_one = 0;
-	for(int i = 0; i < s->n_lights; ++i)
+	for(const yafgpu_light &l : s->h_lights)
 	{
-		const int r = light_pairs(s->h_lights[(size_t)i], rp.aa_light_sample_multiplier);   // shadow parks (MIS pairs)
+		const int r = light_pairs(l, rp.aa_light_sample_multiplier);
 		r_all += r; r_one = std::max(r_one, r);
 	}
-	int iters = 1 + r_all;
-	if(rp.integrator == YAFGPU_INTEGRATOR_PATH)
-		iters += std::max(1, rp.path_samples) * ((1 + r_one) + std::max(0, rp.bounces - 1) * (1 + r_one));
+	// two MIS pairs per park (WfArgs::multi): not with transparent shadows (their filter products are kept per pair), not with recursion frames —
+	// and only where a light estimate can have a second pair at all: the kernels that carry it are a little slower on the first
+	p.want_multi = !p.transp && p.frames == 0 && sw.multi_pair && r_all > 1;
+	p.shade = pick_shade_variant(s, sw, p.frames, false, p.want_multi);
+	if(!p.shade && p.want_multi)
+	{	// no kernel with the second pair for these materials: the one without it rather than the general kernel
+		p.shade = pick_shade_variant(s, sw, p.frames, false, false);
+		if(p.shade) p.want_multi = false;
+	}
+	// a record pass runs its own, smaller program where one was built for the scene's materials (else the pass's kernel, which branches on WfArgs::replay)
+	p.record = rpl.replay ? pick_shade_variant(s, sw, p.frames, true, false) : nullptr;
+	if(sw.verbose) std::fprintf(stderr, "[yafgpu] shading kernel: %s (materials 0x%x, frames %d), serial replay: %s\n", p.shade ? p.shade->name : "general", s->mat_mask, p.frames,
+	                            rpl.replay ? (rpl.replay_lights ? (rpl.need_rr ? "roulette + light counter" : "light counter") : "roulette") : "off");
+	p.iters = 1 + r_all;
+	if(path) p.iters += std::max(1, rp.path_samples) * ((1 + r_one) + std::max(0, rp.bounces - 1) * (1 + r_one));
 	// a record pass asks for closest hits only: the camera ray + per path sample one query per segment
-	const int iters_record = 1 + (path ? std::max(1, rp.path_samples) * std::max(1, rp.bounces) : 0);
-	// opt-in (YAFGPU_OVERLAP=1): +2-4 % on the bench scenes, but per-kernel durations then overlap in a profiler trace, so
-	// the default keeps one kernel on the GPU at a time and the roofline numbers comparable with rocprofv3's
-	// ... except for small chunks (a tile shard of a multi-GPU render, a small frame): with a few rays per lane a persistent
-	// launch is mostly tail, and the two traversal launches of an iteration side by side are worth +5 % at half the metric
-	// frame, +8 % at a quarter, +12 % at an eighth (bench.py --emulate-shard).  YAFGPU_OVERLAP=0 / 1 force either.
-	// ... and always since a path parks its next segment beside a vertex's last shadow pair (WfArgs::speculate): the middle phases of a
-	// pass then have BOTH queues full, and the two launches side by side are worth +2 % on the whole metric frame too (profiles/r03_ab_speculate.txt).
-	// The per-kernel durations of the roofline come from the profiled pass, which keeps one kernel on the GPU at a time either way.
-	bool overlap = (uint64_t)cap_pixels * spp < (12ull << 20);
-	{
-		const char *sp = std::getenv("YAFGPU_SPECULATE");
-		if(!(sp && std::atoi(sp) == 0)) overlap = true;
-	}
-	if(const char *e = std::getenv("YAFGPU_OVERLAP")) overlap = std::atoi(e) != 0;
-	if(overlap && !s->side_stream)
-	{
-		HIP_OK(hipStreamCreateWithFlags(&s->side_stream, hipStreamNonBlocking));
-		HIP_OK(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-		HIP_OK(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
-	}
-	EventPair evp;          // destroyed on every return
-	hipEvent_t (&ev)[2] = evp.e;
-	if(s->profiling) { HIP_OK(hipEventCreate(&ev[0])); HIP_OK(hipEventCreate(&ev[1])); for(int k = 0; k < 4; ++k) { s->prof_ms[k] = 0; s->prof_launches[k] = 0; } }
-	auto timed = [&](int slot, auto &&launch) -> int {
-		if(s->profiling) HIP_OK(hipEventRecord(ev[0], stream));
-		launch();
-		HIP_OK(hipGetLastError());
-		if(s->profiling)
-		{
-			HIP_OK(hipEventRecord(ev[1], stream));
-			HIP_OK(hipEventSynchronize(ev[1]));
-			float ms = 0.f; HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-			s->prof_ms[slot] += ms; s->prof_launches[slot] += 1;
-		}
-		return 0;
-	};
-	// phase 0: the whole program for a chunk.  A sharded light counter (lc_sharded) splits it: phase 1 = record pass + the tiles'
-	// roulette walk and call counts, for every chunk; then the ranks exchange the counts; phase 2 = the rest, from the bases the
-	// exchange gave (a pass of one chunk keeps its events from phase 1, one of several records them again).
-	std::vector<std::pair<int, uint32_t>> own_calls;
-	auto process_chunk = [&](const Chunk &ch, size_t &seg_off, int phase) -> int
-	{
-		if(s->aborted()) return fail(-30, "aborted");
-		WfArgs a{};
-		a.ra = ra;
-		a.state = s->wf_state; a.cap = s->wf_cap; a.results = s->wf_results; a.frames = frames; a.frame_recs = frame_recs; a.has_glossy = s->has_glossy ? 1 : 0;
-		a.pixel_begin = ch.pixel_begin; a.n_pixels = ch.n_pixels; a.n_paths = a.n_pixels * spp;
-		a.pix_prefix = s->d_pix_prefix; a.pix_xy = s->wf_pix_xy; a.pix_listed = masked ? 1 : 0;
-		if(masked) HIP_OK(hipMemcpyAsync(s->wf_pix_xy, listed.data() + ch.pixel_begin, (size_t)a.n_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-		a.ev_flags = s->rp_flags; a.ev_p = s->rp_p; a.ev_kill = s->rp_kill; a.ev_calls = s->rp_calls; a.lc_base = s->rp_base;
-		a.replay_lights = replay_lights ? 1 : 0; a.ev_m = (int)ev_m;
-		a.multi = want_multi ? 1 : 0;
-		a.speculate = 1;      // the next segment beside a vertex's last shadow pair (WfArgs::speculate); YAFGPU_SPECULATE=0: the sequential phases
-		if(const char *e = std::getenv("YAFGPU_SPECULATE")) a.speculate = std::atoi(e) != 0 ? 1 : 0;
-		a.hit_cache = use_hits ? s->rp_hits : nullptr; a.hit_k = (int)hit_k;
-		const size_t cp = s->wf_cap;
-		uint32_t *qset[2][3] = {{s->wf_queues, s->wf_queues + cp, s->wf_queues + 5 * cp},
-		                        {s->wf_queues + 6 * cp, s->wf_queues + 7 * cp, s->wf_queues + 11 * cp}};   // closest, shadow rays (4*cap), resume
-		uint32_t *cnt[2] = {s->wf_counts, s->wf_counts + 32};
-		a.verdict = s->wf_verdict; a.shadow_filt = transp ? s->wf_filt : nullptr;
-		const uint32_t g_gen = std::min<uint32_t>((a.n_paths + kBlock - 1) / kBlock, (uint32_t)cus * 8u);
-		int rc;
-		// one run of the path program over the chunk: generate, then iterations of {closest-hit, any-hit, shade} until
-		// every path has ended.  Without recursion the number of queries per path is bounded a priori (n_iters) and the
-		// loop never asks the device anything.  With recursiveRaytrace a sample may visit up to 2^raydepth levels, so past
-		// that bound the loop runs on while any queue is non-empty (one 20-byte read-back per iteration).
-		auto run = [&](int n_iters, bool record) -> int {
-			a.cnt_in = cnt[0]; a.cnt_out = cnt[1];
-			a.q_closest_in = nullptr; a.q_shadow_in = qset[0][1]; a.q_resume_in = qset[0][2];
-			a.q_closest_out = qset[1][0]; a.q_shadow_out = qset[1][1]; a.q_resume_out = qset[1][2];
-			if((rc = timed(3, [&] { hipLaunchKernelGGL(wf_generate, dim3(g_gen), dim3(kBlock), 0, stream, a); }))) return rc;
-			int cur = 0;
-			const int iter_cap = n_iters * (frames > 0 ? (1 << (frames + 1)) : 1) * (s->has_glossy ? (s->has_glossy_two ? 32 : 16) : 1);      // (a safety net: the loop ends when the queues are empty)
-			for(int it = 0; it < iter_cap; ++it)
-			{
-				if(frames > 0 && it >= n_iters)
-				{
-					uint32_t pending[5];
-					HIP_OK(hipMemcpyAsync(pending, a.cnt_in, sizeof pending, hipMemcpyDeviceToHost, stream));
-					HIP_OK(hipStreamSynchronize(stream));
-					if(pending[0] == 0u && pending[1] == 0u && pending[4] == 0u) break;
-				}
-				else if(frames == 0 && it >= n_iters) break;
-				HIP_OK(hipMemsetAsync(a.cnt_out, 0, 8 * sizeof(uint32_t), stream));
-				const bool overlap_now = overlap && it > 0 && !s->profiling && !record;
-				if(overlap_now)
-				{	// fork point: everything enqueued so far (the previous shade, the counter reset) precedes both launches
-					HIP_OK(hipEventRecord(s->ev_fork, stream));
-					HIP_OK(hipStreamWaitEvent(s->side_stream, s->ev_fork, 0));
-				}
-				if(!record && a.replay == 2 && a.hit_cache != nullptr)
-				{	// the record pass answered these queries already: wf_shade reads them from its cache where it would read the traversal's answers
-				}
-				else if((rc = timed(0, [&] {
-					if(stats) hipLaunchKernelGGL((wf_trace<false, true>), dim3(g_trace_c), dim3(kBlock), 0, stream, a);
-					else hipLaunchKernelGGL((wf_trace<false, false>), dim3(g_trace_c), dim3(kBlock), 0, stream, a); }))) return rc;
-				// The two traversal launches of an iteration are independent (each drains its own queue, writes its own
-				// answers), and a persistent kernel's tail leaves CUs idle: outside profiling the any-hit launch goes to a
-				// side stream so that its waves fill the closest-hit launch's tail (and vice versa).
-				const bool fork = overlap_now;
-				hipStream_t any_stream = fork ? s->side_stream : stream;
-				if(it > 0 && !record)      // (a record pass has no shadow rays)
-				{
-					HIP_OK(hipMemsetAsync(s->wf_verdict, 0, ((size_t)4 * a.n_paths + 31) / 32 * sizeof(uint32_t), any_stream));     // occluded rays set their bit
-					if((rc = timed(1, [&] {
-						if(transp) hipLaunchKernelGGL(wf_trace_ts, dim3(cus * 8), dim3(kBlock), 0, any_stream, a);
-						else if(stats) hipLaunchKernelGGL((wf_trace<true, true>), dim3(g_trace_s), dim3(kBlock), 0, any_stream, a);
-						else hipLaunchKernelGGL((wf_trace<true, false>), dim3(g_trace_s), dim3(kBlock), 0, any_stream, a); }))) return rc;
-				}
-				if(fork)
-				{
-					HIP_OK(hipEventRecord(s->ev_join, s->side_stream));
-					HIP_OK(hipStreamWaitEvent(stream, s->ev_join, 0));
-				}
-				int variant_rc = 0;
-				if((rc = timed(2, [&] {
-					if(record && record_variant) variant_rc = record_variant->launch(&a, sizeof a, g_shade_rec, stream);
-					else if(shade_variant) variant_rc = shade_variant->launch(&a, sizeof a, g_shade, stream);
-					else hipLaunchKernelGGL(wf_shade, dim3(g_shade), dim3(kBlock), 0, stream, a); }))) return rc;
-				if(variant_rc) return fail(-21, "shading kernel variant and main unit disagree on the argument layout");
-				// swap queues: what shade produced is the next iteration's input
-				cur ^= 1;
-				a.cnt_in = cnt[cur]; a.cnt_out = cnt[cur ^ 1];
-				a.q_closest_in = qset[cur][0]; a.q_shadow_in = qset[cur][1]; a.q_resume_in = qset[cur][2];
-				a.q_closest_out = qset[cur ^ 1][0]; a.q_shadow_out = qset[cur ^ 1][1]; a.q_resume_out = qset[cur ^ 1][2];
-			}
-			return 0;
-		};
-		if(replay)
-		{
-			const bool have_events = phase == 2 && chunks.size() == 1;
-			if(!have_events)
-			{	// record pass: the paths alone (no light estimates, no roulette kills), rays not counted
-				a.replay = 1;
-				yafgpu_counters *const keep = a.ra.counters;
-				a.ra.counters = nullptr;
-				HIP_OK(hipMemsetAsync(s->rp_flags, 0, (size_t)a.n_paths * ev_m * n_ps * sizeof(uint32_t), stream));
-				if((rc = run(iters_record, true))) return rc;
-				a.ra.counters = keep;
-			}
-			const uint32_t n_seg = ch.tile_end - ch.tile_begin;
-			ReplayArgs r{};
-			r.seg_begin = s->rp_seg_begin + seg_off; r.seg_seed = s->rp_seg_seed + seg_off; r.n_seg = n_seg; r.spp = spp; r.n_paths = ev_m * n_ps; r.n_prob = n_prob;
-			r.bounces = (uint32_t)std::max(rp.bounces, 1);
-			r.ev_flags = s->rp_flags; r.ev_p = s->rp_p; r.ev_kill = s->rp_kill; r.ev_calls = s->rp_calls; r.lc_base = s->rp_base;
-			r.seg_total = s->rp_seg_total + seg_off; r.lc_counter = s->rp_counter;
-			r.seg_base_in = phase == 2 ? s->rp_seg_base + seg_off : nullptr;
-			if((rc = timed(3, [&] {
-				if(!have_events) hipLaunchKernelGGL(wf_replay_tiles, dim3(n_seg), dim3(kWave), 0, stream, r);
-				if(phase == 0) hipLaunchKernelGGL(wf_replay_bases, dim3(1), dim3(1), 0, stream, r);
-				if(phase != 1) hipLaunchKernelGGL(wf_replay_samples, dim3(n_seg), dim3(kWave), 0, stream, r); }))) return rc;
-			if(phase == 1)
-			{	// this chunk's calls per tile, by global tile index
-				std::vector<uint32_t> totals(n_seg);
-				HIP_OK(hipMemcpyAsync(totals.data(), s->rp_seg_total + seg_off, n_seg * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-				HIP_OK(hipStreamSynchronize(stream));
-				const int ntx = (rp.width + rp.tile_size - 1) / rp.tile_size;
-				for(uint32_t k = 0; k < n_seg; ++k)
-				{
-					const int4 &t = s->h_tiles[ch.tile_begin + k];
-					own_calls.emplace_back(((t.y - rp.ystart) / rp.tile_size) * ntx + (t.x - rp.xstart) / rp.tile_size, totals[k]);
-				}
-				seg_off += n_seg + 1;
-				return 0;
-			}
-			if(std::getenv("YAFGPU_VERBOSE"))
-			{
-				uint32_t cnt_now = 0;
-				HIP_OK(hipMemcpyAsync(&cnt_now, s->rp_counter, sizeof cnt_now, hipMemcpyDeviceToHost, stream));
-				HIP_OK(hipStreamSynchronize(stream));
-				std::fprintf(stderr, "[yafgpu] replay chunk of %u tiles: light counter now %u\n", n_seg, cnt_now);
-			}
-			a.replay = 2;
-			seg_off += n_seg + 1;
-		}
-		if((rc = run(iters, false))) return rc;
-		const uint32_t g_acc = std::min<uint32_t>((a.n_pixels + kBlock - 1) / kBlock, (uint32_t)cus * 8u);
-		if(pass_piped)
-		{	// the film on the caller's stream, after this pass's path work and (by that stream's order) after the previous pass's film
-			HIP_OK(hipEventRecord(s->pipe_done[pipe_k], stream));
-			HIP_OK(hipStreamWaitEvent(caller, s->pipe_done[pipe_k], 0));
-			WfArgs acc = a;
-			acc.ra.counters = caller_counters;
-			hipLaunchKernelGGL(wf_accumulate, dim3(g_acc), dim3(kBlock), 0, caller, acc);
-			if(caller_counters) hipLaunchKernelGGL(add_counters, dim3(1), dim3(64), 0, caller, caller_counters, (const yafgpu_counters *)s->pipe_counters[pipe_k]);
-			HIP_OK(hipGetLastError());
-			HIP_OK(hipEventRecord(s->pipe_acc[pipe_k], caller));
-			s->pipe_acc_set[pipe_k] = true;
-			return 0;
-		}
-		if((rc = timed(3, [&] { hipLaunchKernelGGL(wf_accumulate, dim3(g_acc), dim3(kBlock), 0, stream, a); }))) return rc;
-		return 0;
-	};
-	int rc = 0;
-	if(lc_sharded)
-	{
-		size_t seg_off = 0;
-		for(const Chunk &ch : chunks) if((rc = process_chunk(ch, seg_off, 1))) return rc;
-		std::vector<uint32_t> base_of_tile;
-		if((rc = lc_exchange_counts(s, rp, own_calls, &base_of_tile))) return rc;
-		// the bases in the layout of the segment tables (n + 1 entries per chunk)
-		const int ntx = (rp.width + rp.tile_size - 1) / rp.tile_size;
-		s->h_seg_base.clear();
-		for(const Chunk &ch : chunks)
-		{
-			for(uint32_t t = ch.tile_begin; t < ch.tile_end; ++t)
-			{
-				const int4 &r = s->h_tiles[t];
-				s->h_seg_base.push_back(base_of_tile[(size_t)(((r.y - rp.ystart) / rp.tile_size) * ntx + (r.x - rp.xstart) / rp.tile_size)]);
-			}
-			s->h_seg_base.push_back(0u);
-		}
-		HIP_OK(hipMemcpyAsync(s->rp_seg_base, s->h_seg_base.data(), s->h_seg_base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-	}
-	size_t seg_off = 0;
-	for(const Chunk &ch : chunks) if((rc = process_chunk(ch, seg_off, lc_sharded ? 2 : 0))) return rc;
+	p.iters_record = 1 + (path ? std::max(1, rp.path_samples) * std::max(1, rp.bounces) : 0);
+	// The closest-hit and the any-hit launch of an iteration side by side on two streams (run_program).  On whenever a path parks its next
+	// segment beside a vertex's last shadow pair (WfArgs::speculate, the default): the middle phases of a pass then have BOTH queues full,
+	// worth +2 % on the whole metric frame (profiles/r03_ab_speculate.txt).  With YAFGPU_SPECULATE=0, by size: chunks under 12 Mi paths,
+	// where a persistent launch with a few rays per lane is mostly tail (+5 % at half the metric frame, +8 % at a quarter, +12 % at an
+	// eighth, bench.py --emulate-shard).  YAFGPU_OVERLAP=0 / 1 overrides both.  Per-kernel durations overlap in a profiler trace then;
+	// the roofline's come from the profiled pass, which keeps one kernel on the GPU at a time either way.
+	p.overlap = sw.overlap >= 0 ? sw.overlap != 0 : (sw.speculate || (uint64_t)cap_pixels * spp < (12ull << 20));
 	return 0;
 }
+
+// One pass on its way: the plan, the buffer set and the streams it runs on
+struct PassCtx
+{
+	yafgpu_scene *s; const PassPlan &p; const Switches &sw; WfSet &w;
+	RenderArgs &ra;                      // ra.counters: where the pass's kernels count (a pipelined pass: the set's own block)
+	hipStream_t stream, caller;          // the pass's path work; the caller's stream (the same unless the pass is pipelined)
+	yafgpu_counters *caller_counters;
+	int g_trace_c = 0, g_trace_s = 0, g_shade = 0, g_shade_rec = 0;      // launch grids
+	Event ev[2];                         // profiling
+	std::vector<std::pair<int, uint32_t>> own_calls;      // sharded light counter: this rank's calls per tile (global tile index, count)
+};
+
+// The pipelining prologue: picks the set whose turn it is and orders its stream.  The counters of the pass go to the set's own block.
+static int begin_piped_pass(yafgpu_scene *s, hipStream_t caller, bool counters, int &k)
+{
+	k = s->pipe_next; s->pipe_next ^= 1;
+	for(WfSet &o : s->sets) { HIP_OK(o.stream.create()); HIP_OK(o.done.create()); HIP_OK(o.acc.create()); }
+	HIP_OK(s->pipe_sync.create());
+	WfSet &w = s->sets[k];
+	if(counters) HIP_OK(w.counters.reserve(1, w.stream));
+	if(!s->pipe_prev)
+	{	// the first of a run (or new tile arrays): what the caller's stream holds so far precedes both internal streams, once
+		HIP_OK(hipEventRecord(s->pipe_sync, caller));
+		for(WfSet &o : s->sets) HIP_OK(hipStreamWaitEvent(o.stream, s->pipe_sync, 0));
+	}
+	// the set's previous pass has been added to the film (its results and pixel list are free again)
+	if(w.acc_set) HIP_OK(hipStreamWaitEvent(w.stream, w.acc, 0));
+	if(counters) HIP_OK(hipMemsetAsync(w.counters, 0, sizeof(yafgpu_counters), w.stream));
+	return 0;
+}
+
+// The set's buffers (and, for a pass that replays, the scene's event tables) large enough for the pass; nothing happens where they are.
+static int reserve_workspace(PassCtx &c)
+{
+	yafgpu_scene *s = c.s; WfSet &w = c.w; const PassPlan &p = c.p; const hipStream_t st = c.stream;
+	HIP_OK(w.pix_prefix.reserve(s->h_pix_prefix.size(), st));
+	if(w.outgrown(p.cap, p.frames * p.frame_recs)) { w.cap = p.cap; w.frame_recs = p.frames * p.frame_recs; }
+	const size_t cap = w.cap;
+	HIP_OK(w.state.reserve((size_t)(kWfRecs + w.frame_recs) * cap, st));
+	HIP_OK(w.results.reserve(cap, st));
+	// two queue sets, each: closest (cap), shadow rays (4*cap: up to two MIS pairs per park), resume (cap)
+	HIP_OK(w.queues.reserve(12 * cap, st));
+	HIP_OK(w.verdict.reserve((4 * cap + 31) / 32 + 16, st));      // one bit per shadow ray (+ 64 bytes)
+	HIP_OK(w.pix_xy.reserve(cap, st));          // pixels of a chunk <= paths of a chunk
+	HIP_OK(w.counts.reserve(64, st));           // two sets of 32 (in / out)
+	if(p.transp) HIP_OK(w.filt.reserve(2 * cap, st));
+	if(p.rpl.replay)
+	{	// event tables of the record pass, per path sample
+		const size_t ents = cap * p.ev_m * p.n_ps;
+		HIP_OK(s->rp_flags.reserve(ents, st));
+		HIP_OK(s->rp_p.reserve(ents * p.n_prob, st));
+		HIP_OK(s->rp_kill.reserve(ents, st));
+		HIP_OK(s->rp_calls.reserve(ents, st));
+		HIP_OK(s->rp_base.reserve(cap, st));
+		if(p.use_hits) HIP_OK(s->rp_hits.reserve(cap * p.hit_k, st));
+		HIP_OK(s->rp_counter.reserve(1, st));
+	}
+	return 0;
+}
+
+// Every chunk's tiles as segments — first pixel of each (chunk-local) and the seed of its Random:
+// rand() + offset * (resx * tile.y + tile.x) + 123 (integrator_tiled.cc:319), offset = pass offset + base sampling
+// offset (:203,263).  One table for the whole pass, uploaded once: chunk k reads its slice [seg_off[k], ...).
+static int upload_segments(PassCtx &c)
+{
+	yafgpu_scene *s = c.s; const PassPlan &p = c.p; const yafgpu_render_params &rp = c.ra.rp;
+	HIP_OK(hipStreamSynchronize(c.stream));        // the previous pass's upload of the table has been read
+	s->h_seg_begin.clear(); s->h_seg_seed.clear();
+	const uint32_t offset = rp.pass_offset + rp.base_sampling_offset;
+	for(const Chunk &ch : p.chunks)
+	{
+		for(uint32_t t = ch.tile_begin; t <= ch.tile_end; ++t) s->h_seg_begin.push_back(p.tile_px[t] - ch.pixel_begin);
+		for(uint32_t t = ch.tile_begin; t < ch.tile_end; ++t)
+		{
+			const int4 &r = s->h_tiles[t];
+			const uint32_t rnd = rp.tile_rand ? (uint32_t)rp.tile_rand[tile_global_index(rp, r)] : 0u;
+			s->h_seg_seed.push_back(rnd + offset * ((uint32_t)s->dev.cam.resx * (uint32_t)r.y + (uint32_t)r.x) + 123u);
+		}
+		s->h_seg_seed.push_back(0u);           // keeps the two tables aligned (n + 1 entries per chunk)
+	}
+	if(c.sw.verbose)
+	{
+		std::fprintf(stderr, "[yafgpu] replay pass_offset %u accumulate %d spp %u: seeds", rp.pass_offset, rp.accumulate, p.spp);
+		for(size_t k = 0; k < std::min<size_t>(s->h_seg_seed.size(), 6); ++k) std::fprintf(stderr, " %u", s->h_seg_seed[k]);
+		std::fprintf(stderr, " ... entries/tile");
+		for(size_t k = 0; k + 1 < std::min<size_t>(s->h_seg_begin.size(), 7); ++k) std::fprintf(stderr, " %u", s->h_seg_begin[k + 1] - s->h_seg_begin[k]);
+		std::fprintf(stderr, "\n");
+	}
+	const size_t segs = s->h_seg_begin.size();
+	HIP_OK(s->rp_seg_begin.reserve(segs, c.stream));
+	HIP_OK(s->rp_seg_seed.reserve(segs, c.stream));
+	HIP_OK(s->rp_seg_total.reserve(segs, c.stream));
+	HIP_OK(s->rp_seg_base.reserve(segs, c.stream));
+	HIP_OK(hipMemcpyAsync(s->rp_seg_begin, s->h_seg_begin.data(), segs * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+	HIP_OK(hipMemcpyAsync(s->rp_seg_seed, s->h_seg_seed.data(), segs * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+	// correlative_sample_number_ is zeroed once per render, before its first pass (integrator_tiled.cc:192-194)
+	if(!rp.accumulate) HIP_OK(hipMemsetAsync(s->rp_counter, 0, sizeof(uint32_t), c.stream));
+	return 0;
+}
+
+// The one place that records profiling events: a launch on the pass's stream and, under profiling, its duration into `slot`
+// (yafgpu_get_profile: trace closest, trace shadow, shade, other).
+template<typename F> static int timed(PassCtx &c, int slot, F &&launch)
+{
+	yafgpu_scene *s = c.s;
+	if(s->profiling) HIP_OK(hipEventRecord(c.ev[0], c.stream));
+	launch();
+	HIP_OK(hipGetLastError());
+	if(s->profiling)
+	{
+		HIP_OK(hipEventRecord(c.ev[1], c.stream));
+		HIP_OK(hipEventSynchronize(c.ev[1]));
+		float ms = 0.f; HIP_OK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+		s->prof_ms[slot] += ms; s->prof_launches[slot] += 1;
+	}
+	return 0;
+}
+
+// One run of the path program over a chunk: generate, then iterations of {closest-hit, any-hit, shade} until
+// every path has ended.  Without recursion the number of queries per path is bounded a priori (n_iters) and the
+// loop never asks the device anything.  With recursiveRaytrace a sample may visit up to 2^raydepth levels, so past
+// that bound the loop runs on while any queue is non-empty (one 20-byte read-back per iteration).
+static int run_program(PassCtx &c, WfArgs &a, int n_iters, bool record)
+{
+	yafgpu_scene *s = c.s; WfSet &w = c.w; const PassPlan &p = c.p; const hipStream_t stream = c.stream;
+	const int cus = s->n_cus;
+	const size_t cp = w.cap;
+	uint32_t *const qset[2][3] = {{w.queues, w.queues + cp, w.queues + 5 * cp},
+	                              {w.queues + 6 * cp, w.queues + 7 * cp, w.queues + 11 * cp}};   // closest, shadow rays (4*cap), resume
+	uint32_t *const cnt[2] = {w.counts, w.counts + 32};
+	int rc;
+	a.cnt_in = cnt[0]; a.cnt_out = cnt[1];
+	a.q_closest_in = nullptr; a.q_shadow_in = qset[0][1]; a.q_resume_in = qset[0][2];
+	a.q_closest_out = qset[1][0]; a.q_shadow_out = qset[1][1]; a.q_resume_out = qset[1][2];
+	const uint32_t g_gen = std::min<uint32_t>((a.n_paths + kBlock - 1) / kBlock, (uint32_t)cus * 8u);
+	if((rc = timed(c, 3, [&] { hipLaunchKernelGGL(wf_generate, dim3(g_gen), dim3(kBlock), 0, stream, a); }))) return rc;
+	int cur = 0;
+	const int iter_cap = n_iters * (p.frames > 0 ? (1 << (p.frames + 1)) : 1) * (s->has_glossy ? (s->has_glossy_two ? 32 : 16) : 1);      // (a safety net: the loop ends when the queues are empty)
+	// the record pass answered the final pass's closest-hit queries already: wf_shade reads them from its cache where it would read the traversal's answers
+	const bool trace_closest = record || a.replay != 2 || a.hit_cache == nullptr;
+	for(int it = 0; it < iter_cap; ++it)
+	{
+		if(p.frames > 0 && it >= n_iters)
+		{
+			uint32_t pending[5];
+			HIP_OK(hipMemcpyAsync(pending, a.cnt_in, sizeof pending, hipMemcpyDeviceToHost, stream));
+			HIP_OK(hipStreamSynchronize(stream));
+			if(pending[0] == 0u && pending[1] == 0u && pending[4] == 0u) break;
+		}
+		else if(p.frames == 0 && it >= n_iters) break;
+		HIP_OK(hipMemsetAsync(a.cnt_out, 0, 8 * sizeof(uint32_t), stream));
+		// The two traversal launches of an iteration are independent (each drains its own queue, writes its own
+		// answers), and a persistent kernel's tail leaves CUs idle: outside profiling the any-hit launch goes to a
+		// side stream so that its waves fill the closest-hit launch's tail (and vice versa).
+		const bool fork = p.overlap && it > 0 && !s->profiling && !record;
+		const hipStream_t any_stream = fork ? (hipStream_t)w.side : stream;
+		if(fork)
+		{	// fork point: everything enqueued so far (the previous shade, the counter reset) precedes both launches
+			HIP_OK(hipEventRecord(w.fork, stream));
+			HIP_OK(hipStreamWaitEvent(w.side, w.fork, 0));
+		}
+		if(trace_closest && (rc = timed(c, 0, [&] {
+			if(p.stats) hipLaunchKernelGGL((wf_trace<false, true>), dim3(c.g_trace_c), dim3(kBlock), 0, stream, a);
+			else hipLaunchKernelGGL((wf_trace<false, false>), dim3(c.g_trace_c), dim3(kBlock), 0, stream, a); }))) return rc;
+		if(it > 0 && !record)      // (a record pass has no shadow rays)
+		{
+			HIP_OK(hipMemsetAsync(w.verdict, 0, ((size_t)4 * a.n_paths + 31) / 32 * sizeof(uint32_t), any_stream));     // occluded rays set their bit
+			if((rc = timed(c, 1, [&] {
+				if(p.transp) hipLaunchKernelGGL(wf_trace_ts, dim3(cus * 8), dim3(kBlock), 0, any_stream, a);
+				else if(p.stats) hipLaunchKernelGGL((wf_trace<true, true>), dim3(c.g_trace_s), dim3(kBlock), 0, any_stream, a);
+				else hipLaunchKernelGGL((wf_trace<true, false>), dim3(c.g_trace_s), dim3(kBlock), 0, any_stream, a); }))) return rc;
+		}
+		if(fork)
+		{
+			HIP_OK(hipEventRecord(w.join, w.side));
+			HIP_OK(hipStreamWaitEvent(stream, w.join, 0));
+		}
+		int variant_rc = 0;
+		if((rc = timed(c, 2, [&] {
+			if(record && p.record) variant_rc = p.record->launch(&a, sizeof a, c.g_shade_rec, stream);
+			else if(p.shade) variant_rc = p.shade->launch(&a, sizeof a, c.g_shade, stream);
+			else hipLaunchKernelGGL(wf_shade, dim3(c.g_shade), dim3(kBlock), 0, stream, a); }))) return rc;
+		if(variant_rc) return fail(-21, "shading kernel variant and main unit disagree on the argument layout");
+		// swap queues: what shade produced is the next iteration's input
+		cur ^= 1;
+		a.cnt_in = cnt[cur]; a.cnt_out = cnt[cur ^ 1];
+		a.q_closest_in = qset[cur][0]; a.q_shadow_in = qset[cur][1]; a.q_resume_in = qset[cur][2];
+		a.q_closest_out = qset[cur ^ 1][0]; a.q_shadow_out = qset[cur ^ 1][1]; a.q_resume_out = qset[cur ^ 1][2];
+	}
+	return 0;
+}
+
+// The serial-state replay of a chunk, up to the final pass's program: the record pass, then the walk of the tiles' streams.
+// phase 0: all of it.  A sharded light counter splits it: phase 1 = the record pass, the tiles' roulette walk and their call counts
+// (read back into c.own_calls); phase 2 = the rest, from the bases the ranks' exchange gave (a pass of one chunk keeps its events
+// from phase 1, one of several records them again).
+static int replay_chunk(PassCtx &c, const Chunk &ch, WfArgs &a, size_t seg_off, int phase)
+{
+	yafgpu_scene *s = c.s; const PassPlan &p = c.p; const yafgpu_render_params &rp = c.ra.rp; const hipStream_t stream = c.stream;
+	int rc;
+	const bool have_events = phase == 2 && p.chunks.size() == 1;
+	if(!have_events)
+	{	// record pass: the paths alone (no light estimates, no roulette kills), rays not counted
+		a.replay = 1;
+		yafgpu_counters *const keep = a.ra.counters;
+		a.ra.counters = nullptr;
+		HIP_OK(hipMemsetAsync(s->rp_flags, 0, (size_t)a.n_paths * p.ev_m * p.n_ps * sizeof(uint32_t), stream));
+		if((rc = run_program(c, a, p.iters_record, true))) return rc;
+		a.ra.counters = keep;
+	}
+	const uint32_t n_seg = ch.tile_end - ch.tile_begin;
+	ReplayArgs r{};
+	r.seg_begin = s->rp_seg_begin + seg_off; r.seg_seed = s->rp_seg_seed + seg_off; r.n_seg = n_seg; r.spp = p.spp; r.n_paths = p.ev_m * p.n_ps; r.n_prob = p.n_prob;
+	r.bounces = (uint32_t)std::max(rp.bounces, 1);
+	r.ev_flags = s->rp_flags; r.ev_p = s->rp_p; r.ev_kill = s->rp_kill; r.ev_calls = s->rp_calls; r.lc_base = s->rp_base;
+	r.seg_total = s->rp_seg_total + seg_off; r.lc_counter = s->rp_counter;
+	r.seg_base_in = phase == 2 ? s->rp_seg_base + seg_off : nullptr;
+	if((rc = timed(c, 3, [&] {
+		if(!have_events) hipLaunchKernelGGL(wf_replay_tiles, dim3(n_seg), dim3(kWave), 0, stream, r);
+		if(phase == 0) hipLaunchKernelGGL(wf_replay_bases, dim3(1), dim3(1), 0, stream, r);
+		if(phase != 1) hipLaunchKernelGGL(wf_replay_samples, dim3(n_seg), dim3(kWave), 0, stream, r); }))) return rc;
+	if(phase == 1)
+	{	// this chunk's calls per tile, by global tile index
+		std::vector<uint32_t> totals(n_seg);
+		HIP_OK(hipMemcpyAsync(totals.data(), s->rp_seg_total + seg_off, n_seg * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+		HIP_OK(hipStreamSynchronize(stream));
+		for(uint32_t k = 0; k < n_seg; ++k) c.own_calls.emplace_back(tile_global_index(rp, s->h_tiles[ch.tile_begin + k]), totals[k]);
+		return 0;
+	}
+	if(c.sw.verbose)
+	{
+		uint32_t cnt_now = 0;
+		HIP_OK(hipMemcpyAsync(&cnt_now, s->rp_counter, sizeof cnt_now, hipMemcpyDeviceToHost, stream));
+		HIP_OK(hipStreamSynchronize(stream));
+		std::fprintf(stderr, "[yafgpu] replay chunk of %u tiles: light counter now %u\n", n_seg, cnt_now);
+	}
+	a.replay = 2;
+	return 0;
+}
+
+// The chunk's results into the film.  A pipelined pass adds them on the caller's stream, after its path work and (by that stream's
+// order) after the previous pass's film, and its counters to the caller's.
+static int accumulate_chunk(PassCtx &c, const WfArgs &a)
+{
+	WfSet &w = c.w;
+	const uint32_t g_acc = std::min<uint32_t>((a.n_pixels + kBlock - 1) / kBlock, (uint32_t)c.s->n_cus * 8u);
+	if(!c.p.piped) return timed(c, 3, [&] { hipLaunchKernelGGL(wf_accumulate, dim3(g_acc), dim3(kBlock), 0, c.stream, a); });
+	HIP_OK(hipEventRecord(w.done, c.stream));
+	HIP_OK(hipStreamWaitEvent(c.caller, w.done, 0));
+	WfArgs acc = a;
+	acc.ra.counters = c.caller_counters;
+	hipLaunchKernelGGL(wf_accumulate, dim3(g_acc), dim3(kBlock), 0, c.caller, acc);
+	if(c.caller_counters) hipLaunchKernelGGL(add_counters, dim3(1), dim3(64), 0, c.caller, c.caller_counters, (const yafgpu_counters *)w.counters);
+	HIP_OK(hipGetLastError());
+	HIP_OK(hipEventRecord(w.acc, c.caller));
+	w.acc_set = true;
+	return 0;
+}
+
+// One chunk of the pass: its arguments, the replay where there is one, the path program, the film.  seg_off: where the chunk's
+// slice of the segment tables begins (advanced past it).
+static int process_chunk(PassCtx &c, const Chunk &ch, size_t &seg_off, int phase)
+{
+	yafgpu_scene *s = c.s; WfSet &w = c.w; const PassPlan &p = c.p;
+	if(s->aborted()) return fail(-30, "aborted");
+	WfArgs a{};
+	a.ra = c.ra;
+	a.state = w.state; a.cap = w.cap; a.results = w.results; a.frames = p.frames; a.frame_recs = p.frame_recs; a.has_glossy = s->has_glossy ? 1 : 0;
+	a.pixel_begin = ch.pixel_begin; a.n_pixels = ch.n_pixels; a.n_paths = a.n_pixels * p.spp;
+	a.pix_prefix = w.pix_prefix; a.pix_xy = w.pix_xy; a.pix_listed = p.masked ? 1 : 0;
+	if(p.masked) HIP_OK(hipMemcpyAsync(w.pix_xy, s->h_listed.data() + ch.pixel_begin, (size_t)a.n_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+	a.ev_flags = s->rp_flags; a.ev_p = s->rp_p; a.ev_kill = s->rp_kill; a.ev_calls = s->rp_calls; a.lc_base = s->rp_base;
+	a.replay_lights = p.rpl.replay_lights ? 1 : 0; a.ev_m = (int)p.ev_m;
+	a.multi = p.want_multi ? 1 : 0;
+	a.speculate = c.sw.speculate ? 1 : 0;
+	a.hit_cache = p.use_hits ? (float4 *)s->rp_hits : nullptr; a.hit_k = (int)p.hit_k;
+	a.verdict = w.verdict; a.shadow_filt = p.transp ? (float4 *)w.filt : nullptr;
+	int rc;
+	if(p.rpl.replay)
+	{
+		rc = replay_chunk(c, ch, a, seg_off, phase);
+		seg_off += ch.tile_end - ch.tile_begin + 1;
+		if(rc || phase == 1) return rc;
+	}
+	if((rc = run_program(c, a, p.iters, false))) return rc;
+	return accumulate_chunk(c, a);
+}
+
+static int render_wavefront(yafgpu_scene *s, RenderArgs &ra, const Switches &sw, const ReplayPlan &rpl, hipStream_t caller, bool stats)
+{
+	const yafgpu_render_params &rp = ra.rp;
+	if(rp.resample_mask) HIP_OK(hipStreamSynchronize(caller));      // the previous pass's uploads of the pixel list (s->h_listed) have been read
+	PassPlan p;
+	int rc = plan_pass(s, rp, sw, rpl, stats, p);
+	if(rc) return rc;
+	if(p.chunks.empty()) return rpl.lc_sharded ? lc_exchange_counts(s, rp, {}, nullptr) : 0;      // (the other ranks wait for this one's counts)
+	int k = 0;      // passes that are not pipelined: set 0, on the caller's stream
+	if(p.piped && (rc = begin_piped_pass(s, caller, ra.counters != nullptr, k))) return rc;
+	s->pipe_prev = p.piped;
+	WfSet &w = s->sets[k];
+	PassCtx c{s, p, sw, w, ra, p.piped ? (hipStream_t)w.stream : caller, caller, ra.counters};
+	if(p.piped && ra.counters) ra.counters = w.counters;
+	if((rc = reserve_workspace(c))) return rc;
+	// on the pass's stream: kernels of the previous pass may still be reading the table (a null-stream copy does not order against a
+	// non-blocking stream); the source is pageable, so the call returns once it has been staged
+	HIP_OK(hipMemcpyAsync(w.pix_prefix, s->h_pix_prefix.data(), s->h_pix_prefix.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+	if(rpl.replay && (rc = upload_segments(c))) return rc;
+	if((rc = device_cus(s))) return rc;
+	c.g_trace_c = stats ? wf_grid((const void *)wf_trace<false, true>, s->n_cus, sw) : wf_grid((const void *)wf_trace<false, false>, s->n_cus, sw);
+	c.g_trace_s = stats ? wf_grid((const void *)wf_trace<true, true>, s->n_cus, sw) : wf_grid((const void *)wf_trace<true, false>, s->n_cus, sw);
+	c.g_shade = wf_grid(p.shade ? p.shade->kernel() : (const void *)wf_shade, s->n_cus, sw);
+	c.g_shade_rec = p.record ? wf_grid(p.record->kernel(), s->n_cus, sw) : c.g_shade;
+	if(p.overlap) { HIP_OK(w.side.create()); HIP_OK(w.fork.create()); HIP_OK(w.join.create()); }
+	if(s->profiling)
+	{
+		for(Event &e : c.ev) HIP_OK(e.create(hipEventDefault));
+		for(int i = 0; i < 4; ++i) { s->prof_ms[i] = 0; s->prof_launches[i] = 0; }
+	}
+	if(rpl.lc_sharded)
+	{	// phase 1 for every chunk, then the ranks exchange the counts
+		size_t seg_off = 0;
+		for(const Chunk &ch : p.chunks) if((rc = process_chunk(c, ch, seg_off, 1))) return rc;
+		std::vector<uint32_t> base_of_tile;
+		if((rc = lc_exchange_counts(s, rp, c.own_calls, &base_of_tile))) return rc;
+		// the bases in the layout of the segment tables (n + 1 entries per chunk)
+		s->h_seg_base.clear();
+		for(const Chunk &ch : p.chunks)
+		{
+			for(uint32_t t = ch.tile_begin; t < ch.tile_end; ++t) s->h_seg_base.push_back(base_of_tile[(size_t)tile_global_index(rp, s->h_tiles[t])]);
+			s->h_seg_base.push_back(0u);
+		}
+		HIP_OK(hipMemcpyAsync(s->rp_seg_base, s->h_seg_base.data(), s->h_seg_base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+	}
+	size_t seg_off = 0;
+	for(const Chunk &ch : p.chunks) if((rc = process_chunk(c, ch, seg_off, rpl.lc_sharded ? 2 : 0))) return rc;
+	return 0;
+}
+
+extern "C" {      // the ABI again
 
 int yafgpu_render_tiles(yafgpu_scene_t *s, const yafgpu_render_params *rp, float *d_planes, yafgpu_counters *d_counters, void *stream_)
 {
@@ -1767,6 +1791,8 @@ int yafgpu_render_tiles(yafgpu_scene_t *s, const yafgpu_render_params *rp, float
 	int rc = validate(s, rp);
 	if(rc) return rc;
 	hipStream_t stream = (hipStream_t)stream_;
+	const Switches sw = read_switches();
+	const ReplayPlan rpl = replay_plan(s, *rp, sw);
 	RenderArgs ra{};
 	ra.sc = s->dev;
 	ra.rp = *rp;
@@ -1784,7 +1810,7 @@ int yafgpu_render_tiles(yafgpu_scene_t *s, const yafgpu_render_params *rp, float
 		{
 			float table[256];
 			host_filter_table(rp->filter_type, table);
-			if(!s->d_filter_table) HIP_OK(hipMalloc((void **)&s->d_filter_table, sizeof table));
+			HIP_OK(s->d_filter_table.reserve(256, stream));
 			HIP_OK(hipMemcpyAsync(s->d_filter_table, table, sizeof table, hipMemcpyHostToDevice, stream));
 			ra.filter_table = s->d_filter_table;
 		}
@@ -1810,16 +1836,10 @@ int yafgpu_render_tiles(yafgpu_scene_t *s, const yafgpu_render_params *rp, float
 	ra.n_tiles = (int)s->h_tiles.size();
 	if(!rp->accumulate) HIP_OK(hipMemsetAsync(d_planes, 0, yafgpu_planes_bytes(rp->width, rp->height), stream));
 	if(ra.n_tiles == 0)      // a rank without tiles still owes the others its (empty) share of the light-counter exchange
-		return replay_plan(s, *rp).lc_sharded ? lc_exchange_counts(s, *rp, {}, nullptr) : 0;
+		return rpl.lc_sharded ? lc_exchange_counts(s, *rp, {}, nullptr) : 0;
 	if(!same)
 	{
-		if(s->h_tiles.size() > s->tiles_cap)
-		{
-			HIP_OK(hipStreamSynchronize(stream));      // the previous pass may still read the old arrays
-			if(s->d_tiles) (void)hipFree(s->d_tiles);
-			s->tiles_cap = s->h_tiles.size();
-			HIP_OK(hipMalloc((void **)&s->d_tiles, s->tiles_cap * sizeof(int4)));
-		}
+		HIP_OK(s->d_tiles.reserve(s->h_tiles.size(), stream));      // (the previous pass may still read the old array)
 		HIP_OK(hipMemcpyAsync(s->d_tiles, s->h_tiles.data(), s->h_tiles.size() * sizeof(int4), hipMemcpyHostToDevice, stream));
 		std::memcpy(s->tile_key, key, sizeof key);
 		s->pipe_prev = false;      // (pipelined passes: the new tile arrays precede the internal streams' next launches)
@@ -1827,8 +1847,7 @@ int yafgpu_render_tiles(yafgpu_scene_t *s, const yafgpu_render_params *rp, float
 	ra.tile_rect = s->d_tiles;
 	ra.planes = d_planes;
 	ra.counters = d_counters;
-	const bool stats = d_counters != nullptr && std::getenv("YAFGPU_STATS") != nullptr;
-	return render_wavefront(s, ra, stream, stats);
+	return render_wavefront(s, ra, sw, rpl, stream, d_counters != nullptr && sw.stats);
 }
 
 int yafgpu_film_combine(const float *d_planes, float *d_film, int32_t width, int32_t height, void *stream_)
@@ -1844,18 +1863,9 @@ int yafgpu_film_combine(const float *d_planes, float *d_film, int32_t width, int
 // planes, combined film and counters of a w x h frame, owned by the scene and reused while the size stays
 static int render_targets(yafgpu_scene *s, int w, int h, float **planes, float **film, yafgpu_counters **cnt)
 {
-	const size_t planes_n = yafgpu_planes_bytes(w, h) / sizeof(float), film_n = (size_t)w * (size_t)h * YAFGPU_FILM_CHANNELS;
-	if(planes_n > s->rt_planes_n || film_n > s->rt_film_n)
-	{
-		HIP_OK(hipDeviceSynchronize());
-		if(s->rt_planes) (void)hipFree(s->rt_planes);
-		if(s->rt_film) (void)hipFree(s->rt_film);
-		s->rt_planes = nullptr; s->rt_film = nullptr; s->rt_planes_n = 0; s->rt_film_n = 0;
-		HIP_OK(hipMalloc((void **)&s->rt_planes, planes_n * sizeof(float)));
-		HIP_OK(hipMalloc((void **)&s->rt_film, film_n * sizeof(float)));
-		s->rt_planes_n = planes_n; s->rt_film_n = film_n;
-	}
-	if(!s->rt_cnt) HIP_OK(hipMalloc((void **)&s->rt_cnt, sizeof(yafgpu_counters)));
+	HIP_OK(s->rt_planes.reserve(yafgpu_planes_bytes(w, h) / sizeof(float), nullptr));
+	HIP_OK(s->rt_film.reserve((size_t)w * (size_t)h * YAFGPU_FILM_CHANNELS, nullptr));
+	HIP_OK(s->rt_cnt.reserve(1, nullptr));
 	*planes = s->rt_planes; *film = s->rt_film; *cnt = s->rt_cnt;
 	return 0;
 }
@@ -2058,18 +2068,12 @@ int yafgpu_render_passes_to_host(yafgpu_scene_t *s, const yafgpu_render_params *
 		const size_t n_px = (size_t)w * (size_t)h;
 		flags.assign(n_px, 0);
 		if(!(aa_thesh > 0.f)) { std::fill(flags.begin(), flags.end(), (uint8_t)1); return w * h; }   // imagefilm.cc:319,460; doMoreSamples :919
-		if(n_px > s->rt_flags_n)
-		{
-			if(s->rt_flags) (void)hipFree(s->rt_flags);
-			s->rt_flags = nullptr; s->rt_flags_n = 0;
-			if(hipMalloc((void **)&s->rt_flags, n_px) != hipSuccess) return fail(-3, "out of device memory (resample flags)");
-			s->rt_flags_n = n_px;
-		}
+		if(s->rt_flags.reserve(n_px, nullptr) != hipSuccess) return fail(-3, "out of device memory (resample flags)");
 		if(hipMemsetAsync(s->rt_flags, 0, n_px, nullptr) != hipSuccess) return fail(-100, "flag reset failed");
 		if(w > 1 && h > 1)
 		{
 			const uint32_t grid = (uint32_t)std::min<size_t>(((size_t)(w - 1) * (size_t)(h - 1) + kBlock - 1) / kBlock, 4096);
-			hipLaunchKernelGGL(aa_detect_kernel, dim3(grid), dim3(kBlock), 0, nullptr, (const float *)d_film, w, h, aa, aa_thesh, s->rt_flags);
+			hipLaunchKernelGGL(aa_detect_kernel, dim3(grid), dim3(kBlock), 0, nullptr, (const float *)d_film, w, h, aa, aa_thesh, s->rt_flags.p);
 			if(hipGetLastError() != hipSuccess) return fail(-100, "detection kernel launch failed");
 		}
 		if(hipMemcpy(flags.data(), s->rt_flags, n_px, hipMemcpyDeviceToHost) != hipSuccess) return fail(-100, "flag download failed");
@@ -2162,7 +2166,7 @@ static int trace_batch(yafgpu_scene_t *s, int32_t n, const float *rays, int32_t 
 	a.state = d_state; a.cap = cap;
 	a.cnt_in = d_cnt; a.verdict = d_verdict;
 	const void *kernel = any ? (const void *)wf_trace<true, false> : (const void *)wf_trace<false, false>;
-	const int grid = wf_grid(kernel, s->n_cus);
+	const int grid = wf_grid(kernel, s->n_cus, read_switches());
 	for(uint32_t o = 0; o < (uint32_t)n; o += cap)
 	{
 		const uint32_t m = std::min(cap, (uint32_t)n - o);

@@ -15,8 +15,15 @@ def _torch_first():
     assert torch.cuda.is_available()
 
 
-def _setup(mode, **kw):
+def _setup(mode, transparent=False, **kw):
     sc = scenes.cornell_soup(600, seed=7, res=(96, 80), sigma=0.07)
+    if transparent:     # every other soup triangle lets shadow rays through, filtered (as in test_gpu_parity.test_transparent_shadows)
+        sc["materials"] = [dict(m) for m in sc["materials"]]
+        sc["materials"].append({"type": "shinydiffusemat", "color": (0.3, 0.9, 0.4), "diffuse_reflect": 0.6, "transparency": 0.7, "transmit_filter": 0.8,
+                                "specular_reflect": 0.2, "fresnel_effect": True, "IOR": 1.3})
+        tm = np.array(sc["tri_mat"], np.int32)
+        tm[np.arange(10, len(tm))[0::2]] = len(sc["materials"]) - 1
+        sc["tri_mat"] = tm
     rd = scenes.render_settings(96, 80, 4, bounces=3, path_samples=1, integrator="pathtracing", **kw)
     yi = Interface()
     scenes.load_scene(yi, sc, rd)
@@ -55,16 +62,30 @@ def test_pipelined_passes_equal_sequential_passes(reuse_planes):
     assert np.array_equal(seq[0].view(np.uint32), seq[4].view(np.uint32))      # (the same pass five times)
 
 
-def test_default_mode_pipelines_small_frames_and_a_frame_change_in_between_is_ordered():
+def test_transparent_shadows_in_pipelined_passes():
+    """each buffer set has its own filter products of the shadow rays (transparent shadows); raydepth 0 keeps the passes free of recursion
+    frames, so they are pipelined"""
+    kw = dict(transparent=True, transpShad=True, shadowDepth=3, raydepth=0)
+    seq, c_seq = _passes(_setup(0, **kw), 5)
+    pip, c_pip = _passes(_setup(1, **kw), 5)
+    assert np.array_equal(c_seq, c_pip), (c_seq, c_pip)
+    assert c_seq[1] > 0      # rays_shadow
+    for k, (a, b) in enumerate(zip(seq, pip)):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), f"pass {k} differs"
+
+
+@pytest.mark.parametrize("order", [((0, 1), (0, 2), (1, 2), (0, 1)), ((1, 2), (0, 2), (0, 1), (1, 2))], ids=["whole_first", "widening"])
+def test_default_mode_pipelines_small_frames_and_a_frame_change_in_between_is_ordered(order):
     """mode -1 (by size) takes these small frames through the pipelined path; a change of the shard between two calls uploads new tile
-    arrays on the caller's stream, which the internal streams must wait for"""
+    arrays on the caller's stream, which the internal streams must wait for.  The second order starts on half the frame and widens:
+    each buffer set then grows while the other set's pass may be in flight"""
     import torch
     yi = _setup(-1)
     ref = _setup(0)
     dev = torch.device("cuda", 0)
     W, H = yi.getRenderSize()
     stream = torch.cuda.current_stream().cuda_stream
-    for shards in ((0, 1), (0, 2), (1, 2), (0, 1)):
+    for shards in order:
         got, want = [], []
         for it, dst in ((yi, got), (ref, want)):
             it.setShard(*shards)
