@@ -58,10 +58,12 @@ struct DevScene
 	const float4 *tri_vn;        // 3 x float4 per triangle (vertex normals) or nullptr
 	const yafgpu_material *mats;
 	const yafgpu_light *lights;
-	const int *faure;            // concatenated Faure permutations
+	const int *faure;            // concatenated Faure permutations — or a copy of their first faure_near ints (wf_shade stages a prefix in LDS)
+	const int *faure_far;        // the whole table (global memory), for a dimension that reaches beyond faure_near
 	const int *faure_off;        // [50] offsets into faure
 	const double *inv_prims;     // [50]
 	int n_lights, n_tris, n_mats, n_faure;      // n_faure: ints in the concatenated Faure permutations
+	int faure_near;              // ints `faure` holds (n_faure unless a kernel staged a prefix)
 	uint32_t n_nodes;
 	float blo[3], bhi[3];
 	yafgpu_camera cam;
@@ -91,8 +93,9 @@ __constant__ int c_prims[50] = {1, 2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, 4
 YG_DEV double scr_halton(const DevScene &sc, int dim, uint32_t n)
 {
 	double value = 0.0;
-	const int *sigma = sc.faure + sc.faure_off[dim];
 	const uint32_t base = (uint32_t)c_prims[dim];
+	const int off = sc.faure_off[dim];
+	const int *sigma = (off + (int)base <= sc.faure_near ? sc.faure : sc.faure_far) + off;
 	double f, factor, dn = (double)n;
 	f = factor = sc.inv_prims[dim];
 	while(n > 0)
@@ -965,7 +968,7 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 		}
 	}
 	if((rc = upload(s, faure.data(), faure.size(), &dv.faure))) { yafgpu_scene_destroy(s); return rc; }
-	dv.n_faure = (int)faure.size();
+	dv.n_faure = (int)faure.size(); dv.faure_far = dv.faure; dv.faure_near = dv.n_faure;
 	if((rc = upload(s, foff.data(), foff.size(), &dv.faure_off))) { yafgpu_scene_destroy(s); return rc; }
 	if((rc = upload(s, invp.data(), invp.size(), &dv.inv_prims))) { yafgpu_scene_destroy(s); return rc; }
 	dv.n_lights = d->n_lights; dv.n_tris = d->n_tris; dv.n_mats = d->n_materials; dv.n_nodes = (uint32_t)s->tree.nodes.size();
@@ -1133,6 +1136,7 @@ struct Switches
 	bool serial_replay = true;                 // YAFGPU_SERIAL_REPLAY=0: per-sample streams instead of the replay
 	bool general_shade = false;                // YAFGPU_SHADE_VARIANT=general: the general shading kernel
 	bool record_variant = true;                // YAFGPU_RECORD_VARIANT=0: the record pass on the pass's own kernel (A/B)
+	bool vertex_lds = true;                    // YAFGPU_VERTEX_LDS=0: every vertex record goes through memory and is stored (WfArgs::vtx_lds, vtx_keep)
 	int blocks_per_cu = 8;                     // YAFGPU_BLOCKS_PER_CU: resident workgroups per CU of the persistent kernels (occupancy experiments)
 	bool stats = false, verbose = false;       // YAFGPU_STATS, YAFGPU_VERBOSE: set at all
 };
@@ -1153,6 +1157,7 @@ static Switches read_switches()
 	sw.serial_replay = env_flag("YAFGPU_SERIAL_REPLAY") != 0;
 	if(const char *e = std::getenv("YAFGPU_SHADE_VARIANT")) sw.general_shade = std::strcmp(e, "general") == 0;
 	sw.record_variant = env_flag("YAFGPU_RECORD_VARIANT") != 0;
+	sw.vertex_lds = env_flag("YAFGPU_VERTEX_LDS") != 0;
 	if(const char *e = std::getenv("YAFGPU_BLOCKS_PER_CU")) sw.blocks_per_cu = std::max(1, std::atoi(e));
 	sw.stats = std::getenv("YAFGPU_STATS") != nullptr;
 	sw.verbose = std::getenv("YAFGPU_VERBOSE") != nullptr;
@@ -1321,6 +1326,7 @@ struct PassPlan
 	uint32_t ev_m = 1, n_ps = 1, n_prob = 1;   // replay: calls per camera sample, path samples per call, roulette probabilities per path sample
 	uint32_t hit_k = 0; bool use_hits = false; // the record pass's closest-hit answers per camera sample; kept for the final pass (WfArgs::hit_cache)
 	bool want_multi = false, transp = false, overlap = false, piped = false;
+	uint32_t vtx_keep = 0xffu;                 // the records 3..10 a park has to store (WfArgs::vtx_keep)
 	const ShadeVariant *shade = nullptr, *record = nullptr;      // nullptr: the general kernel / the pass's own kernel
 	int iters = 0, iters_record = 0;           // upper bound of kd-tree queries per path = iterations needed (every path advances one query per iteration)
 };
@@ -1421,6 +1427,15 @@ static int plan_pass(yafgpu_scene *s, const yafgpu_render_params &rp, const Swit
 	// two MIS pairs per park (WfArgs::multi): not with transparent shadows (their filter products are kept per pair), not with recursion frames —
 	// and only where a light estimate can have a second pair at all: the kernels that carry it are a little slower on the first
 	p.want_multi = !p.transp && p.frames == 0 && sw.multi_pair && r_all > 1;
+	// The vertex records a later resume reads (WfArgs::vtx_keep), from the readers in wf_advance.  Everything, whenever a step of a LATER resume
+	// rebuilds the vertex: st_start_path for the next path sample (3..6), st_dl_eval / st_beside for the next pair of an estimate that takes
+	// several parks (r_all > 1: several lights, or several samples of one), st_recurse* and st_return with recursion frames, st_dl_done's
+	// emission under shader nodes, bump or caustic paths (7..10).  Otherwise a later resume reads three words: bsdfs0 (5.w, st_dl_done),
+	// integrate()'s w (6.w, the samplers) and the material of the path vertex (7.w, st_dl_done) — those three records are stored, 3, 4, 8, 9 and
+	// 10 are not.  What is only known per path is decided there: a park for a shadow pair ALONE (st_beside did not go ahead) stores the whole
+	// vertex, for st_extend / st_start_path after the answers, and the pwo a segment that sampled nothing keeps is always stored (vtx_set's keep).
+	// A record pass on a light-estimate kernel stores everything too (vtx_flush).
+	p.vtx_keep = (sw.vertex_lds && rp.path_samples <= 1 && r_all <= 1 && p.frames == 0 && !s->has_textures && !s->has_bump && !rp.trace_caustics) ? 0x1cu : 0xffu;
 	p.shade = pick_shade_variant(s, sw, p.frames, false, p.want_multi);
 	if(!p.shade && p.want_multi)
 	{	// no kernel with the second pair for these materials: the one without it rather than the general kernel
@@ -1720,6 +1735,7 @@ static int process_chunk(PassCtx &c, const Chunk &ch, size_t &seg_off, int phase
 	a.replay_lights = p.rpl.replay_lights ? 1 : 0; a.ev_m = (int)p.ev_m;
 	a.multi = p.want_multi ? 1 : 0;
 	a.speculate = c.sw.speculate ? 1 : 0;
+	a.vtx_lds = c.sw.vertex_lds ? 1 : 0; a.vtx_keep = p.vtx_keep;
 	a.hit_cache = p.use_hits ? (float4 *)s->rp_hits : nullptr; a.hit_k = (int)p.hit_k;
 	a.verdict = w.verdict; a.shadow_filt = p.transp ? (float4 *)w.filt : nullptr;
 	int rc;

@@ -75,6 +75,11 @@ struct WfArgs
 	// bits, two more bits of the shadow-queue entry): the shadow answers steer nothing, so the second pair is what the resumed path would have
 	// evaluated next, and a light with n samples costs n / 2 state round trips per vertex.  Not with transparent shadows or recursion frames.
 	int multi;
+	// The vertex scratchpad of the light-estimate kernels (vtx_set / vtx_get below).  vtx_lds: a record 3..10 written earlier in the same resume
+	// is read back from LDS, and its store waits for the park (0: every write goes straight to memory, every read comes from there,
+	// YAFGPU_VERTEX_LDS=0).  vtx_keep: bit k - 3 = a LATER resume may read record k, so a park stores it; a record whose bit is clear only hands
+	// the vertex from one step to the next of the resume that made it and never reaches memory (plan_pass; all ones whenever in doubt).
+	int vtx_lds; uint32_t vtx_keep;
 	uint32_t *cnt_in;                 // [0] closest count, [1] shadow-ray count, [2] closest fetch cursor, [3] shadow fetch cursor, [4] resume count
 	uint32_t *cnt_out;                // same layout, filled by wf_shade for the next iteration
 };
@@ -321,6 +326,7 @@ struct Hot
 #if !YAFGPU_FEAT_LIGHTS
 	float4 vt[8]; uint32_t vvalid;      // records 3..10 of this resume's vertex, in registers (a record pass's kernel)
 #endif
+	// (a light-estimate kernel keeps the state of its vertex scratchpad in bits 8..31 of `dirty`, see vtx_set: a register of its own is one more to spill)
 };
 constexpr uint32_t kHotAccBits = 0x70u, kHot14 = 0x08u, kHot18 = 0x80u;
 constexpr uint32_t kDlcAccZero = 1u << 18, kDlcTotZero = 1u << 19;
@@ -397,11 +403,18 @@ YG_DEV void hot_zero_acc(const WfArgs &a, uint32_t slot, Hot &h)
 		h.dirty |= kHot14;
 	}
 }
+YG_DEV void hot_init(Hot &h)
+{
+	h.valid = 0u; h.dirty = 0u; h.acc_zero = 0u; h.tot_zero = 0u;
+#if !YAFGPU_FEAT_LIGHTS
+	h.vvalid = 0u;
+#endif
+}
 // with_path: throughput and path colour (11, 12) exist — not during the camera vertex's own estimate (st_start_path sets them up)
 YG_DEV void hot_preload(const WfArgs &a, uint32_t slot, Hot &h, bool with_path)
 {
 	h.r14 = REC(14);
-	h.valid = 0x88u; h.dirty = 0u; h.acc_zero = 0u;
+	h.valid = 0x88u; h.dirty &= ~0xffu; h.acc_zero = 0u;
 	if(with_path || !YAFGPU_ACC_ZERO_FLAG) { h.r11 = REC(11); h.r12 = REC(12); h.valid |= 0x03u; }
 	h.tot_zero = (YAFGPU_ACC_ZERO_FLAG && (ubits(h.r14.w) & kDlcTotZero)) ? 1u : 0u;
 	if(h.tot_zero) h.r18 = make_float4(0.f, 0.f, 0.f, 0.f); else h.r18 = REC(18);
@@ -451,6 +464,88 @@ template<int K> YG_DEV float4 vtx_get(const WfArgs &a, uint32_t slot, Hot &h)
 }
 #endif
 
+#if YAFGPU_FEAT_LIGHTS
+// The vertex records of a light-estimate kernel.  st_after_closest makes a vertex (3..6 at a camera hit, 7..10 along a path) that the steps
+// of the same resume read again — st_dl_eval, then st_beside or st_extend / st_start_path — and of which later resumes want a few words
+// only.  A resume keeps the vertex it handles in LDS, four float4 per thread ([k][threadIdx.x]: a thread only ever touches its own column,
+// so there is nothing to synchronise); records k and k + 4 share a slot, and writing one while the other is held sends that one to memory
+// first.  The stores happen once, at the park (vtx_flush), and only for the records a later resume can read (WfArgs::vtx_keep).
+__shared__ float4 s_wf_vtx[4][kBlock];
+// (The column index of a READ goes through an empty asm: the optimizer must not see that a read meets the write of an earlier step, or it
+// forwards the value in registers — which is what the scratchpad is there to avoid: the path program has no registers to spare.)
+YG_DEV uint32_t vtx_rcol() { uint32_t t = threadIdx.x; asm("; vertex scratchpad, read column" : "+v"(t)); return t; }
+YG_DEV uint32_t vtx_wcol() { uint32_t t = threadIdx.x; asm("; vertex scratchpad, write column" : "+v"(t)); return t; }
+// room for record K in its slot: the record it shares the slot with goes to memory first if it is only held here
+template<int K> YG_DEV void vtx_claim(const WfArgs &a, uint32_t slot, Hot &h)
+{
+	constexpr uint32_t other = 1u << ((K - 3) ^ 4);
+	if(h.dirty & (other << 16)) REC(K < 7 ? K + 4 : K - 4) = s_wf_vtx[(K - 3) & 3][vtx_wcol()];
+	h.dirty &= ~(other * 0x01010100u);
+}
+// Every read comes out of LDS: a record this resume has not written is fetched into its slot first.  (One source per read: a read that
+// merges an LDS and a memory path costs the diffuse variant 12 more spilled registers than reading memory alone.)
+template<int K> YG_DEV float4 vtx_get(const WfArgs &a, uint32_t slot, Hot &h)
+{
+	static_assert(K >= 3 && K <= 10, "not a vertex record");
+	constexpr uint32_t bit = 1u << (K - 3);
+	if(!(h.dirty & (bit << 8)) || !a.vtx_lds)
+	{
+		vtx_claim<K>(a, slot, h);
+		s_wf_vtx[(K - 3) & 3][vtx_wcol()] = REC(K);
+		h.dirty |= bit << 8;
+	}
+	return s_wf_vtx[(K - 3) & 3][vtx_rcol()];
+}
+// A whole vertex (K0 = 3 or 7) for st_dl_eval, which reads it in the scratchpad and nowhere else (vtx_held): what this resume did not
+// write is fetched.  wf_advance calls this where few registers are live — at the head of a resumed shadow answer whose estimate has
+// another pair to go, and after st_after_closest with the scratchpad switched off — because a fetch inside st_dl_eval, the widest step,
+// costs the diffuse variant 24 more spilled registers (33 against 9).
+template<int K0> YG_DEV void vtx_need(const WfArgs &a, uint32_t slot, Hot &h)
+{
+	constexpr uint32_t bits = 0xfu << (K0 + 5);
+	if((h.dirty & bits) == bits && a.vtx_lds) return;
+	vtx_claim<K0>(a, slot, h); vtx_claim<K0 + 1>(a, slot, h); vtx_claim<K0 + 2>(a, slot, h); vtx_claim<K0 + 3>(a, slot, h);
+	const float4 r0 = REC(K0), r1 = REC(K0 + 1), r2 = REC(K0 + 2), r3 = REC(K0 + 3);
+	const uint32_t t = vtx_wcol();
+	s_wf_vtx[0][t] = r0; s_wf_vtx[1][t] = r1; s_wf_vtx[2][t] = r2; s_wf_vtx[3][t] = r3;
+	h.dirty |= bits;
+}
+template<int K> YG_DEV float4 vtx_held(const WfArgs &a, uint32_t slot, Hot &h) { return s_wf_vtx[(K - 3) & 3][vtx_rcol()]; }
+// keep: a later resume reads this record in every regime (the pwo a segment that sampled nothing keeps, st_start_path)
+template<int K> YG_DEV void vtx_set(const WfArgs &a, uint32_t slot, Hot &h, float4 v, bool keep = false)
+{
+	static_assert(K >= 3 && K <= 10, "not a vertex record");
+	if(!a.vtx_lds) { REC(K) = v; return; }
+	vtx_claim<K>(a, slot, h);
+	s_wf_vtx[(K - 3) & 3][vtx_wcol()] = v;
+	h.dirty |= (1u << (K - 3)) * (keep ? 0x01010100u : 0x00010100u);
+}
+// one word of a record: from the scratchpad where the record is there, else those four bytes from memory
+template<int K> YG_DEV float vtx_get_w(const WfArgs &a, uint32_t slot, Hot &h)
+{
+	return ((h.dirty & (1u << (K + 5))) && a.vtx_lds) ? s_wf_vtx[(K - 3) & 3][vtx_rcol()].w : REC(K).w;
+}
+// integrate()'s `w` (record 6's .w): rewritten after every sample() — in place where the record waits in LDS, so that it goes out once
+YG_DEV void vtx_set_w(const WfArgs &a, uint32_t slot, Hot &h, float w)
+{
+	if((h.dirty & (8u << 8)) && a.vtx_lds) { s_wf_vtx[3][vtx_wcol()].w = w; h.dirty |= 8u << 16; }
+	else REC(6).w = w;
+}
+// all: st_extend / st_start_path will read the vertex in a later resume (wf_advance)
+YG_DEV void vtx_flush(const WfArgs &a, uint32_t slot, const Hot &h, bool all)
+{
+	const uint32_t keep = (all || a.replay == 1) ? 0xffu : (a.vtx_keep | (h.dirty >> 24));
+	const uint32_t out = (h.dirty >> 16) & keep & 0xffu;
+#pragma unroll
+	for(int j = 0; j < 4; ++j)
+		if(out & (0x11u << j))
+		{	// (a slot holds one of its two records)
+			const float4 v = s_wf_vtx[j][threadIdx.x];
+			if(out & (1u << j)) wf_rec(a, 3 + j, slot) = v; else wf_rec(a, 7 + j, slot) = v;
+		}
+}
+#endif
+
 #define FREC(L, j) wf_rec(a, kWfRecs + a.frame_recs * (L) + (j), slot)      // recursion frames, see st_recurse
 // path caustics (yafgpu_render_params::trace_caustics): a kernel built with 0 serves renders with caustic_type "none"
 #ifndef YAFGPU_FEAT_CAUSTIC
@@ -470,12 +565,22 @@ template<int K> YG_DEV float4 vtx_get(const WfArgs &a, uint32_t slot, Hot &h)
 #endif
 #if YAFGPU_FEAT_LIGHTS
 #define A_REPLAY (a.replay)
-#define VGET(k) REC(k)
-#define VSET(k, v) (REC(k) = (v))
+#define VGET(k) vtx_get<k>(a, slot, h)
+#define VSET(k, v) vtx_set<k>(a, slot, h, (v))
+#define VSET_KEEP(k, v) vtx_set<k>(a, slot, h, (v), true)
+#define VHELD(k) vtx_held<k>(a, slot, h)
+#define VNEED(k) vtx_need<k>(a, slot, h)
+#define VGET_W(k) vtx_get_w<k>(a, slot, h)
+#define VSET_W(w) vtx_set_w(a, slot, h, (w))
 #else
 #define A_REPLAY 1
 #define VGET(k) vtx_get<k>(a, slot, h)
 #define VSET(k, v) vtx_set<k>(a, slot, h, (v))
+#define VSET_KEEP(k, v) (REC(k) = (v))
+#define VHELD(k) vtx_get<k>(a, slot, h)
+#define VNEED(k) ((void)0)
+#define VGET_W(k) (vtx_get<k>(a, slot, h).w)
+#define VSET_W(w) (REC(6).w = (w))
 #endif
 // recursiveRaytrace (frames, absorption): a kernel built with 0 serves scenes without specular / filter materials
 #ifndef YAFGPU_FEAT_RECURSE
@@ -594,7 +699,7 @@ YG_DEV int st_after_closest(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint
 	const uint32_t mb = mat_init_bsdf(pm, dat_n);
 	float4 misc = REC(19);
 	V3 pwo = -dir;                                                                              // :271
-	if(c.stage == kStFirst && ubits(misc.y) == kNone) pwo = v3(REC(10));                       // :224: keeps the first segment's pwo
+	if(c.stage == kStFirst && ubits(misc.y) == kNone) pwo = v3(VGET(10));                      // :224: keeps the first segment's pwo
 	// .w of 8..10: p_ray.dir_ of the segment that ended here — what Material::sample leaves in `wi` when it samples nothing
 	VSET(7, f4(hit.p, fbits((uint32_t)hit.mat))); VSET(8, f4(hit.n, dir.x)); VSET(9, f4(hit.ng, dir.y)); VSET(10, f4(pwo, dir.z));
 	if(A_REPLAY != 1) hot_zero_tot(a, slot, h);
@@ -708,8 +813,9 @@ YG_DEV int st_dl_eval(const WfArgs &a, uint32_t slot, Hot &h, const Ctl &c, uint
 	const uint32_t w = second ? w2 : ubits(HGET(14).w);
 	const int li = (int)(w & 0xffu), is = (int)(w >> 20), l_end = (int)((w >> 8) & 0xffu);
 	SurfPt sp; V3 wo;
-	if(c.dl_on_sp0) { const float4 p = REC(3); make_sp(v3(p), v3(REC(4)), v3(REC(5)), (int)ubits(p.w), sp); wo = v3(REC(6)); }
-	else { const float4 p = REC(7); make_sp(v3(p), v3(REC(8)), v3(REC(9)), (int)ubits(p.w), sp); wo = v3(REC(10)); }
+	// (a light-estimate kernel: the vertex waits in the scratchpad, whichever resume made it — wf_advance sees to that, vtx_need)
+	if(c.dl_on_sp0) { const float4 p = VHELD(3); make_sp(v3(p), v3(VHELD(4)), v3(VHELD(5)), (int)ubits(p.w), sp); wo = v3(VHELD(6)); }
+	else { const float4 p = VHELD(7); make_sp(v3(p), v3(VHELD(8)), v3(VHELD(9)), (int)ubits(p.w), sp); wo = v3(VHELD(10)); }
 	wf_frame_parked(a, slot, c.dl_on_sp0 ? 0 : 1, sp);
 	yafgpu_material mat_tmp;
 	const yafgpu_material &mat = wf_mat_parked(a, slot, c.dl_on_sp0 ? 0 : 1, sp, mat_tmp);
@@ -765,7 +871,7 @@ YG_DEV int st_dl_done(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, bool besid
 	if(!rec) hot_zero_tot(a, slot, h);              // taken: nothing reads it again before the next vertex zeroes it
 	if(c.stage == kStPrimary)
 	{
-		const uint32_t bsdfs0 = ubits(VGET(5).w);
+		const uint32_t bsdfs0 = ubits(VGET_W(5));
 		if(bsdfs0 & kDiffuse) c.col = c.col + total;                                            // :156
 		const uint32_t path_flags = rp.no_recursive ? (uint32_t)kAll : (uint32_t)kDiffuse;
 		if(rp.integrator != YAFGPU_INTEGRATOR_PATH || !(bsdfs0 & path_flags)) return W_RECURSE;
@@ -773,7 +879,7 @@ YG_DEV int st_dl_done(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, bool besid
 		if(beside) { c.stage = kStFirst; return W_NEXT_VERTEX; }      // st_start_path's work was done by st_beside
 		return W_START_PATH;
 	}
-	const yafgpu_material &pm_rec = sc.mats[(int)ubits(VGET(7).w)];
+	const yafgpu_material &pm_rec = sc.mats[(int)ubits(VGET_W(7))];
 	BsdfDat dat_n;
 	const uint32_t mb = mat_init_bsdf(pm_rec, dat_n);      // the flags do not depend on the nodes
 	yafgpu_material pm_tmp; (void)pm_tmp;
@@ -782,8 +888,8 @@ YG_DEV int st_dl_done(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, bool besid
 #if YAFGPU_FEAT_TEXTURE
 	if((c.stage == kStFirst || caustic) && (mb & kEmit) && pm_rec.n_nodes > 0 && sc.tex.nodes != nullptr)
 	{	// its own emission reads the diffuse shader (emit(), material_shiny_diffuse.cc:295-306)
-		const float4 p7 = REC(7);
-		SurfPt hp; hp.p = v3(p7); hp.n = v3(REC(8)); hp.ng = v3(REC(9)); hp.mat = (int)ubits(p7.w);
+		const float4 p7 = VGET(7);
+		SurfPt hp; hp.p = v3(p7); hp.n = v3(VGET(8)); hp.ng = v3(VGET(9)); hp.mat = (int)ubits(p7.w);
 		pm_p = &wf_mat_parked(a, slot, 1, hp, pm_tmp);
 	}
 #endif
@@ -844,9 +950,9 @@ YG_DEV int st_dl_done(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, bool besid
 	{
 		if(caustic && (mb & kEmit) && !rec)
 		{	// :290 a vertex reached through a caustic lobe adds what it emits, its lights included (include_lights_ is set)
-			const float4 p7 = REC(7);
-			SurfPt hp; hp.p = v3(p7); hp.n = v3(REC(8)); hp.ng = v3(REC(9)); hp.mat = (int)ubits(p7.w);
-			lcol = lcol + mat_emit(pm, hp, v3(REC(10)), true);
+			const float4 p7 = VGET(7);
+			SurfPt hp; hp.p = v3(p7); hp.n = v3(VGET(8)); hp.ng = v3(VGET(9)); hp.mat = (int)ubits(p7.w);
+			lcol = lcol + mat_emit(pm, hp, v3(VGET(10)), true);
 		}
 		path_col = path_col + lcol * throughput;                                                // :292
 		++c.depth;
@@ -887,10 +993,10 @@ YG_DEV int st_extend(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c)
 	// `w` and `p_ray.dir_` are variables of integrate() that sample() may leave untouched (a material with no lobe to
 	// sample returns Rgb(1) and nothing else, material_shiny_diffuse.cc sample()): the path then carries on straight
 	// through with the previous weight (integrator_path_tracer.cc:243-249).  They live in REC(6).w and in 8..10.w.
-	float w = REC(6).w;
+	float w = VGET_W(6);
 	V3 p_dir = mk(VGET(8).w, VGET(9).w, r10.w);
 	const Col scol = mat_sample(pm, dat_n, hit, pwo, p_dir, bs, w) * w;
-	REC(6).w = w;
+	VSET_W(w);
 	if(is_black(scol)) { ++c.path_i; return W_START_PATH; }                                      // :249 `break`
 	if(A_REPLAY != 1 || ra.rp.bounces - 1 > ra.rp.rr_min_bounces)      // (a record pass without a roulette test to record has no use for the throughput)
 	{
@@ -930,8 +1036,8 @@ YG_DEV int st_start_path(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint32_
 	float w = r6.w;                                   // integrate()'s `w`: 0 at its start, then whatever the last sample() left
 	V3 p_dir = mk(0.f, 0.f, 0.f);
 	const Col scol = mat_sample(m, dat0, sp0, wo0, p_dir, bs, w) * w;
-	REC(6).w = w;
-	if(bs.sampled == kNone || !YAFGPU_ACC_ZERO_FLAG) REC(10) = f4(wo0, 0.f);      // pwo = wo: only a segment that sampled nothing keeps it (:224, st_after_closest)
+	VSET_W(w);
+	if(bs.sampled == kNone || !YAFGPU_ACC_ZERO_FLAG) VSET_KEEP(10, f4(wo0, 0.f));      // pwo = wo: only a segment that sampled nothing keeps it (:224, st_after_closest)
 	if(A_REPLAY == 1)
 	{	// (record pass: the throughput alone, and only for a roulette test's probability)
 		if(rp.bounces - 1 > rp.rr_min_bounces) HSET(11, f4(scol, 0.f));
@@ -970,14 +1076,14 @@ YG_DEV int st_beside(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint32_t pi
 	}
 	if(c.stage == kStPrimary)
 	{	// st_dl_done will go to st_start_path(path_i = 0): :186-216
-		const float4 r5 = REC(5);
+		const float4 r5 = VGET(5);
 		const uint32_t path_flags = rp.no_recursive ? (uint32_t)kAll : (uint32_t)kDiffuse;
 		if(!(ubits(r5.w) & path_flags)) return W_PARK_SHADOW;
 		c.incl = 0;
-		const float4 p = REC(3);
-		SurfPt sp0; make_sp(v3(p), v3(REC(4)), v3(r5), (int)ubits(p.w), sp0);
+		const float4 p = VGET(3);
+		SurfPt sp0; make_sp(v3(p), v3(VGET(4)), v3(r5), (int)ubits(p.w), sp0);
 		wf_frame_parked(a, slot, 0, sp0);
-		const float4 r6 = REC(6);
+		const float4 r6 = VGET(6);
 		const V3 wo0 = v3(r6);
 		yafgpu_material m_tmp;
 		const yafgpu_material &m = wf_mat_parked(a, slot, 0, sp0, m_tmp);
@@ -991,8 +1097,8 @@ YG_DEV int st_beside(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint32_t pi
 		float w = r6.w;
 		V3 p_dir = mk(0.f, 0.f, 0.f);
 		const Col scol = mat_sample(m, dat0, sp0, wo0, p_dir, bs, w) * w;
-		REC(6).w = w;
-		if(bs.sampled == kNone || !YAFGPU_ACC_ZERO_FLAG) REC(10) = f4(wo0, 0.f);
+		VSET_W(w);
+		if(bs.sampled == kNone || !YAFGPU_ACC_ZERO_FLAG) VSET_KEEP(10, f4(wo0, 0.f));
 		Mwc rr; rr.init(fnv32a(ordinal) + 123u);
 		HSET(11, f4(scol, fbits(rr.x)));
 		HSET(12, make_float4(0.f, 0.f, 0.f, fbits(rr.c)));
@@ -1012,10 +1118,10 @@ YG_DEV int st_beside(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint32_t pi
 		const uint32_t e = wf_event(a, slot, a.ev_m > 1 ? ubits(REC(19).z) : 0u, c.path_i);
 		if((int)a.ev_kill[e] == c.depth) return W_PARK_SHADOW;
 	}
-	const float4 p = REC(7);
-	SurfPt hit; make_sp(v3(p), v3(REC(8)), v3(REC(9)), (int)ubits(p.w), hit);
+	const float4 p = VGET(7);
+	SurfPt hit; make_sp(v3(p), v3(VGET(8)), v3(VGET(9)), (int)ubits(p.w), hit);
 	wf_frame_parked(a, slot, 1, hit);
-	const float4 r10 = REC(10);
+	const float4 r10 = VGET(10);
 	const V3 pwo = v3(r10);
 	yafgpu_material pm_tmp;
 	const yafgpu_material &pm = wf_mat_parked(a, slot, 1, hit, pm_tmp);
@@ -1026,11 +1132,11 @@ YG_DEV int st_beside(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint32_t pi
 	bs.s_1 = (float)scr_halton(sc, d_4 + 3, offs);
 	bs.s_2 = (float)scr_halton(sc, d_4 + 4, offs);
 	bs.pdf = 0.f; bs.sampled = kNone; bs.flags = kAll;
-	float w = REC(6).w;
-	V3 p_dir = mk(REC(8).w, REC(9).w, r10.w);
+	float w = VGET_W(6);
+	V3 p_dir = mk(VGET(8).w, VGET(9).w, r10.w);
 	const Col scol = mat_sample(pm, dat_n, hit, pwo, p_dir, bs, w) * w;
 	if(is_black(scol)) return W_PARK_SHADOW;          // the path sample ends here (:249): nothing was written, st_extend finds it again
-	REC(6).w = w;
+	VSET_W(w);
 	REC(26) = f4(p_dir, ra.ray_min_dist);
 	// (.w: st_extend's include_lights_ for the segment — the vertex being estimated still needs the one it was reached with)
 	REC(27) = f4(scol, fbits((rp.trace_caustics && (bs.sampled & (kSpecular | kGlossy | kFilter))) ? 1u : 0u));
@@ -1057,16 +1163,16 @@ YG_DEV V3 wf_transp_origin(const yafgpu_material &m, V3 p, V3 dir, int raylevel)
 	return p + dir * f;
 }
 // recursiveRaytrace's perfect specular branch (:971-1025) at level c.level, whose working records hold the level's hit
-YG_DEV int st_recurse_spec(const WfArgs &a, uint32_t slot, Ctl &c)
+YG_DEV int st_recurse_spec(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c)
 {
 	const RenderArgs &ra = a.ra; const DevScene &sc = ra.sc; const yafgpu_render_params &rp = ra.rp; (void)sc; (void)rp;
 	if(!YAFGPU_FEAT_RECURSE) return W_RETURN;
-	const float4 r5 = REC(5);
+	const float4 r5 = VGET(5);
 	if(!(ubits(r5.w) & (kSpecular | kFilter))) return W_RETURN;
-	const float4 p = REC(3);
-	SurfPt sp0; make_sp(v3(p), v3(REC(4)), v3(r5), (int)ubits(p.w), sp0);
+	const float4 p = VGET(3);
+	SurfPt sp0; make_sp(v3(p), v3(VGET(4)), v3(r5), (int)ubits(p.w), sp0);
 	wf_frame_parked(a, slot, 0, sp0);
-	const V3 wo0 = v3(REC(6));
+	const V3 wo0 = v3(VGET(6));
 	yafgpu_material m_tmp;
 	const yafgpu_material &m = wf_mat_parked(a, slot, 0, sp0, m_tmp);
 	BsdfDat dat0; mat_init_bsdf(m, dat0);
@@ -1106,17 +1212,17 @@ enum : uint32_t { kGlSecond = 1u << 16,      // a second direction waits in F3 /
                   kGlVolFirst = 1u << 18, kGlVolSecond = 1u << 19,      // that ray runs inside the absorbing material (:935, :949)
                   kGlTwo = 1u << 20,         // the two-direction form (factor association :940, :954)
                   kGlBits = 0x1fu << 16 };
-YG_DEV int st_glossy_begin(const WfArgs &a, uint32_t slot, Ctl &c)
+YG_DEV int st_glossy_begin(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c)
 {
 	const int L = c.level;
-	const float4 r3 = REC(3), r5 = REC(5);
+	const float4 r3 = VGET(3), r5 = VGET(5);
 	const DivState dv = wf_div(a, slot, L);
 	const int gsam = dv.division > 1 ? max(1, 8 / dv.division) : 8;
 	FREC(L, 0) = f4(c.col, REC(19).w);
 	FREC(L, 2) = f4(v3(r3), fbits(16u | ((uint32_t)c.add << 8)));
-	FREC(L, 6) = f4(v3(REC(4)), fbits((uint32_t)gsam << 8));
+	FREC(L, 6) = f4(v3(VGET(4)), fbits((uint32_t)gsam << 8));
 	FREC(L, 7) = r5;
-	FREC(L, 8) = REC(6);
+	FREC(L, 8) = VGET(6);
 	FREC(L, 9) = make_float4(0.f, 0.f, 0.f, r3.w);
 	if(YAFGPU_FEAT_TEXTURE && a.ra.sc.tex.nodes != nullptr) FREC(L, 11) = REC(22);
 	if(YAFGPU_FEAT_TEXTURE && a.ra.sc.tex.has_bump) FREC(L, 12) = REC(24);
@@ -1179,15 +1285,15 @@ YG_DEV int st_glossy_next(const WfArgs &a, uint32_t slot, Ctl &c, uint32_t pixel
 	return W_PARK_CLOSEST;
 }
 // the level's own radiance is complete: recursiveRaytrace (:782-1028; the dispersive branch is refused on the host)
-YG_DEV int st_recurse(const WfArgs &a, uint32_t slot, Ctl &c)
+YG_DEV int st_recurse(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c)
 {
 	const yafgpu_render_params &rp = a.ra.rp;
 	if(!YAFGPU_FEAT_RECURSE || c.level + 1 > rp.raydepth + c.add || c.level >= a.frames) return W_RETURN;          // :791
-	if(a.has_glossy && (ubits(REC(5).w) & kGlossy)) return st_glossy_begin(a, slot, c);
+	if(a.has_glossy && (ubits(VGET_W(5)) & kGlossy)) return st_glossy_begin(a, slot, h, c);
 	return W_RECURSE_SPEC;
 }
 // an integrate() ends with (c.col, alpha): hand it to the level above, which either sends its transmitted ray or ends too
-YG_DEV int st_return(const WfArgs &a, uint32_t slot, Ctl &c, float &alpha_out)
+YG_DEV int st_return(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, float &alpha_out)
 {
 	const yafgpu_render_params &rp = a.ra.rp;
 	float alpha = REC(19).w;
@@ -1237,7 +1343,7 @@ YG_DEV int st_return(const WfArgs &a, uint32_t slot, Ctl &c, float &alpha_out)
 			}
 			c.col = c3(f0) + gcol * (1.f / (float)gsam);
 			// the level's hit again, for the specular branch that follows
-			REC(3) = f4(v3(f2), f9.w); REC(4) = f4(v3(f6), 0.f); REC(5) = FREC(P, 7); REC(6) = FREC(P, 8);
+			VSET(3, f4(v3(f2), f9.w)); VSET(4, f4(v3(f6), 0.f)); VSET(5, FREC(P, 7)); VSET(6, FREC(P, 8));
 			if(YAFGPU_FEAT_TEXTURE && a.ra.sc.tex.nodes != nullptr) REC(22) = FREC(P, 11);
 			if(YAFGPU_FEAT_TEXTURE && a.ra.sc.tex.has_bump) REC(24) = FREC(P, 12);
 			REC(19) = make_float4(0.f, 0.f, a.ev_m > 1 ? REC(19).z : 0.f, alpha_p);
@@ -1284,10 +1390,7 @@ YG_DEV int wf_advance(const WfArgs &a, uint32_t slot, uint32_t pixel_sample, uin
 	// previous one had just stored), and they are written back once, when the path parks.  (Also forwarding the
 	// vertex st_after_closest writes to st_dl_eval in registers costs more in spills than the round trip it saves:
 	// 6.9 -> 7.7 ms on C2.)
-	Hot h; h.valid = 0u; h.dirty = 0u; h.acc_zero = 0u; h.tot_zero = 0u;
-#if !YAFGPU_FEAT_LIGHTS
-	h.vvalid = 0u;
-#endif
+	Hot h; hot_init(h);
 	uint32_t w_last = 0u;      // the (li, l_end, is) word of the last pair the path is about to park for (st_beside)
 	float alpha = 0.f;
 	uint2 verdict = make_uint2(0u, 0u), verdict2 = verdict;
@@ -1297,6 +1400,19 @@ YG_DEV int wf_advance(const WfArgs &a, uint32_t slot, uint32_t pixel_sample, uin
 		verdict = make_uint2((w >> sh) & 1u, (w >> (sh + 1u)) & 1u);
 		verdict2 = make_uint2((w >> (sh + 2u)) & 1u, (w >> (sh + 3u)) & 1u);
 		hot_preload(a, slot, h, c.stage != kStPrimary);
+		if(YAFGPU_FEAT_LIGHTS && !beside)
+		{	// will st_dl_next name another pair of this vertex's estimate (another sample of the light, or another light)?  Then st_dl_eval runs
+			// in this resume, on a vertex an earlier one made.  (A second pair parked with this one counts: it is such a pair.)
+			const uint32_t w14 = ubits(h.r14.w);
+			const int li = (int)(w14 & 0xffu), l_end = (int)((w14 >> 8) & 0xffu), is = (int)(w14 >> 20);
+			bool more = li + 1 < l_end;
+			if(!more && li < l_end)
+			{
+				const yafgpu_light &light = a.ra.sc.lights[li];
+				more = !light_is_dirac(light.type) && is + 1 < dl_area_samples(a.ra, light, wf_div(a, slot, c.level).division);
+			}
+			if(more) { if(c.dl_on_sp0) VNEED(3); else VNEED(7); }
+		}
 	}
 	// The step graph has no backward edge except NEXT <-> EVAL, so the program is written out once in topological
 	// order (a dispatch loop makes the optimizer thread the transitions, duplicate the steps and keep the union
@@ -1322,6 +1438,7 @@ YG_DEV int wf_advance(const WfArgs &a, uint32_t slot, uint32_t pixel_sample, uin
 		if(where == W_NEXT_VERTEX) where = W_AFTER_CLOSEST;
 	}
 	if(where == W_AFTER_CLOSEST) where = st_after_closest(a, slot, h, c, ordinal, ans, beside);
+	if(YAFGPU_FEAT_LIGHTS && !a.vtx_lds && where == W_DL_NEXT) { if(c.dl_on_sp0) VNEED(3); else VNEED(7); }      // (the vertex just made went to memory)
 	if(YAFGPU_FEAT_LIGHTS)
 	{
 		if(where == W_AFTER_SHADOW) where = st_after_shadow(a, slot, h, verdict);
@@ -1364,21 +1481,29 @@ YG_DEV int wf_advance(const WfArgs &a, uint32_t slot, uint32_t pixel_sample, uin
 	if(YAFGPU_FEAT_LIGHTS && where == W_PARK_SHADOW) where = st_beside(a, slot, h, c, pixel_sample, sampling_offs, ordinal, w_last);
 	if(where == W_EXTEND) where = st_extend(a, slot, h, c);
 	if(where == W_START_PATH) where = st_start_path(a, slot, h, c, pixel_sample, sampling_offs, ordinal);
-	if(where == W_RECURSE) where = st_recurse(a, slot, c);
+	if(where == W_RECURSE) where = st_recurse(a, slot, h, c);
 #if YAFGPU_FEAT_RECURSE
 	// recursion: return -> (next glossy trajectory | the specular branch of the level above) -> park or return again
 	for(;;)
 	{
 		if(where == W_GLOSSY_NEXT) where = st_glossy_next(a, slot, c, pixel_sample, sampling_offs);
-		if(where == W_RECURSE_SPEC) where = st_recurse_spec(a, slot, c);
+		if(where == W_RECURSE_SPEC) where = st_recurse_spec(a, slot, h, c);
 		if(where != W_RETURN) break;
-		where = st_return(a, slot, c, alpha);
+		where = st_return(a, slot, h, c, alpha);
 		if(where != W_GLOSSY_NEXT && where != W_RECURSE_SPEC) break;
 	}
 #else
-	if(where == W_RETURN) where = st_return(a, slot, c, alpha);
+	if(where == W_RETURN) where = st_return(a, slot, h, c, alpha);
 #endif
 	if(where != W_FINISH) hot_flush(a, slot, h, where == W_PARK_CLOSEST);      // a path that ends needs none of them again
+#if YAFGPU_FEAT_LIGHTS
+	if(where != W_FINISH)
+	{	// a park for a shadow pair ALONE: the sampler st_beside did not run comes after the answers and reads the whole vertex — st_start_path
+		// at the camera hit, st_extend along the path unless st_dl_done ends the path sample there for want of bounces
+		const bool sampler_later = c.stage == kStPrimary || (c.stage == kStFirst ? 1 : c.depth + 1) < a.ra.rp.bounces;
+		vtx_flush(a, slot, h, where == W_PARK_SHADOW && sampler_later);
+	}
+#endif
 	if(where == W_PARK_CLOSEST) { c.pc = kPcAfterClosest; REC(13) = f4(c.col, fbits(pack_ctl(c))); return kReqClosest; }
 	if(where == W_PARK_SHADOW) { c.pc = kPcAfterShadow; REC(13) = f4(c.col, fbits(pack_ctl(c))); return kReqShadow; }
 	if(where == W_PARK_BOTH) { c.pc = kPcAfterBoth; REC(13) = f4(c.col, fbits(pack_ctl(c))); return kReqBoth; }
@@ -1400,7 +1525,7 @@ __global__ __launch_bounds__(kBlock, PROBE_WAVES) void probe_advance(const WfArg
 }
 #define PROBE(name, call) __global__ __launch_bounds__(kBlock, PROBE_WAVES) void name(const WfArgs a, int *out) { \
 	const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; Ctl c = load_ctl(a, slot); int m = 0; (void)m; \
-	Hot h; hot_preload(a, slot, h, true); const int w = call; hot_flush(a, slot, h, false); \
+	Hot h; hot_init(h); hot_preload(a, slot, h, true); const int w = call; hot_flush(a, slot, h, false); \
 	a.state[(size_t)13 * a.cap + slot] = f4(c.col, fbits(pack_ctl(c))); out[slot] = w + m; }
 PROBE(probe_after_closest, st_after_closest(a, slot, h, c, slot * 7u, a.state[2 * (size_t)a.cap + slot], false))
 PROBE(probe_after_shadow, st_after_shadow(a, slot, h, make_uint2(slot & 1u, slot & 2u)))
@@ -1899,17 +2024,21 @@ constexpr int kShadeTabBytes = 16384;     // 3 blocks per CU at 3 waves per SIMD
 #ifndef YAFGPU_SHADE_LDS_FAURE
 #define YAFGPU_SHADE_LDS_FAURE 1
 #endif
-constexpr int kShadeFaureBytes = YAFGPU_SHADE_LDS_FAURE ? 20480 : 0;      // 5117 ints for the 50 dimensions
+// Only a prefix of the 50 dimensions is staged (all of them are 20 KB): a render indexes dimensions up to 4 * bounces + 4, and the room goes to
+// the vertex scratchpad (s_wf_vtx, 16 KB) with three blocks per CU still fitting.  8 KB hold dimensions 0..33, enough up to 8 bounces; a
+// dimension beyond the prefix is read from global memory (scr_halton).
+constexpr int kShadeFaureBytes = YAFGPU_SHADE_LDS_FAURE ? 8192 : 0;
 __global__ __launch_bounds__(kBlock, YAFGPU_SHADE_WAVES) void wf_shade(const WfArgs a_in)
 {
 #if YAFGPU_SHADE_LDS_TABLES
 	__shared__ uint4 s_tab[(kShadeTabBytes + kShadeFaureBytes) / 16];
 	WfArgs a = a_in;
-	if(YAFGPU_SHADE_LDS_FAURE && (uint32_t)a_in.ra.sc.n_faure * 4u <= (uint32_t)kShadeFaureBytes)
+	if(YAFGPU_SHADE_LDS_FAURE)
 	{
 		int *dst = (int *)s_tab + kShadeTabBytes / 4;
-		for(uint32_t w = threadIdx.x; w < (uint32_t)a_in.ra.sc.n_faure; w += blockDim.x) dst[w] = a_in.ra.sc.faure[w];
-		a.ra.sc.faure = dst;        // (the barrier below, or the one of the first queue round, orders the copy before any use)
+		const uint32_t n_near = min((uint32_t)a_in.ra.sc.n_faure, (uint32_t)kShadeFaureBytes / 4u);
+		for(uint32_t w = threadIdx.x; w < n_near; w += blockDim.x) dst[w] = a_in.ra.sc.faure[w];
+		a.ra.sc.faure = dst; a.ra.sc.faure_near = (int)n_near;      // (faure_far stays the whole table in global memory)
 		__syncthreads();
 	}
 	{
