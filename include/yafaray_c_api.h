@@ -88,6 +88,9 @@ yafaray_bool_t yafaray_getMeshCornerNormals(yafaray_interface_t *yi, unsigned in
 /* extension (test support): the scene's enabled lights in Scene::addLight order, as the device gets them: up to max_lights
  * yafgpu_light records (include/yafgpu.h, 136 bytes each) into out; returns how many lights the scene has */
 int yafaray_getLights(yafaray_interface_t *yi, void *out, int max_lights);
+/* extension (test support): the yafgpu_background record (include/yafgpu.h, 12 words) createBackground made under `name`, as the
+ * device scene would get it; false when there is no such background */
+yafaray_bool_t yafaray_getBackground(yafaray_interface_t *yi, const char *name, void *out);
 /* extension (not in the reference): bulk form of addVertex/addTriangle for large meshes;
  * verts = n_verts*3 floats, indices = n_tris*3 ints, one material for all triangles */
 yafaray_bool_t yafaray_addTriangles(yafaray_interface_t *yi, int n_verts, const float *verts, int n_tris, const int *indices,

@@ -31,7 +31,9 @@ extern "C" {
 enum { YAFGPU_MAT_SHINYDIFFUSE = 0, YAFGPU_MAT_GLOSSY = 1, YAFGPU_MAT_LIGHT = 2, YAFGPU_MAT_GLASS = 3, YAFGPU_MAT_MIRROR = 4,
        YAFGPU_MAT_COATED_GLOSSY = 5, /* glossy's fields + mirror_color, mirror_strength, glass_ior = IOR, c_flags[0..2], n_bsdf */
        YAFGPU_MAT_ROUGH_GLASS = 6 /* glass's fields (glass_ior, filter_color, mirror_color, fake_shadow, beer_sigma) + rg_a2: RoughGlassMaterial, material_rough_glass.cc */ };
-enum { YAFGPU_LIGHT_AREA = 0, YAFGPU_LIGHT_POINT = 1, YAFGPU_LIGHT_DIRECTIONAL = 2, YAFGPU_LIGHT_SUN = 3, YAFGPU_LIGHT_SPHERE = 4 };
+enum { YAFGPU_LIGHT_AREA = 0, YAFGPU_LIGHT_POINT = 1, YAFGPU_LIGHT_DIRECTIONAL = 2, YAFGPU_LIGHT_SUN = 3, YAFGPU_LIGHT_SPHERE = 4,
+       YAFGPU_LIGHT_BACKGROUND = 5 /* BackgroundLight (light_background.cc): samples the scene's yafgpu_background through its Pdf1D tables */ };
+enum { YAFGPU_BACKGROUND_NONE = 0, YAFGPU_BACKGROUND_CONSTANT = 1, YAFGPU_BACKGROUND_TEXTURE = 2 };
 enum { YAFGPU_INTEGRATOR_PATH = 0, YAFGPU_INTEGRATOR_DIRECT = 1 };
 enum { YAFGPU_FILTER_BOX = 0, YAFGPU_FILTER_MITCHELL = 1, YAFGPU_FILTER_GAUSS = 2, YAFGPU_FILTER_LANCZOS = 3 };
 
@@ -142,7 +144,8 @@ typedef struct yafgpu_node
  *                ctor does (createCs__ of the direction, light_directional.cc:39) and read by nothing here (photon emission only)
  *   sun          samples, direction (normalised), du / dv (createCs__ of the direction AS GIVEN, sic light_sun.cc:36), cos_angle,
  *                invpdf, pdf, col_pdf (color * pdf); color (col * power) is kept for reference only
- *   sphere       samples, position (center), radius, square_radius, square_radius_epsilon, color (col * power) */
+ *   sphere       samples, position (center), radius, square_radius, square_radius_epsilon, color (col * power)
+ *   background   samples, clamp_intersect (0 = no clamp), abs_intersect; what it emits is the scene's yafgpu_background */
 typedef struct yafgpu_light
 {
 	int32_t type, samples, cast_shadows;
@@ -162,8 +165,24 @@ typedef struct yafgpu_light
 	float color[3];
 	float area;
 	float position[3];
-	float pad1[2];
+	float clamp_intersect;         /* background: clamp_intersect_ (Light::setClampIntersect, light_background.cc:182) */
+	int32_t abs_intersect;         /* background: abs_inter_ (:178); the background factories always pass false */
 } yafgpu_light;
+
+/* The background after its factory ran on the host (background_constant.cc:51-88, background_texture.cc:33-39, :91-165).
+ *   constant  color (col * power), has_ibl, shoots_caustic (always 1, background_constant.cc:69)
+ *   texture   texture (index into the scene's textures), projection (0 spherical, 1 angular), power, rotation (2 * rot / 360),
+ *             sin_r / cos_r (fSin__ / fCos__ of pi * rotation), has_ibl, shoots_caustic (with_caustic)
+ * With has_ibl the scene has exactly one YAFGPU_LIGHT_BACKGROUND light; yafgpu_scene_create builds its tables on the device. */
+typedef struct yafgpu_background
+{
+	int32_t kind;                  /* YAFGPU_BACKGROUND_* */
+	float color[3];
+	float power;
+	int32_t texture, projection;
+	float rotation, sin_r, cos_r;
+	int32_t has_ibl, shoots_caustic;
+} yafgpu_background;
 
 /* PerspectiveCamera after setAxis (camera_perspective.cc:60-74) */
 typedef struct yafgpu_camera
@@ -204,6 +223,8 @@ typedef struct yafgpu_scene_desc
 	int32_t build_on_device;     /* kd-tree builder: 1 = on the GPU (kdtree_build_device.hip), -1 = host builder,
 	                                0 = by size (GPU from 65 536 triangles on).  Both give the same query results.
 	                                The environment variable YAFGPU_BUILD=device|host overrides it. */
+	yafgpu_background background; /* kind 0: none.  A texture background is evaluated per escaping ray (yafgpu_render_params::background is
+	                                the constant case's colour and keeps working without this record) */
 } yafgpu_scene_desc;
 
 typedef struct yafgpu_render_params

@@ -71,7 +71,7 @@ struct IntegratorCfg
 };
 
 struct CameraCfg { yafgpu_camera cam; };
-struct BackgroundCfg { float color[3]; };
+struct BackgroundCfg { float color[3]; yafgpu_background rec; };      // color: the constant colour (yafgpu_render_params::background); rec: what the device scene gets
 
 } // namespace
 
@@ -113,6 +113,7 @@ struct yafaray_interface
 	bool prepared = false;
 	bool scene_dirty = true;            // something the device scene is made of changed since it was built (Scene::update's state_.changes_, scene.cc:784-790)
 	yafgpu_camera scene_cam{}; int scene_threads = 0;
+	std::string scene_background;       // the background the device scene was built with (background_name; empty: none)
 	int shard_index = 0, shard_count = 1;
 	std::vector<float> film;
 	yafaray_render_stats_t stats{};
@@ -1151,6 +1152,13 @@ int yafaray_getLights(yafaray_interface_t *yi, void *out, int max_lights)
 	for(int i = 0; out && i < std::min(n, max_lights); ++i) std::memcpy((char *)out + (size_t)i * sizeof(yafgpu_light), &yi->light_order[(size_t)i]->l, sizeof(yafgpu_light));
 	return n;
 }
+yafaray_bool_t yafaray_getBackground(yafaray_interface_t *yi, const char *name, void *out)
+{
+	auto it = name ? yi->backgrounds.find(name) : yi->backgrounds.end();
+	if(it == yi->backgrounds.end()) return fail(yi, "getBackground: no such background");
+	if(out) std::memcpy(out, &it->second->b.rec, sizeof(yafgpu_background));
+	return 1;
+}
 yafaray_bool_t yafaray_getMeshCornerNormals(yafaray_interface_t *yi, unsigned int id, float *out, int n_floats)
 {
 	auto it = yi->meshes.find(id);
@@ -1389,21 +1397,70 @@ yafaray_camera_t *yafaray_createCamera(yafaray_interface_t *yi, const char *name
 	yi->prepared = false; yi->scene_dirty = true;
 	return raw;
 }
+// The light a background with `ibl` brings along: ConstantBackground::factory / TextureBackground::factory build a "bglight" ParamMap
+// (samples, with_caustic, with_diffuse, abs_intersect = false, cast_shadows) and hand the light to Scene::addLight on the spot
+// (background_constant.cc:71-85, background_texture.cc:133-162).  light_enabled is not among those parameters: BackgroundLight::factory's
+// default (true) stands.  with_caustic / with_diffuse steer photon emission only, which this path does not have.
+static void add_background_light(yafaray_interface *yi, const char *fixed_name, int samples, bool cast_shadows, float clamp_intersect)
+{
+	auto l = std::make_unique<yafaray_light>();
+	std::memset(&l->l, 0, sizeof l->l);
+	l->l.type = YAFGPU_LIGHT_BACKGROUND; l->l.samples = samples; l->l.cast_shadows = cast_shadows ? 1 : 0;
+	l->l.clamp_intersect = clamp_intersect; l->l.abs_intersect = 0;
+	// the reference's fixed name collides when a second background of the kind asks for a light (createLight returns null and the factory
+	// dereferences it); here every one gets a name of its own and prepareRender refuses the scene
+	std::string name = fixed_name;
+	for(int k = 2; yi->lights.count(name); ++k) name = std::string(fixed_name) + "#" + std::to_string(k);
+	yi->light_order.push_back(l.get());
+	yi->lights[name] = std::move(l);
+}
 yafaray_background_t *yafaray_createBackground(yafaray_interface_t *yi, const char *name)
 {
 	std::string type;
+	const ParamMap &p = yi->params;
 	if(!name) { fail(yi, "createBackground: null name"); return nullptr; }
-	if(!yi->params.get("type", type)) { fail(yi, "createBackground: type of background not specified"); return nullptr; }
-	if(type != "constant") { fail(yi, "createBackground: background type \"" + type + "\" is outside the GPU path's scope (constant)"); return nullptr; }
-	bool ibl = false; yi->params.get("ibl", ibl);
-	if(ibl) { fail(yi, "createBackground: image-based lighting (ibl) is not supported by the GPU path"); return nullptr; }
-	float col[3] = {0, 0, 0}; float power = 1.f;
-	yi->params.getColor("color", col); yi->params.get("power", power);   // background_constant.cc:49-66
+	if(!p.get("type", type)) { fail(yi, "createBackground: type of background not specified"); return nullptr; }
+	if(type != "constant" && type != "textureback")
+	{ fail(yi, "createBackground: background type \"" + type + "\" is outside the GPU path's scope (constant, textureback)"); return nullptr; }
 	auto b = std::make_unique<yafaray_background>();
-	for(int k = 0; k < 3; ++k) b->b.color[k] = power * col[k];
+	std::memset(&b->b, 0, sizeof b->b);
+	yafgpu_background &rec = b->b.rec;
+	bool ibl = false, cast_shadows = true, caus = true, diff = true; int ibl_sam = 16; float power = 1.f;
+	p.get("ibl", ibl); p.get("ibl_samples", ibl_sam); p.get("cast_shadows", cast_shadows); p.get("with_caustic", caus); p.get("with_diffuse", diff);
+	p.get("power", power);
+	(void)diff;
+	if(type == "constant")
+	{	// ConstantBackground::factory, background_constant.cc:51-88
+		float col[3] = {0, 0, 0};
+		p.getColor("color", col);
+		for(int k = 0; k < 3; ++k) b->b.color[k] = rec.color[k] = power * col[k];
+		rec.kind = YAFGPU_BACKGROUND_CONSTANT; rec.power = power; rec.texture = -1;
+		rec.has_ibl = ibl ? 1 : 0;
+		rec.shoots_caustic = 1;          // :69: the constructor gets `true` whatever with_caustic says
+		if(ibl) add_background_light(yi, "constantBackground_bgLight", ibl_sam, cast_shadows, 0.f);
+	}
+	else
+	{	// TextureBackground::factory, background_texture.cc:91-165
+		std::string texname, mapping;
+		float rot = 0.f, ibl_blur = 0.f, ibl_clamp_sampling = 0.f;
+		if(!p.get("texture", texname)) { fail(yi, "createBackground: no texture given for texture background (parameter \"texture\")"); return nullptr; }
+		auto t = yi->textures.find(texname);
+		if(t == yi->textures.end()) { fail(yi, "createBackground: texture '" + texname + "' for textureback does not exist"); return nullptr; }
+		p.get("smartibl_blur", ibl_blur); p.get("ibl_clamp_sampling", ibl_clamp_sampling); p.get("rotation", rot);
+		if(ibl_blur > 0.f) { fail(yi, "createBackground: smartibl_blur > 0 needs mip maps, which the GPU path does not have (set smartibl_blur to 0)"); return nullptr; }
+		rec.kind = YAFGPU_BACKGROUND_TEXTURE; rec.texture = t->second->index; rec.power = power;
+		rec.projection = (p.get("mapping", mapping) && (mapping == "probe" || mapping == "angular")) ? 1 : 0;      // Angular, else Spherical
+		// the constructor, :33-39: M_PI * rotation_ is a double product, narrowed where fSin__ / fCos__ take it
+		rec.rotation = 2.0f * rot / 360.f;
+		const float arg = (float)(3.14159265358979323846 * (double)rec.rotation);
+		rec.sin_r = host_fsin_poly(arg);
+		rec.cos_r = host_fsin_poly(arg + (float)1.57079632679489661923);
+		rec.has_ibl = ibl ? 1 : 0; rec.shoots_caustic = caus ? 1 : 0;
+		if(ibl) add_background_light(yi, "textureBackground_bgLight", ibl_sam, cast_shadows, ibl_clamp_sampling > 0.f ? ibl_clamp_sampling : 0.f);
+	}
 	yafaray_background *raw = b.get();
 	yi->backgrounds[name] = std::move(b);
-	yi->prepared = false;
+	yi->prepared = false; yi->scene_dirty = true;
 	return raw;
 }
 yafaray_integrator_t *yafaray_createIntegrator(yafaray_interface_t *yi, const char *name)
@@ -1504,6 +1561,17 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 		if(b == yi->backgrounds.end()) return fail(yi, "please specify an _existing_ Background!!");
 		bg = &b->second->b;
 	}
+	{	// One image-based-lighting background per scene, and it is the one in use.  (The reference adds a background's light when the
+		// background is created, selected or not, and two of one kind collide on the light's fixed name.)
+		int n_bg_lights = 0;
+		for(auto *l : yi->light_order) if(l->l.type == YAFGPU_LIGHT_BACKGROUND) ++n_bg_lights;
+		if(n_bg_lights > 1) return fail(yi, "render: more than one background was created with ibl; the GPU path takes one image-based-lighting background per scene");
+		if(n_bg_lights == 1 && !(bg && bg->rec.has_ibl))
+			return fail(yi, "render: a background created with ibl is not the one background_name selects; its light would shine without it");
+		if(bg && bg->rec.has_ibl && bg->rec.kind == YAFGPU_BACKGROUND_CONSTANT && !((bg->rec.color[0] + bg->rec.color[1] + bg->rec.color[2]) * 0.333333f > 0.f))
+			return fail(yi, "render: a constant background with ibl needs a colour with energy; this one is black (its light's distribution would divide by zero)");
+	}
+	const std::string bg_name = bg ? name : std::string();
 	int aa_passes = 1, aa_samples = 1, tile_size = 32, width = 320, height = 240, xstart = 0, ystart = 0;
 	int base_offset = 0, node = 0;
 	float filt_sz = 1.5f, shadow_bias = (float)0.0005, min_raydist = (float)0.00005, clamp_samples = 0.f, clamp_indirect = 0.f;
@@ -1576,7 +1644,7 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 	// Scene::update: flatten visible non-base meshes in object-id order (scene.cc:797-817)
 	if(yi->state != 0) return fail(yi, "render: scene is not in the ready state (missing endGeometry?)");
 	int threads = -1; p.get("threads", threads);
-	if(yi->gpu && !yi->scene_dirty && std::memcmp(&yi->scene_cam, &cam->second->c.cam, sizeof yi->scene_cam) == 0 && yi->scene_threads == threads)
+	if(yi->gpu && !yi->scene_dirty && std::memcmp(&yi->scene_cam, &cam->second->c.cam, sizeof yi->scene_cam) == 0 && yi->scene_threads == threads && yi->scene_background == bg_name)
 	{	// nothing the device scene is made of changed: keep it, tree and all (Scene::update rebuilds only on changes, scene.cc:784-790)
 		yafgpu_scene_set_exchange(yi->gpu, yi->exchange, yi->exchange_user);
 		yi->prepared = true;
@@ -1637,7 +1705,8 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 		mats.push_back(rec);
 	}
 	std::vector<yafgpu_texture> textures; std::vector<float> texels;
-	if(any_nodes)
+	const bool bg_texture = bg && bg->rec.kind == YAFGPU_BACKGROUND_TEXTURE;
+	if(any_nodes || bg_texture)
 		for(auto *t : yi->texture_order)
 		{
 			if((texels.size() + t->texels.size()) / 4 > 0xffffffffull) return fail(yi, "render: more than 2^32 texels in the scene's image textures");
@@ -1655,15 +1724,19 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 	if(any_nodes)
 	{
 		d.tri_uv = tri_uv.data(); d.tri_orco = tri_orco.data();
-		d.n_textures = (int32_t)textures.size(); d.textures = textures.data();
-		d.n_texels = texels.size() / 4; d.texels = texels.data();
 		d.n_nodes = (int32_t)nodes.size(); d.nodes = nodes.data();
 	}
+	if(any_nodes || bg_texture)
+	{
+		d.n_textures = (int32_t)textures.size(); d.textures = textures.data();
+		d.n_texels = texels.size() / 4; d.texels = texels.data();
+	}
+	if(bg) d.background = bg->rec;
 	d.camera = cam->second->c.cam;
 	d.build_threads = 0;
 	if(threads > 0) d.build_threads = threads;
 	if(yafgpu_scene_create(&d, &yi->gpu)) return fail(yi, std::string("scene upload: ") + yafgpu_last_error());
-	yi->scene_dirty = false; yi->scene_cam = cam->second->c.cam; yi->scene_threads = threads;
+	yi->scene_dirty = false; yi->scene_cam = cam->second->c.cam; yi->scene_threads = threads; yi->scene_background = bg_name;
 	yafgpu_scene_set_pass_pipelining(yi->gpu, yi->pass_pipelining);
 	yafgpu_scene_set_abort_flag(yi->gpu, &yi->abort_flag);
 	yafgpu_scene_set_exchange(yi->gpu, yi->exchange, yi->exchange_user);

@@ -68,6 +68,7 @@ struct DevScene
 	float blo[3], bhi[3];
 	yafgpu_camera cam;
 	TexScene tex;                // textures, texels, shader nodes, per-triangle texture coordinates (nodes == nullptr: none)
+	BgScene bg;                  // the background record and the background light's tables (kind 0: none; tab == nullptr: no light)
 };
 
 struct RenderArgs
@@ -580,8 +581,75 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			o[0] = ok ? 1.f : 0.f; o[1] = d_1; o[2] = ok ? d_2 : 0.f;
 			break;
 		}
+		case 22:
+		{	// Background::eval: in dir.xyz -> rgb
+			if(n_in < 3 || n_out < 3 || sc.bg.rec.kind == YAFGPU_BACKGROUND_NONE) break;
+			const Col c = bg_eval(sc.bg, sc.tex, mk(x[0], x[1], x[2]));
+			o[0] = c.r; o[1] = c.g; o[2] = c.b;
+			break;
+		}
+		case 23:
+		{	// BackgroundLight::illumSample: in s_1, s_2 -> ok, wi.dir, wi.tmax, pdf, ls.col
+			if(n_in < 2 || n_out < 9 || sc.bg.tab == nullptr) break;
+			Col c = mkc(0.f, 0.f, 0.f); V3 d = mk(0.f, 0.f, 0.f); float tmax = 0.f, pdf = 0.f;
+			const bool ok = bglight_illum_sample(sc.bg, sc.tex, x[0], x[1], d, tmax, pdf, c);
+			o[0] = ok ? 1.f : 0.f;
+			o[1] = d.x; o[2] = d.y; o[3] = d.z; o[4] = tmax; o[5] = pdf; o[6] = c.r; o[7] = c.g; o[8] = c.b;
+			break;
+		}
+		case 24:
+		{	// BackgroundLight::intersect of the scene's background light: in dir.xyz -> ok, t, ipdf, col
+			if(n_in < 3 || n_out < 6 || sc.bg.tab == nullptr) break;
+			int k = 0;
+			while(k < sc.n_lights && sc.lights[k].type != YAFGPU_LIGHT_BACKGROUND) ++k;
+			if(k >= sc.n_lights) break;
+			Col c = mkc(0.f, 0.f, 0.f); float t = 0.f, ipdf = 0.f;
+			const bool ok = bglight_intersect(sc.lights[k], sc.bg, sc.tex, mk(x[0], x[1], x[2]), t, c, ipdf);
+			o[0] = ok ? 1.f : 0.f; o[1] = t; o[2] = ipdf; o[3] = c.r; o[4] = c.g; o[5] = c.b;
+			break;
+		}
+		case 25:
+		{	// the background light's tables: in y (as bits; y = kBgRows reads v_dist_) -> count, integral, 1 / integral, 1 / count, func_ (kBgMaxU), cdf_ (kBgMaxU + 1)
+			if(n_in < 1 || sc.bg.tab == nullptr) break;
+			const uint32_t y = __float_as_uint(x[0]);
+			if(y > (uint32_t)kBgRows) break;
+			const float *row = sc.bg.tab + (size_t)y * kBgRowStride;
+			for(int k = 0; k < min(n_out, kBgCdf + kBgMaxU + 1); ++k) o[k] = row[k];
+			break;
+		}
 		default: break;
 	}
+}
+
+// BackgroundLight::init (light_background.cc:78-120): the background's energy on a latitude-longitude grid, one workgroup per row y.
+// The threads evaluate the row's cells; one thread then accumulates the row in index order (pdf1d_build), which is what makes the
+// tables the reference's bit for bit.
+__global__ __launch_bounds__(kBlock) void bg_rows_kernel(const DevScene sc, float *tab)
+{
+	const int y = (int)blockIdx.x;
+	if(y >= kBgRows) return;
+	float *row = tab + (size_t)y * kBgRowStride;
+	const float inv = 1.f / (float)kBgRows;
+	const float fy = ((float)y + 0.5f) * inv;
+	const float sintheta = bg_sin_sample(fy);
+	const int nu = min(kBgMaxU, max(1, kBgMinU + (int)(sintheta * (float)(kBgMaxU - kBgMinU))));      // (the bounds only say what the arithmetic already gives)
+	const float inu = 1.f / (float)nu;
+	for(int xi = (int)threadIdx.x; xi < nu; xi += (int)blockDim.x)
+	{
+		const float fx = ((float)xi + 0.5f) * inu;
+		const Col c = bg_eval(sc.bg, sc.tex, bg_inv_spheremap(fx, fy));
+		row[kBgFunc + xi] = ((c.r + c.g + c.b) * 0.333333f) * sintheta;      // Rgb::energy, color.h:58
+	}
+	__syncthreads();
+	if(threadIdx.x == 0) pdf1d_build(row, nu);
+}
+// v_dist_: the same construction over the rows' integrals (:106, :109); one workgroup, after bg_rows_kernel
+__global__ __launch_bounds__(kBlock) void bg_vdist_kernel(float *tab)
+{
+	float *row = tab + (size_t)kBgRows * kBgRowStride;
+	for(int y = (int)threadIdx.x; y < kBgRows; y += (int)blockDim.x) row[kBgFunc + y] = tab[(size_t)y * kBgRowStride + 1];
+	__syncthreads();
+	if(threadIdx.x == 0 && blockIdx.x == 0) pdf1d_build(row, kBgRows);
 }
 
 } // namespace yafgpu
@@ -779,7 +847,22 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 	for(int i = 0; i < d->n_tris; ++i)
 		if(d->tri_mat[i] < 0 || d->tri_mat[i] >= d->n_materials) return fail(-3, "triangle material index out of range");
 	for(int i = 0; i < d->n_lights; ++i)
-		if(d->lights[i].type < YAFGPU_LIGHT_AREA || d->lights[i].type > YAFGPU_LIGHT_SPHERE) return fail(-2, "light " + std::to_string(i) + ": unknown type");
+		if(d->lights[i].type < YAFGPU_LIGHT_AREA || d->lights[i].type > YAFGPU_LIGHT_BACKGROUND) return fail(-2, "light " + std::to_string(i) + ": unknown type");
+	{	// the background and its light: one record, at most one light, and the light only with a background that asks for it
+		const yafgpu_background &b = d->background;
+		int n_bg_lights = 0;
+		for(int i = 0; i < d->n_lights; ++i) if(d->lights[i].type == YAFGPU_LIGHT_BACKGROUND) ++n_bg_lights;
+		if(b.kind < YAFGPU_BACKGROUND_NONE || b.kind > YAFGPU_BACKGROUND_TEXTURE) return fail(-2, "background: unknown kind");
+		if(n_bg_lights > 1) return fail(-2, "more than one background light");
+		if(n_bg_lights != ((b.kind != YAFGPU_BACKGROUND_NONE && b.has_ibl) ? 1 : 0)) return fail(-2, "a background light needs a background with has_ibl, and such a background its light");
+		if(b.kind == YAFGPU_BACKGROUND_TEXTURE)
+		{
+			if(!d->textures || b.texture < 0 || b.texture >= d->n_textures) return fail(-24, "the background's texture does not exist");
+			if(b.projection != 0 && b.projection != 1) return fail(-2, "background: unknown projection");
+		}
+		if(b.kind == YAFGPU_BACKGROUND_CONSTANT && b.has_ibl && !((b.color[0] + b.color[1] + b.color[2]) * 0.333333f > 0.f))
+			return fail(-2, "a constant background with a light needs a colour with energy (Pdf1D would divide by zero)");
+	}
 	for(int i = 0; i < d->n_materials; ++i)
 	{
 		// recursiveRaytrace (integrator_montecarlo.cc:782-1028): the perfect specular branch and both cases of the glossy branch (reflect
@@ -911,8 +994,20 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 	if((rc = upload(s, d->materials, (size_t)d->n_materials, &dv.mats))) { yafgpu_scene_destroy(s); return rc; }
 	if((rc = upload(s, d->lights, (size_t)d->n_lights, &dv.lights))) { yafgpu_scene_destroy(s); return rc; }
 	std::memset(&dv.tex, 0, sizeof dv.tex);
+	if((d->n_nodes > 0 && d->nodes) || d->background.kind == YAFGPU_BACKGROUND_TEXTURE)
+	{	// image textures: what the shader nodes and a texture background look up
+		for(int i = 0; i < d->n_textures; ++i)
+		{
+			const yafgpu_texture &t = d->textures[i];
+			if(t.width <= 0 || t.height <= 0 || (uint64_t)t.texel_first + (uint64_t)t.width * (uint64_t)t.height > d->n_texels) { yafgpu_scene_destroy(s); return fail(-24, "a texture's texel range lies outside the texel array"); }
+		}
+		const float4 *texels = nullptr;
+		if((rc = upload(s, d->textures, (size_t)std::max(d->n_textures, 0), &dv.tex.textures))) { yafgpu_scene_destroy(s); return rc; }
+		if((rc = upload(s, (const float4 *)d->texels, (size_t)d->n_texels, &texels))) { yafgpu_scene_destroy(s); return rc; }
+		dv.tex.texels = texels; dv.tex.n_textures = d->n_textures;
+	}
 	if(d->n_nodes > 0 && d->nodes)
-	{	// shader nodes, image textures and the per-triangle texture coordinates they read
+	{	// shader nodes and the per-triangle texture coordinates they read
 		for(int i = 0; i < d->n_materials; ++i)
 		{
 			const yafgpu_material &m = d->materials[i];
@@ -947,16 +1042,7 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 			const yafgpu_node &n = d->nodes[i];
 			if(n.type == YAFGPU_NODE_TEXTURE_MAPPER && (n.texture < 0 || n.texture >= d->n_textures)) { yafgpu_scene_destroy(s); return fail(-24, "a texture_mapper node refers to a texture that does not exist"); }
 		}
-		for(int i = 0; i < d->n_textures; ++i)
-		{
-			const yafgpu_texture &t = d->textures[i];
-			if(t.width <= 0 || t.height <= 0 || (uint64_t)t.texel_first + (uint64_t)t.width * (uint64_t)t.height > d->n_texels) { yafgpu_scene_destroy(s); return fail(-24, "a texture's texel range lies outside the texel array"); }
-		}
-		const float4 *texels = nullptr;
 		if((rc = upload(s, d->nodes, (size_t)d->n_nodes, &dv.tex.nodes))) { yafgpu_scene_destroy(s); return rc; }
-		if((rc = upload(s, d->textures, (size_t)std::max(d->n_textures, 0), &dv.tex.textures))) { yafgpu_scene_destroy(s); return rc; }
-		if((rc = upload(s, (const float4 *)d->texels, (size_t)d->n_texels, &texels))) { yafgpu_scene_destroy(s); return rc; }
-		dv.tex.texels = texels; dv.tex.n_textures = d->n_textures;
 		if(d->tri_uv && (rc = upload(s, d->tri_uv, nt * 6, &dv.tex.tri_uv))) { yafgpu_scene_destroy(s); return rc; }
 		if(d->tri_orco && (rc = upload(s, d->tri_orco, nt * 9, &dv.tex.tri_orco))) { yafgpu_scene_destroy(s); return rc; }
 		if(s->has_bump)
@@ -994,6 +1080,28 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 	s->n_lights = d->n_lights;
 	s->h_lights.assign(d->lights, d->lights + d->n_lights);
 	for(const yafgpu_light &l : s->h_lights) s->light_mask |= 1u << (uint32_t)l.type;
+	dv.bg.rec = d->background; dv.bg.tab = nullptr;
+	// a texture background is evaluated per escaping ray by the code that comes with the background light: such a scene asks for a
+	// kernel built with that light's bit whether or not the light is there
+	if(d->background.kind == YAFGPU_BACKGROUND_TEXTURE) s->light_mask |= 1u << (uint32_t)YAFGPU_LIGHT_BACKGROUND;
+	if(d->background.kind != YAFGPU_BACKGROUND_NONE && d->background.has_ibl)
+	{	// BackgroundLight::init: the tables are built where the texture evaluator is, once per scene
+		float *tab = nullptr;
+		const size_t n_tab = (size_t)(kBgRows + 1) * kBgRowStride;
+		if(hipMalloc((void **)&tab, n_tab * sizeof(float)) != hipSuccess) { yafgpu_scene_destroy(s); return fail(-100, "no device memory for the background light's tables"); }
+		s->allocs.push_back(tab);
+		s->info.device_bytes += n_tab * sizeof(float);
+		hipError_t e = hipMemset(tab, 0, n_tab * sizeof(float));
+		if(e == hipSuccess)
+		{
+			hipLaunchKernelGGL(bg_rows_kernel, dim3((uint32_t)kBgRows), dim3(kBlock), 0, nullptr, dv, tab);
+			hipLaunchKernelGGL(bg_vdist_kernel, dim3(1), dim3(kBlock), 0, nullptr, tab);
+			e = hipGetLastError();
+		}
+		if(e == hipSuccess) e = hipDeviceSynchronize();
+		if(e != hipSuccess) { yafgpu_scene_destroy(s); return fail(-100, std::string("background light tables: ") + hipGetErrorString(e)); }
+		dv.bg.tab = tab;
+	}
 	s->info.upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
 	(void)t0;
 	*out = s;
@@ -1233,6 +1341,7 @@ static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, const Switc
 	if(sw.general_shade || (record_pass && !sw.record_variant)) return nullptr;
 	const bool needs_recurse = frames > 0 || s->has_volumetric;
 	if(s->has_textures || s->has_aniso) return nullptr;        // the variants are built without shader nodes and without the anisotropic lobe
+	if(s->dev.bg.rec.kind == YAFGPU_BACKGROUND_TEXTURE) return nullptr;      // ... and without the evaluation of a texture background (a record pass's escaping rays ask for it too)
 	for(const ShadeVariant &v : kShadeVariants)
 	{
 		uint32_t mask = 0u, light_mask = 0u; int recurse = 0, lights = 1, multi = 0;

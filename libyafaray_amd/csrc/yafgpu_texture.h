@@ -658,4 +658,188 @@ YG_DEV void mat_resolve(const TexScene &ts, const yafgpu_camera &cam, const yafg
 	if(m.sh_ior >= 0) { const float cur = m.ior_base + stack[m.sh_ior].f; out.ior_squared = cur * cur; }
 }
 
+// ---- backgrounds and the background light (image-based lighting) ----
+//
+//   ConstantBackground      src/background/background_constant.cc:41-49
+//   TextureBackground       src/background/background_texture.cc:33-39 (the host fills rotation / sin_r / cos_r), eval :51-89
+//   angmap__ / spheremap__ / invSpheremap__      include/texture/texture.h:83-94, :111-128, :131-140
+//   Pdf1D                   include/utility/util_sample.h:89-141
+//   BackgroundLight         src/light/light_background.cc (init :78-120, calcFromSample :122-133, calcFromDir :135-146,
+//                           illumSample :162-171, intersect :173-184)
+//
+// The light's tables live in global memory, one fixed-stride row per Pdf1D: row y < kBgRows is u_dist_[y], row kBgRows is v_dist_.
+// A row is (count, integral, 1 / integral, 1 / count), then kBgMaxU floats of func_, then kBgMaxU + 1 floats of cdf_.
+constexpr int kBgRows = 360, kBgMaxU = 720, kBgMinU = 16;      // MAX_VSAMPLES, MAX_USAMPLES, MIN_SAMPLES (light_background.cc:33-35)
+constexpr int kBgFunc = 4, kBgCdf = kBgFunc + kBgMaxU;
+constexpr int kBgRowStride = 1448;                              // 4 + 720 + 721 = 1445, rounded up to 32 bytes
+struct BgScene { yafgpu_background rec; const float *tab; };     // tab: (kBgRows + 1) * kBgRowStride floats, or nullptr without the light
+
+YG_DEV void bg_angmap(V3 p, float &u, float &v)
+{
+	float r = p.x * p.x + p.z * p.z;
+	u = v = 0.f;
+	if(r > 0.f)
+	{
+		const float phi_ratio = (float)(k1Pi * (double)f_acos(p.y));
+		r = phi_ratio / f_sqrt(r);
+		u = p.x * r;
+		v = p.z * r;
+	}
+}
+// (M_2PI, M_1_2PI and M_1_PI are double: the sums and products they stand in are formed in double and narrowed once)
+YG_DEV void bg_spheremap(V3 p, float &u, float &v)
+{
+	const float sqrt_r_phi = p.x * p.x + p.y * p.y;
+	const float sqrt_r_theta = sqrt_r_phi + p.z * p.z;
+	u = 0.f; v = 0.f;
+	if(sqrt_r_phi > 0.f)
+	{
+		float phi_ratio;
+		if(p.y < 0.f) phi_ratio = (float)((k2Pi - (double)f_acos(p.x / f_sqrt(sqrt_r_phi))) * k12Pi);
+		else phi_ratio = (float)((double)f_acos(p.x / f_sqrt(sqrt_r_phi)) * k12Pi);
+		u = 1.f - phi_ratio;
+	}
+	v = (float)((double)1.f - ((double)f_acos(p.z / f_sqrt(sqrt_r_theta)) * k1Pi));
+}
+YG_DEV V3 bg_inv_spheremap(float u, float v)
+{
+	const float theta = (float)((double)v * kPi);
+	const float phi = (float)(-((double)u * k2Pi));
+	const float costheta = f_cos(theta), sintheta = f_sin(theta);
+	const float cosphi = f_cos(phi), sinphi = f_sin(phi);
+	return mk(sintheta * cosphi, sintheta * sinphi, -costheta);
+}
+// Background::eval: what a ray that leaves the scene in direction `dir` picks up
+YG_DEV Col bg_eval(const BgScene &bg, const TexScene &ts, V3 dir)
+{
+	if(bg.rec.kind != YAFGPU_BACKGROUND_TEXTURE) return mkc(bg.rec.color[0], bg.rec.color[1], bg.rec.color[2]);
+	float u = 0.f, v = 0.f;
+	if(bg.rec.projection == 1)
+	{
+		V3 d = dir;
+		d.x = dir.x * bg.rec.cos_r + dir.y * bg.rec.sin_r;
+		d.y = dir.x * -bg.rec.sin_r + dir.y * bg.rec.cos_r;
+		bg_angmap(d, u, v);
+	}
+	else
+	{
+		bg_spheremap(dir, u, v);
+		u = 2.f * u - 1.f;
+		v = 2.f * v - 1.f;
+		u += bg.rec.rotation;
+		if(u > 1.f) u -= 2.f;
+	}
+	const Rgba4 c = tex_get_color(ts, ts.textures[bg.rec.texture], mk(u, v, 0.f));
+	const float min_component = 1.0e-5f;
+	Col ret = mkc(c.r, c.g, c.b);
+	if(ret.r < min_component) ret.r = min_component;
+	if(ret.g < min_component) ret.g = min_component;
+	if(ret.b < min_component) ret.b = min_component;
+	return ret * bg.rec.power;
+}
+
+// Pdf1D's constructor over the n values already in the row's func_ (cumulateStep1DDf__: the running sum in double, in index order)
+YG_DEV void pdf1d_build(float *row, int n)
+{
+	const float *f = row + kBgFunc;
+	float *cdf = row + kBgCdf;
+	double c = 0.0;
+	const double delta = 1.0 / (double)n;
+	cdf[0] = 0.f;
+	for(int i = 1; i < n + 1; ++i)
+	{
+		c += (double)f[i - 1] * delta;
+		cdf[i] = (float)c;
+	}
+	const float integral = (float)c;
+	for(int i = 1; i < n + 1; ++i) cdf[i] /= integral;
+	row[0] = (float)n; row[1] = integral; row[2] = 1.f / integral; row[3] = 1.f / (float)n;
+}
+// Pdf1D::sample.  std::lower_bound over the n + 1 cdf entries as a search of fixed length: ten halvings empty a range of 721, and a
+// comparison that a NaN makes false only shortens the range, so no table can keep a wave in here.
+YG_DEV float pdf1d_sample(const float *row, float u, float &pdf)
+{
+	const int n = (int)row[0];
+	const float *cdf = row + kBgCdf;
+	int first = 0, len = n + 1;
+#pragma unroll 1
+	for(int k = 0; k < 10; ++k)
+	{
+		if(len > 0)
+		{
+			const int half = len >> 1, mid = first + half;
+			if(cdf[mid] < u) { first = mid + 1; len -= half + 1; }
+			else len = half;
+		}
+	}
+	int index = first - 1;
+	if(index < 0) index = 0;
+	if(index > n - 1) index = n - 1;      // (u above cdf_[n] = 1 never comes from the samplers; the reference would read past its arrays)
+	const float delta = (u - cdf[index]) / (cdf[index + 1] - cdf[index]);
+	pdf = row[kBgFunc + index] * row[2];
+	return (float)index + delta;
+}
+YG_DEV float bg_clamp_zero(float val) { return val > 0.f ? 1.f / val : 0.f; }            // clampZero__, light_background.cc:48-52
+YG_DEV float bg_sin_sample(float s) { return f_sin((float)((double)s * kPi)); }            // sinSample__, :54-57
+YG_DEV int bg_clamp_sample(float s, int m) { return max(0, min((int)s, m - 1)); }          // CLAMP_SAMPLE, :42
+// BackgroundLight::calcFromSample with inv = false
+YG_DEV float bglight_calc_from_sample(const BgScene &bg, float s_1, float s_2, float &u, float &v)
+{
+	const float *vd = bg.tab + (size_t)kBgRows * kBgRowStride;
+	float pdf_1 = 0.f, pdf_2 = 0.f;
+	v = pdf1d_sample(vd, s_2, pdf_2);
+	const int iv = bg_clamp_sample(v + 0.4999f, kBgRows);
+	const float *ud = bg.tab + (size_t)iv * kBgRowStride;
+	u = pdf1d_sample(ud, s_1, pdf_1);
+	u *= ud[3];
+	v *= vd[3];
+	return smax(0.000001f, ((pdf_1 * pdf_2) * (float)k12Pi) * bg_clamp_zero(bg_sin_sample(v)));
+}
+// BackgroundLight::calcFromDir with inv = true
+YG_DEV float bglight_calc_from_dir(const BgScene &bg, V3 dir, float &u, float &v)
+{
+	const float *vd = bg.tab + (size_t)kBgRows * kBgRowStride;
+	bg_spheremap(dir, u, v);
+	const int iv = bg_clamp_sample(v * (float)kBgRows + 0.4999f, kBgRows);
+	const float *ud = bg.tab + (size_t)iv * kBgRowStride;
+	const int nu = (int)ud[0];
+	const int iu = bg_clamp_sample(u * (float)nu + 0.4999f, nu);
+	const float pdf_1 = ud[kBgFunc + iu] * ud[2];
+	const float pdf_2 = vd[kBgFunc + iv] * vd[2];
+	return smax(0.000001f, ((float)k2Pi * bg_sin_sample(v)) * bg_clamp_zero(pdf_1 * pdf_2));
+}
+// BackgroundLight::illumSample: never fails; an infinite shadow ray; the colour is the background's in the sampled direction
+YG_DEV bool bglight_illum_sample(const BgScene &bg, const TexScene &ts, float s_1, float s_2, V3 &wi_dir, float &wi_tmax, float &pdf, Col &col)
+{
+	float u = 0.f, v = 0.f;
+	wi_tmax = -1.f;
+	pdf = bglight_calc_from_sample(bg, s_1, s_2, u, v);
+	wi_dir = bg_inv_spheremap(u, v);
+	col = bg_eval(bg, ts, wi_dir);
+	return true;
+}
+// BackgroundLight::intersect: always succeeds; returns the INVERSE pdf.  The colour is the background's at the direction the (u, v) of
+// `dir` maps back to (sic :180), not at `dir` itself.  The reference leaves t alone; -1 makes the shadow ray infinite, as for the sun.
+YG_DEV bool bglight_intersect(const yafgpu_light &l, const BgScene &bg, const TexScene &ts, V3 dir, float &t, Col &col, float &ipdf)
+{
+	float u = 0.f, v = 0.f;
+	const V3 abs_dir = l.abs_intersect ? -dir : dir;
+	ipdf = bglight_calc_from_dir(bg, abs_dir, u, v);
+	col = bg_eval(bg, ts, bg_inv_spheremap(u, v));
+	const float max_value = l.clamp_intersect;      // Rgb::clampProportionalRgb, color.h:412-445
+	if(max_value > 0.f)
+	{
+		const float max_rgb = smax(col.r, smax(col.g, col.b));
+		const float adj = max_value / max_rgb;
+		if(max_rgb > max_value)
+		{
+			if(col.r >= max_rgb) { col.r = max_value; col.g *= adj; col.b *= adj; }
+			else if(col.g >= max_rgb) { col.g = max_value; col.r *= adj; col.b *= adj; }
+			else { col.b = max_value; col.r *= adj; col.g *= adj; }
+		}
+	}
+	t = -1.f;
+	return true;
+}
+
 } // namespace yafgpu

@@ -151,6 +151,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		float ls_pdf;
 		Col l_col = mkc(0.f, 0.f, 0.f);
 		if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN)) sunlight_illum_sample(light, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col);
+		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) bglight_illum_sample(ra.sc.bg, ra.sc.tex, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col);
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPHERE)) { if(!spherelight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col)) return false; }
 		else if(!arealight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf)) return false;
 		r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
@@ -158,14 +159,15 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		{
 			const Col surf_col = mat_eval(mat, dat, sp, wo, r_dir, kAll);
 			const float angle = mat.flat ? 1.f : fabsf(dot(sp.n, r_dir));
-			// the light colour of this half is what illumSample returned (ls.col_, :178-262): col_pdf for the sun, the fixed colour otherwise
+			// the light colour of this half is what illumSample returned (ls.col_, :178-262): col_pdf for the sun, the background in the sampled
+			// direction for the background light, the fixed colour otherwise
 			if(YG_LIGHT_HAS(YAFGPU_LIGHT_SPHERE) && !light_can_intersect(light.type))
 			{	// a light the BSDF half cannot hit takes no MIS weight (:244-258)
 				contrib = ((surf_col * l_col) * angle) / ls_pdf;
 				return true;
 			}
 			const float m_pdf = mat_pdf(mat, dat, sp, wo, r_dir, kMisFlags);
-			const Col ls_col = YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) ? l_col : col3(light.color);
+			const Col ls_col = (YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) || YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) ? l_col : col3(light.color);
 			if(m_pdf > 1e-6f)
 			{
 				const float l_2 = ls_pdf * ls_pdf, m_2 = m_pdf * m_pdf;
@@ -181,9 +183,10 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 	BsdfSample bs; bs.s_1 = s_1; bs.s_2 = s_2; bs.pdf = 0.f; bs.flags = kMisFlags; bs.sampled = kNone;
 	const Col surf_col = mat_sample(mat, dat, sp, wo, r_dir, bs, W);
 	float light_ipdf;
-	// Light::intersect: the sun's also returns its colour (lcol = col_pdf) and t = -1, an infinite shadow ray
+	// Light::intersect: the sun's also returns its colour (lcol = col_pdf) and t = -1, an infinite shadow ray; so does the background light's
 	Col l_col = mkc(0.f, 0.f, 0.f);
 	if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN)) { if(!(bs.pdf > 1e-6f && sunlight_intersect(light, r_dir, r_tmax, l_col, light_ipdf))) return false; }
+	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) { if(!(bs.pdf > 1e-6f && bglight_intersect(light, ra.sc.bg, ra.sc.tex, r_dir, r_tmax, l_col, light_ipdf))) return false; }
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPHERE)) return false;      // (canIntersect() is false: st_dl_eval never asks)
 	else if(!(bs.pdf > 1e-6f && arealight_intersect(light, sp.p, r_dir, r_tmax, light_ipdf))) return false;
 	if(light_ipdf > 1e-6f)
@@ -191,7 +194,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		const float l_pdf = 1.f / light_ipdf;
 		const float l_2 = l_pdf * l_pdf, m_2 = bs.pdf * bs.pdf;
 		const float w = m_2 / (l_2 + m_2);
-		contrib = ((surf_col * (YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) ? l_col : col3(light.color))) * w) * W;
+		contrib = ((surf_col * ((YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) || YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) ? l_col : col3(light.color))) * w) * W;
 	}
 	return true;
 }
@@ -641,7 +644,11 @@ YG_DEV int st_after_closest(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint
 		if(YAFGPU_FEAT_RECURSE && c.level > 0) FREC(c.level - 1, 3).w = got ? ans.y : -1.f;
 		if(!got)
 		{
-			if(rp.has_background && !rp.bg_transp_refract) c.col = c.col + mkc(rp.background[0], rp.background[1], rp.background[2]);
+			if(rp.has_background && !rp.bg_transp_refract)
+			{	// a texture background is a function of the ray's direction (integrator_path_tracer.cc:326-331, integrator_direct_light.cc:172-176)
+				if(YG_LIGHT_HAS(YAFGPU_LIGHT_BACKGROUND) && sc.bg.rec.kind == YAFGPU_BACKGROUND_TEXTURE) c.col = c.col + bg_eval(sc.bg, sc.tex, v3(REC(1)));
+				else c.col = c.col + mkc(rp.background[0], rp.background[1], rp.background[2]);
+			}
 			// (z: the sample's call ordinal and light calls so far belong to the whole sample, see WfArgs::ev_m)
 			REC(19) = make_float4(0.f, 0.f, (a.ev_m > 1 && c.level > 0) ? fbits(ubits(REC(19).z) + (1u << 24)) : 0.f, alpha);      // (a call that ends here is a call too: its ordinal is its own)
 			return W_RETURN;
@@ -686,7 +693,18 @@ YG_DEV int st_after_closest(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint
 		if(!rec) HSET(14, make_float4(0.f, 0.f, 0.f, fbits(pack_dlc(0, 0, 0, 0))));
 		return W_DL_DONE;
 	}
-	if(!got) { ++c.path_i; return W_START_PATH; }                                              // :218 / :259-266
+	if(!got)
+	{	// :218 / :259-266: a segment that escapes after a caustic bounce picks up a background that has a light and shoots caustics
+		if(YG_LIGHT_HAS(YAFGPU_LIGHT_BACKGROUND) && YAFGPU_FEAT_CAUSTIC && A_REPLAY != 1 && c.stage == kStDepth && rp.trace_caustics && c.incl &&
+		   rp.has_background && sc.bg.rec.kind != YAFGPU_BACKGROUND_NONE && sc.bg.rec.has_ibl && sc.bg.rec.shoots_caustic)
+		{
+			const V3 dir = v3(beside ? REC(26) : REC(1));
+			const float4 r12 = HGET(12);
+			HSET(12, f4(c3(r12) + c3(HGET(11)) * bg_eval(sc.bg, sc.tex, dir), r12.w));
+		}
+		++c.path_i;
+		return W_START_PATH;
+	}
 	const float4 r0 = REC(0), r1 = beside ? REC(26) : REC(1);
 	const V3 dir = v3(r1);
 	SurfPt hit;

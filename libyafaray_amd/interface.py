@@ -50,7 +50,7 @@ C_API_SYMBOLS = [
     "yafaray_createInterface", "yafaray_destroyInterface", "yafaray_getLastError", "yafaray_getVersion",
     "yafaray_startScene", "yafaray_startGeometry", "yafaray_endGeometry", "yafaray_getNextFreeId",
     "yafaray_startTriMesh", "yafaray_endTriMesh", "yafaray_addVertex", "yafaray_addNormal", "yafaray_addTriangle",
-    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_addTriangles",
+    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_addTriangles",
     "yafaray_startTriMeshPtr", "yafaray_addVertexWithOrco", "yafaray_addUv", "yafaray_addTriangleWithUv",
     "yafaray_startCurveMesh", "yafaray_endCurveMesh", "yafaray_addInstance",
     "yafaray_paramsSetColorArray", "yafaray_paramsSetMatrix", "yafaray_paramsSetMatrixD", "yafaray_setInputColorSpace",
@@ -100,6 +100,7 @@ def load():
         "yafaray_addTriangle": (ci, [vp, ci, ci, ci, vp]), "yafaray_smoothMesh": (ci, [vp, C.c_uint, cd]),
         "yafaray_getMeshCornerNormals": (ci, [vp, C.c_uint, C.POINTER(cf), ci]),
         "yafaray_getLights": (ci, [vp, vp, ci]),
+        "yafaray_getBackground": (ci, [vp, cp, vp]),
         "yafaray_addTriangles": (ci, [vp, ci, C.POINTER(cf), ci, C.POINTER(ci), vp]),
         "yafaray_startTriMeshPtr": (ci, [vp, C.POINTER(C.c_uint), ci, ci, ci, ci, ci, ci]),
         "yafaray_addVertexWithOrco": (ci, [vp, cd, cd, cd, cd, cd, cd]), "yafaray_addUv": (ci, [vp, cf, cf]),
@@ -327,6 +328,14 @@ class Interface:
         if n > 0:
             self._L.yafaray_getLights(self._h, out.ctypes.data_as(C.c_void_p), n)
         return out
+
+    def getBackground(self, name):
+        """the yafgpu_background record (include/yafgpu.h) createBackground made under `name`, as a dict"""
+        out = np.zeros(12, dtype=np.float32)
+        self._ok(self._L.yafaray_getBackground(self._h, _b(name), out.ctypes.data_as(C.c_void_p)), "getBackground")
+        i = out.view(np.int32)
+        return {"kind": int(i[0]), "color": out[1:4].copy(), "power": out[4], "texture": int(i[5]), "projection": int(i[6]),
+                "rotation": out[7], "sin_r": out[8], "cos_r": out[9], "has_ibl": int(i[10]), "shoots_caustic": int(i[11])}
 
     # -- params
     def paramsSetPoint(self, name, x, y, z):

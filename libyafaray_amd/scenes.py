@@ -129,7 +129,11 @@ def load_scene(yi, scene, render):
     bg = render.get("background")
     if bg is not None:
         yi.paramsClearAll()
-        yi.paramsSet({"type": "constant", "color": _color(bg)})
+        if isinstance(bg, dict):
+            # createBackground's own parameters (type constant | textureback, ibl, ...); a textureback names one of scene["textures"]
+            yi.paramsSet({k: (_color(v) if k in _COLOR_KEYS else v) for k, v in bg.items()})
+        else:
+            yi.paramsSet({"type": "constant", "color": _color(bg)})
         yi.createBackground("world_background")
     yi.paramsClearAll()
     integ = {"type": render.get("integrator", "pathtracing")}
