@@ -91,6 +91,9 @@ int yafaray_getLights(yafaray_interface_t *yi, void *out, int max_lights);
 /* extension (test support): the yafgpu_background record (include/yafgpu.h, 12 words) createBackground made under `name`, as the
  * device scene would get it; false when there is no such background */
 yafaray_bool_t yafaray_getBackground(yafaray_interface_t *yi, const char *name, void *out);
+/* extension (test support): the ambient occlusion settings createIntegrator parsed for the integrator `name` (do_AO, AO_samples,
+ * AO_distance narrowed to float, AO_color as three floats); any out pointer may be NULL; false when there is no such integrator */
+yafaray_bool_t yafaray_getIntegratorAO(yafaray_interface_t *yi, const char *name, int *do_ao, int *samples, float *distance, float *color3);
 /* extension (not in the reference): bulk form of addVertex/addTriangle for large meshes;
  * verts = n_verts*3 floats, indices = n_tris*3 ints, one material for all triangles */
 yafaray_bool_t yafaray_addTriangles(yafaray_interface_t *yi, int n_verts, const float *verts, int n_tris, const int *indices,

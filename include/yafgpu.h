@@ -266,6 +266,12 @@ typedef struct yafgpu_render_params
 	int32_t trace_caustics;        /* PathIntegrator::trace_caustics_ (integrator_path_tracer.cc:85): caustic_type "path" — the factory's default when the
 	                                  parameter is absent — or "both": after a bounce through a specular, glossy or filter lobe the next vertex shows its
 	                                  lights and adds its emission (:252-253, :290).  0 = caustic_type "none" */
+	/* Ambient occlusion of the direct lighting integrator (DirectLightIntegrator::integrate, integrator_direct_light.cc:145;
+	   MonteCarloIntegrator::sampleAmbientOcclusion, integrator_montecarlo.cc:1030-1088): at every hit with a diffuse component,
+	   ao_samples shadow rays of length ao_distance in directions drawn from the material's BSDF.  Read only where integrator is
+	   YAFGPU_INTEGRATOR_DIRECT; ao_samples in [1, 4095], and at most 254 lights beside it (yafgpu_wavefront.h, pack_dlc) */
+	int32_t do_ao, ao_samples;
+	float ao_distance, ao_color[3];
 } yafgpu_render_params;
 
 /* Scene::setAntialiasing (scene.cc:761-778; defaults environment.cc:682-695) */

@@ -68,6 +68,12 @@ struct IntegratorCfg
 	bool no_recursive = false, bg_transp = false, bg_transp_refract = false, transp_shad = false;
 	bool trace_caustics = false;     // PathIntegrator: caustic_type_ is Path unless the parameter says "none" (integrator_path_tracer.cc:36, :85, :382-387)
 	int shadow_depth = 5;            // integrator_path_tracer.cc:352, integrator_direct_light.cc:201
+	// ambient occlusion (integrator_direct_light.cc:200-207,220-223; integrator_path_tracer.cc:355-358,375-378 reads the same four, for
+	// render passes this path does not have): only directlighting's integrate() uses it (:145)
+	bool do_ao = false;
+	int ao_samples = 32;
+	float ao_distance = 1.f;         // read as double, kept as float (ao_dist_)
+	float ao_color[3] = {1.f, 1.f, 1.f};
 };
 
 struct CameraCfg { yafgpu_camera cam; };
@@ -1159,6 +1165,17 @@ yafaray_bool_t yafaray_getBackground(yafaray_interface_t *yi, const char *name, 
 	if(out) std::memcpy(out, &it->second->b.rec, sizeof(yafgpu_background));
 	return 1;
 }
+yafaray_bool_t yafaray_getIntegratorAO(yafaray_interface_t *yi, const char *name, int *do_ao, int *samples, float *distance, float *color3)
+{
+	auto it = name ? yi->integrators.find(name) : yi->integrators.end();
+	if(it == yi->integrators.end()) return fail(yi, "getIntegratorAO: no such integrator");
+	const IntegratorCfg &c = it->second->c;
+	if(do_ao) *do_ao = c.do_ao ? 1 : 0;
+	if(samples) *samples = c.ao_samples;
+	if(distance) *distance = c.ao_distance;
+	if(color3) for(int k = 0; k < 3; ++k) color3[k] = c.ao_color[k];
+	return 1;
+}
 yafaray_bool_t yafaray_getMeshCornerNormals(yafaray_interface_t *yi, unsigned int id, float *out, int n_floats)
 {
 	auto it = yi->meshes.find(id);
@@ -1479,7 +1496,15 @@ yafaray_integrator_t *yafaray_createIntegrator(yafaray_interface_t *yi, const ch
 		p.get("raydepth", c.raydepth); p.get("shadowDepth", c.shadow_depth); p.get("transpShad", transp_shad); p.get("do_AO", do_ao);
 		p.get("bg_transp", c.bg_transp); p.get("bg_transp_refract", c.bg_transp_refract);
 		c.transp_shad = transp_shad;     // checked against the materials at render time (TriKdTree::intersectTs, row K3)
-		if(do_ao) { fail(yi, "createIntegrator: ambient occlusion is not supported by the GPU path"); return nullptr; }
+		{	// integrator_direct_light.cc:204-207,220-223 / integrator_path_tracer.cc:355-358,375-378
+			double ao_dist = 1.0;
+			p.get("AO_samples", c.ao_samples); p.get("AO_distance", ao_dist); p.getColor("AO_color", c.ao_color);
+			c.do_ao = do_ao; c.ao_distance = (float)ao_dist;
+			// sampleAmbientOcclusion divides by the sample count (integrator_montecarlo.cc:1087); the device path counts the samples of an
+			// estimate in 12 bits.  (pathtracing never samples it, but a sample count no integrator could use is refused all the same.)
+			if(do_ao && c.ao_samples < 1) { fail(yi, "createIntegrator: AO_samples must be at least 1 (the ambient occlusion estimate is divided by it)"); return nullptr; }
+			if(do_ao && c.ao_samples > 4095) { fail(yi, "createIntegrator: AO_samples above 4095 are not supported by the GPU path (it counts the samples of an estimate in 12 bits)"); return nullptr; }
+		}
 		if(type == "pathtracing")
 		{	// PathIntegrator::factory, integrator_path_tracer.cc:349-422
 			p.get("path_samples", c.path_samples); p.get("bounces", c.bounces);
@@ -1619,6 +1644,12 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 	rp.path_samples = ic.path_samples; rp.bounces = ic.bounces; rp.rr_min_bounces = ic.rr_min_bounces;
 	rp.no_recursive = ic.no_recursive; rp.bg_transp = ic.bg_transp; rp.bg_transp_refract = ic.bg_transp_refract;
 	rp.trace_caustics = (ic.type == "pathtracing" && ic.trace_caustics) ? 1 : 0;
+	// ambient occlusion: DirectLightIntegrator::integrate alone samples it (integrator_direct_light.cc:145)
+	rp.do_ao = (ic.type == "directlighting" && ic.do_ao) ? 1 : 0;
+	rp.ao_samples = ic.ao_samples; rp.ao_distance = ic.ao_distance;
+	for(int k = 0; k < 3; ++k) rp.ao_color[k] = ic.ao_color[k];
+	if(rp.do_ao && yi->light_order.size() > 254)
+		return fail(yi, "render: do_AO with more than 254 lights is not supported by the GPU path (ambient occlusion takes a light's place in an 8-bit count)");
 	rp.width = width; rp.height = height; rp.xstart = xstart; rp.ystart = ystart;
 	rp.aa_minsamples = aa_samples; rp.aa_pixelwidth = filt_sz; rp.filter_type = filter_type; rp.tile_size = tile_size;
 	rp.base_sampling_offset = (uint32_t)base_offset + (uint32_t)node * 100000u;   // imagefilm.h:124

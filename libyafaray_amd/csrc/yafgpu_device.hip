@@ -617,6 +617,33 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			for(int k = 0; k < min(n_out, kBgCdf + kBgMaxU + 1); ++k) o[k] = row[k];
 			break;
 		}
+		case 26:
+		{	// ao_candidate, one sample of sampleAmbientOcclusion: in material index, p, n, ng, wo, s_1, s_2, shadow bias auto (0 / 1), shadow bias,
+			// AO distance, AO colour, then for a material with shader nodes or bump the triangle (as bits) and its barycentrics u, v
+			// -> wanted, ray direction, tmin, tmax, contribution, emit() * pdf
+			if(n_in < 21 || n_out < 12) break;
+			const uint32_t k = __float_as_uint(x[0]);
+			if(k >= (uint32_t)sc.n_mats) break;
+			SurfPt sp; make_sp(mk(x[1], x[2], x[3]), mk(x[4], x[5], x[6]), mk(x[7], x[8], x[9]), (int)k, sp);
+			const V3 wo = mk(x[10], x[11], x[12]);
+			yafgpu_material m_tmp;
+			const yafgpu_material *mp = &sc.mats[k];
+			if(n_in >= 24 && (mp->n_nodes > 0 || mp->n_bump > 0))
+			{	// the vertex as st_after_closest makes it: the bumped frame, then the material its nodes resolve to there
+				const uint32_t tri = __float_as_uint(x[21]);
+				if(tri >= (uint32_t)sc.n_tris) break;
+				wf_bump_hit(sc, sp, (int)tri, x[22], x[23]);
+				mp = &wf_mat_hit(sc, sp, (int)tri, x[22], x[23], m_tmp);
+			}
+			BsdfDat d;
+			const uint32_t fl = mat_init_bsdf(*mp, d);
+			AoParams ao; ao.bias_auto = x[15] != 0.f ? 1 : 0; ao.shadow_bias = x[16]; ao.dist = x[17]; ao.col = mkc(x[18], x[19], x[20]);
+			V3 dir; float tmin, tmax; Col contrib, emit;
+			const bool go = ao_candidate(ao, x[13], x[14], sp, *mp, d, fl, wo, true, dir, tmin, tmax, contrib, emit);
+			o[0] = go ? 1.f : 0.f; o[1] = dir.x; o[2] = dir.y; o[3] = dir.z; o[4] = tmin; o[5] = tmax;
+			o[6] = contrib.r; o[7] = contrib.g; o[8] = contrib.b; o[9] = emit.r; o[10] = emit.g; o[11] = emit.b;
+			break;
+		}
 		default: break;
 	}
 }
@@ -1217,6 +1244,12 @@ static int validate(const yafgpu_scene *s, const yafgpu_render_params *rp)
 	for(const yafgpu_light &l : s->h_lights)
 		if(!light_is_dirac(l.type) && std::ceil((float)l.samples * rp->aa_light_sample_multiplier) > 4095.f)
 			return fail(-19, "a sampled light (area, sun, sphere) with more than 4095 samples per estimate (samples x AA light-sample multiplier): the device path counts them in 12 bits");
+	if(rp->do_ao && rp->integrator == YAFGPU_INTEGRATOR_DIRECT)
+	{	// ambient occlusion rides the light estimate as the light after the last one (yafgpu_wavefront.h, ao_candidate)
+		if(rp->ao_samples < 1) return fail(-19, "ao_samples < 1: the ambient occlusion estimate is divided by its sample count");
+		if(rp->ao_samples > 4095) return fail(-19, "ao_samples > 4095: the device path counts the samples of an estimate in 12 bits");
+		if(s->h_lights.size() > 254) return fail(-19, "ambient occlusion with more than 254 lights: the device path counts the lights of an estimate, ambient occlusion among them, in 8 bits");
+	}
 	return 0;
 }
 
@@ -1336,9 +1369,10 @@ static const ShadeVariant kShadeVariants[] = {
 	{"glossy_rec", yafgpu_shade_glossy_rec_describe, yafgpu_shade_glossy_rec_kernel, yafgpu_shade_glossy_rec_launch},
 	{"full", yafgpu_shade_full_describe, yafgpu_shade_full_kernel, yafgpu_shade_full_launch},      // everything but shader nodes
 };
-static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, const Switches &sw, int frames, bool record_pass, bool want_multi)
+static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, const Switches &sw, int frames, bool record_pass, bool want_multi, bool ao)
 {
 	if(sw.general_shade || (record_pass && !sw.record_variant)) return nullptr;
+	if(ao) return nullptr;                                     // ... and without ambient occlusion (YAFGPU_FEAT_AO)
 	const bool needs_recurse = frames > 0 || s->has_volumetric;
 	if(s->has_textures || s->has_aniso) return nullptr;        // the variants are built without shader nodes and without the anisotropic lobe
 	if(s->dev.bg.rec.kind == YAFGPU_BACKGROUND_TEXTURE) return nullptr;      // ... and without the evaluation of a texture background (a record pass's escaping rays ask for it too)
@@ -1533,6 +1567,9 @@ static int plan_pass(yafgpu_scene *s, const yafgpu_render_params &rp, const Swit
 		const int r = light_pairs(l, rp.aa_light_sample_multiplier);
 		r_all += r; r_one = std::max(r_one, r);
 	}
+	// ambient occlusion (direct lighting): one more light, a shadow park per sample (two samples per park with WfArgs::multi)
+	const bool ao = rp.do_ao != 0 && rp.integrator == YAFGPU_INTEGRATOR_DIRECT;
+	if(ao) r_all += std::max(rp.ao_samples, 1);
 	// two MIS pairs per park (WfArgs::multi): not with transparent shadows (their filter products are kept per pair), not with recursion frames —
 	// and only where a light estimate can have a second pair at all: the kernels that carry it are a little slower on the first
 	p.want_multi = !p.transp && p.frames == 0 && sw.multi_pair && r_all > 1;
@@ -1545,14 +1582,14 @@ static int plan_pass(yafgpu_scene *s, const yafgpu_render_params &rp, const Swit
 	// vertex, for st_extend / st_start_path after the answers, and the pwo a segment that sampled nothing keeps is always stored (vtx_set's keep).
 	// A record pass on a light-estimate kernel stores everything too (vtx_flush).
 	p.vtx_keep = (sw.vertex_lds && rp.path_samples <= 1 && r_all <= 1 && p.frames == 0 && !s->has_textures && !s->has_bump && !rp.trace_caustics) ? 0x1cu : 0xffu;
-	p.shade = pick_shade_variant(s, sw, p.frames, false, p.want_multi);
+	p.shade = pick_shade_variant(s, sw, p.frames, false, p.want_multi, ao);
 	if(!p.shade && p.want_multi)
 	{	// no kernel with the second pair for these materials: the one without it rather than the general kernel
-		p.shade = pick_shade_variant(s, sw, p.frames, false, false);
+		p.shade = pick_shade_variant(s, sw, p.frames, false, false, ao);
 		if(p.shade) p.want_multi = false;
 	}
 	// a record pass runs its own, smaller program where one was built for the scene's materials (else the pass's kernel, which branches on WfArgs::replay)
-	p.record = rpl.replay ? pick_shade_variant(s, sw, p.frames, true, false) : nullptr;
+	p.record = rpl.replay ? pick_shade_variant(s, sw, p.frames, true, false, false) : nullptr;
 	if(sw.verbose) std::fprintf(stderr, "[yafgpu] shading kernel: %s (materials 0x%x, frames %d), serial replay: %s\n", p.shade ? p.shade->name : "general", s->mat_mask, p.frames,
 	                            rpl.replay ? (rpl.replay_lights ? (rpl.need_rr ? "roulette + light counter" : "light counter") : "roulette") : "off");
 	p.iters = 1 + r_all;

@@ -5,9 +5,11 @@
 // that use a subset run a kernel compiled for that subset: this file is compiled once per variant with
 //
 //   -DYAFGPU_VARIANT_NAME=<name>  -DYAFGPU_MAT_MASK=<bit per YAFGPU_MAT_* handled>  -DYAFGPU_LIGHT_MASK=<bit per YAFGPU_LIGHT_* handled>
-//   -DYAFGPU_FEAT_RECURSE=<0|1>  [-DYAFGPU_FEAT_LIGHTS=0]  [-DYAFGPU_FEAT_MULTI=0]
+//   -DYAFGPU_FEAT_RECURSE=<0|1>  [-DYAFGPU_FEAT_LIGHTS=0]  [-DYAFGPU_FEAT_MULTI=0]  [-DYAFGPU_FEAT_AO=0]
 //
 // (FEAT_LIGHTS=0: the program of a serial-state replay's RECORD pass — no light estimate, the vertex of a resume in registers)
+// (FEAT_AO: ambient occlusion.  No variant has it — pick_shade_variant sends a render with do_AO to the main unit's general kernel — so
+// the flag is 0 here whether or not the command line says so; asking for 1 is an error)
 //
 // and includes the main unit with everything but wf_shade and what it calls compiled out.  All of its symbols live in
 // their own namespace (the macro below renames `yafgpu`), so the variants and the main unit link into one library; the
@@ -17,6 +19,11 @@
 #endif
 #ifndef YAFGPU_LIGHT_MASK
 #error "compile with -DYAFGPU_LIGHT_MASK=... (the light types the variant handles)"
+#endif
+#ifndef YAFGPU_FEAT_AO
+#define YAFGPU_FEAT_AO 0
+#elif YAFGPU_FEAT_AO
+#error "a shade variant with ambient occlusion: pick_shade_variant (yafgpu_device.hip) assumes that none has it"
 #endif
 #define YAFGPU_VARIANT_TU 1
 #define YG_CAT2(a, b) a##b

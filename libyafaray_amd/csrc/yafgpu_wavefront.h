@@ -605,6 +605,61 @@ YG_DEV DivState wf_div(const WfArgs &a, uint32_t slot, int level)
 }
 YG_DEV float add_mod_1(float x, float y) { const float t = x + y; return t > 1 ? t - 1.f : t; }      // util_sample.h:183-187
 
+// Ambient occlusion of the direct lighting integrator (integrator_direct_light.cc:145; MonteCarloIntegrator::sampleAmbientOcclusion,
+// integrator_montecarlo.cc:1030-1088).  It rides the light estimate as a pseudo-light at index n_lights, taken after the last real
+// light: one half only, its own sample count and offsets, its samples' contributions added to ccol (record 15) in sample order.  A
+// kernel built with 0 serves renders without it (every unit of yafgpu_shade_variant.hip).
+#ifndef YAFGPU_FEAT_AO
+#define YAFGPU_FEAT_AO 1
+#endif
+YG_DEV bool ao_enabled(const yafgpu_render_params &rp) { return YAFGPU_FEAT_AO && rp.do_ao && rp.integrator == YAFGPU_INTEGRATOR_DIRECT; }
+YG_DEV int ao_n_samples(const yafgpu_render_params &rp, int division)      // :1040-1041 (no aa_light_sample_multiplier here)
+{
+	int n = rp.ao_samples;
+	if(division > 1) n = max(1, n / division);
+	return n;
+}
+// (s_1, s_2) of AO sample `is`: Halton(2) / Halton(3) restarted at offs - 1 (:1043-1049, no per-light offset), rotated under trajectory splitting (:1056-1060)
+YG_DEV void ao_samples(const yafgpu_render_params &rp, int is, const DivState &dv, uint32_t pixel_sample, uint32_t sampling_offs, float &s_1, float &s_2)
+{
+	const int n = ao_n_samples(rp, dv.division);
+	const uint32_t offs = (uint32_t)n * pixel_sample + sampling_offs;
+	Halton hal_2, hal_3;
+	hal_2.init(2u); hal_3.init(3u);
+	hal_2.set_start(offs - 1u); hal_3.set_start(offs - 1u);
+	s_1 = 0.f; s_2 = 0.f;
+	for(int k = 0; k <= is; ++k) { s_1 = hal_2.next(); s_2 = hal_3.next(); }   // the incremental sequence, replayed
+	if(dv.division > 1) { s_1 = add_mod_1(s_1, dv.dc_1); s_2 = add_mod_1(s_2, dv.dc_2); }
+}
+// what of the integrator and the scene one AO sample reads
+struct AoParams { int bias_auto; float shadow_bias, dist; Col col; };
+YG_DEV AoParams ao_params(const RenderArgs &ra)
+{
+	AoParams ao; ao.bias_auto = ra.rp.shadow_bias_auto; ao.shadow_bias = ra.shadow_bias; ao.dist = ra.rp.ao_distance;
+	ao.col = mkc(ra.rp.ao_color[0], ra.rp.ao_color[1], ra.rp.ao_color[2]);
+	return ao;
+}
+// One sample of sampleAmbientOcclusion's loop (:1051-1085), the AO analogue of dl_candidate: the shadow ray (tmin is the SHADOW bias,
+// tmax the AO distance), the radiance it carries if unoccluded — ao_col * surf_col * cos * w, left to right, with the cosine that w
+// already holds once more, as the reference has it (:1081-1083) — and emit() * pdf, which the reference adds for an emitting
+// material whatever the shadow ray says (:1072-1075).  Returns whether the ray is wanted: a contribution of exactly zero (a sample
+// that chose no lobe leaves w = 0, a direction below the surface returns black) needs no answer, and goes without a ray.
+YG_DEV bool ao_candidate(const AoParams &ao, float s_1, float s_2, const SurfPt &sp, const yafgpu_material &mat, const BsdfDat &dat, uint32_t bsdfs, V3 wo,
+                         bool include_lights, V3 &r_dir, float &r_tmin, float &r_tmax, Col &contrib, Col &emit)
+{
+	r_tmin = ao.bias_auto ? ao.shadow_bias * smax(1.f, length(sp.p)) : ao.shadow_bias;
+	r_tmax = ao.dist;
+	float w = 0.f;
+	BsdfSample bs; bs.s_1 = s_1; bs.s_2 = s_2; bs.pdf = 0.f; bs.flags = kGlossy | kDiffuse | kReflect; bs.sampled = kNone;
+	r_dir = mk(0.f, 0.f, 0.f);
+	const Col surf_col = mat_sample(mat, dat, sp, wo, r_dir, bs, w);
+	emit = mkc(0.f, 0.f, 0.f);
+	if(bsdfs & kEmit) emit = mat_emit(mat, sp, wo, include_lights) * bs.pdf;
+	const float cs = fabsf(dot(sp.n, r_dir));
+	contrib = ((ao.col * surf_col) * cs) * w;
+	return !is_black(contrib);
+}
+
 // where the answer of the closest-hit query a path is parked on lives in the record pass's cache: from what its control word and
 // record 19 hold at the park — (call, path sample, segment); a level's own ray (segment 0) belongs to the call about to start
 YG_DEV uint32_t wf_hit_key(const WfArgs &a, uint32_t slot, uint32_t ctl, uint32_t z19)
@@ -683,9 +738,10 @@ YG_DEV int st_after_closest(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint
 		const bool rec = A_REPLAY == 1;
 		if(!rec) hot_zero_tot(a, slot, h);
 		c.path_i = 0; c.depth = 0;
-		if((bsdfs0 & kDiffuse) && sc.n_lights > 0 && A_REPLAY != 1)      // (a record pass only follows the paths)
+		const bool ao = ao_enabled(rp);      // the pseudo-light after the last light (ao_candidate): it runs in a scene without lights too
+		if((bsdfs0 & kDiffuse) && (sc.n_lights > 0 || ao) && A_REPLAY != 1)      // (a record pass only follows the paths)
 		{
-			HSET(14, make_float4(0.f, 0.f, 0.f, fbits(pack_dlc(0, sc.n_lights, 0, 0))));
+			HSET(14, make_float4(0.f, 0.f, 0.f, fbits(pack_dlc(0, sc.n_lights + (ao ? 1 : 0), 0, 0))));
 			hot_zero_acc(a, slot, h);
 			c.dl_on_sp0 = 1;
 			return W_DL_NEXT;
@@ -766,7 +822,7 @@ YG_DEV int st_after_shadow(const WfArgs &a, uint32_t slot, Hot &h, uint2 verdict
 	const uint32_t w = ubits(r14.w);
 	const int li = (int)(w & 0xffu), l_end = (int)((w >> 8) & 0xffu), mask = second ? mask2 : (int)((w >> 16) & 0x3u), is = (int)(w >> 20);
 	if(second) { const float4 r29 = REC(29); r14.x = r29.x; r14.y = r29.y; r14.z = r29.z; }
-	const bool dirac = light_is_dirac(sc.lights[li].type);
+	const bool dirac = !(YAFGPU_FEAT_AO && li >= sc.n_lights) && light_is_dirac(sc.lights[li].type);      // (ambient occlusion adds to ccol, like a sampled light's first half)
 	// transparent shadows (integrator_montecarlo.cc:114,182,309): what an unblocked ray picked up on its way scales the
 	// light.  (The reference scales the light colour before forming the contribution, here the parked contribution is
 	// scaled: same product, other rounding order.)
@@ -803,6 +859,19 @@ YG_DEV int st_dl_next(const WfArgs &a, uint32_t slot, Hot &h, int level)
 	const int l_end = (int)((w >> 8) & 0xffu);
 	while(li < l_end)
 	{
+		if(YAFGPU_FEAT_AO && li >= sc.n_lights)
+		{	// ambient occlusion, after the last light: its samples are in ccol; col / (float)n (integrator_montecarlo.cc:1087) waits in record 16
+			// for st_dl_done, which adds it to the level's colour AFTER the lights' total (integrator_direct_light.cc:132, :145)
+			const int n = ao_n_samples(ra.rp, division);
+			if(is < n)
+			{
+				HSET(14, make_float4(0.f, 0.f, 0.f, fbits(pack_dlc(li, l_end, 0, is))));
+				return W_DL_EVAL;
+			}
+			HSET(16, f4(c3(HGET(15)) / (float)n, 0.f));
+			is = 0; ++li;
+			continue;
+		}
 		const yafgpu_light &light = sc.lights[li];
 		const bool dirac = light_is_dirac(light.type);
 		const int n = dirac ? 1 : dl_area_samples(ra, light, division);
@@ -837,7 +906,33 @@ YG_DEV int st_dl_eval(const WfArgs &a, uint32_t slot, Hot &h, const Ctl &c, uint
 	wf_frame_parked(a, slot, c.dl_on_sp0 ? 0 : 1, sp);
 	yafgpu_material mat_tmp;
 	const yafgpu_material &mat = wf_mat_parked(a, slot, c.dl_on_sp0 ? 0 : 1, sp, mat_tmp);
-	BsdfDat dat; mat_init_bsdf(mat, dat);
+	BsdfDat dat;
+	const uint32_t bsdfs = mat_init_bsdf(mat, dat); (void)bsdfs;
+	if(YAFGPU_FEAT_AO && li >= sc.n_lights)
+	{	// one sample of sampleAmbientOcclusion (ao_candidate): the first ray of the pair, no second half.  It looks neither at cast_shadows
+		// nor at the material's receive_shadows (integrator_montecarlo.cc:1077)
+		float s_1, s_2;
+		ao_samples(ra.rp, is, wf_div(a, slot, c.level), pixel_sample, sampling_offs, s_1, s_2);
+		V3 d; float tmin, tmax; Col contrib, emit;
+		const bool go = ao_candidate(ao_params(ra), s_1, s_2, sp, mat, dat, bsdfs, wo, c.incl != 0, d, tmin, tmax, contrib, emit);
+		if(second)
+		{	// (an emitting material's emit() * pdf goes straight into ccol: out of order before the first pair's answer)
+			if(!go || (bsdfs & kEmit)) return W_DL_NEXT;
+			REC(28) = f4(d, tmax); REC(29) = f4(contrib, tmin);
+			out_mask = 1;
+			return W_PARK_SHADOW;
+		}
+		if(bsdfs & kEmit) HSET(15, f4(c3(HGET(15)) + emit, 0.f));      // :1072-1075, before this sample's own contribution
+		if(go)
+		{
+			REC(0) = f4(sp.p, tmin); REC(1) = f4(d, tmax);
+			HSET(14, f4(contrib, fbits(pack_dlc(li, l_end, 1, is))));
+			out_mask = 1;
+			return W_PARK_SHADOW;
+		}
+		HSET(14, make_float4(0.f, 0.f, 0.f, fbits(pack_dlc(li, l_end, 0, is + 1))));
+		return W_DL_NEXT;
+	}
 	const yafgpu_light &light = sc.lights[li];
 	const bool dirac = light_is_dirac(light.type), bsdf_half = light_can_intersect(light.type);
 	const bool cast_shadows = light.cast_shadows && mat.receive_shadows;
@@ -891,6 +986,11 @@ YG_DEV int st_dl_done(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, bool besid
 	{
 		const uint32_t bsdfs0 = ubits(VGET_W(5));
 		if(bsdfs0 & kDiffuse) c.col = c.col + total;                                            // :156
+		if(YAFGPU_FEAT_AO && l_end > sc.n_lights)
+		{	// ambient occlusion ran (st_dl_next left its estimate in record 16): (col + direct) + ao, integrator_direct_light.cc:132-145
+			c.col = c.col + c3(HGET(16));
+			hot_zero_acc(a, slot, h);
+		}
 		const uint32_t path_flags = rp.no_recursive ? (uint32_t)kAll : (uint32_t)kDiffuse;
 		if(rp.integrator != YAFGPU_INTEGRATOR_PATH || !(bsdfs0 & path_flags)) return W_RECURSE;
 		c.path_i = 0;
@@ -1424,7 +1524,8 @@ YG_DEV int wf_advance(const WfArgs &a, uint32_t slot, uint32_t pixel_sample, uin
 			const uint32_t w14 = ubits(h.r14.w);
 			const int li = (int)(w14 & 0xffu), l_end = (int)((w14 >> 8) & 0xffu), is = (int)(w14 >> 20);
 			bool more = li + 1 < l_end;
-			if(!more && li < l_end)
+			if(YAFGPU_FEAT_AO && !more && li < l_end && li >= a.ra.sc.n_lights) more = is + 1 < ao_n_samples(a.ra.rp, wf_div(a, slot, c.level).division);
+			else if(!more && li < l_end)
 			{
 				const yafgpu_light &light = a.ra.sc.lights[li];
 				more = !light_is_dirac(light.type) && is + 1 < dl_area_samples(a.ra, light, wf_div(a, slot, c.level).division);
@@ -1480,8 +1581,13 @@ YG_DEV int wf_advance(const WfArgs &a, uint32_t slot, uint32_t pixel_sample, uin
 						if(YAFGPU_FEAT_MULTI && a.multi)
 						{	// the pair st_dl_next would name after this one: the light's next sample, or the next light's first
 							const int li = (int)(w_last & 0xffu), l_end = (int)((w_last >> 8) & 0xffu), is = (int)(w_last >> 20);
-							const yafgpu_light &light = a.ra.sc.lights[li];
-							const int n = light_is_dirac(light.type) ? 1 : dl_area_samples(a.ra, light, wf_div(a, slot, c.level).division);
+							int n;
+							if(YAFGPU_FEAT_AO && li >= a.ra.sc.n_lights) n = ao_n_samples(a.ra.rp, wf_div(a, slot, c.level).division);
+							else
+							{
+								const yafgpu_light &light = a.ra.sc.lights[li];
+								n = light_is_dirac(light.type) ? 1 : dl_area_samples(a.ra, light, wf_div(a, slot, c.level).division);
+							}
 							const bool same = is + 1 < n;
 							if(same || li + 1 < l_end) { second = true; w2 = pack_dlc(same ? li : li + 1, l_end, 0, same ? is + 1 : 0); where = W_DL_EVAL; }
 						}

@@ -50,7 +50,7 @@ C_API_SYMBOLS = [
     "yafaray_createInterface", "yafaray_destroyInterface", "yafaray_getLastError", "yafaray_getVersion",
     "yafaray_startScene", "yafaray_startGeometry", "yafaray_endGeometry", "yafaray_getNextFreeId",
     "yafaray_startTriMesh", "yafaray_endTriMesh", "yafaray_addVertex", "yafaray_addNormal", "yafaray_addTriangle",
-    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_addTriangles",
+    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getIntegratorAO", "yafaray_addTriangles",
     "yafaray_startTriMeshPtr", "yafaray_addVertexWithOrco", "yafaray_addUv", "yafaray_addTriangleWithUv",
     "yafaray_startCurveMesh", "yafaray_endCurveMesh", "yafaray_addInstance",
     "yafaray_paramsSetColorArray", "yafaray_paramsSetMatrix", "yafaray_paramsSetMatrixD", "yafaray_setInputColorSpace",
@@ -101,6 +101,7 @@ def load():
         "yafaray_getMeshCornerNormals": (ci, [vp, C.c_uint, C.POINTER(cf), ci]),
         "yafaray_getLights": (ci, [vp, vp, ci]),
         "yafaray_getBackground": (ci, [vp, cp, vp]),
+        "yafaray_getIntegratorAO": (ci, [vp, cp, C.POINTER(ci), C.POINTER(ci), C.POINTER(cf), C.POINTER(cf)]),
         "yafaray_addTriangles": (ci, [vp, ci, C.POINTER(cf), ci, C.POINTER(ci), vp]),
         "yafaray_startTriMeshPtr": (ci, [vp, C.POINTER(C.c_uint), ci, ci, ci, ci, ci, ci]),
         "yafaray_addVertexWithOrco": (ci, [vp, cd, cd, cd, cd, cd, cd]), "yafaray_addUv": (ci, [vp, cf, cf]),
@@ -336,6 +337,14 @@ class Interface:
         i = out.view(np.int32)
         return {"kind": int(i[0]), "color": out[1:4].copy(), "power": out[4], "texture": int(i[5]), "projection": int(i[6]),
                 "rotation": out[7], "sin_r": out[8], "cos_r": out[9], "has_ibl": int(i[10]), "shoots_caustic": int(i[11])}
+
+    def getIntegratorAO(self, name):
+        """the ambient occlusion settings createIntegrator parsed for the integrator `name`, as a dict"""
+        do_ao, samples, dist = C.c_int(0), C.c_int(0), C.c_float(0.0)
+        col = (C.c_float * 3)()
+        self._ok(self._L.yafaray_getIntegratorAO(self._h, _b(name), C.byref(do_ao), C.byref(samples), C.byref(dist), col), "getIntegratorAO")
+        return {"do_AO": bool(do_ao.value), "AO_samples": int(samples.value), "AO_distance": np.float32(dist.value),
+                "AO_color": np.array(list(col), dtype=np.float32)}
 
     # -- params
     def paramsSetPoint(self, name, x, y, z):

@@ -143,6 +143,12 @@ def load_scene(yi, scene, render):
             integ[k] = render[k]
     # (render["caustic_type"]: "none" unless given; "path" is the reference's own default when the parameter is absent, integrator_path_tracer.cc:36)
     integ["caustic_type"] = render.get("caustic_type", "none")
+    # ambient occlusion (integrator_direct_light.cc:220-223): forwarded as given, the factory's defaults stand in for what is absent
+    for k in ("do_AO", "AO_samples", "AO_distance"):
+        if k in render:
+            integ[k] = render[k]
+    if "AO_color" in render:
+        integ["AO_color"] = _color(render["AO_color"])
     yi.paramsSet(integ)
     yi.createIntegrator("default")
     yi.paramsClearAll()
