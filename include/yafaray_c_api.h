@@ -91,6 +91,9 @@ int yafaray_getLights(yafaray_interface_t *yi, void *out, int max_lights);
 /* extension (test support): the yafgpu_background record (include/yafgpu.h, 12 words) createBackground made under `name`, as the
  * device scene would get it; false when there is no such background */
 yafaray_bool_t yafaray_getBackground(yafaray_interface_t *yi, const char *name, void *out);
+/* extension (test support): the yafgpu_camera record (include/yafgpu.h, 69 words) createCamera made under `name`, as the device scene
+ * would get it — but for the bokeh corner table `ls`, which yafgpu_scene_create fills; false when there is no such camera */
+yafaray_bool_t yafaray_getCamera(yafaray_interface_t *yi, const char *name, void *out);
 /* extension (test support): the ambient occlusion settings createIntegrator parsed for the integrator `name` (do_AO, AO_samples,
  * AO_distance narrowed to float, AO_color as three floats); any out pointer may be NULL; false when there is no such integrator */
 yafaray_bool_t yafaray_getIntegratorAO(yafaray_interface_t *yi, const char *name, int *do_ao, int *samples, float *distance, float *color3);

@@ -184,7 +184,18 @@ typedef struct yafgpu_background
 	int32_t has_ibl, shoots_caustic;
 } yafgpu_background;
 
-/* PerspectiveCamera after setAxis (camera_perspective.cc:60-74) */
+enum { YAFGPU_CAMERA_PERSPECTIVE = 0, YAFGPU_CAMERA_ARCHITECT = 1, YAFGPU_CAMERA_ANGULAR = 2, YAFGPU_CAMERA_EQUIRECTANGULAR = 3 };
+/* AngularProjection (camera_angular.h); an unknown word in the ParamMap means equidistant (camera_angular.cc:109-113) */
+enum { YAFGPU_ANGULAR_EQUIDISTANT = 0, YAFGPU_ANGULAR_ORTHOGRAPHIC = 1, YAFGPU_ANGULAR_STEREOGRAPHIC = 2, YAFGPU_ANGULAR_EQUISOLID_ANGLE = 3,
+       YAFGPU_ANGULAR_RECTILINEAR = 4 };
+
+/* A camera after its constructor and setAxis ran on the host.  Which fields each type reads:
+ *   perspective      (camera_perspective.cc:29-74) everything up to aspect_ratio, as documented per field
+ *   architect        (camera_architect.cc:29-66) the same fields; vup / vto come from its own setAxis (vup_ = aspect_ratio_ * (0, 0, -1))
+ *   angular          (camera_angular.cc:29-53) position, the clip planes, resx / resy, aspect_ratio, cam_x / cam_y / cam_z, vright / vup / vto
+ *                    (the unit axes; `mirrored` negates vright alone), focal_length, max_radius, circular, projection
+ *   equirectangular  (camera_equirectangular.cc:29-47) as angular without the last four
+ * The last two never sample a lens (Camera::sampleLense): their aperture and the other depth-of-field fields are 0. */
 typedef struct yafgpu_camera
 {
 	float position[3], vto[3], vup[3], vright[3];
@@ -200,6 +211,12 @@ typedef struct yafgpu_camera
 	/* for the `window` / `normal` texture coordinates (PerspectiveCamera::screenproject, Camera::getAxis) */
 	float cam_x[3], cam_y[3], cam_z[3];
 	float focal_distance, aspect_ratio;
+	int32_t type;                  /* YAFGPU_CAMERA_*: a zeroed record is a perspective camera */
+	/* angular */
+	float focal_length;            /* focal_length_, by projection (camera_angular.cc:37-41) */
+	float max_radius;              /* max_radius_ = max_angle / angle */
+	int32_t circular;              /* circular_: a sample outside max_radius carries no ray (shootRay's wt = 0) */
+	int32_t projection;            /* YAFGPU_ANGULAR_* */
 } yafgpu_camera;
 
 typedef struct yafgpu_scene_desc

@@ -896,6 +896,92 @@ bool make_camera(yafaray_interface *yi, const ParamMap &p, yafgpu_camera &c)
 	c.bokeh_bias = bkhbias == "center" ? 1 : bkhbias == "edge" ? 2 : 0;
 	return true;
 }
+// ArchitectCamera::factory, ctor, setAxis — camera_architect.cc:92-133, :29-50, :52-66.  The factory's parameters and defaults are
+// PerspectiveCamera's (farClip -1 included) and the ctor runs PerspectiveCamera's first, so the record starts as make_camera's; then the
+// class's own setAxis replaces vup_ by aspect_ratio_ * Vec3(0, 0, -1) — verticals stay vertical — and rebuilds vto_ from it.  dof_rt_ /
+// dof_up_ still follow cam_x_ / cam_y_ (:58-59) and the corner table is filled again with the same values (:37-49).  The rays are
+// PerspectiveCamera::shootRay's (the class does not override it): nothing differs on the device but screenproject.
+bool make_architect_camera(yafaray_interface *yi, const ParamMap &p, yafgpu_camera &c)
+{
+	if(!make_camera(yi, p, c)) return false;
+	c.type = YAFGPU_CAMERA_ARCHITECT;
+	const float up_axis[3] = {0.f, 0.f, -1.f};
+	for(int k = 0; k < 3; ++k)
+	{
+		const float vright = c.cam_x[k], vup = c.aspect_ratio * up_axis[k];
+		c.vto[k] = (c.cam_z[k] * c.focal_distance) - 0.5f * (vup + vright);
+		c.vup[k] = vup / (float)c.resy;
+	}
+	return true;
+}
+// AngularCamera::factory + ctor + setAxis (camera_angular.cc:82-121, :29-53) and EquirectangularCamera's (camera_equirectangular.cc:67-90,
+// :29-47) over Camera::Camera (camera.cc:46-66).  vright_ / vup_ / vto_ are the unit axes.  Neither class overrides Camera::sampleLense()
+// (camera.h: false), so the integrator never draws lens samples for them: `aperture` stays 0 in the record whatever the ParamMap carries —
+// the device keys the lens stream on it (wf_generate) — and so do the other depth-of-field fields.
+// The unqualified tan() of the ctor (:38, :40) is the double C function, its result narrowed into focal_length_; fSin__ is the float polynomial.
+bool make_panoramic_camera(yafaray_interface *yi, const ParamMap &p, bool angular, yafgpu_camera &c)
+{
+	float from[3] = {0, 1, 0}, to[3] = {0, 0, 0}, up[3] = {0, 1, 1};
+	int resx = 320, resy = 200;
+	double aspect_d = 1.0, angle_degrees = 90, max_angle_degrees = 90;
+	std::string projection_string;
+	bool circular = true, mirrored = false;
+	float near_clip = 0.0f, far_clip = -1.0e38f;
+	p.getPoint("from", from); p.getPoint("to", to); p.getPoint("up", up); p.get("resx", resx); p.get("resy", resy);
+	p.get("aspect_ratio", aspect_d);
+	if(angular)
+	{
+		p.get("angle", angle_degrees);
+		max_angle_degrees = angle_degrees;
+		p.get("max_angle", max_angle_degrees);
+		p.get("circular", circular); p.get("mirrored", mirrored); p.get("projection", projection_string);
+	}
+	p.get("nearClip", near_clip); p.get("farClip", far_clip);
+	const float aspect = (float)aspect_d;
+	const float aspect_ratio = aspect * (float)resy / (float)resx;
+	float cy[3], cz[3], cx[3];
+	for(int k = 0; k < 3; ++k) { cy[k] = up[k] - from[k]; cz[k] = to[k] - from[k]; }
+	cross3(cz, cy, cx);
+	cross3(cz, cx, cy);
+	normalize3(cx); normalize3(cy); normalize3(cz);
+	std::memset(&c, 0, sizeof c);
+	c.type = angular ? YAFGPU_CAMERA_ANGULAR : YAFGPU_CAMERA_EQUIRECTANGULAR;
+	c.resx = resx; c.resy = resy;
+	for(int k = 0; k < 3; ++k)
+	{
+		c.position[k] = from[k];
+		c.near_n[k] = cz[k]; c.near_p[k] = from[k] + cz[k] * near_clip;
+		c.far_n[k] = cz[k]; c.far_p[k] = from[k] + cz[k] * far_clip;
+		c.vright[k] = cx[k]; c.vup[k] = cy[k]; c.vto[k] = cz[k];
+		c.cam_x[k] = cx[k]; c.cam_y[k] = cy[k]; c.cam_z[k] = cz[k];
+	}
+	c.aspect_ratio = aspect_ratio;
+	if(!angular) return true;
+	if(!(angle_degrees > 0.0)) return fail(yi, "createCamera: angular camera: angle must be above 0 degrees");
+	const float angle = (float)(angle_degrees * 3.14159265358979323846 / (double)180.f), max_angle = (float)(max_angle_degrees * 3.14159265358979323846 / (double)180.f);
+	c.max_radius = max_angle / angle;
+	c.circular = circular ? 1 : 0;
+	c.projection = projection_string == "orthographic" ? YAFGPU_ANGULAR_ORTHOGRAPHIC : projection_string == "stereographic" ? YAFGPU_ANGULAR_STEREOGRAPHIC
+	             : projection_string == "equisolid_angle" ? YAFGPU_ANGULAR_EQUISOLID_ANGLE : projection_string == "rectilinear" ? YAFGPU_ANGULAR_RECTILINEAR
+	             : YAFGPU_ANGULAR_EQUIDISTANT;
+	if(c.projection == YAFGPU_ANGULAR_ORTHOGRAPHIC) c.focal_length = 1.f / host_fsin_poly(angle);
+	else if(c.projection == YAFGPU_ANGULAR_STEREOGRAPHIC) c.focal_length = (float)((double)(1.f / 2.f) / std::tan((double)(angle / 2.f)));
+	else if(c.projection == YAFGPU_ANGULAR_EQUISOLID_ANGLE) c.focal_length = 1.f / 2.f / host_fsin_poly(angle / 2.f);
+	else if(c.projection == YAFGPU_ANGULAR_RECTILINEAR) c.focal_length = (float)((double)1.f / std::tan((double)angle));
+	else c.focal_length = 1.f / angle;
+	if(mirrored) for(int k = 0; k < 3; ++k) c.vright[k] *= -1.0f;      // :116, after the ctor: cam_x_ (screenproject) keeps its sign
+	if(c.projection == YAFGPU_ANGULAR_ORTHOGRAPHIC || c.projection == YAFGPU_ANGULAR_EQUISOLID_ANGLE)
+	{	// shootRay :68 / :70 takes asin(radius / focal_length_) resp. asin(radius / (2 focal_length_)): above 1 the reference hands the integrator
+		// a NaN direction.  Such a camera is refused here instead.  The largest radius a sample reaches is the frame's corner, or the circle's.
+		float radius = std::sqrt(1.f + aspect_ratio * aspect_ratio);
+		if(circular && c.max_radius < radius) radius = c.max_radius;
+		const float arg = c.projection == YAFGPU_ANGULAR_ORTHOGRAPHIC ? radius / c.focal_length : radius / (2.f * c.focal_length);
+		if(!(arg <= 1.f))
+			return fail(yi, "createCamera: angular camera: projection \"" + projection_string + "\" reaches past its domain with this angle / max_angle"
+			            " (asin of " + std::to_string(arg) + " at the largest radius " + std::to_string(radius) + "): use circular with a smaller max_angle, or a smaller angle");
+	}
+	return true;
+}
 
 void set_param(yafaray_interface *yi, const char *name, const Param &v) { if(name) yi->cparams->dicc[name] = v; }
 
@@ -1158,6 +1244,13 @@ int yafaray_getLights(yafaray_interface_t *yi, void *out, int max_lights)
 	for(int i = 0; out && i < std::min(n, max_lights); ++i) std::memcpy((char *)out + (size_t)i * sizeof(yafgpu_light), &yi->light_order[(size_t)i]->l, sizeof(yafgpu_light));
 	return n;
 }
+yafaray_bool_t yafaray_getCamera(yafaray_interface_t *yi, const char *name, void *out)
+{
+	auto it = name ? yi->cameras.find(name) : yi->cameras.end();
+	if(it == yi->cameras.end()) return fail(yi, "getCamera: no such camera");
+	if(out) std::memcpy(out, &it->second->c.cam, sizeof(yafgpu_camera));
+	return 1;
+}
 yafaray_bool_t yafaray_getBackground(yafaray_interface_t *yi, const char *name, void *out)
 {
 	auto it = name ? yi->backgrounds.find(name) : yi->backgrounds.end();
@@ -1406,9 +1499,15 @@ yafaray_camera_t *yafaray_createCamera(yafaray_interface_t *yi, const char *name
 	std::string type;
 	if(!name) { fail(yi, "createCamera: null name"); return nullptr; }
 	if(!yi->params.get("type", type)) { fail(yi, "createCamera: type of camera not specified"); return nullptr; }
-	if(type != "perspective") { fail(yi, "createCamera: camera type \"" + type + "\" is outside the GPU path's scope (perspective)"); return nullptr; }
+	if(type != "perspective" && type != "architect" && type != "angular" && type != "equirectangular")
+	{	// Camera::factory, camera.cc:34-44, knows "orthographic" too: not built yet
+		fail(yi, "createCamera: camera type \"" + type + "\" is outside the GPU path's scope (perspective, architect, angular, equirectangular)");
+		return nullptr;
+	}
 	auto c = std::make_unique<yafaray_camera>();
-	if(!make_camera(yi, yi->params, c->c.cam)) return nullptr;
+	const bool made = type == "perspective" ? make_camera(yi, yi->params, c->c.cam) : type == "architect" ? make_architect_camera(yi, yi->params, c->c.cam)
+	                : make_panoramic_camera(yi, yi->params, type == "angular", c->c.cam);
+	if(!made) return nullptr;
 	yafaray_camera *raw = c.get();
 	yi->cameras[name] = std::move(c);
 	yi->prepared = false; yi->scene_dirty = true;

@@ -395,10 +395,10 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 		}
 		case 7:
 		{
-			V3 f, d; float t0, t1;
-			if(n_in >= 4) camera_shoot(sc.cam, x[0], x[1], x[2], x[3], f, d, t0, t1);
-			else camera_shoot(sc.cam, x[0], x[1], f, d, t0, t1);
-			o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = d.x; o[4] = d.y; o[5] = d.z; o[6] = t0; o[7] = t1; o[8] = 1.f;
+			V3 f, d; float t0, t1, wt;
+			if(n_in >= 4) camera_shoot<true>(sc.cam, x[0], x[1], x[2], x[3], f, d, t0, t1, wt);
+			else camera_shoot<true>(sc.cam, x[0], x[1], 0.5f, 0.5f, f, d, t0, t1, wt);
+			o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = d.x; o[4] = d.y; o[5] = d.z; o[6] = t0; o[7] = t1; o[8] = wt;
 			break;
 		}
 		case 8:
@@ -1741,7 +1741,23 @@ static int run_program(PassCtx &c, WfArgs &a, int n_iters, bool record)
 	a.q_closest_in = nullptr; a.q_shadow_in = qset[0][1]; a.q_resume_in = qset[0][2];
 	a.q_closest_out = qset[1][0]; a.q_shadow_out = qset[1][1]; a.q_resume_out = qset[1][2];
 	const uint32_t g_gen = std::min<uint32_t>((a.n_paths + kBlock - 1) / kBlock, (uint32_t)cus * 8u);
-	if((rc = timed(c, 3, [&] { hipLaunchKernelGGL(wf_generate, dim3(g_gen), dim3(kBlock), 0, stream, a); }))) return rc;
+	{	// A camera whose samples may carry no ray (the circular angular camera) has wf_generate list the live ones in the first iteration's
+		// closest-hit queue, counted from zero; every other camera keeps the identity queue and a count of n_paths.  The perspective and
+		// architect cameras run the kernel's instance without the other two types' code.
+		const int cam_type = a.ra.sc.cam.type;
+		const bool panoramic = cam_type == YAFGPU_CAMERA_ANGULAR || cam_type == YAFGPU_CAMERA_EQUIRECTANGULAR;
+		const bool may_die = cam_type == YAFGPU_CAMERA_ANGULAR && a.ra.sc.cam.circular != 0;
+		WfArgs g = a;
+		g.q_closest_out = may_die ? qset[0][0] : nullptr;
+		if(may_die)
+		{
+			HIP_OK(hipMemsetAsync(a.cnt_in, 0, 8 * sizeof(uint32_t), stream));
+			a.q_closest_in = qset[0][0];
+		}
+		if((rc = timed(c, 3, [&] {
+			if(panoramic) hipLaunchKernelGGL(wf_generate<true>, dim3(g_gen), dim3(kBlock), 0, stream, g);
+			else hipLaunchKernelGGL(wf_generate<false>, dim3(g_gen), dim3(kBlock), 0, stream, g); }))) return rc;
+	}
 	int cur = 0;
 	const int iter_cap = n_iters * (p.frames > 0 ? (1 << (p.frames + 1)) : 1) * (s->has_glossy ? (s->has_glossy_two ? 32 : 16) : 1);      // (a safety net: the loop ends when the queues are empty)
 	// the record pass answered the final pass's closest-hit queries already: wf_shade reads them from its cache where it would read the traversal's answers

@@ -1217,10 +1217,53 @@ YG_DEV void camera_lens_uv(const yafgpu_camera &c, float r_1, float r_2, float &
 	else shirley_disk(r_1, r_2, u, v);
 }
 
-// PerspectiveCamera::shootRay, camera_perspective.cc:133-156; rayPlaneIntersection__ util_geometry.h:34-37
-YG_DEV void camera_shoot(const yafgpu_camera &c, float px, float py, float lu, float lv, V3 &from, V3 &dir, float &tmin, float &tmax)
+// Camera::shootRay per type.  wt: the weight the reference returns — 0 = the sample carries no ray (outside the angular camera's circle);
+// from / dir / tmin / tmax are not to be used then.
+//   perspective, architect  PerspectiveCamera::shootRay, camera_perspective.cc:133-156 (ArchitectCamera does not override it)
+//   angular                 AngularCamera::shootRay, camera_angular.cc:55-80
+//   equirectangular         EquirectangularCamera::shootRay, camera_equirectangular.cc:49-65
+// rayPlaneIntersection__ util_geometry.h:34-37.  The unqualified atan2 / asin / atan of the angular camera are the double C functions, their
+// results narrowed (and the equirectangular angles are double products narrowed): the double device functions are called here too.
+// The directions of the last two are not normalised.  Their dot(dir, cam_z) may be zero: a tmin of 0 / 0 becomes 0 (Cameras).
+// kPanoramic = false compiles the perspective / architect branch alone (wf_generate's instance for those types keeps the registers it had:
+// the double libm calls cost the other instance 75 VGPRs).
+template<bool kPanoramic>
+YG_DEV void camera_shoot(const yafgpu_camera &c, float px, float py, float lu, float lv, V3 &from, V3 &dir, float &tmin, float &tmax, float &wt)
 {
+	wt = 1.f;
 	from = vec3(c.position);
+	if(kPanoramic && (c.type == YAFGPU_CAMERA_ANGULAR || c.type == YAFGPU_CAMERA_EQUIRECTANGULAR))
+	{
+		if(c.type == YAFGPU_CAMERA_ANGULAR)
+		{
+			const float u = 1.f - 2.f * (px / (float)c.resx);
+			float v = 2.f * (py / (float)c.resy) - 1.f;
+			v *= c.aspect_ratio;
+			const float radius = f_sqrt(u * u + v * v);
+			if(c.circular && radius > c.max_radius) { wt = 0.f; dir = mk(0.f, 0.f, 0.f); tmin = 0.f; tmax = -1.f; return; }
+			float theta = 0.f;
+			if(!((u == 0.f) && (v == 0.f))) theta = (float)atan2((double)v, (double)u);
+			float phi = 0.f;
+			if(c.projection == YAFGPU_ANGULAR_ORTHOGRAPHIC) phi = (float)asin((double)(radius / c.focal_length));
+			else if(c.projection == YAFGPU_ANGULAR_STEREOGRAPHIC) phi = (float)(2.0 * atan((double)(radius / (2.f * c.focal_length))));
+			else if(c.projection == YAFGPU_ANGULAR_EQUISOLID_ANGLE) phi = (float)(2.0 * asin((double)(radius / (2.f * c.focal_length))));
+			else if(c.projection == YAFGPU_ANGULAR_RECTILINEAR) phi = (float)atan((double)(radius / c.focal_length));
+			else phi = radius / c.focal_length;
+			dir = (vec3(c.vright) * f_cos(theta) + vec3(c.vup) * f_sin(theta)) * f_sin(phi) + vec3(c.vto) * f_cos(phi);
+		}
+		else
+		{
+			const float u = 2.f * px / (float)c.resx - 1.f;
+			const float v = 2.f * py / (float)c.resy - 1.f;
+			const float phi = (float)(3.14159265358979323846 * (double)u);
+			const float theta = (float)(1.57079632679489661923 * (double)v);
+			dir = (vec3(c.vto) * f_cos(phi) + vec3(c.vright) * f_sin(phi)) * f_cos(theta) + vec3(c.vup) * f_sin(theta);
+		}
+		tmin = dot(vec3(c.near_n), vec3(c.near_p) - from) / dot(dir, vec3(c.near_n));
+		tmax = dot(vec3(c.far_n), vec3(c.far_p) - from) / dot(dir, vec3(c.far_n));
+		if(tmin != tmin) tmin = 0.f;
+		return;
+	}
 	dir = normalize(vec3(c.vright) * px + vec3(c.vup) * py + vec3(c.vto));
 	tmin = dot(vec3(c.near_n), vec3(c.near_p) - from) / dot(dir, vec3(c.near_n));
 	tmax = dot(vec3(c.far_n), vec3(c.far_p) - from) / dot(dir, vec3(c.far_n));
@@ -1232,10 +1275,6 @@ YG_DEV void camera_shoot(const yafgpu_camera &c, float px, float py, float lu, f
 		from = from + li;
 		dir = normalize(dir * c.dof_distance - li);
 	}
-}
-YG_DEV void camera_shoot(const yafgpu_camera &c, float px, float py, V3 &from, V3 &dir, float &tmin, float &tmax)
-{
-	camera_shoot(c, px, py, 0.5f, 0.5f, from, dir, tmin, tmax);
 }
 
 } // namespace yafgpu

@@ -301,6 +301,34 @@ struct TexPoint { V3 p, n, ng, orco_p, orco_ng; float u, v; bool has_uv; V3 nu, 
 
 constexpr int kMaxNodes = 16;       // nodes per material on the device (a layer stack of 8 textures; the host refuses more)
 
+// Camera::screenproject per type: what the `window` texture coordinate reads (TextureMapperNode::getCoords, shader_node_basic.cc)
+//   perspective                PerspectiveCamera::screenproject, camera_perspective.cc:158-173
+//   architect                  ArchitectCamera::screenproject, camera_architect.cc:68-90, with its focal-distance correction `fod`
+//   angular, equirectangular   camera_angular.cc:123-140 = camera_equirectangular.cc:92-109: the direction normalised, the quotient in double
+YG_DEV V3 camera_screenproject(const yafgpu_camera &cam, V3 p)
+{
+	if(cam.type == YAFGPU_CAMERA_ARCHITECT)
+	{
+		const V3 dir = p - vec3(cam.position);
+		const V3 camy = mk(0.f, 0.f, 1.f);
+		const V3 camz = cross(camy, vec3(cam.cam_x));
+		const V3 camx = cross(camz, camy);
+		const float dx = dot(dir, camx), dy = dot(dir, vec3(cam.cam_y)), dz = dot(dir, camz);
+		const float fod = dot(camy * cam.focal_distance, vec3(cam.cam_y)) / dot(camx, vec3(cam.cam_x));
+		return mk(2.f * dx * fod / dz, 2.f * dy * cam.focal_distance / (dz * cam.aspect_ratio), 0.f);
+	}
+	if(cam.type == YAFGPU_CAMERA_ANGULAR || cam.type == YAFGPU_CAMERA_EQUIRECTANGULAR)
+	{
+		const V3 dir = normalize(p - vec3(cam.position));
+		const float dx = dot(vec3(cam.cam_x), dir), dy = dot(vec3(cam.cam_y), dir), dz = dot(vec3(cam.cam_z), dir);
+		const double den = 4.0 * 3.14159265358979323846 * (double)dz;
+		return mk((float)((double)-dx / den), (float)((double)-dy / den), 0.f);
+	}
+	const V3 dir = p - vec3(cam.position);
+	const float dx = dot(dir, vec3(cam.cam_x)), dy = dot(dir, vec3(cam.cam_y)), dz = dot(dir, vec3(cam.cam_z));
+	return mk(2.0f * dx * cam.focal_distance / dz, -2.0f * dy * cam.focal_distance / (dz * cam.aspect_ratio), 0.f);
+}
+
 // NodeMaterial::evalNodes over nodes[0 .. n_nodes) in evaluation order; stack[k] = node k's result
 YG_DEV void nodes_eval(const TexScene &ts, const yafgpu_node *nodes, int n_nodes, const yafgpu_camera &cam, const TexPoint &sp, NodeResult *stack)
 {
@@ -320,10 +348,8 @@ YG_DEV void nodes_eval(const TexScene &ts, const yafgpu_node *nodes, int n_nodes
 				ng = mk(m[0] * sp.ng.x + m[1] * sp.ng.y + m[2] * sp.ng.z, m[4] * sp.ng.x + m[5] * sp.ng.y + m[6] * sp.ng.z, m[8] * sp.ng.x + m[9] * sp.ng.y + m[10] * sp.ng.z);
 			}
 			else if(n.texco == kTcWin)
-			{	// PerspectiveCamera::screenproject, camera_perspective.cc:158-173
-				const V3 dir = sp.p - vec3(cam.position);
-				const float dx = dot(dir, vec3(cam.cam_x)), dy = dot(dir, vec3(cam.cam_y)), dz = dot(dir, vec3(cam.cam_z));
-				texpt = mk(2.0f * dx * cam.focal_distance / dz, -2.0f * dy * cam.focal_distance / (dz * cam.aspect_ratio), 0.f);
+			{
+				texpt = camera_screenproject(cam, sp.p);
 				ng = sp.ng;
 			}
 			else if(n.texco == kTcNor) { texpt = mk(dot(sp.n, vec3(cam.cam_x)), -dot(sp.n, vec3(cam.cam_y)), 0.f); ng = sp.ng; }
@@ -524,9 +550,7 @@ YG_DEV V3 mapper_get_coords(const yafgpu_node &n, const yafgpu_camera &cam, cons
 	}
 	else if(n.texco == kTcWin)
 	{
-		const V3 dir = sp.p - vec3(cam.position);
-		const float dx = dot(dir, vec3(cam.cam_x)), dy = dot(dir, vec3(cam.cam_y)), dz = dot(dir, vec3(cam.cam_z));
-		texpt = mk(2.0f * dx * cam.focal_distance / dz, -2.0f * dy * cam.focal_distance / (dz * cam.aspect_ratio), 0.f);
+		texpt = camera_screenproject(cam, sp.p);
 		ng = sp.ng;
 	}
 	else if(n.texco == kTcNor) { texpt = mk(dot(sp.n, vec3(cam.cam_x)), -dot(sp.n, vec3(cam.cam_y)), 0.f); ng = sp.ng; }

@@ -37,7 +37,7 @@ struct WfArgs
 	// closest queue: one entry per path (the path's ray).  shadow queue: one entry per shadow RAY,
 	// slot | which<<31 — a path parks with up to two (the light-sampling and the BSDF-sampling ray of one
 	// MIS pair).  resume queue: the paths (once each) that wait for shadow answers.
-	const uint32_t *q_closest_in, *q_shadow_in, *q_resume_in;   // nullptr closest queue = identity (first iteration)
+	const uint32_t *q_closest_in, *q_shadow_in, *q_resume_in;   // nullptr closest queue = identity (first iteration, unless the camera can leave samples without a ray)
 	uint32_t *q_closest_out, *q_shadow_out, *q_resume_out;
 	uint32_t *verdict;                // any-hit answers: BIT 4*slot + 2*pair + which, set for an occluded ray (zeroed before every any-hit launch)
 	float4 *shadow_filt;              // [2*slot + which] product of the transparencies a shadow ray passed (transparent shadows), or nullptr
@@ -1711,6 +1711,8 @@ YG_DEV void wf_push(uint32_t *queue, uint32_t *count, bool pred, uint32_t slot)
 
 #ifndef YAFGPU_VARIANT_TU      // a shade-kernel variant unit compiles wf_shade only
 // camera rays: TiledIntegrator::renderTile :378-410
+// kPanoramic: the instance for the angular and equirectangular cameras (camera_shoot<true>; samples may carry no ray)
+template<bool kPanoramic>
 __global__ __launch_bounds__(kBlock) void wf_generate(const WfArgs a)
 {
 	for(uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < a.n_paths; slot += gridDim.x * blockDim.x)
@@ -1735,13 +1737,23 @@ __global__ __launch_bounds__(kBlock) void wf_generate(const WfArgs a)
 			hal_u.set_start(start); hal_v.set_start(start);
 			for(int k = 0; k <= sample; ++k) { lens_u = hal_u.next(); lens_v = hal_v.next(); }
 		}
-		camera_shoot(a.ra.sc.cam, (float)px + dx, (float)py + dy, lens_u, lens_v, from, dir, tmin, tmax);
-		float4 *b = a.state + slot; const size_t c = a.cap;
-		b[0 * c] = f4(from, tmin);
-		b[1 * c] = f4(dir, tmax);
-		b[13 * c] = make_float4(0.f, 0.f, 0.f, fbits((uint32_t)kPcAfterClosest | ((uint32_t)kStPrimary << 2)));
+		float wt;
+		camera_shoot<kPanoramic>(a.ra.sc.cam, (float)px + dx, (float)py + dy, lens_u, lens_v, from, dir, tmin, tmax, wt);
+		// renderTile :410-416: a sample without a ray (wt == 0) goes to the film as tmp_passes_zero — black, alpha 1 (ColorPasses::initColor,
+		// renderpasses.cc:489-502) — and integrate() is never called: born finished, in no queue, no event of the serial-state replay
+		const bool live = !kPanoramic || wt != 0.f;
+		if(live)
+		{
+			float4 *b = a.state + slot; const size_t c = a.cap;
+			b[0 * c] = f4(from, tmin);
+			b[1 * c] = f4(dir, tmax);
+			b[13 * c] = make_float4(0.f, 0.f, 0.f, fbits((uint32_t)kPcAfterClosest | ((uint32_t)kStPrimary << 2)));
+		}
+		else a.results[slot] = make_float4(0.f, 0.f, 0.f, 1.f);
+		// a camera that can leave samples dead lists the live ones (the host zeroed the counts); every other one keeps the identity queue
+		if(kPanoramic && a.q_closest_out != nullptr) wf_push(a.q_closest_out, &a.cnt_in[0], live, slot);
 	}
-	if(blockIdx.x == 0 && threadIdx.x == 0) { a.cnt_in[0] = a.n_paths; a.cnt_in[1] = 0u; a.cnt_in[2] = 0u; a.cnt_in[3] = 0u; a.cnt_in[4] = 0u; }
+	if((!kPanoramic || a.q_closest_out == nullptr) && blockIdx.x == 0 && threadIdx.x == 0) { a.cnt_in[0] = a.n_paths; a.cnt_in[1] = 0u; a.cnt_in[2] = 0u; a.cnt_in[3] = 0u; a.cnt_in[4] = 0u; }
 }
 
 // The traversal kernels: Scene::intersect (scene.cc:896-927) / Scene::isShadowed (:962-994) over a queue.

@@ -50,7 +50,7 @@ C_API_SYMBOLS = [
     "yafaray_createInterface", "yafaray_destroyInterface", "yafaray_getLastError", "yafaray_getVersion",
     "yafaray_startScene", "yafaray_startGeometry", "yafaray_endGeometry", "yafaray_getNextFreeId",
     "yafaray_startTriMesh", "yafaray_endTriMesh", "yafaray_addVertex", "yafaray_addNormal", "yafaray_addTriangle",
-    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getIntegratorAO", "yafaray_addTriangles",
+    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getCamera", "yafaray_getIntegratorAO", "yafaray_addTriangles",
     "yafaray_startTriMeshPtr", "yafaray_addVertexWithOrco", "yafaray_addUv", "yafaray_addTriangleWithUv",
     "yafaray_startCurveMesh", "yafaray_endCurveMesh", "yafaray_addInstance",
     "yafaray_paramsSetColorArray", "yafaray_paramsSetMatrix", "yafaray_paramsSetMatrixD", "yafaray_setInputColorSpace",
@@ -101,6 +101,7 @@ def load():
         "yafaray_getMeshCornerNormals": (ci, [vp, C.c_uint, C.POINTER(cf), ci]),
         "yafaray_getLights": (ci, [vp, vp, ci]),
         "yafaray_getBackground": (ci, [vp, cp, vp]),
+        "yafaray_getCamera": (ci, [vp, cp, vp]),
         "yafaray_getIntegratorAO": (ci, [vp, cp, C.POINTER(ci), C.POINTER(ci), C.POINTER(cf), C.POINTER(cf)]),
         "yafaray_addTriangles": (ci, [vp, ci, C.POINTER(cf), ci, C.POINTER(ci), vp]),
         "yafaray_startTriMeshPtr": (ci, [vp, C.POINTER(C.c_uint), ci, ci, ci, ci, ci, ci]),
@@ -337,6 +338,28 @@ class Interface:
         i = out.view(np.int32)
         return {"kind": int(i[0]), "color": out[1:4].copy(), "power": out[4], "texture": int(i[5]), "projection": int(i[6]),
                 "rotation": out[7], "sin_r": out[8], "cos_r": out[9], "has_ibl": int(i[10]), "shoots_caustic": int(i[11])}
+
+    CAMERA_WORDS = 69
+    CAMERA_INT_FIELDS = ("resx", "resy", "bokeh_type", "bokeh_bias", "type", "circular", "projection")
+
+    def getCamera(self, name):
+        """the yafgpu_camera record (include/yafgpu.h) createCamera made under `name`, as a dict: float32 arrays / scalars, ints
+        for the fields of CAMERA_INT_FIELDS"""
+        out = np.zeros(self.CAMERA_WORDS, dtype=np.float32)
+        self._ok(self._L.yafaray_getCamera(self._h, _b(name), out.ctypes.data_as(C.c_void_p)), "getCamera")
+        layout = [("position", 3), ("vto", 3), ("vup", 3), ("vright", 3), ("near_p", 3), ("near_n", 3), ("far_p", 3), ("far_n", 3),
+                  ("resx", 1), ("resy", 1), ("aperture", 1), ("dof_distance", 1), ("bokeh_type", 1), ("bokeh_bias", 1), ("bokeh_rotation", 1),
+                  ("dof_rt", 3), ("dof_up", 3), ("ls", 16), ("cam_x", 3), ("cam_y", 3), ("cam_z", 3), ("focal_distance", 1), ("aspect_ratio", 1),
+                  ("type", 1), ("focal_length", 1), ("max_radius", 1), ("circular", 1), ("projection", 1)]
+        rec, at, i = {}, 0, out.view(np.int32)
+        for field, n in layout:
+            if field in self.CAMERA_INT_FIELDS:
+                rec[field] = int(i[at])
+            else:
+                rec[field] = out[at:at + n].copy() if n > 1 else out[at]
+            at += n
+        assert at == self.CAMERA_WORDS
+        return rec
 
     def getIntegratorAO(self, name):
         """the ambient occlusion settings createIntegrator parsed for the integrator `name`, as a dict"""
