@@ -97,6 +97,15 @@ yafaray_bool_t yafaray_getCamera(yafaray_interface_t *yi, const char *name, void
 /* extension (test support): the ambient occlusion settings createIntegrator parsed for the integrator `name` (do_AO, AO_samples,
  * AO_distance narrowed to float, AO_color as three floats); any out pointer may be NULL; false when there is no such integrator */
 yafaray_bool_t yafaray_getIntegratorAO(yafaray_interface_t *yi, const char *name, int *do_ao, int *samples, float *distance, float *color3);
+/* extension (test support): what MaskMaterial::factory's restatement parsed for the mask_mat `name`.  out8 receives eight 32-bit words:
+ * the indices of material1 and material2 in creation order, threshold_ (a float's bits), the mask node's slot among the mask's nodes,
+ * how many nodes that is, receive_shadows, visibility (0 normal, 1 no_shadows, 2 shadow_only, 3 invisible) and the union of both
+ * sub-materials' bsdf flags; false when there is no such material or it is no mask_mat */
+yafaray_bool_t yafaray_getMaskMaterial(yafaray_interface_t *yi, const char *name, void *out8);
+/* extension (test support): the material table as the device scene would get it: the materials in creation order, then for every
+ * mask_mat the two hidden clones of its sub-materials it picks from.  Up to max_materials yafgpu_material records (include/yafgpu.h,
+ * 384 bytes each) into out; returns how many records the table has */
+int yafaray_getMaterialTable(yafaray_interface_t *yi, void *out, int max_materials);
 /* extension (not in the reference): bulk form of addVertex/addTriangle for large meshes;
  * verts = n_verts*3 floats, indices = n_tris*3 ints, one material for all triangles */
 yafaray_bool_t yafaray_addTriangles(yafaray_interface_t *yi, int n_verts, const float *verts, int n_tris, const int *indices,

@@ -30,7 +30,18 @@ extern "C" {
 
 enum { YAFGPU_MAT_SHINYDIFFUSE = 0, YAFGPU_MAT_GLOSSY = 1, YAFGPU_MAT_LIGHT = 2, YAFGPU_MAT_GLASS = 3, YAFGPU_MAT_MIRROR = 4,
        YAFGPU_MAT_COATED_GLOSSY = 5, /* glossy's fields + mirror_color, mirror_strength, glass_ior = IOR, c_flags[0..2], n_bsdf */
-       YAFGPU_MAT_ROUGH_GLASS = 6 /* glass's fields (glass_ior, filter_color, mirror_color, fake_shadow, beer_sigma) + rg_a2: RoughGlassMaterial, material_rough_glass.cc */ };
+       YAFGPU_MAT_ROUGH_GLASS = 6, /* glass's fields (glass_ior, filter_color, mirror_color, fake_shadow, beer_sigma) + rg_a2: RoughGlassMaterial, material_rough_glass.cc */
+       /* MaskMaterial (material_mask.cc): a shader node's scalar picks one of two other records of the table at every hit.  Never a vertex's
+          material: the device replaces it by the chosen record when it makes the vertex.  (Not "YAFGPU_MAT_MASK": that name is the shading
+          units' compile-time set of material types, csrc/build.sh.)  The record adds no field; it reads
+            c_index[0], c_index[1]   the records chosen for mask <= threshold / mask > threshold: hidden clones of material1 / material2 that
+                                     carry the mask's material-level fields (see yafaray_c_api.cpp, flatten_materials)
+            transmit_filter          threshold_, a float (material_mask.cc:30-31, :45)
+            node_first, n_nodes      the nodes the mask shader reaches, in evaluation order;  sh_diffuse: the mask node's index among them
+            is_transparent           isTransparent(): either sub-material's (:86-89)
+            bsdf_flags               the union of both sub-materials' flags (:34)
+            visibility, receive_shadows   the mask's own (:150-163); flat 0, additional_depth 0, no volume handler: its factory reads none */
+       YAFGPU_MAT_MASKED = 7 };
 enum { YAFGPU_LIGHT_AREA = 0, YAFGPU_LIGHT_POINT = 1, YAFGPU_LIGHT_DIRECTIONAL = 2, YAFGPU_LIGHT_SUN = 3, YAFGPU_LIGHT_SPHERE = 4,
        YAFGPU_LIGHT_BACKGROUND = 5 /* BackgroundLight (light_background.cc): samples the scene's yafgpu_background through its Pdf1D tables */ };
 enum { YAFGPU_BACKGROUND_NONE = 0, YAFGPU_BACKGROUND_CONSTANT = 1, YAFGPU_BACKGROUND_TEXTURE = 2 };
@@ -41,7 +52,8 @@ enum { YAFGPU_FILTER_BOX = 0, YAFGPU_FILTER_MITCHELL = 1, YAFGPU_FILTER_GAUSS = 
  * material_glossy.cc:32-50, material_simple.cc:36-39).  64 floats, 16-byte aligned. */
 typedef struct yafgpu_material
 {
-	int32_t type, visibility, receive_shadows, flat;
+	int32_t type, visibility, receive_shadows, flat;      /* flat: 1 = flat_material; 2 = only the material's own test sees it (ShinyDiffuseMaterial::eval,
+	                                                         material_shiny_diffuse.cc:275), not the integrator's isFlat(): a flat material under a mask */
 	uint32_t bsdf_flags;
 	int32_t n_bsdf;
 	uint32_t c_flags[4];

@@ -81,7 +81,8 @@ struct BackgroundCfg { float color[3]; yafgpu_background rec; };      // color: 
 
 } // namespace
 
-struct yafaray_material { yafgpu_material m; int index; std::vector<yafgpu_node> nodes; };   // nodes: evaluation order, `texture` = index into texture_order
+struct yafaray_material { yafgpu_material m; int index; std::vector<yafgpu_node> nodes; int mask_sub[2] = {-1, -1}; };   // nodes: evaluation order, `texture` = index into texture_order; mask_sub: a mask_mat's material1 / material2 (their `index`)
+static_assert(sizeof(yafgpu_material) == 384, "yafaray_getMaterialTable hands out 96-word records");
 struct yafaray_texture { yafgpu_texture t; int index; std::vector<float> texels; };            // texels: height * width * 4, as ImageHandler::getPixel returns them
 struct yafaray_light { yafgpu_light l; };
 struct yafaray_camera { CameraCfg c; };
@@ -732,6 +733,97 @@ bool make_mirror(const ParamMap &p, yafgpu_material &m)
 }
 
 // AreaLight::factory + ctor, light_area.cc:169-205, :34-52
+// Material::isTransparent of the types on this path (yafgpu_shading.h mat_is_transparent)
+bool record_is_transparent(const yafgpu_material &m)
+{
+	return (m.type == YAFGPU_MAT_SHINYDIFFUSE && m.is_transparent) || ((m.type == YAFGPU_MAT_GLASS || m.type == YAFGPU_MAT_ROUGH_GLASS) && m.fake_shadow);
+}
+
+// MaskMaterial::factory + ctor, material_mask.cc:133-190, :30-37.  The record's layout: include/yafgpu.h, YAFGPU_MAT_MASKED.
+// It reads threshold (a double, kept as a float), material1, material2, receive_shadows, visibility, the node list and `mask` — and
+// neither additionaldepth, flat_material, absorption, samplingfactor nor a bump shader.  Where the reference returns nullptr this
+// refuses with the cause; a missing `mask`, which leaves the reference a null node to crash on at the first hit, is refused too.
+bool make_mask(yafaray_interface *yi, const ParamMap &p, yafaray_material &out)
+{
+	yafgpu_material &m = out.m;
+	double thresh = 0.5; bool recv = true; std::string vis = "normal", name;
+	p.get("threshold", thresh);
+	const yafaray_material *sub[2] = {nullptr, nullptr};
+	for(int k = 0; k < 2; ++k)
+	{	// :143-146, :159
+		const std::string key = k == 0 ? "material1" : "material2";
+		if(!p.get(key, name)) return fail(yi, "mask_mat: " + key + " is missing (material_mask.cc:143-145)");
+		auto it = yi->materials.find(name);
+		if(it == yi->materials.end()) return fail(yi, "mask_mat: " + key + " \"" + name + "\" names no material defined so far (material_mask.cc:159)");
+		if(it->second->m.type == YAFGPU_MAT_MASKED) return fail(yi, "mask_mat: " + key + " \"" + name + "\" is a mask_mat itself: nesting masks is not built on the GPU path");
+		sub[k] = it->second.get();
+	}
+	p.get("receive_shadows", recv); p.get("visibility", vis);
+	// :165-185: unlike the other node materials, no mask without its nodes
+	LoadedNodes ld;
+	const int rc = load_nodes(yi, yi->eparams, ld);
+	if(rc == 0) return false;
+	if(rc < 0) return fail(yi, "mask_mat: the shader node list failed to load (MaskMat: loadNodes() failed, material_mask.cc:180-185)");
+	if(!p.get("mask", name)) return fail(yi, "mask_mat: no mask parameter: the reference keeps a null mask node and crashes at the first hit (material_mask.cc:168, :44)");
+	auto node = ld.by_name.find(name);
+	if(node == ld.by_name.end()) return fail(yi, "mask_mat: mask shader node \"" + name + "\" does not exist (material_mask.cc:172-177)");
+	int slot[1] = {node->second};
+	if(!sort_nodes(yi, ld, slot, 1, out.nodes)) return false;
+	// recursiveRaytrace's glossy branch enters on the CHOSEN material's lobes and picks its case from the mask's flags, the union
+	// (integrator_montecarlo.cc:895-919): beside a transmitting partner a glossy sub-material lands in the reflect + transmit case, whose
+	// two-direction sample MaskMaterial does not override (Material's default returns black and sends nothing); rough glass, which
+	// takes that case alone, finds the same empty default under any mask
+	const uint32_t both = sub[0]->m.bsdf_flags | sub[1]->m.bsdf_flags;
+	if((both & 0x2u) && (both & 0x10u) && (both & 0x20u))
+		return fail(yi, "mask_mat: a glossy sub-material beside one that transmits (or rough glass): recursiveRaytrace reads the union of their flags and takes the "
+		                "two-direction sample MaskMaterial does not have (integrator_montecarlo.cc:895-919)");
+	std::memset(&m, 0, sizeof m);
+	clear_shader_slots(m);
+	m.type = YAFGPU_MAT_MASKED; m.visibility = visibility_from(vis); m.receive_shadows = recv;
+	m.transmit_filter = (float)thresh;                 // threshold_
+	m.bsdf_flags = both;                               // :34
+	m.is_transparent = (record_is_transparent(sub[0]->m) || record_is_transparent(sub[1]->m)) ? 1 : 0;      // :86-89
+	m.n_nodes = (int32_t)out.nodes.size(); m.sh_diffuse = slot[0];
+	m.c_index[0] = m.c_index[1] = -1;                  // the clones' places in the table: flatten_materials
+	out.mask_sub[0] = sub[0]->index; out.mask_sub[1] = sub[1]->index;
+	return true;
+}
+
+// The material table of the device scene: the materials in creation order, then, for every mask_mat, a clone of each of its two
+// sub-materials, which is what a vertex on the mask gets (yafgpu_wavefront.h wf_mask_hit).  A clone is the sub-material with the
+// material-level values the integrators read off sp.material_, the MASK, in the reference: receive_shadows (integrator_montecarlo.cc:91)
+// and visibility are the mask's; isFlat() (:105, :189) is false, while ShinyDiffuseMaterial::eval's own flat_material_ test
+// (material_shiny_diffuse.cc:275) stays the sub-material's (flat 2); getAdditionalDepth() (integrator_path_tracer.cc:149) and the
+// transparent bias (integrator_montecarlo.cc:1003-1011) are 0; getVolumeHandler() (:912, :991, integrator_path_tracer.cc:276) is null,
+// so glass under a mask does not absorb.  Its nodes are the sub-material's own range, shared.
+void flatten_materials(const yafaray_interface *yi, std::vector<yafgpu_material> &mats, std::vector<yafgpu_node> &nodes)
+{
+	mats.clear(); nodes.clear();
+	for(auto *m : yi->material_order)
+	{
+		yafgpu_material rec = m->m;
+		rec.node_first = (int32_t)nodes.size();           // rec.n_nodes colour nodes, then the bump shader's list
+		rec.bump_first += rec.node_first;
+		nodes.insert(nodes.end(), m->nodes.begin(), m->nodes.end());
+		mats.push_back(rec);
+	}
+	const size_t n = mats.size();
+	for(size_t i = 0; i < n; ++i)
+	{
+		if(mats[i].type != YAFGPU_MAT_MASKED) continue;
+		for(int k = 0; k < 2; ++k)
+		{
+			yafgpu_material c = mats[(size_t)yi->material_order[i]->mask_sub[k]];
+			c.receive_shadows = mats[i].receive_shadows; c.visibility = mats[i].visibility;
+			c.flat = c.flat ? 2 : 0;
+			c.additional_depth = 0; c.transp_bias_factor = 0.f; c.transp_bias_mult = 0;
+			c.has_vol_i = 0; c.beer_sigma[0] = c.beer_sigma[1] = c.beer_sigma[2] = 0.f;
+			mats[i].c_index[k] = (int32_t)mats.size();
+			mats.push_back(c);
+		}
+	}
+}
+
 bool make_arealight(const ParamMap &p, yafgpu_light &l)
 {
 	float corner[3] = {0, 0, 0}, p1[3] = {0, 0, 0}, p2[3] = {0, 0, 0}, color[3] = {1, 1, 1};
@@ -1269,6 +1361,27 @@ yafaray_bool_t yafaray_getIntegratorAO(yafaray_interface_t *yi, const char *name
 	if(color3) for(int k = 0; k < 3; ++k) color3[k] = c.ao_color[k];
 	return 1;
 }
+yafaray_bool_t yafaray_getMaskMaterial(yafaray_interface_t *yi, const char *name, void *out8)
+{
+	auto it = name ? yi->materials.find(name) : yi->materials.end();
+	if(it == yi->materials.end() || it->second->m.type != YAFGPU_MAT_MASKED) return fail(yi, "getMaskMaterial: no such mask_mat");
+	const yafaray_material &mm = *it->second;
+	if(out8)
+	{
+		int32_t w[8] = {mm.mask_sub[0], mm.mask_sub[1], 0, mm.m.sh_diffuse, mm.m.n_nodes, mm.m.receive_shadows, mm.m.visibility, (int32_t)mm.m.bsdf_flags};
+		std::memcpy(&w[2], &mm.m.transmit_filter, 4);
+		std::memcpy(out8, w, sizeof w);
+	}
+	return 1;
+}
+int yafaray_getMaterialTable(yafaray_interface_t *yi, void *out, int max_materials)
+{
+	std::vector<yafgpu_material> mats; std::vector<yafgpu_node> nodes;
+	flatten_materials(yi, mats, nodes);
+	const int n = (int)mats.size();
+	for(int i = 0; out && i < std::min(n, max_materials); ++i) std::memcpy((char *)out + (size_t)i * sizeof(yafgpu_material), &mats[(size_t)i], sizeof(yafgpu_material));
+	return n;
+}
 yafaray_bool_t yafaray_getMeshCornerNormals(yafaray_interface_t *yi, unsigned int id, float *out, int n_floats)
 {
 	auto it = yi->meshes.find(id);
@@ -1349,9 +1462,10 @@ yafaray_material_t *yafaray_createMaterial(yafaray_interface_t *yi, const char *
 	else if(type == "rough_glass") ok = make_rough_glass(yi, yi->params, m->m, m->nodes);
 	else if(type == "coated_glossy") ok = make_coated_glossy(yi, yi->params, m->m, m->nodes);
 	else if(type == "mirror") ok = make_mirror(yi->params, m->m);
-	else { fail(yi, "createMaterial: material type \"" + type + "\" is outside the GPU path's scope (shinydiffusemat, glossy, coated_glossy, glass, mirror, light_mat)"); return nullptr; }
+	else if(type == "mask_mat") ok = make_mask(yi, yi->params, *m);
+	else { fail(yi, "createMaterial: material type \"" + type + "\" is outside the GPU path's scope (shinydiffusemat, glossy, coated_glossy, glass, rough_glass, mirror, light_mat, mask_mat)"); return nullptr; }
 	if(!ok) return nullptr;
-	if(type != "shinydiffusemat" && type != "glossy" && type != "coated_glossy" && type != "glass") clear_shader_slots(m->m);
+	if(type != "shinydiffusemat" && type != "glossy" && type != "coated_glossy" && type != "glass" && type != "mask_mat") clear_shader_slots(m->m);
 	note_srand(yi, ++g_material_index_auto);        // Material::Material, material.cc:53-57
 	m->index = (int)yi->material_order.size();
 	yafaray_material *raw = m.get();
@@ -1826,14 +1940,7 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 	}
 	if(yi->material_order.empty()) return fail(yi, "render: no materials defined");
 	std::vector<yafgpu_material> mats; std::vector<yafgpu_node> nodes;
-	for(auto *m : yi->material_order)
-	{
-		yafgpu_material rec = m->m;
-		rec.node_first = (int32_t)nodes.size();           // rec.n_nodes colour nodes, then the bump shader's list
-		rec.bump_first += rec.node_first;
-		nodes.insert(nodes.end(), m->nodes.begin(), m->nodes.end());
-		mats.push_back(rec);
-	}
+	flatten_materials(yi, mats, nodes);
 	std::vector<yafgpu_texture> textures; std::vector<float> texels;
 	const bool bg_texture = bg && bg->rec.kind == YAFGPU_BACKGROUND_TEXTURE;
 	if(any_nodes || bg_texture)

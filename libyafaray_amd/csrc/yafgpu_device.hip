@@ -279,8 +279,14 @@ YG_DEV bool kd_trace_ts(const DevScene &sc, LaneStack &stk, uint32_t *seen /* [k
 			if(!tri_test(r0, r1, r2, from, dir, t, u, v)) continue;
 			const uint32_t vis = __float_as_uint(r1.w) >> 30;
 			if(!(t < dist && t >= ray_tmin && (vis == 0u || vis == 2u))) continue;
-			const yafgpu_material &m = sc.mats[__float_as_uint(r1.w) & 0x3FFFFFFFu];
-			if(!mat_is_transparent(m)) return true;
+			const yafgpu_material *mp = &sc.mats[__float_as_uint(r1.w) & 0x3FFFFFFFu];
+#if YAFGPU_FEAT_TEXTURE
+			const bool masked = sc.tex.nodes != nullptr && mp->type == YAFGPU_MAT_MASKED;
+			// MaskMaterial::isTransparent, material_mask.cc:86-89: either sub-material's
+			if(masked ? !mp->is_transparent : !mat_is_transparent(*mp)) return true;
+#else
+			if(!mat_is_transparent(*mp)) return true;
+#endif
 			bool known = false;
 			for(int k = 0; k < n_seen; ++k) known = known || (seen[k * kWave] == ti);
 			if(known) continue;
@@ -288,6 +294,12 @@ YG_DEV bool kd_trace_ts(const DevScene &sc, LaneStack &stk, uint32_t *seen /* [k
 			if(n_seen <= kTsMaxDepth) seen[(n_seen++) * kWave] = ti;
 			SurfPt sp;
 			get_surface(sc, (int)ti, from + dir * t, u, v, sp);
+#if YAFGPU_FEAT_TEXTURE
+			// MaskMaterial::getTransparency, :91-99: the mask's nodes again, against 0.5 and not threshold_; the chosen material's
+			// getTransparency follows, black for one that is opaque (the ray goes on with nothing left to carry)
+			if(masked) mp = &sc.mats[mask_select(sc.tex, sc.cam, *mp, (int)ti, u, v, sp.p, sp.n, sp.ng, true)];
+#endif
+			const yafgpu_material &m = *mp;
 			if(m.n_nodes > 0 && sc.tex.nodes != nullptr)
 			{	// getTransparency reads the diffuse shader and the component nodes (material_shiny_diffuse.cc:541-563)
 				TexPoint tp; tex_point(sc.tex, (int)ti, u, v, sp.p, sp.n, sp.ng, tp);
@@ -629,9 +641,11 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			yafgpu_material m_tmp;
 			const yafgpu_material *mp = &sc.mats[k];
 			if(n_in >= 24 && (mp->n_nodes > 0 || mp->n_bump > 0))
-			{	// the vertex as st_after_closest makes it: the bumped frame, then the material its nodes resolve to there
+			{	// the vertex as st_after_closest makes it: the record a mask picks, the bumped frame, then the material its nodes resolve to there
 				const uint32_t tri = __float_as_uint(x[21]);
 				if(tri >= (uint32_t)sc.n_tris) break;
+				wf_mask_hit(sc, sp, (int)tri, x[22], x[23]);
+				mp = &sc.mats[sp.mat];
 				wf_bump_hit(sc, sp, (int)tri, x[22], x[23]);
 				mp = &wf_mat_hit(sc, sp, (int)tri, x[22], x[23], m_tmp);
 			}
@@ -642,6 +656,22 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			const bool go = ao_candidate(ao, x[13], x[14], sp, *mp, d, fl, wo, true, dir, tmin, tmax, contrib, emit);
 			o[0] = go ? 1.f : 0.f; o[1] = dir.x; o[2] = dir.y; o[3] = dir.z; o[4] = tmin; o[5] = tmax;
 			o[6] = contrib.r; o[7] = contrib.g; o[8] = contrib.b; o[9] = emit.r; o[10] = emit.g; o[11] = emit.b;
+			break;
+		}
+		case 27:
+		{	// the mask material's selection (mask_value / mask_select / wf_mask_hit): in material index, triangle (both as bits), barycentrics u, v,
+			// p, n, ng -> the mask scalar, the choice under threshold_ (0 / 1), the choice under 0.5, the index the vertex gets (as bits)
+			if(n_in < 13 || n_out < 4 || sc.tex.nodes == nullptr) break;
+			const uint32_t k = __float_as_uint(x[0]), tri = __float_as_uint(x[1]);
+			if(k >= (uint32_t)sc.n_mats || tri >= (uint32_t)sc.n_tris) break;
+			const yafgpu_material &m = sc.mats[k];
+			SurfPt sp; make_sp(mk(x[4], x[5], x[6]), mk(x[7], x[8], x[9]), mk(x[10], x[11], x[12]), (int)k, sp);
+			wf_mask_hit(sc, sp, (int)tri, x[2], x[3]);
+			o[3] = __uint_as_float((uint32_t)sp.mat);
+			if(m.type != YAFGPU_MAT_MASKED) break;
+			o[0] = mask_value(sc.tex, sc.cam, m, (int)tri, x[2], x[3], sp.p, sp.n, sp.ng);
+			o[1] = mask_select(sc.tex, sc.cam, m, (int)tri, x[2], x[3], sp.p, sp.n, sp.ng, false) == m.c_index[1] ? 1.f : 0.f;
+			o[2] = mask_select(sc.tex, sc.cam, m, (int)tri, x[2], x[3], sp.p, sp.n, sp.ng, true) == m.c_index[1] ? 1.f : 0.f;
 			break;
 		}
 		default: break;
@@ -773,6 +803,7 @@ struct yafgpu_scene
 	Event pipe_sync; bool pipe_prev = false;
 	int pipe_next = 0, pass_pipelining = -1;      // -1: by size (plan_pass), 0 / 1: forced (yafgpu_scene_set_pass_pipelining)
 	uint32_t mat_mask = 0u;              // bit per YAFGPU_MAT_* present; picks the shading kernel variant
+	std::vector<char> mat_used;          // per material record: some triangle refers to it, or a mask in use picks it
 	uint32_t light_mask = 0u;            // bit per YAFGPU_LIGHT_* present; a variant must have been built for all of them
 	bool has_volumetric = false;
 	int max_add_depth = 0;               // the largest Material::additional_depth_ of the scene: recursion frames beyond raydepth
@@ -894,7 +925,24 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 	{
 		// recursiveRaytrace (integrator_montecarlo.cc:782-1028): the perfect specular branch and both cases of the glossy branch (reflect
 		// only; reflect + transmit, which is rough glass and nothing else) are on the device path; the dispersive branch is not
-		if(d->materials[i].type < 0 || d->materials[i].type > YAFGPU_MAT_ROUGH_GLASS) return fail(-3, "material " + std::to_string(i) + ": unknown type");
+		if(d->materials[i].type < 0 || d->materials[i].type > YAFGPU_MAT_MASKED) return fail(-3, "material " + std::to_string(i) + ": unknown type");
+		if(d->materials[i].type == YAFGPU_MAT_MASKED)
+		{	// a mask picks between two records that are materials themselves (no nesting), through a node of its own range; the union of flags it
+			// carries (material_mask.cc:34) is no lobe of its own, so the two tests below are its sub-materials' to pass
+			const yafgpu_material &m = d->materials[i];
+			for(int k = 0; k < 2; ++k)
+				if(m.c_index[k] < 0 || m.c_index[k] >= d->n_materials || d->materials[m.c_index[k]].type == YAFGPU_MAT_MASKED)
+					return fail(-3, "mask material " + std::to_string(i) + ": a sub-material index outside the table, or a mask under a mask (nesting is not built)");
+			if(!d->nodes || m.n_nodes < 1 || m.sh_diffuse < 0 || m.sh_diffuse >= m.n_nodes || m.n_bump != 0)
+				return fail(-24, "mask material " + std::to_string(i) + ": needs shader nodes and a mask node among them, and has no bump shader");
+			// recursiveRaytrace's glossy branch picks its case from the MASK's flags, the union (integrator_montecarlo.cc:895-919): next to a
+			// transmitting partner a glossy sub-material lands in the reflect + transmit case, whose two-direction sample MaskMaterial leaves
+			// at Material's empty default
+			const uint32_t both = d->materials[m.c_index[0]].bsdf_flags | d->materials[m.c_index[1]].bsdf_flags;
+			if((both & kGlossy) && (both & kReflect) && (both & kTransmit))
+				return fail(-4, "mask material " + std::to_string(i) + ": a glossy sub-material beside a transmitting one (recursiveRaytrace reads the union of their flags, integrator_montecarlo.cc:895-919)");
+			continue;
+		}
 		if(d->materials[i].bsdf_flags & kDispersive)
 			return fail(-4, "material with a dispersive lobe needs recursiveRaytrace's dispersive branch, which the GPU path does not implement");
 		if((d->materials[i].bsdf_flags & kGlossy) && (d->materials[i].bsdf_flags & kTransmit) && d->materials[i].type != YAFGPU_MAT_ROUGH_GLASS)
@@ -906,11 +954,16 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 	{	// What the scene's materials ask of the pipeline — recursion frames, the glossy loop's wider frames, extra depth, the transparent-shadow
 		// kernel, the kernel variant — is taken from the materials some triangle actually USES: a definition nothing refers to can never be
 		// hit, and must not cost frames, a kernel variant or (through the size of the replay's event tables) the exactness of the serial state
-		std::vector<char> used((size_t)d->n_materials, 0);
+		// A mask material in use stands for the two records it picks from: those count, the mask's own type and union of flags do not (it is
+		// never a vertex's material).  A mask nothing refers to sizes nothing either, and neither do its records.
+		std::vector<char> &used = s->mat_used;
+		used.assign((size_t)d->n_materials, 0);
 		for(int i = 0; i < d->n_tris; ++i) used[(size_t)d->tri_mat[i]] = 1;
 		for(int i = 0; i < d->n_materials; ++i)
+			if(used[(size_t)i] && d->materials[i].type == YAFGPU_MAT_MASKED) used[(size_t)d->materials[i].c_index[0]] = used[(size_t)d->materials[i].c_index[1]] = 1;
+		for(int i = 0; i < d->n_materials; ++i)
 		{
-			if(!used[(size_t)i]) continue;
+			if(!used[(size_t)i] || d->materials[i].type == YAFGPU_MAT_MASKED) continue;
 			const yafgpu_material &m = d->materials[i];
 			s->mat_mask |= 1u << (uint32_t)m.type;
 			if(m.bsdf_flags & kVolumetric) s->has_volumetric = true;
@@ -1040,7 +1093,7 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 			const yafgpu_material &m = d->materials[i];
 			if(m.n_nodes < 0 || m.n_nodes > kMaxNodes || m.node_first < 0 || m.node_first + m.n_nodes > d->n_nodes)
 			{ yafgpu_scene_destroy(s); return fail(-24, "a material's shader nodes: more than " + std::to_string(kMaxNodes) + " nodes, or a range outside the node array"); }
-			if(m.n_nodes > 0) s->has_textures = true;
+			if(m.n_nodes > 0 && (m.type != YAFGPU_MAT_MASKED || s->mat_used[(size_t)i])) s->has_textures = true;      // (a mask nothing refers to picks no kernel)
 			if(m.n_bump < 0 || m.n_bump > kMaxNodes || (m.n_bump > 0 && (m.bump_first < 0 || m.bump_first + m.n_bump > d->n_nodes || m.sh_bump < 0 || m.sh_bump >= m.n_bump)))
 			{ yafgpu_scene_destroy(s); return fail(-24, "a material's bump shader: more than " + std::to_string(kMaxNodes) + " nodes, or a range outside the node array"); }
 			if(m.n_bump > 0) { s->has_textures = true; s->has_bump = true; }

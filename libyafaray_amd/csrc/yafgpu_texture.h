@@ -682,6 +682,24 @@ YG_DEV void mat_resolve(const TexScene &ts, const yafgpu_camera &cam, const yafg
 	if(m.sh_ior >= 0) { const float cur = m.ior_base + stack[m.sh_ior].f; out.ior_squared = cur * cur; }
 }
 
+// The mask material (MaskMaterial, material_mask.cc; record layout: yafgpu.h, YAFGPU_MAT_MASKED).  mask_value: evalNodes over the mask's
+// own nodes and mask_->getScalar(stack) (:43-44, :94-95) at a hit whose frame no bump has touched yet.  mask_select: the record the hit
+// gets — material2's clone if the value exceeds threshold_ (initBsdf, :45-49), or, for a shadow ray's getTransparency, the literal 0.5
+// whatever the threshold is (:96, sic: a double there, and 0.5 is exact in both formats).
+YG_DEV float mask_value(const TexScene &ts, const yafgpu_camera &cam, const yafgpu_material &m, int tri, float bu, float bv, V3 p, V3 n, V3 ng)
+{
+	TexPoint tp; tex_point(ts, tri, bu, bv, p, n, ng, tp);
+	NodeResult stack[kMaxNodes];
+	nodes_eval(ts, ts.nodes + m.node_first, m.n_nodes < kMaxNodes ? m.n_nodes : kMaxNodes, cam, tp, stack);
+	return stack[m.sh_diffuse].f;
+}
+YG_DEV int mask_select(const TexScene &ts, const yafgpu_camera &cam, const yafgpu_material &m, int tri, float bu, float bv, V3 p, V3 n, V3 ng, bool transparency)
+{
+	const float val = mask_value(ts, cam, m, tri, bu, bv, p, n, ng);
+	const bool mv = transparency ? val > 0.5f : val > m.transmit_filter;
+	return m.c_index[mv ? 1 : 0];
+}
+
 // ---- backgrounds and the background light (image-based lighting) ----
 //
 //   ConstantBackground      src/background/background_constant.cc:41-49

@@ -126,6 +126,9 @@ YG_DEV void dl_samples(const RenderArgs &ra, const yafgpu_light &light, int li, 
 	for(int k = 0; k <= is; ++k) { s_1 = hal_2.next(); s_2 = hal_3.next(); }   // the incremental sequence, replayed
 }
 
+// Material::isFlat() as doLightEstimation reads it (:105, :189).  Off sp.material_: under a mask that is the mask's, false, while the chosen
+// material's own eval keeps its flag (yafgpu_material::flat 2).  Masks live in kernels with textures only; the others test the word as before.
+YG_DEV bool wf_is_flat(const yafgpu_material &mat) { return YAFGPU_FEAT_TEXTURE ? (mat.flat & 1) != 0 : mat.flat != 0; }
 // One candidate of MonteCarloIntegrator::doLightEstimation (integrator_montecarlo.cc:78-345): light
 // `li`, half `phase` of the MIS pair (0 light sampling :161-262, 1 BSDF sampling :285-333; Dirac lights
 // have a single half :94-148).  Returns whether a shadow ray is wanted and, if so, the ray and the
@@ -142,7 +145,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		if(YG_LIGHT_IS(light, YAFGPU_LIGHT_DIRECTIONAL)) { if(!directionallight_illuminate(light, sp.p, lcol, r_dir, r_tmax)) return false; }
 		else if(!pointlight_illuminate(light, sp.p, lcol, r_dir, r_tmax)) return false;
 		r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
-		const float angle = mat.flat ? 1.f : fabsf(dot(sp.n, r_dir));
+		const float angle = wf_is_flat(mat) ? 1.f : fabsf(dot(sp.n, r_dir));
 		contrib = (mat_eval(mat, dat, sp, wo, r_dir, kAll) * lcol) * angle;
 		return true;
 	}
@@ -158,7 +161,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		if(ls_pdf > 1e-6f)
 		{
 			const Col surf_col = mat_eval(mat, dat, sp, wo, r_dir, kAll);
-			const float angle = mat.flat ? 1.f : fabsf(dot(sp.n, r_dir));
+			const float angle = wf_is_flat(mat) ? 1.f : fabsf(dot(sp.n, r_dir));
 			// the light colour of this half is what illumSample returned (ls.col_, :178-262): col_pdf for the sun, the background in the sampled
 			// direction for the background light, the fixed colour otherwise
 			if(YG_LIGHT_HAS(YAFGPU_LIGHT_SPHERE) && !light_can_intersect(light.type))
@@ -243,6 +246,21 @@ YG_DEV const yafgpu_material &wf_mat_hit(const DevScene &sc, const SurfPt &sp, i
 	}
 #endif
 	return m;
+}
+// A hit on a triangle of a mask material (MaskMaterial::initBsdf, material_mask.cc:40-51): the vertex gets the record the mask picks there,
+// before that record's own bump and nodes run — every later step, park and resume sees an ordinary material.  (A mask has nodes, so a
+// scene without node data has none; a kernel without textures never meets one: a mask some triangle uses sends the scene to the general
+// kernel, yafgpu_scene_create's has_textures.)
+YG_DEV void wf_mask_hit(const DevScene &sc, SurfPt &sp, int tri, float bu, float bv)
+{
+#if YAFGPU_FEAT_TEXTURE
+	if(sc.tex.nodes == nullptr) return;
+	const yafgpu_material &m = sc.mats[sp.mat];
+	if(m.type != YAFGPU_MAT_MASKED) return;
+	sp.mat = mask_select(sc.tex, sc.cam, m, tri, bu, bv, sp.p, sp.n, sp.ng, false);
+#else
+	(void)sc; (void)sp; (void)tri; (void)bu; (void)bv;
+#endif
 }
 // Bump mapping (NodeMaterial::evalBump + Material::applyBump at the head of every initBsdf, material_shiny_diffuse.cc:171-175,
 // material_glossy.cc:56, material_coated_glossy.cc:73, material_glass.cc:62): the shading frame the rest of the vertex sees.
@@ -713,6 +731,7 @@ YG_DEV int st_after_closest(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint
 		const V3 dir = v3(r1);
 		SurfPt sp0;
 		get_surface(sc, tri, v3(r0) + dir * ans.y, ans.z, ans.w, sp0);
+		wf_mask_hit(sc, sp0, tri, ans.z, ans.w);
 		if(YAFGPU_FEAT_TEXTURE && sc.tex.has_bump) { const bool bumped = wf_bump_hit(sc, sp0, tri, ans.z, ans.w); REC(24) = f4(sp0.nu, bumped ? 1.f : 0.f); }
 		yafgpu_material m_tmp;
 		const yafgpu_material &m = wf_mat_hit(sc, sp0, tri, ans.z, ans.w, m_tmp);
@@ -765,6 +784,7 @@ YG_DEV int st_after_closest(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint
 	const V3 dir = v3(r1);
 	SurfPt hit;
 	get_surface(sc, tri, v3(r0) + dir * ans.y, ans.z, ans.w, hit);
+	wf_mask_hit(sc, hit, tri, ans.z, ans.w);
 	if(YAFGPU_FEAT_TEXTURE && sc.tex.has_bump) { const bool bumped = wf_bump_hit(sc, hit, tri, ans.z, ans.w); REC(25) = f4(hit.nu, bumped ? 1.f : 0.f); }
 	yafgpu_material pm_tmp;
 	const yafgpu_material &pm = wf_mat_hit(sc, hit, tri, ans.z, ans.w, pm_tmp);

@@ -50,7 +50,7 @@ C_API_SYMBOLS = [
     "yafaray_createInterface", "yafaray_destroyInterface", "yafaray_getLastError", "yafaray_getVersion",
     "yafaray_startScene", "yafaray_startGeometry", "yafaray_endGeometry", "yafaray_getNextFreeId",
     "yafaray_startTriMesh", "yafaray_endTriMesh", "yafaray_addVertex", "yafaray_addNormal", "yafaray_addTriangle",
-    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getCamera", "yafaray_getIntegratorAO", "yafaray_addTriangles",
+    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getCamera", "yafaray_getIntegratorAO", "yafaray_getMaskMaterial", "yafaray_getMaterialTable", "yafaray_addTriangles",
     "yafaray_startTriMeshPtr", "yafaray_addVertexWithOrco", "yafaray_addUv", "yafaray_addTriangleWithUv",
     "yafaray_startCurveMesh", "yafaray_endCurveMesh", "yafaray_addInstance",
     "yafaray_paramsSetColorArray", "yafaray_paramsSetMatrix", "yafaray_paramsSetMatrixD", "yafaray_setInputColorSpace",
@@ -103,6 +103,8 @@ def load():
         "yafaray_getBackground": (ci, [vp, cp, vp]),
         "yafaray_getCamera": (ci, [vp, cp, vp]),
         "yafaray_getIntegratorAO": (ci, [vp, cp, C.POINTER(ci), C.POINTER(ci), C.POINTER(cf), C.POINTER(cf)]),
+        "yafaray_getMaskMaterial": (ci, [vp, cp, vp]),
+        "yafaray_getMaterialTable": (ci, [vp, vp, ci]),
         "yafaray_addTriangles": (ci, [vp, ci, C.POINTER(cf), ci, C.POINTER(ci), vp]),
         "yafaray_startTriMeshPtr": (ci, [vp, C.POINTER(C.c_uint), ci, ci, ci, ci, ci, ci]),
         "yafaray_addVertexWithOrco": (ci, [vp, cd, cd, cd, cd, cd, cd]), "yafaray_addUv": (ci, [vp, cf, cf]),
@@ -368,6 +370,29 @@ class Interface:
         self._ok(self._L.yafaray_getIntegratorAO(self._h, _b(name), C.byref(do_ao), C.byref(samples), C.byref(dist), col), "getIntegratorAO")
         return {"do_AO": bool(do_ao.value), "AO_samples": int(samples.value), "AO_distance": np.float32(dist.value),
                 "AO_color": np.array(list(col), dtype=np.float32)}
+
+    def getMaskMaterial(self, name):
+        """what createMaterial parsed for the mask_mat `name`, as a dict: the indices of material1 / material2 in creation order, the
+        threshold as the float32 it is kept as, the mask node's slot among the mask's n_nodes nodes, and the material-level fields"""
+        out = np.zeros(8, dtype=np.int32)
+        self._ok(self._L.yafaray_getMaskMaterial(self._h, _b(name), out.ctypes.data_as(C.c_void_p)), "getMaskMaterial")
+        return {"material1": int(out[0]), "material2": int(out[1]), "threshold": out.view(np.float32)[2], "mask_slot": int(out[3]), "n_nodes": int(out[4]),
+                "receive_shadows": bool(out[5]), "visibility": int(out[6]), "bsdf_flags": int(out[7]) & 0xffffffff}
+
+    MATERIAL_WORDS = 96
+    # word offsets of the yafgpu_material fields (include/yafgpu.h) that tests of the material table read
+    MATERIAL_FIELDS = {"type": 0, "visibility": 1, "receive_shadows": 2, "flat": 3, "bsdf_flags": 4, "c_index": 10, "transmit_filter": 27, "is_transparent": 30,
+                       "has_vol_i": 61, "beer_sigma": 62, "node_first": 65, "n_nodes": 66, "sh_diffuse": 67, "bump_first": 79, "n_bump": 80,
+                       "additional_depth": 82, "transp_bias_factor": 83, "transp_bias_mult": 84}
+
+    def getMaterialTable(self):
+        """the material table as the device scene gets it: one row of the 96 words of a yafgpu_material (include/yafgpu.h) per record, as
+        int32 (view a float field as float32) — the materials in creation order, then two hidden clones per mask_mat"""
+        n = self._L.yafaray_getMaterialTable(self._h, None, 0)
+        out = np.zeros((max(n, 0), self.MATERIAL_WORDS), dtype=np.int32)
+        if n > 0:
+            self._L.yafaray_getMaterialTable(self._h, out.ctypes.data_as(C.c_void_p), n)
+        return out
 
     # -- params
     def paramsSetPoint(self, name, x, y, z):
