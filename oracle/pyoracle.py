@@ -570,6 +570,9 @@ class OracleScene:
             mdescs.append(d)
         mats = (MaterialDesc * len(scene["materials"]))(*mdescs)
         lights = (LightDesc * max(1, len(scene["lights"])))(*[light_desc(l) for l in scene["lights"]])
+        if scene["camera"].get("type", "perspective") != "perspective":
+            # the restatement holds PerspectiveCamera alone: any other type would be rendered as one, silently
+            raise ValueError(f"oracle: camera type {scene['camera']['type']!r} is not restated (perspective only)")
         cam = camera_desc(scene["camera"])
         self.h = L.yor_scene_create(n, fptr(self.verts), self.tri_mat.ctypes.data_as(C.POINTER(C.c_int32)),
                                     None if self.vn is None else fptr(self.vn),

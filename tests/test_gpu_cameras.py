@@ -8,14 +8,11 @@ import numpy as np
 import pytest
 
 from libyafaray_amd import Interface, scenes
-from oracle import pyoracle as po
+from tests.film_fixture import BACKGROUND, FACE_COLOURS, H, TILE, W, box_scene, box_settings, sample_offsets
 from tests.test_cameras_host import (F, PROJECTIONS, RECORD, architect_record, screenproject, shoot)
-from tests.test_gpu_ao import M32, sampling_offs
 from tests.test_gpu_components import exact
 
 pytestmark = pytest.mark.gpu
-
-W, H, TILE = 24, 16, 7
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -39,28 +36,6 @@ def angular(projection="equidistant", circular=True, mirrored=False, **kw):
 
 
 # ---- scenes ----------------------------------------------------------------------------------------------------------
-FACE_COLOURS = [(0.5, 0.25, 0.125), (0.125, 0.5, 0.25), (0.25, 0.125, 0.5), (0.75, 0.5, 0.25), (0.25, 0.75, 0.5), (0.5, 0.25, 0.75)]
-BACKGROUND = (0.125, 0.375, 0.625)
-
-
-def box_scene(cam, removed=2):
-    """a closed box of half-width 2 around the camera: six light_mat quads, double sided, colours in eighths (sums of a few samples are
-    exact); face `removed` (+x) is left out so that some rays escape to the background"""
-    q, r = scenes._quad, 2.0
-    faces = [q((-r, -r, r), (r, -r, r), (r, r, r), (-r, r, r)), q((-r, -r, -r), (r, -r, -r), (r, -r, r), (-r, -r, r)),
-             q((r, -r, -r), (r, r, -r), (r, r, r), (r, -r, r)), q((r, r, -r), (-r, r, -r), (-r, r, r), (r, r, r)),
-             q((-r, r, -r), (-r, -r, -r), (-r, -r, r), (-r, r, r)), q((-r, -r, -r), (-r, r, -r), (r, r, -r), (r, -r, -r))]
-    keep = [k for k in range(6) if k != removed]
-    verts = np.concatenate([faces[k] for k in keep]).astype(F)
-    mats = np.repeat(np.arange(len(keep)), 2).astype(np.int32)
-    materials = [{"type": "light_mat", "color": FACE_COLOURS[k], "power": 1.0, "double_sided": True} for k in keep]
-    return {"verts": verts, "tri_mat": mats, "vnormals": None, "materials": materials, "lights": [], "camera": dict(cam)}
-
-
-def box_settings(spp=1, **kw):
-    return scenes.render_settings(kw.pop("width", W), kw.pop("height", H), spp, integrator="directlighting", tile_size=TILE, background=BACKGROUND, **kw)
-
-
 def soup_scene(cam, n_lights=2):
     sc = scenes.cornell_soup(12, seed=1, n_lights=n_lights, res=(cam["resx"], cam["resy"]))
     sc["camera"] = dict(cam)
@@ -167,29 +142,13 @@ def sample_positions(rd):
     """the camera samples of a render, pixel by pixel: [(film pixels the sample is added to, x, y)] — the positions of
     TiledIntegrator::renderTile (integrator_tiled.cc:386-403) and the footprint of the box filter of half-width 0.501
     (ImageFilm::addSample), enumerated as tests/test_gpu_ao.py::Restatement.camera_samples does"""
-    L = po.lib()
-    spp, passes = int(rd.get("AA_minsamples", 1)), int(rd.get("AA_passes", 1))
-    inc = int(rd.get("AA_inc_samples", spp))
-    schedule = [(0, spp)] + [(spp + k * inc, inc) for k in range(passes - 1)]
-    assert passes == 1 or rd.get("AA_threshold") == 0.0
     x0, y0 = rd.get("xstart", 0), rd.get("ystart", 0)
     out = []
-    for py in range(y0, y0 + rd["height"]):
-        for px in range(x0, x0 + rd["width"]):
-            so = sampling_offs(px, py)
-            for pass_offset, n in schedule:
-                for s in range(n):
-                    pixel_sample = (pass_offset + s) & M32
-                    if passes > 1:
-                        dx, dy = F(L.yor_ri_vdc(pixel_sample, so)), F(L.yor_ri_s(pixel_sample, so))
-                    elif n > 1:
-                        d_1 = F(1.0 / float(F(n)))
-                        dx, dy = F((0.5 + float(F(s))) * float(d_1)), F(L.yor_ri_lp((s + so) & M32, 0))
-                    else:
-                        dx, dy = F(0.5), F(0.5)
-                    edge = lambda d: int(float(d) + float(F(0.501)) - 1.0 + (0.5 - 1.4e-11)) >= 1
-                    pixels = [(py + j - y0, px + i - x0) for j in range(1 + edge(dy)) for i in range(1 + edge(dx))]
-                    out.append(([(y, x) for y, x in pixels if y < rd["height"] and x < rd["width"]], F(F(px) + dx), F(F(py) + dy)))
+    for px, py, dx, dy in zip(*(sample_offsets(rd)[k] for k in (0, 1, 4, 5))):
+        px, py = int(px), int(py)
+        edge = lambda d: int(float(d) + float(F(0.501)) - 1.0 + (0.5 - 1.4e-11)) >= 1
+        pixels = [(py + j - y0, px + i - x0) for j in range(1 + edge(dy)) for i in range(1 + edge(dx))]
+        out.append(([(y, x) for y, x in pixels if y < rd["height"] and x < rd["width"]], F(F(px) + dx), F(F(py) + dy)))
     return out
 
 
