@@ -79,10 +79,19 @@ int yafaray_addVertexWithOrco(yafaray_interface_t *yi, double x, double y, doubl
 int yafaray_addUv(yafaray_interface_t *yi, float u, float v);                    /* :71 */
 yafaray_bool_t yafaray_addTriangleWithUv(yafaray_interface_t *yi, int a, int b, int c, int uv_a, int uv_b, int uv_c,
                                          const yafaray_material_t *mat);          /* :70, the UV overload of addTriangle */
+/* Scene::addInstance (scene.cc:1105-1130): one more object, under an id of its own from getNextFreeId, whose triangles are the base
+ * mesh's under obj_to_world (row major).  Any mesh can be the base, flagged BASEMESH (type & 0x0200) or not; no geometry-state check.  The
+ * instance keeps the base's has_orco / has_uv / is_smooth / normals_exported flags AS THEY ARE NOW (object_geom.cc:104-121): a base
+ * smoothed later leaves it unsmoothed.  Refused, with the cause in getLastError: a base id that names no mesh, a null matrix, a matrix
+ * with a non-finite entry, a base that is itself an instance.  The triangles are made on the device at scene set-up. */
+yafaray_bool_t yafaray_addInstance(yafaray_interface_t *yi, unsigned int base_object_id, const float *obj_to_world_16); /* :73 */
+/* extension (test support): what addInstance stored, in object-id order: up to max_instances records of 22 32-bit words: own id, base
+ * id, has_orco, has_uv, is_smooth, normals_exported (the flags as they stood at the call), then the 16 matrix floats.  Returns the
+ * number of instances */
+int yafaray_getInstances(yafaray_interface_t *yi, void *out, int max_instances);
 /* refused with a diagnostic (outside the path's scope): */
 yafaray_bool_t yafaray_startCurveMesh(yafaray_interface_t *yi, unsigned int id, int vertices, int obj_pass_index);       /* :62 */
 yafaray_bool_t yafaray_endCurveMesh(yafaray_interface_t *yi, const yafaray_material_t *mat, float strand_start, float strand_end, float strand_shape); /* :65 */
-yafaray_bool_t yafaray_addInstance(yafaray_interface_t *yi, unsigned int base_object_id, const float *obj_to_world_16); /* :73 */
 /* extension (test support): the per-triangle-corner normals smoothMesh computed, n_tris*9 floats; an all-zero triple = geometric normal */
 yafaray_bool_t yafaray_getMeshCornerNormals(yafaray_interface_t *yi, unsigned int id, float *out, int n_floats);
 /* extension (test support): the scene's enabled lights in Scene::addLight order, as the device gets them: up to max_lights

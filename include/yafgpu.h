@@ -231,6 +231,38 @@ typedef struct yafgpu_camera
 	int32_t projection;            /* YAFGPU_ANGULAR_* */
 } yafgpu_camera;
 
+/* Instanced geometry (Scene::addInstance, scene.cc:1105-1130).  The reference has no second tree level: a TriangleObjectInstance's
+ * TriangleInstance triangles go into the one kd-tree beside every other triangle (scene.cc:797-817), so an instance is more rows of the
+ * triangle, shading and texture-coordinate arrays.  With segments, yafgpu_scene_create makes ALL rows of the scene on the device, in segment
+ * order (csrc/yafgpu_assemble.hip); only the base meshes and the matrices cross the bus.
+ *   plain segment     rows [first, first + count) of the descriptor's own arrays (verts, tri_mat, vnormals, tri_uv, tri_orco), as they are
+ *   instance segment  rows [first, first + count) of the base pools below under matrix m (row major, Matrix4 * Point3, matrix4.h:89-94) */
+enum { YAFGPU_SEGMENT_PLAIN = 0, YAFGPU_SEGMENT_INSTANCE = 1 };
+/* what TriangleObjectInstance copied from its base when it was made (object_geom.cc:104-121) */
+enum { YAFGPU_INSTANCE_SMOOTH = 1,     /* is_smooth_ || normals_exported_: TriangleInstance::getSurface reads vertex normals (triangle.cc:210-222) */
+       YAFGPU_INSTANCE_ORCO = 2,       /* has_orco_: the base's orco values (triangle.cc:224-235), else the hit point */
+       YAFGPU_INSTANCE_UV = 4 };       /* has_uv_: the base's UVs (triangle.cc:247-256) */
+typedef struct yafgpu_segment
+{
+	int32_t kind;                /* YAFGPU_SEGMENT_* */
+	int32_t first, count;
+	uint32_t flags;              /* YAFGPU_INSTANCE_*, instance segments only */
+	float m[16];                 /* obj_to_world, instance segments only */
+} yafgpu_segment;
+typedef struct yafgpu_instancing
+{
+	int32_t n_segments;          /* 0: no instanced geometry, every other field is ignored */
+	const yafgpu_segment *segments;      /* in object-id order: the flattening order of Scene::update */
+	/* base mesh pools, one row per base triangle */
+	int32_t n_base_tris;
+	const float *base_verts;     /* n_base_tris*9: the corners a, b, c */
+	const int32_t *base_mat;     /* n_base_tris: the base triangle's material (triangle.cc:296) */
+	const float *base_vnormals;  /* NULL or n_base_tris*9: the base's vertex normals per corner; an all-zero triple = the corner has none */
+	const uint8_t *base_vn_index0;       /* with base_vnormals, n_base_tris bytes: bit c set = corner c's normal has index 0 in the base's normal
+	                                        array, which TriangleInstance::getSurface's `index > 0` test sends to the geometric normal */
+	const float *base_uv, *base_orco;    /* NULL or n_base_tris*6 / *9, as tri_uv / tri_orco (first word NaN: none) */
+} yafgpu_instancing;
+
 typedef struct yafgpu_scene_desc
 {
 	int32_t n_tris;
@@ -254,6 +286,9 @@ typedef struct yafgpu_scene_desc
 	                                The environment variable YAFGPU_BUILD=device|host overrides it. */
 	yafgpu_background background; /* kind 0: none.  A texture background is evaluated per escaping ray (yafgpu_render_params::background is
 	                                the constant case's colour and keeps working without this record) */
+	yafgpu_instancing inst;      /* optional, zeroed = none: then n_tris rows of the arrays above are the scene, made by the host loop as
+	                                ever.  With segments the arrays above hold the plain triangles only (n_tris of them) and the scene is
+	                                the segments' rows; yafgpu_tree_info::n_tris counts those */
 } yafgpu_scene_desc;
 
 typedef struct yafgpu_render_params

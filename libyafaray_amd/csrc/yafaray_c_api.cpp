@@ -53,12 +53,21 @@ struct Mesh
 	std::vector<int> tri_mat;
 	bool normals_exported = false, smooth = false, visible = true, base = false;
 	std::vector<float> smooth_normals; // per triangle corner, filled by smoothMesh
+	bool smooth_by_vertex = false;     // smoothMesh's loop for angle >= 180 gave every corner the normal whose index is its vertex index (scene.cc:420-448)
 	// texture coordinates as the exporter gives them (TriangleObject::points_ interleaves orco, uv_values_ / uv_offsets_;
 	// object_geom/object_geom_mesh.cc): kept for the shader nodes; untextured shading never reads them
 	bool has_orco = false, has_uv = false;
 	std::vector<float> orco;          // xyz per vertex
 	std::vector<float> uv;            // u, v per addUv
 	std::vector<int> tri_uv;          // uv_a, uv_b, uv_c per triangle (when has_uv)
+};
+
+// TriangleObjectInstance (object_geom.cc:104-121): the base, obj_to_world and the four flags it copied from the base when it was made
+struct Instance
+{
+	unsigned int base = 0;
+	float m[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};     // row major
+	bool has_orco = false, has_uv = false, smooth = false, normals_exported = false;
 };
 
 struct IntegratorCfg
@@ -109,6 +118,7 @@ struct yafaray_interface
 	// scene state (scene.cc:110-131): 0 ready, 1 geometry, 2 object
 	int state = -1;
 	std::map<unsigned int, Mesh> meshes;
+	std::map<unsigned int, Instance> instances;      // object ids are shared with meshes: the id decides the place in the flattening order
 	Mesh *cur = nullptr, *last = nullptr;   // last: Scene's cur_obj_ outlives endTriMesh (smoothMesh(0, angle))
 	unsigned int next_id = 1;
 	bool geometry_changed = true;
@@ -1094,18 +1104,19 @@ const char *yafaray_getVersion(void) { return "yafgpu-0.1 (MI355X path-tracing c
 yafaray_bool_t yafaray_startScene(yafaray_interface_t *yi, int type)
 {
 	if(type != 0) return fail(yi, "startScene: only scene type 0 (\"triangle\") is supported (import_xml.cc:339-347)");
-	yi->state = 0; yi->meshes.clear(); yi->cur = nullptr; yi->last = nullptr; yi->geometry_changed = true; yi->prepared = false; yi->scene_dirty = true;
+	yi->state = 0; yi->meshes.clear(); yi->instances.clear(); yi->cur = nullptr; yi->last = nullptr; yi->geometry_changed = true; yi->prepared = false; yi->scene_dirty = true;
 	return 1;
 }
 yafaray_bool_t yafaray_startGeometry(yafaray_interface_t *yi) { if(yi->state != 0) return fail(yi, "startGeometry: wrong state"); yi->state = 1; return 1; }
 yafaray_bool_t yafaray_endGeometry(yafaray_interface_t *yi) { if(yi->state != 1) return fail(yi, "endGeometry: wrong state"); yi->state = 0; return 1; }
-unsigned int yafaray_getNextFreeId(yafaray_interface_t *yi) { while(yi->meshes.count(yi->next_id)) ++yi->next_id; return yi->next_id++; }
+unsigned int yafaray_getNextFreeId(yafaray_interface_t *yi) { while(yi->meshes.count(yi->next_id) || yi->instances.count(yi->next_id)) ++yi->next_id; return yi->next_id++; }
 
 yafaray_bool_t yafaray_startTriMesh(yafaray_interface_t *yi, unsigned int id, int vertices, int triangles, yafaray_bool_t has_orco, yafaray_bool_t has_uv, int type, int)
 {
 	if(yi->state != 1) return fail(yi, "startTriMesh: wrong state");
 	if((type & 0xFF) != 0) return fail(yi, "startTriMesh: only TRIM meshes (type 0) are supported");
 	note_srand(yi, ++g_object_index_auto);          // ObjectGeometric::ObjectGeometric, object_geom.cc:39-43
+	yi->instances.erase(id);                        // meshes_[id] is one slot: a mesh started under an instance's id takes its place
 	Mesh &m = yi->meshes[id];
 	m = Mesh();
 	m.visible = !(type & 0x0100); m.base = (type & 0x0200) != 0;
@@ -1191,7 +1202,45 @@ yafaray_bool_t yafaray_startTriMeshPtr(yafaray_interface_t *yi, unsigned int *id
 // outside the hot path's scope: refused with a diagnostic, never routed anywhere else
 yafaray_bool_t yafaray_startCurveMesh(yafaray_interface_t *yi, unsigned int, int, int) { return fail(yi, "startCurveMesh: curve (strand) meshes are outside the GPU path's scope"); }
 yafaray_bool_t yafaray_endCurveMesh(yafaray_interface_t *yi, const yafaray_material_t *, float, float, float) { return fail(yi, "endCurveMesh: curve (strand) meshes are outside the GPU path's scope"); }
-yafaray_bool_t yafaray_addInstance(yafaray_interface_t *yi, unsigned int, const float *) { return fail(yi, "addInstance: instanced base meshes are outside the GPU path's scope"); }
+// Scene::addInstance, scene.cc:1105-1130.  No geometry-state check: the XML loader issues it at document level (import_xml.cc:450-460,
+// :640-671).  Any mesh can be a base, flagged BASEMESH or not.
+yafaray_bool_t yafaray_addInstance(yafaray_interface_t *yi, unsigned int base_object_id, const float *obj_to_world)
+{
+	if(yi->instances.count(base_object_id))
+		return fail(yi, "addInstance: the base object " + std::to_string(base_object_id) + " is itself an instance; instances of instances are not built (TriangleObjectInstance takes a TriangleObject's own triangles, object_geom.cc:104-121)");
+	auto base = yi->meshes.find(base_object_id);
+	if(base == yi->meshes.end()) return fail(yi, "addInstance: base mesh for instance doesn't exist: " + std::to_string(base_object_id));
+	if(!obj_to_world) return fail(yi, "addInstance: null matrix");
+	for(int k = 0; k < 16; ++k)
+		if(!std::isfinite(obj_to_world[k])) return fail(yi, "addInstance: non-finite matrix entry m" + std::to_string(k / 4) + std::to_string(k % 4));
+	const unsigned int id = yafaray_getNextFreeId(yi);
+	note_srand(yi, ++g_object_index_auto);          // TriangleObjectInstance is an ObjectGeometric: its constructor runs (object_geom.cc:39-43)
+	Instance &in = yi->instances[id];
+	in.base = base_object_id;
+	std::memcpy(in.m, obj_to_world, sizeof in.m);
+	// copied now (object_geom.cc:108-111): a base smoothed after this call leaves the instance unsmoothed
+	const Mesh &b = base->second;
+	in.has_orco = b.has_orco; in.has_uv = b.has_uv; in.smooth = b.smooth; in.normals_exported = b.normals_exported;
+	yi->geometry_changed = true; yi->prepared = false; yi->scene_dirty = true;
+	return 1;
+}
+// what addInstance stored, for tests: records of 22 words {own id, base id, has_orco, has_uv, is_smooth, normals_exported, 16 floats}
+// in object-id order; returns the number of instances
+int yafaray_getInstances(yafaray_interface_t *yi, void *out, int max_instances)
+{
+	const int n = (int)yi->instances.size();
+	int i = 0;
+	for(const auto &kv : yi->instances)
+	{
+		if(!out || i >= max_instances) break;
+		const Instance &in = kv.second;
+		int32_t w[22] = {(int32_t)kv.first, (int32_t)in.base, in.has_orco ? 1 : 0, in.has_uv ? 1 : 0, in.smooth ? 1 : 0, in.normals_exported ? 1 : 0};
+		std::memcpy(&w[6], in.m, sizeof in.m);
+		std::memcpy((char *)out + (size_t)i * sizeof w, w, sizeof w);
+		++i;
+	}
+	return n;
+}
 unsigned int yafaray_createObject(yafaray_interface_t *yi, const char *) { fail(yi, "createObject: parametric objects (sphere) are outside the GPU path's scope (triangle meshes only)"); return 0u; }
 void *yafaray_createVolumeRegion(yafaray_interface_t *yi, const char *) { fail(yi, "createVolumeRegion: volume regions are outside the GPU path's scope (volume integrator \"none\" only)"); return nullptr; }
 void *yafaray_createImageHandler(yafaray_interface_t *yi, const char *, yafaray_bool_t) { fail(yi, "createImageHandler: image files are written by the caller from the ColorOutput callbacks; no image handlers on the GPU path"); return nullptr; }
@@ -1231,6 +1280,7 @@ yafaray_bool_t yafaray_smoothMesh(yafaray_interface_t *yi, unsigned int id, doub
 {
 	if(yi->state != 1) return fail(yi, "smoothMesh: wrong state (call it between endTriMesh and endGeometry)");
 	Mesh *mp = nullptr;
+	if(id && yi->instances.count(id)) return fail(yi, "smoothMesh: object " + std::to_string(id) + " is an instance: a TriangleObjectInstance has no normals of its own to smooth (it reads its base's)");
 	if(id) { auto it = yi->meshes.find(id); if(it == yi->meshes.end()) return fail(yi, "smoothMesh: no such mesh"); mp = &it->second; }
 	else { mp = yi->last; if(!mp) return fail(yi, "smoothMesh: no current mesh"); }
 	Mesh &m = *mp;
@@ -1239,6 +1289,7 @@ yafaray_bool_t yafaray_smoothMesh(yafaray_interface_t *yi, unsigned int id, doub
 	yi->geometry_changed = true; yi->prepared = false; yi->scene_dirty = true;
 	if(m.normals_exported && m.normals.size() == m.points.size()) { m.smooth = true; return 1; }      // :402-406
 	m.smooth_normals.assign(nt * 9, 0.f);
+	m.smooth_by_vertex = angle >= 180.f;
 	// face normals: Triangle::recNormal, triangle.h:295-302
 	std::vector<float> fn(nt * 3);
 	for(size_t t = 0; t < nt; ++t)
@@ -1747,7 +1798,7 @@ void yafaray_clearAll(yafaray_interface_t *yi)
 {
 	if(yi->gpu) { yafgpu_scene_destroy(yi->gpu); yi->gpu = nullptr; }
 	yi->materials.clear(); yi->material_order.clear(); yi->textures.clear(); yi->texture_order.clear(); yi->lights.clear(); yi->light_order.clear();
-	yi->cameras.clear(); yi->backgrounds.clear(); yi->integrators.clear(); yi->meshes.clear();
+	yi->cameras.clear(); yi->backgrounds.clear(); yi->integrators.clear(); yi->meshes.clear(); yi->instances.clear();
 	yi->params.dicc.clear(); yi->eparams.clear(); yi->cparams = &yi->params;
 	yi->state = -1; yi->prepared = false; yi->scene_dirty = true; yi->geometry_changed = true; yi->film.clear();
 }
@@ -1902,26 +1953,35 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 	for(auto *m : yi->material_order) if(!m->nodes.empty()) any_nodes = true;
 	std::vector<float> tri_uv, tri_orco;
 	const float kNoOrco = std::numeric_limits<float>::quiet_NaN();
-	for(auto &kv : yi->meshes)
+	// one mesh's rows: corner vertices, materials, vertex normals and texture coordinates per triangle corner
+	auto append_rows = [&](const Mesh &m, bool with_normals, std::vector<float> &verts, std::vector<int32_t> &tri_mat, std::vector<float> &vnormals,
+	                       std::vector<float> &tri_uv, std::vector<float> &tri_orco, std::vector<uint8_t> *index0)
 	{
-		const Mesh &m = kv.second;
-		if(!m.visible || m.base) continue;
 		const size_t nt = m.tri_mat.size();
 		for(size_t t = 0; t < nt; ++t)
 		{
+			uint8_t zero_marks = 0;
 			for(int c = 0; c < 3; ++c)
 			{
 				const int vi = m.tri[3 * t + (size_t)c];
 				verts.push_back(m.points[3 * (size_t)vi]); verts.push_back(m.points[3 * (size_t)vi + 1]); verts.push_back(m.points[3 * (size_t)vi + 2]);
-				if(any_normals)
+				if(with_normals)
 				{
 					if(m.smooth && !m.smooth_normals.empty())
-					{ for(int q = 0; q < 3; ++q) vnormals.push_back(m.smooth_normals[9 * t + 3 * (size_t)c + (size_t)q]); }
+					{
+						for(int q = 0; q < 3; ++q) vnormals.push_back(m.smooth_normals[9 * t + 3 * (size_t)c + (size_t)q]);
+						// the angle-dependent loop appends its normals behind one slot per vertex (scene.cc:417-418, :519): none of them has index 0
+						if(m.smooth_by_vertex && vi == 0) zero_marks |= (uint8_t)(1u << c);
+					}
 					else if(m.normals_exported && m.normals.size() >= 3 * ((size_t)vi + 1))
-					{ vnormals.push_back(m.normals[3 * (size_t)vi]); vnormals.push_back(m.normals[3 * (size_t)vi + 1]); vnormals.push_back(m.normals[3 * (size_t)vi + 2]); }
+					{
+						vnormals.push_back(m.normals[3 * (size_t)vi]); vnormals.push_back(m.normals[3 * (size_t)vi + 1]); vnormals.push_back(m.normals[3 * (size_t)vi + 2]);
+						if(vi == 0) zero_marks |= (uint8_t)(1u << c);      // with exported normals the index is the vertex index
+					}
 					else { vnormals.push_back(0.f); vnormals.push_back(0.f); vnormals.push_back(0.f); }
 				}
 			}
+			if(with_normals && index0) index0->push_back(zero_marks);
 			tri_mat.push_back(m.tri_mat[t]);
 			if(any_nodes)
 			{
@@ -1937,6 +1997,41 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 				}
 			}
 		}
+	};
+	// instances (Scene::addInstance, scene.cc:1105-1130): the flattened scene becomes a list of segments in object-id order, plain meshes as
+	// rows of the arrays above, instances as rows of the base pools under their matrix; the device makes the triangles (yafgpu_instancing)
+	std::vector<yafgpu_segment> segments;
+	std::vector<float> base_verts, base_vnormals, base_uv, base_orco; std::vector<int32_t> base_mat; std::vector<uint8_t> base_index0;
+	std::map<unsigned int, std::pair<int32_t, int32_t>> base_rows;      // base id -> its rows of the pools
+	bool base_normals = false;
+	for(auto &kv : yi->instances) if(kv.second.smooth || kv.second.normals_exported) base_normals = true;
+	auto mesh_it = yi->meshes.begin(); auto inst_it = yi->instances.begin();
+	while(mesh_it != yi->meshes.end() || inst_it != yi->instances.end())
+	{
+		if(inst_it == yi->instances.end() || (mesh_it != yi->meshes.end() && mesh_it->first < inst_it->first))
+		{
+			const Mesh &m = (mesh_it++)->second;
+			if(!m.visible || m.base) continue;
+			yafgpu_segment sg{}; sg.kind = YAFGPU_SEGMENT_PLAIN; sg.first = (int32_t)tri_mat.size();
+			append_rows(m, any_normals, verts, tri_mat, vnormals, tri_uv, tri_orco, nullptr);
+			sg.count = (int32_t)tri_mat.size() - sg.first;
+			segments.push_back(sg);
+			continue;
+		}
+		const Instance &in = (inst_it++)->second;      // visible_ is true whatever the base's visibility (object_geom.cc:112)
+		auto base = yi->meshes.find(in.base);
+		if(base == yi->meshes.end()) return fail(yi, "render: an instance's base mesh " + std::to_string(in.base) + " no longer exists");
+		auto rows = base_rows.find(in.base);
+		if(rows == base_rows.end())
+		{
+			const int32_t first = (int32_t)base_mat.size();
+			append_rows(base->second, base_normals, base_verts, base_mat, base_vnormals, base_uv, base_orco, &base_index0);
+			rows = base_rows.emplace(in.base, std::make_pair(first, (int32_t)base_mat.size() - first)).first;
+		}
+		yafgpu_segment sg{}; sg.kind = YAFGPU_SEGMENT_INSTANCE; sg.first = rows->second.first; sg.count = rows->second.second;
+		sg.flags = ((in.smooth || in.normals_exported) ? (uint32_t)YAFGPU_INSTANCE_SMOOTH : 0u) | (in.has_orco ? (uint32_t)YAFGPU_INSTANCE_ORCO : 0u) | (in.has_uv ? (uint32_t)YAFGPU_INSTANCE_UV : 0u);
+		std::memcpy(sg.m, in.m, sizeof sg.m);
+		segments.push_back(sg);
 	}
 	if(yi->material_order.empty()) return fail(yi, "render: no materials defined");
 	std::vector<yafgpu_material> mats; std::vector<yafgpu_node> nodes;
@@ -1967,6 +2062,13 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 	{
 		d.n_textures = (int32_t)textures.size(); d.textures = textures.data();
 		d.n_texels = texels.size() / 4; d.texels = texels.data();
+	}
+	if(!yi->instances.empty())
+	{
+		d.inst.n_segments = (int32_t)segments.size(); d.inst.segments = segments.data();
+		d.inst.n_base_tris = (int32_t)base_mat.size(); d.inst.base_verts = base_verts.data(); d.inst.base_mat = base_mat.data();
+		if(base_normals) { d.inst.base_vnormals = base_vnormals.data(); d.inst.base_vn_index0 = base_index0.data(); }
+		if(any_nodes) { d.inst.base_uv = base_uv.data(); d.inst.base_orco = base_orco.data(); }
 	}
 	if(bg) d.background = bg->rec;
 	d.camera = cam->second->c.cam;

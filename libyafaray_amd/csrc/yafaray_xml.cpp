@@ -286,6 +286,32 @@ static yafaray_bool_t load_xml_impl(yafaray_interface_t *yi, const char *path)
 			if(!yafaray_endTriMesh(yi)) { errors.push_back(yafaray_getLastError(yi)); ok = false; }
 			if(!yafaray_endGeometry(yi)) { errors.push_back(yafaray_getLastError(yi)); ok = false; }
 		}
+		else if(el == "instance")
+		{	// :450-460, startElInstance__ / endElInstance__ :640-671: <instance base_object_id="N"><transform m00=".." ... m33=".."/></instance>,
+			// every <transform> one addInstance; the values through atof into a float[4][4]
+			int base = -1;
+			for(const auto &kv : t.attrs) if(kv.first == "base_object_id") base = atoi(kv.second.c_str());
+			for(; t.kind == Tok::Open;)
+			{
+				Tok p = lx.next();
+				if(p.kind == Tok::End) { ok = false; break; }
+				if(p.kind == Tok::Close) { if(p.name == "instance") break; continue; }
+				if(p.name != "transform") continue;
+				float m[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned int given = 0u;
+				for(const auto &kv : p.attrs)
+				{
+					const std::string &k = kv.first;
+					if(k.size() == 3 && k[0] == 'm' && k[1] >= '0' && k[1] <= '3' && k[2] >= '0' && k[2] <= '3')
+					{
+						const int at = 4 * (k[1] - '0') + (k[2] - '0');
+						m[at] = (float)atof(kv.second.c_str()); given |= 1u << at;
+					}
+				}
+				// the reference multiplies with the uninitialised floats of its float[4][4] here (:650-661)
+				if(given != 0xffffu) { errors.push_back("<instance base_object_id=\"" + std::to_string(base) + "\">: <transform> does not give all sixteen mIJ attributes"); ok = false; continue; }
+				if(!yafaray_addInstance(yi, (unsigned int)base, m)) { errors.push_back(yafaray_getLastError(yi)); ok = false; }
+			}
+		}
 		else if(el == "smooth")
 		{	// :429-444
 			unsigned int id = 0; double angle = 181;

@@ -30,6 +30,7 @@
 #include "yafgpu_math.h"
 #include "yafgpu_shading.h"
 #include "yafgpu_texture.h"
+#include "yafgpu_assemble.h"
 
 namespace yafgpu {
 
@@ -674,6 +675,27 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			o[2] = mask_select(sc.tex, sc.cam, m, (int)tri, x[2], x[3], sp.p, sp.n, sp.ng, true) == m.c_index[1] ? 1.f : 0.f;
 			break;
 		}
+		case 28:
+		{	// the rows the device holds for a triangle: in the triangle index (as bits) -> 44 floats: the three float4 records [0, 12), the
+			// geometric normal with the smooth flag [12, 16), the three vertex-normal records [16, 28), the six UV floats [28, 34), the nine
+			// orco floats [34, 43), and at [43] which of the optional arrays the scene has (as bits: 1 vertex normals, 2 UVs, 4 orcos;
+			// an array it has not reads as zeros)
+			if(n_in < 1 || n_out < 44) break;
+			const uint32_t tri = __float_as_uint(x[0]);
+			if(tri >= (uint32_t)sc.n_tris) break;
+			for(int r = 0; r < 3; ++r) { const float4 q = sc.tri[3 * (size_t)tri + (size_t)r]; o[4 * r] = q.x; o[4 * r + 1] = q.y; o[4 * r + 2] = q.z; o[4 * r + 3] = q.w; }
+			{ const float4 q = sc.tri_ng[tri]; o[12] = q.x; o[13] = q.y; o[14] = q.z; o[15] = q.w; }
+			uint32_t have = 0u;
+			if(sc.tri_vn != nullptr)
+			{
+				have |= 1u;
+				for(int r = 0; r < 3; ++r) { const float4 q = sc.tri_vn[3 * (size_t)tri + (size_t)r]; o[16 + 4 * r] = q.x; o[17 + 4 * r] = q.y; o[18 + 4 * r] = q.z; o[19 + 4 * r] = q.w; }
+			}
+			if(sc.tex.tri_uv != nullptr) { have |= 2u; for(int k = 0; k < 6; ++k) o[28 + k] = sc.tex.tri_uv[6 * (size_t)tri + (size_t)k]; }
+			if(sc.tex.tri_orco != nullptr) { have |= 4u; for(int k = 0; k < 9; ++k) o[34 + k] = sc.tex.tri_orco[9 * (size_t)tri + (size_t)k]; }
+			o[43] = __uint_as_float(have);
+			break;
+		}
 		default: break;
 	}
 }
@@ -846,6 +868,111 @@ template<typename T> static int upload(yafgpu_scene *s, const T *src, size_t n, 
 	return 0;
 }
 
+// ---- instanced geometry (yafgpu_instancing): the scene's rows are made by yafgpu_assemble.hip -------------------------------
+// Every range the kernel will index is checked here, on the host, before anything is launched.
+static int check_instancing(const yafgpu_scene_desc *d)
+{
+	const yafgpu_instancing &in = d->inst;
+	if(!in.segments) return fail(-1, "instanced geometry: null segment list");
+	if(in.n_base_tris < 0) return fail(-3, "instanced geometry: negative base triangle count");
+	if(d->n_tris > 0 && (!d->verts || !d->tri_mat)) return fail(-1, "instanced geometry: plain triangles without vertices or materials");
+	if(in.n_base_tris > 0 && (!in.base_verts || !in.base_mat)) return fail(-1, "instanced geometry: base triangles without vertices or materials");
+	if(in.base_vnormals && !in.base_vn_index0) return fail(-1, "instanced geometry: base vertex normals without their index-0 marks");
+	uint64_t total = 0;
+	for(int k = 0; k < in.n_segments; ++k)
+	{
+		const yafgpu_segment &sg = in.segments[k];
+		if(sg.kind != YAFGPU_SEGMENT_PLAIN && sg.kind != YAFGPU_SEGMENT_INSTANCE) return fail(-3, "instanced geometry: segment " + std::to_string(k) + ": unknown kind");
+		const int64_t room = sg.kind == YAFGPU_SEGMENT_INSTANCE ? in.n_base_tris : d->n_tris;
+		if(sg.first < 0 || sg.count < 0 || (int64_t)sg.first + (int64_t)sg.count > room)
+			return fail(-3, "instanced geometry: segment " + std::to_string(k) + ": rows outside the " + (sg.kind == YAFGPU_SEGMENT_INSTANCE ? "base pools" : "plain arrays"));
+		total += (uint64_t)sg.count;
+	}
+	if(total > (uint64_t)INT32_MAX / 9u) return fail(-3, "instanced geometry: more than " + std::to_string(INT32_MAX / 9) + " triangles after flattening");
+	for(int i = 0; i < in.n_base_tris; ++i)
+		if(in.base_mat[i] < 0 || in.base_mat[i] >= d->n_materials) return fail(-3, "base triangle material index out of range");
+	for(size_t k = 0; k < (size_t)in.n_base_tris * 9; ++k)
+		if(!std::isfinite(in.base_verts[k])) return fail(-3, "non-finite vertex coordinate in base triangle " + std::to_string(k / 9));
+	return 0;
+}
+
+struct AssembledRows      // device arrays owned by the scene (yafgpu_scene::allocs)
+{
+	uint32_t n = 0;
+	const float4 *rec = nullptr, *ng = nullptr, *vn = nullptr;
+	const float *uv = nullptr, *orco = nullptr, *e3 = nullptr;
+	const yafgpu_material *mats = nullptr;
+};
+
+template<typename T> static int scene_alloc(yafgpu_scene *s, size_t n, T **dst)
+{
+	void *p = nullptr;
+	const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+	HIP_OK(hipMalloc(&p, bytes));
+	s->allocs.push_back(p);
+	s->info.device_bytes += bytes;
+	*dst = (T *)p;
+	return 0;
+}
+template<typename T> static int temp_upload(DevMem<T> &m, const T *src, size_t n)
+{
+	if(!src || n == 0) return 0;
+	HIP_OK(m.alloc(n));
+	HIP_OK(hipMemcpy(m.p, src, n * sizeof(T), hipMemcpyHostToDevice));
+	return 0;
+}
+
+// h_verts: the flattened scene's corner vertices, the only output that comes back (the tree builders and the non-finite check read them)
+static int assemble_scene(yafgpu_scene *s, const yafgpu_scene_desc *d, AssembledRows &out, std::vector<float> &h_verts)
+{
+	const yafgpu_instancing &in = d->inst;
+	std::vector<yafgpu_segment> segs; std::vector<uint32_t> first;
+	bool smooth_segment = d->vnormals != nullptr;
+	for(int k = 0; k < in.n_segments; ++k)
+	{
+		const yafgpu_segment &sg = in.segments[k];
+		if(sg.count == 0) continue;
+		first.push_back(out.n); segs.push_back(sg); out.n += (uint32_t)sg.count;
+		if(sg.kind == YAFGPU_SEGMENT_INSTANCE && (sg.flags & YAFGPU_INSTANCE_SMOOTH) && in.base_vnormals) smooth_segment = true;
+	}
+	first.push_back(out.n);
+	h_verts.assign((size_t)out.n * 9, 0.f);
+	int rc = 0;
+	if((rc = upload(s, d->materials, (size_t)d->n_materials, &out.mats))) return rc;
+	const size_t np = (size_t)d->n_tris, nb = (size_t)in.n_base_tris, n = out.n;
+	const bool texcoords = d->n_nodes > 0 && d->nodes;      // what the shader nodes read
+	bool bump = false;
+	for(int i = 0; i < d->n_materials && texcoords; ++i) if(d->materials[i].n_bump > 0) bump = true;
+	DevMem<yafgpu_segment> d_segs; DevMem<uint32_t> d_first;
+	DevMem<float> p_verts, p_vn, p_uv, p_orco, b_verts, b_vn, b_uv, b_orco, d_verts; DevMem<int32_t> p_mat, b_mat; DevMem<uint8_t> b_vn0;
+	if((rc = temp_upload(d_segs, segs.data(), segs.size())) || (rc = temp_upload(d_first, first.data(), first.size()))) return rc;
+	if((rc = temp_upload(p_verts, d->verts, np * 9)) || (rc = temp_upload(p_mat, d->tri_mat, np)) || (rc = temp_upload(p_vn, d->vnormals, np * 9))) return rc;
+	if(texcoords && ((rc = temp_upload(p_uv, d->tri_uv, np * 6)) || (rc = temp_upload(p_orco, d->tri_orco, np * 9)))) return rc;
+	if((rc = temp_upload(b_verts, in.base_verts, nb * 9)) || (rc = temp_upload(b_mat, in.base_mat, nb))) return rc;
+	if((rc = temp_upload(b_vn, in.base_vnormals, nb * 9)) || (rc = temp_upload(b_vn0, in.base_vn_index0, in.base_vnormals ? nb : 0))) return rc;
+	if(texcoords && ((rc = temp_upload(b_uv, in.base_uv, nb * 6)) || (rc = temp_upload(b_orco, in.base_orco, nb * 9)))) return rc;
+	float4 *rec = nullptr, *ng = nullptr, *vn = nullptr; float *uv = nullptr, *orco = nullptr, *e3 = nullptr;
+	if((rc = scene_alloc(s, 3 * n, &rec)) || (rc = scene_alloc(s, n, &ng))) return rc;
+	if(smooth_segment && (rc = scene_alloc(s, 3 * n, &vn))) return rc;
+	if(texcoords && ((rc = scene_alloc(s, 6 * n, &uv)) || (rc = scene_alloc(s, 9 * n, &orco)))) return rc;
+	if(bump && (rc = scene_alloc(s, 3 * n, &e3))) return rc;
+	HIP_OK(d_verts.alloc(9 * n));
+	AssembleArgs a{};
+	a.segs = d_segs.p; a.seg_first = d_first.p; a.n_segs = (int)segs.size(); a.n_out = out.n;
+	a.p_verts = p_verts.p; a.p_mat = p_mat.p; a.p_vn = p_vn.p; a.p_uv = p_uv.p; a.p_orco = p_orco.p;
+	a.b_verts = b_verts.p; a.b_mat = b_mat.p; a.b_vn = b_vn.p; a.b_vn0 = b_vn0.p; a.b_uv = b_uv.p; a.b_orco = b_orco.p;
+	a.mats = out.mats;
+	a.rec = rec; a.ng = ng; a.vn = vn; a.uv = uv; a.orco = orco; a.e3 = e3; a.verts = d_verts.p;
+	HIP_OK(assemble_rows(a));
+	HIP_OK(hipDeviceSynchronize());
+	if(n) HIP_OK(hipMemcpy(h_verts.data(), d_verts.p, 9 * n * sizeof(float), hipMemcpyDeviceToHost));
+	// a matrix that overflows a coordinate is refused as a bad vertex is
+	for(size_t k = 0; k < h_verts.size(); ++k)
+		if(!std::isfinite(h_verts[k])) return fail(-3, "non-finite vertex coordinate in triangle " + std::to_string(k / 9));
+	out.rec = rec; out.ng = ng; out.vn = vn; out.uv = uv; out.orco = orco; out.e3 = e3;
+	return 0;
+}
+
 // Faure permutations (the reference ships them as a table, src/common/faure_tables.cc; they are
 // the standard construction of Faure 1992 and are regenerated here rather than copied)
 static void faure_perm(int b, std::vector<int> &out)
@@ -950,6 +1077,8 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 		if(d->materials[i].type == YAFGPU_MAT_ROUGH_GLASS && !(d->materials[i].rg_a2 > 0.f))
 			return fail(-3, "rough glass material " + std::to_string(i) + ": rg_a2 (alpha squared) must be positive");
 	}
+	const bool instanced = d->inst.n_segments > 0;
+	if(instanced) { const int irc = check_instancing(d); if(irc) return irc; }
 	auto *s = new yafgpu_scene();
 	{	// What the scene's materials ask of the pipeline — recursion frames, the glossy loop's wider frames, extra depth, the transparent-shadow
 		// kernel, the kernel variant — is taken from the materials some triangle actually USES: a definition nothing refers to can never be
@@ -958,7 +1087,14 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 		// never a vertex's material).  A mask nothing refers to sizes nothing either, and neither do its records.
 		std::vector<char> &used = s->mat_used;
 		used.assign((size_t)d->n_materials, 0);
-		for(int i = 0; i < d->n_tris; ++i) used[(size_t)d->tri_mat[i]] = 1;
+		if(!instanced) for(int i = 0; i < d->n_tris; ++i) used[(size_t)d->tri_mat[i]] = 1;
+		else
+			for(int k = 0; k < d->inst.n_segments; ++k)
+			{	// the rows some segment makes a triangle of
+				const yafgpu_segment &sg = d->inst.segments[k];
+				const int32_t *mat = sg.kind == YAFGPU_SEGMENT_INSTANCE ? d->inst.base_mat : d->tri_mat;
+				for(int i = sg.first; i < sg.first + sg.count; ++i) used[(size_t)mat[i]] = 1;
+			}
 		for(int i = 0; i < d->n_materials; ++i)
 			if(used[(size_t)i] && d->materials[i].type == YAFGPU_MAT_MASKED) used[(size_t)d->materials[i].c_index[0]] = used[(size_t)d->materials[i].c_index[1]] = 1;
 		for(int i = 0; i < d->n_materials; ++i)
@@ -975,34 +1111,47 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 			if((m.type == YAFGPU_MAT_SHINYDIFFUSE && m.is_transparent) || ((m.type == YAFGPU_MAT_GLASS || m.type == YAFGPU_MAT_ROUGH_GLASS) && m.fake_shadow)) s->has_transparent = true;
 		}
 	}
+	// instanced geometry: every row of the scene is made on the device, and the vertices come back for the tree builders
+	AssembledRows rows; std::vector<float> rows_verts;
+	double assemble_seconds = 0.0;
+	if(instanced)
+	{
+		const auto ta = std::chrono::steady_clock::now();
+		const int arc = assemble_scene(s, d, rows, rows_verts);
+		if(arc) { yafgpu_scene_destroy(s); return arc; }
+		assemble_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
+	}
+	const float *verts = instanced ? rows_verts.data() : d->verts;
+	const int n_tris = instanced ? (int)rows.n : d->n_tris;
 	const auto t0 = std::chrono::steady_clock::now();
 	{
 		// 0: by size -- the device builder wins from a few ten thousand triangles on (1 M: 0.07 s against 0.33 s)
-		bool on_device = d->build_on_device > 0 || (d->build_on_device == 0 && d->n_tris >= 65536);
+		bool on_device = d->build_on_device > 0 || (d->build_on_device == 0 && n_tris >= 65536);
 		if(const char *e = std::getenv("YAFGPU_BUILD")) on_device = std::strcmp(e, "device") == 0;
 		if(on_device)
 		{
 			std::string err;
 			// heavily overlapping geometry can outgrow the builder's arrays: more room, and past that the host builder
 			// (same format, same cost model) rather than no tree
-			const int brc = build_kdtree_device_retry(d->verts, d->n_tris, kDepthCap, s->tree, &err);
-			if(brc == -2 || brc == -3) build_kdtree(d->verts, d->n_tris, kDepthCap, d->build_threads, s->tree);     // arrays outgrown / no device memory for them
-			else if(brc) { delete s; return fail(-20, err); }
+			const int brc = build_kdtree_device_retry(verts, n_tris, kDepthCap, s->tree, &err);
+			if(brc == -2 || brc == -3) build_kdtree(verts, n_tris, kDepthCap, d->build_threads, s->tree);     // arrays outgrown / no device memory for them
+			else if(brc) { yafgpu_scene_destroy(s); return fail(-20, err); }
 		}
-		else build_kdtree(d->verts, d->n_tris, kDepthCap, d->build_threads, s->tree);
+		else build_kdtree(verts, n_tris, kDepthCap, d->build_threads, s->tree);
 	}
 	s->info.build_seconds = s->tree.build_seconds;
 	s->info.n_nodes = (uint32_t)s->tree.nodes.size();
 	s->info.n_leaf_refs = (uint32_t)s->tree.refs.size();
 	s->info.max_depth = (uint32_t)s->tree.max_depth;
-	s->info.n_tris = (uint32_t)d->n_tris;
+	s->info.n_tris = (uint32_t)n_tris;
 	const auto t1 = std::chrono::steady_clock::now();
 
 	// triangle records: Triangle::updateIntersectionCachedValues (triangle.h:197-207), recNormal (:295-302)
-	const size_t nt = (size_t)d->n_tris;
-	std::vector<float4> rec(3 * nt), ng(nt), vn;
+	// (with instanced geometry yafgpu_assemble.hip has made them, by these expressions)
+	const size_t nt = (size_t)n_tris;
+	std::vector<float4> rec(instanced ? 0 : 3 * nt), ng(instanced ? 0 : nt), vn;
 	bool any_smooth = false;
-	for(size_t i = 0; i < nt; ++i)
+	for(size_t i = 0; i < nt && !instanced; ++i)
 	{
 		const float *v = d->verts + 9 * i;
 		const float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]}, e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
@@ -1067,11 +1216,15 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 		if((rc = upload(s, (const uint2 *)tl.leaves.data(), tl.leaves.size() / 2, &dv.tl_leaves))) { yafgpu_scene_destroy(s); return rc; }
 	}
 	if((rc = upload(s, s->tree.refs.data(), s->tree.refs.size(), &dv.refs))) { yafgpu_scene_destroy(s); return rc; }
-	if((rc = upload(s, rec.data(), rec.size(), &dv.tri))) { yafgpu_scene_destroy(s); return rc; }
-	if((rc = upload(s, ng.data(), ng.size(), &dv.tri_ng))) { yafgpu_scene_destroy(s); return rc; }
-	dv.tri_vn = nullptr;
-	if(any_smooth && (rc = upload(s, vn.data(), vn.size(), &dv.tri_vn))) { yafgpu_scene_destroy(s); return rc; }
-	if((rc = upload(s, d->materials, (size_t)d->n_materials, &dv.mats))) { yafgpu_scene_destroy(s); return rc; }
+	if(instanced) { dv.tri = rows.rec; dv.tri_ng = rows.ng; dv.tri_vn = rows.vn; dv.mats = rows.mats; }      // already where the kernels read them
+	else
+	{
+		if((rc = upload(s, rec.data(), rec.size(), &dv.tri))) { yafgpu_scene_destroy(s); return rc; }
+		if((rc = upload(s, ng.data(), ng.size(), &dv.tri_ng))) { yafgpu_scene_destroy(s); return rc; }
+		dv.tri_vn = nullptr;
+		if(any_smooth && (rc = upload(s, vn.data(), vn.size(), &dv.tri_vn))) { yafgpu_scene_destroy(s); return rc; }
+		if((rc = upload(s, d->materials, (size_t)d->n_materials, &dv.mats))) { yafgpu_scene_destroy(s); return rc; }
+	}
 	if((rc = upload(s, d->lights, (size_t)d->n_lights, &dv.lights))) { yafgpu_scene_destroy(s); return rc; }
 	std::memset(&dv.tex, 0, sizeof dv.tex);
 	if((d->n_nodes > 0 && d->nodes) || d->background.kind == YAFGPU_BACKGROUND_TEXTURE)
@@ -1123,9 +1276,10 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 			if(n.type == YAFGPU_NODE_TEXTURE_MAPPER && (n.texture < 0 || n.texture >= d->n_textures)) { yafgpu_scene_destroy(s); return fail(-24, "a texture_mapper node refers to a texture that does not exist"); }
 		}
 		if((rc = upload(s, d->nodes, (size_t)d->n_nodes, &dv.tex.nodes))) { yafgpu_scene_destroy(s); return rc; }
-		if(d->tri_uv && (rc = upload(s, d->tri_uv, nt * 6, &dv.tex.tri_uv))) { yafgpu_scene_destroy(s); return rc; }
-		if(d->tri_orco && (rc = upload(s, d->tri_orco, nt * 9, &dv.tex.tri_orco))) { yafgpu_scene_destroy(s); return rc; }
-		if(s->has_bump)
+		if(instanced) { dv.tex.tri_uv = rows.uv; dv.tex.tri_orco = rows.orco; if(s->has_bump) { dv.tex.tri_e3 = rows.e3; dv.tex.has_bump = 1; } }
+		if(!instanced && d->tri_uv && (rc = upload(s, d->tri_uv, nt * 6, &dv.tex.tri_uv))) { yafgpu_scene_destroy(s); return rc; }
+		if(!instanced && d->tri_orco && (rc = upload(s, d->tri_orco, nt * 9, &dv.tex.tri_orco))) { yafgpu_scene_destroy(s); return rc; }
+		if(s->has_bump && !instanced)
 		{	// the third edge of Triangle::getSurface's dPdU / dPdV (triangle.cc:80-111): c - b, rounded once like e1 and e2 of the record
 			std::vector<float> e3(nt * 3);
 			for(size_t i = 0; i < nt; ++i) for(int k = 0; k < 3; ++k) e3[3 * i + k] = d->verts[9 * i + 6 + k] - d->verts[9 * i + 3 + k];
@@ -1137,7 +1291,7 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 	dv.n_faure = (int)faure.size(); dv.faure_far = dv.faure; dv.faure_near = dv.n_faure;
 	if((rc = upload(s, foff.data(), foff.size(), &dv.faure_off))) { yafgpu_scene_destroy(s); return rc; }
 	if((rc = upload(s, invp.data(), invp.size(), &dv.inv_prims))) { yafgpu_scene_destroy(s); return rc; }
-	dv.n_lights = d->n_lights; dv.n_tris = d->n_tris; dv.n_mats = d->n_materials; dv.n_nodes = (uint32_t)s->tree.nodes.size();
+	dv.n_lights = d->n_lights; dv.n_tris = n_tris; dv.n_mats = d->n_materials; dv.n_nodes = (uint32_t)s->tree.nodes.size();
 	for(int k = 0; k < 3; ++k) { dv.blo[k] = s->tree.bound_lo[k]; dv.bhi[k] = s->tree.bound_hi[k]; }
 	dv.cam = d->camera;
 	{	// PerspectiveCamera ctor, camera_perspective.cc:42-54: corner table of the polygonal bokeh shapes
@@ -1182,7 +1336,7 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 		if(e != hipSuccess) { yafgpu_scene_destroy(s); return fail(-100, std::string("background light tables: ") + hipGetErrorString(e)); }
 		dv.bg.tab = tab;
 	}
-	s->info.upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+	s->info.upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count() + assemble_seconds;
 	(void)t0;
 	*out = s;
 	return 0;

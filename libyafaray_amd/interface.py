@@ -52,7 +52,7 @@ C_API_SYMBOLS = [
     "yafaray_startTriMesh", "yafaray_endTriMesh", "yafaray_addVertex", "yafaray_addNormal", "yafaray_addTriangle",
     "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getCamera", "yafaray_getIntegratorAO", "yafaray_getMaskMaterial", "yafaray_getMaterialTable", "yafaray_addTriangles",
     "yafaray_startTriMeshPtr", "yafaray_addVertexWithOrco", "yafaray_addUv", "yafaray_addTriangleWithUv",
-    "yafaray_startCurveMesh", "yafaray_endCurveMesh", "yafaray_addInstance",
+    "yafaray_startCurveMesh", "yafaray_endCurveMesh", "yafaray_addInstance", "yafaray_getInstances",
     "yafaray_paramsSetColorArray", "yafaray_paramsSetMatrix", "yafaray_paramsSetMatrixD", "yafaray_setInputColorSpace",
     "yafaray_createObject", "yafaray_createVolumeRegion", "yafaray_createImageHandler",
     "yafaray_setLoggingAndBadgeSettings", "yafaray_setupRenderPasses", "yafaray_setInteractive", "yafaray_getRenderParameters",
@@ -110,7 +110,7 @@ def load():
         "yafaray_addVertexWithOrco": (ci, [vp, cd, cd, cd, cd, cd, cd]), "yafaray_addUv": (ci, [vp, cf, cf]),
         "yafaray_addTriangleWithUv": (ci, [vp, ci, ci, ci, ci, ci, ci, vp]),
         "yafaray_startCurveMesh": (ci, [vp, C.c_uint, ci, ci]), "yafaray_endCurveMesh": (ci, [vp, vp, cf, cf, cf]),
-        "yafaray_addInstance": (ci, [vp, C.c_uint, C.POINTER(cf)]),
+        "yafaray_addInstance": (ci, [vp, C.c_uint, C.POINTER(cf)]), "yafaray_getInstances": (ci, [vp, vp, ci]),
         "yafaray_paramsSetColorArray": (None, [vp, cp, C.POINTER(cf), ci]), "yafaray_paramsSetMatrix": (None, [vp, cp, C.POINTER(cf), ci]),
         "yafaray_paramsSetMatrixD": (None, [vp, cp, C.POINTER(cd), ci]), "yafaray_setInputColorSpace": (None, [vp, cp, cf]),
         "yafaray_createObject": (C.c_uint, [vp, cp]), "yafaray_createVolumeRegion": (vp, [vp, cp]), "yafaray_createImageHandler": (vp, [vp, cp, ci]),
@@ -251,8 +251,18 @@ class Interface:
         return self._ok(self._L.yafaray_endCurveMesh(self._h, mat, strand_start, strand_end, strand_shape), "endCurveMesh")
 
     def addInstance(self, base_object_id, obj_to_world):
-        m = (C.c_float * 16)(*[float(x) for x in np.asarray(obj_to_world, np.float32).reshape(16)])
+        """Scene::addInstance: the base mesh's triangles under obj_to_world (4 x 4, row major) as one more object; None passes a null matrix"""
+        m = None if obj_to_world is None else (C.c_float * 16)(*[float(x) for x in np.asarray(obj_to_world, np.float32).reshape(16)])
         return self._ok(self._L.yafaray_addInstance(self._h, base_object_id, m), "addInstance")
+
+    def getInstances(self):
+        """what addInstance stored, in object-id order: a list of dicts with the instance's own id, its base, the flags it copied from the
+        base at the call and the matrix as float32 (4, 4)"""
+        n = self._L.yafaray_getInstances(self._h, None, 0)
+        out = np.zeros((max(n, 1), 22), dtype=np.int32)
+        self._L.yafaray_getInstances(self._h, out.ctypes.data_as(C.c_void_p), n)
+        return [{"id": int(r[0]), "base": int(r[1]), "has_orco": bool(r[2]), "has_uv": bool(r[3]), "is_smooth": bool(r[4]), "normals_exported": bool(r[5]),
+                 "matrix": r[6:].view(np.float32).reshape(4, 4).copy()} for r in out[:n]]
 
     def createObject(self, name):
         return self._obj(self._L.yafaray_createObject(self._h, _b(name)), "createObject")
