@@ -199,6 +199,52 @@ typedef struct yafaray_render_stats
  * reference's film file (imagefilm.cc:1560-1657), i.e. what its ImageFilm holds before normalisation. */
 yafaray_bool_t yafaray_getFilm(yafaray_interface_t *yi, float *film, int width, int height);
 yafaray_bool_t yafaray_getRenderStats(yafaray_interface_t *yi, yafaray_render_stats_t *stats);
+/* ---- film files: save, merge and resume renders (ImageFilm::imageFilmSave / imageFilmLoad / imageFilmLoadAllInFolder /
+ * imageFilmFileBackup, imagefilm.cc:1330-1685) ----
+ * The file, little-endian: "YAF_FILMv1" 0x00 | the eleven words below | (n_passes + n_aux) x h x w x { float r, g, b, a, weight }, rows
+ * outermost.  What yafaray_getFilm returns is one such pass. */
+typedef struct yafaray_film_header
+{
+	uint32_t computer_node;          /* adv_computer_node */
+	uint32_t base_sampling_offset;   /* adv_base_sampling_offset, before the node's 100000 is added (imagefilm.h:124) */
+	uint32_t sampling_offset;        /* samples per pixel taken so far: offset + samples of the last pass that ran (integrator_tiled.cc:270) */
+	int32_t w, h, cx0, cx1, cy0, cy1;        /* width, height, xstart, xstart + width, ystart, ystart + height */
+	int32_t n_passes, n_aux;
+} yafaray_film_header_t;
+/* Host functions, usable without a GPU (merge tools).  Both return 0 on failure, with the cause in yafaray_filmLastError (per thread).
+ * writeFilmFile writes the combined pass alone: n_passes = 1 and n_aux = 0 go into the file whatever hdr says.  The reference always
+ * carries one auxiliary pass (the sampling factor, renderpasses.cc:277-279) and insists on its own counts when it loads, so a file
+ * written here is not for the reference to load.
+ * readFilmFile accepts n_passes >= 1 and n_aux >= 0, the reference's files among them, and reads pass 0 into film_hw5 (n_floats must be
+ * h * w * 5); film_hw5 = NULL reads the header alone.  Refused, with hdr and the buffer untouched: a wrong or unterminated magic, a
+ * negative count, and a file whose length is not exactly what its header promises — checked in 64 bits before anything is read or
+ * allocated (the reference reads on and takes what its variables held, file.cc:183-188).  Neither throws. */
+yafaray_bool_t yafaray_writeFilmFile(const char *path, const yafaray_film_header_t *hdr, const float *film_hw5);
+yafaray_bool_t yafaray_readFilmFile(const char *path, yafaray_film_header_t *hdr, float *film_hw5, uint64_t n_floats);
+const char *yafaray_filmLastError(void);
+/* The stand-in for session__.getPathImageOutput(): the image output path without extension, e.g. "out/frame0007"; this interface's
+ * film file is "<path> - node NNNN.film", NNNN = adv_computer_node in four digits (imagefilm.cc:1330-1338).  NULL or "" detaches it.
+ * What the render parameter film_save_load then does in yafaray_render (and only there: prepareRender / renderPassDevice callers own
+ * their memory):
+ *   no film path   nothing, whatever the parameters say (the reference with an output that is no image file, imagefilm.cc:900-904)
+ *   "save"         an existing film file of this node is renamed to "<file>-previous.bak" before the render; the film is written after
+ *                  a render that finished (an aborted or failed one writes nothing)
+ *   "load-save"    first every regular file of the path's directory ("." when it has none) with the extension "film" whose base name
+ *                  STARTS WITH the path's base name is loaded, in the order of the sorted path strings, and added to a zero film in
+ *                  float32 — this node's own earlier file among them, and "frame1" also takes "frame10 - node 0000.film" (the reference's
+ *                  rule, imagefilm.cc:1497-1500).  A file with another w, h, cx0, cx1, cy0 or cy1 than the render, or one readFilmFile
+ *                  refuses, is skipped whole; the warnings are in yafaray_getLastError after the render.  sampling_offset and
+ *                  base_sampling_offset become the maximum of the render's own and every loaded file's.  With at least one film loaded
+ *                  the render is resumed (integrator_tiled.cc:196-203): pass 1 is skipped — it still spends its tile seeds — and the
+ *                  adaptive passes 1 .. AA_passes - 1 go on from the loaded sampling_offset; AA_passes = 1 only combines the films.
+ *                  With none it is an ordinary render.  Then the backup and the final save as for "save".
+ *   anything else  "none" (environment.cc:524-526)
+ * Refused by yafaray_render with a film path set: film_autosave_interval_type other than "none" (no autosave between passes), and a
+ * saving or loading mode with shard_count > 1 (a rank's film is its share of the frame). */
+void yafaray_setFilmPath(yafaray_interface_t *yi, const char *path);
+const char *yafaray_getFilmPath(const yafaray_interface_t *yi);
+/* what the last yafaray_render loaded: the number of film files (0: an ordinary render) and the merged offsets; any pointer may be NULL */
+void yafaray_getFilmResume(yafaray_interface_t *yi, int *n_loaded, unsigned int *sampling_offset, unsigned int *base_sampling_offset);
 /* pixel-tile sharding: must be set before render; tile t belongs to shard t % count */
 void yafaray_setShard(yafaray_interface_t *yi, int shard_index, int shard_count);
 /* Multi-pass (adaptive) anti-aliasing on a sharded frame: between passes the noise detection (integrator_tiled.cc:136-258)

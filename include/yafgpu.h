@@ -352,6 +352,18 @@ typedef struct yafgpu_aa_schedule
 	   Material / ObjectGeometric constructor (material.cc:56, object_geom.cc:42), rand_skip values consumed by its colour
 	   loop since; then one rand() per tile per pass that runs.  rand_srand < 0: every tile draws 0. */
 	int32_t rand_srand, rand_skip;
+	/* A resumed render (session__.renderResumed(), integrator_tiled.cc:196-203; read by yafgpu_render_passes_to_host alone): the film
+	   so far instead of the first pass.  The first pass then launches no path work and counts no camera samples (resampled[0] = 0) but
+	   still consumes its block of tile seeds, as renderTile does with zero samples (:319); the adaptive passes 1 .. passes - 1 follow
+	   on the seeded film with their sample numbers starting at resume_sampling_offset.  passes <= 1: the films are only combined. */
+	const float *resume_film;      /* HOST pointer, [height][width][5] floats, or NULL: an ordinary render */
+	uint32_t resume_sampling_offset;       /* samples per pixel the film holds (renderPass's `offset` of the pass that follows) */
+	/* More films to add to resume_film on the device, in the order they are handed out (ImageFilm::imageFilmLoadAllInFolder's
+	   col += , weight += in float32, starting from a zero film, imagefilm.cc:1520-1531): called until it returns 0; it writes the next
+	   film, n_floats = height * width * 5 values, into dst (host memory) and returns 1, or a negative number on failure, which fails
+	   the render.  NULL: resume_film is the only film, and goes into the planes as it is. */
+	int (*resume_next)(void *user, float *dst, uint64_t n_floats);
+	void *resume_user;
 } yafgpu_aa_schedule;
 
 typedef struct yafgpu_counters   /* device atomics, accumulated per launch */

@@ -11,9 +11,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include <dirent.h>
+#include <sys/stat.h>
+
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
+#include <exception>
 #include <functional>
 #include <limits>
 #include <list>
@@ -151,6 +156,9 @@ struct yafaray_interface
 	int input_color_space = 3; float input_gamma = 1.f;       // 0 sRGB, 1 XYZ (D65), 2 LinearRGB, 3 RawManualGamma
 	yafaray_output_t output2{}; bool has_output2 = false;
 	bool interactive = false; std::string badge_position = "none";
+	// film files (yafaray_setFilmPath): the stand-in for session__.getPathImageOutput(), and what the last render loaded
+	std::string film_path;
+	int film_n_loaded = 0; uint32_t film_sampling_offset = 0u, film_base_sampling_offset = 0u;
 };
 
 namespace {
@@ -2251,34 +2259,230 @@ int yafaray_getRenderParameters(yafaray_interface_t *yi, char *buf, int len)
 	return (int)out.size();
 }
 
-yafaray_bool_t yafaray_render(yafaray_interface_t *yi, const yafaray_output_t *output, const yafaray_progress_t *progress)
+// ---- film files: ImageFilm::getFilmPath / imageFilmLoadAllInFolder / imageFilmFileBackup / imageFilmSave (imagefilm.cc:1330-1338,
+// :1467-1557, :1659-1685, :1560-1657) around one yafaray_render.  The reader and the writer are yafimg::read_film / write_film.
+static thread_local std::string g_film_err;      // yafaray_filmLastError: of this thread's last yafaray_readFilmFile / yafaray_writeFilmFile
+
+static_assert(sizeof(yafaray_film_header_t) == sizeof(yafimg::FilmHeader), "yafaray_film_header_t is yafimg::FilmHeader");
+
+static std::string film_file_of_node(const std::string &film_path, unsigned int node)
+{
+	char digits[16];
+	std::snprintf(digits, sizeof digits, "%04u", node);      // setfill('0') << setw(4): wider numbers keep their digits
+	return film_path + " - node " + digits + ".film";
+}
+// Path::Path(full_path) (file.cc:45-73): the directory up to the last separator, the base name up to the last dot, the extension
+static void split_path(const std::string &full_path, std::string &dir, std::string &base, std::string &ext)
+{
+	std::string full_name = full_path;
+	const size_t sep = full_path.find_last_of("\\/");
+	dir.clear();
+	if(sep != std::string::npos) { full_name = full_path.substr(sep + 1); dir = full_path.substr(0, sep); }
+	if(dir.empty()) full_name = full_path;
+	const size_t dot = full_name.find_last_of('.');
+	if(dot != std::string::npos) { base = full_name.substr(0, dot); ext = full_name.substr(dot + 1); }
+	else { base = full_name; ext.clear(); }
+}
+static bool is_regular_file(const std::string &path)
+{
+	struct stat st;
+	return ::stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode);
+}
+
+// the films a load-save render adds up, in the order they are added
+struct FilmSource
+{
+	std::vector<std::string> files;      // accepted by their headers, sorted by path
+	size_t next = 0;
+	std::string warnings, error;
+	// yafgpu_aa_schedule::resume_next: the next film's pass 0 into dst
+	static int next_film(void *user, float *dst, uint64_t n_floats)
+	{
+		FilmSource *src = (FilmSource *)user;
+		if(src->next >= src->files.size()) return 0;
+		const std::string &path = src->files[src->next++];
+		yafimg::FilmHeader hd;
+		if(!yafimg::read_film(path, hd, dst, n_floats, src->error)) return -1;      // it passed the header check a moment ago
+		return 1;
+	}
+};
+
+// steps 1 and 2 of the loading, and the header checks: every regular file of the film path's directory with the extension "film" whose
+// base name starts with the path's base name, sorted, less those whose header does not fit this render (a warning each)
+static void collect_films(const std::string &film_path, const yafimg::FilmHeader &want, FilmSource &src, uint32_t &sampling_offset, uint32_t &base_sampling_offset)
+{
+	std::string dir, base, ext;
+	split_path(film_path, dir, base, ext);
+	if(dir.empty()) dir = ".";
+	std::vector<std::string> found;
+	if(DIR *d = ::opendir(dir.c_str()))
+	{
+		while(const dirent *e = ::readdir(d))
+		{
+			const std::string name = e->d_name, path = dir + "/" + name;
+			std::string f_dir, f_base, f_ext;
+			split_path(name, f_dir, f_base, f_ext);
+			if(f_ext == "film" && f_base.rfind(base, 0) == 0 && is_regular_file(path)) found.push_back(path);
+		}
+		::closedir(d);
+	}
+	std::sort(found.begin(), found.end());
+	for(const std::string &path : found)
+	{
+		yafimg::FilmHeader hd; std::string why;
+		bool ok = yafimg::read_film(path, hd, nullptr, 0, why);
+		if(ok && (hd.w != want.w || hd.h != want.h || hd.cx0 != want.cx0 || hd.cx1 != want.cx1 || hd.cy0 != want.cy0 || hd.cy1 != want.cy1))
+		{
+			ok = false;
+			why = "film file '" + path + "' is of another frame: w " + std::to_string(hd.w) + " h " + std::to_string(hd.h) + " window x " + std::to_string(hd.cx0) + ".." +
+			      std::to_string(hd.cx1) + " y " + std::to_string(hd.cy0) + ".." + std::to_string(hd.cy1) + ", the render has w " + std::to_string(want.w) + " h " +
+			      std::to_string(want.h) + " window x " + std::to_string(want.cx0) + ".." + std::to_string(want.cx1) + " y " + std::to_string(want.cy0) + ".." + std::to_string(want.cy1);
+		}
+		if(!ok) { src.warnings += (src.warnings.empty() ? "film file skipped: " : "; film file skipped: ") + why; continue; }
+		src.files.push_back(path);
+		sampling_offset = std::max(sampling_offset, hd.sampling_offset);                   // imagefilm.cc:1546-1547
+		base_sampling_offset = std::max(base_sampling_offset, hd.base_sampling_offset);
+	}
+}
+
+// ImageFilm::sampling_offset_ after the render: offset + samples of the last renderPass that was called (integrator_tiled.cc:270); a pass
+// that resamples no pixel is not called (:238) while acum advances all the same (:240)
+static uint32_t stored_sampling_offset(const yafgpu_aa_schedule &aa, int aa_minsamples, bool resumed, uint32_t resume_offset, const std::vector<int32_t> &resampled)
+{
+	const int aa_samples = std::max(1, aa_minsamples), inc = aa.inc_samples > 0 ? aa.inc_samples : aa_samples;
+	int acum = resumed ? (int)resume_offset : aa_samples;
+	uint32_t stored = (uint32_t)acum;
+	float sample_mult = 1.f;
+	for(int i = 1; i < aa.passes; ++i)
+	{
+		sample_mult *= aa.sample_multiplier_factor;
+		const int n = (int)std::ceil((float)inc * sample_mult);
+		if((size_t)i < resampled.size() && resampled[(size_t)i] > 0) stored = (uint32_t)(acum + n);
+		acum += n;
+	}
+	return stored;
+}
+
+static yafaray_bool_t render_checked(yafaray_interface_t *yi, const yafaray_output_t *output, const yafaray_progress_t *progress)
 {
 	// an abort that arrived before this call belongs to an earlier render (Scene::render clears the flag too, scene.cc:1040)
 	yi->abort_flag = 0;
+	yi->film_n_loaded = 0; yi->film_sampling_offset = 0u; yi->film_base_sampling_offset = 0u;
+	// film files: without a film path the parameters have no effect (imagefilm.cc:900-904: an output that is no image file)
+	std::string film_mode = "none", autosave = "none";
+	yi->params.get("film_save_load", film_mode); yi->params.get("film_autosave_interval_type", autosave);
+	const bool film_load = !yi->film_path.empty() && film_mode == "load-save";                      // environment.cc:524-526: any other word is "none"
+	const bool film_save = !yi->film_path.empty() && (film_load || film_mode == "save");
+	if(!yi->film_path.empty() && autosave != "none")
+		return fail(yi, "render: film_autosave_interval_type = \"" + autosave + "\": saving the film between passes or on a timer is not supported by the GPU path (set it to \"none\")");
+	if(film_save && yi->shard_count > 1)
+		return fail(yi, "render: film_save_load = \"" + film_mode + "\" with a film path on a sharded frame (shard_count " + std::to_string(yi->shard_count) +
+		                "): a rank's film is its share of the frame, not a film of the frame");
 	if(progress && progress->init) progress->init(progress->user, 100);
 	if(progress && progress->setTag) progress->setTag(progress->user, "Rendering...");
 	if(!yafaray_prepareRender(yi)) return 0;
 	if(yi->abort_flag) return fail(yi, "aborted");
 	const int w = yi->rp.width, h = yi->rp.height;
 	yi->film.assign((size_t)w * (size_t)h * 5, 0.f);
+	int base_offset = 0, node = 0;
+	yi->params.get("adv_base_sampling_offset", base_offset); yi->params.get("adv_computer_node", node);
+	yafimg::FilmHeader hdr;
+	hdr.computer_node = (uint32_t)node; hdr.base_sampling_offset = (uint32_t)base_offset; hdr.sampling_offset = 0u;
+	hdr.w = w; hdr.h = h; hdr.cx0 = yi->rp.xstart; hdr.cx1 = yi->rp.xstart + w; hdr.cy0 = yi->rp.ystart; hdr.cy1 = yi->rp.ystart + h;
+	FilmSource source;
+	std::vector<float> first_film;
+	yafgpu_aa_schedule aa = yi->aa;
+	if(film_load)
+	{
+		collect_films(yi->film_path, hdr, source, hdr.sampling_offset, hdr.base_sampling_offset);
+		if(!source.files.empty())
+		{	// the first film goes straight to the device; the others follow through FilmSource::next_film, one at a time
+			first_film.resize(yi->film.size());
+			if(FilmSource::next_film(&source, first_film.data(), (uint64_t)first_film.size()) < 0) return fail(yi, "render: " + source.error);
+			yi->film_n_loaded = (int)source.files.size();
+			yi->film_sampling_offset = hdr.sampling_offset; yi->film_base_sampling_offset = hdr.base_sampling_offset;
+			aa.resume_film = first_film.data(); aa.resume_sampling_offset = hdr.sampling_offset;
+			if(source.next < source.files.size()) { aa.resume_next = FilmSource::next_film; aa.resume_user = &source; }
+			yi->rp.base_sampling_offset = hdr.base_sampling_offset + (uint32_t)node * 100000u;      // imagefilm.h:124 over the merged value
+		}
+	}
+	const std::string film_file = film_save ? film_file_of_node(yi->film_path, (unsigned int)node) : std::string();
+	if(film_save && is_regular_file(film_file))
+	{	// imageFilmFileBackup: the earlier film of this node stays at hand
+		const std::string backup = film_file + "-previous.bak";
+		auto name_of = [](const std::string &p) { const size_t sep = p.find_last_of("\\/"); return sep == std::string::npos ? p : p.substr(sep + 1); };
+		if(std::rename(film_file.c_str(), backup.c_str()) != 0) source.warnings += std::string(source.warnings.empty() ? "" : "; ") + "film file backup to '" + backup + "' failed";
+		else for(std::string &f : source.files) if(name_of(f) == name_of(film_file)) f += "-previous.bak";      // a film still to be added is read from where it is now
+	}
 	yafgpu_counters cn{};
 	hipEvent_t e0, e1;
 	(void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
 	(void)hipEventRecord(e0, nullptr);
 	yi->resampled.assign((size_t)std::max(1, yi->aa.passes), 0);
-	const int rc = yafgpu_render_passes_to_host(yi->gpu, &yi->rp, &yi->aa, yi->film.data(), &cn, yi->resampled.data());
+	const int rc = yafgpu_render_passes_to_host(yi->gpu, &yi->rp, &aa, yi->film.data(), &cn, yi->resampled.data());
 	(void)hipEventRecord(e1, nullptr);
 	(void)hipEventSynchronize(e1);
 	float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1);
 	(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-	if(rc) return fail(yi, std::string("render: ") + yafgpu_last_error());
+	if(rc) return fail(yi, std::string("render: ") + yafgpu_last_error() + (source.error.empty() ? "" : " (" + source.error + ")"));
 	yi->stats.rays_closest = cn.rays_closest; yi->stats.rays_shadow = cn.rays_shadow; yi->stats.interior_steps = cn.interior_steps;
 	yi->stats.leaves = cn.leaves; yi->stats.tri_tests = cn.tri_tests; yi->stats.camera_samples = cn.camera_samples; yi->stats.restarts = cn.restarts;
 	yi->stats.render_seconds = (double)ms * 1e-3;
+	if(film_save)
+	{	// imageFilmSave, at the end of a render that finished
+		hdr.sampling_offset = stored_sampling_offset(yi->aa, yi->rp.aa_minsamples, aa.resume_film != nullptr, aa.resume_sampling_offset, yi->resampled);
+		std::string why;
+		if(!yafimg::write_film(film_file, hdr, yi->film.data(), why)) return fail(yi, "render: " + why);
+	}
+	if(!source.warnings.empty()) yi->err = source.warnings;      // the render stands; the warnings are there to be read
 	if(progress && progress->update) progress->update(progress->user, 100);
 	if(progress && progress->done) progress->done(progress->user);
 	deliver(yi, output);
 	return 1;
+}
+
+yafaray_bool_t yafaray_render(yafaray_interface_t *yi, const yafaray_output_t *output, const yafaray_progress_t *progress)
+{
+	try { return render_checked(yi, output, progress); }
+	catch(const std::exception &e) { try { yi->err = std::string("render: ") + e.what(); } catch(...) {} }
+	return 0;
+}
+
+void yafaray_setFilmPath(yafaray_interface_t *yi, const char *path) { yi->film_path = path ? path : ""; }
+const char *yafaray_getFilmPath(const yafaray_interface_t *yi) { return yi->film_path.c_str(); }
+void yafaray_getFilmResume(yafaray_interface_t *yi, int *n_loaded, unsigned int *sampling_offset, unsigned int *base_sampling_offset)
+{
+	if(n_loaded) *n_loaded = yi->film_n_loaded;
+	if(sampling_offset) *sampling_offset = yi->film_sampling_offset;
+	if(base_sampling_offset) *base_sampling_offset = yi->film_base_sampling_offset;
+}
+const char *yafaray_filmLastError(void) { return g_film_err.c_str(); }
+yafaray_bool_t yafaray_writeFilmFile(const char *path, const yafaray_film_header_t *hdr, const float *film_hw5)
+{
+	try
+	{
+		g_film_err.clear();
+		if(!path || !hdr) { g_film_err = "writeFilmFile: null argument"; return 0; }
+		yafimg::FilmHeader hd;
+		std::memcpy(&hd, hdr, sizeof hd);
+		return yafimg::write_film(path, hd, film_hw5, g_film_err) ? 1 : 0;
+	}
+	catch(...) {}
+	return 0;
+}
+yafaray_bool_t yafaray_readFilmFile(const char *path, yafaray_film_header_t *hdr, float *film_hw5, uint64_t n_floats)
+{
+	try
+	{
+		g_film_err.clear();
+		if(!path || !hdr) { g_film_err = "readFilmFile: null argument"; return 0; }
+		yafimg::FilmHeader hd;
+		if(!yafimg::read_film(path, hd, film_hw5, n_floats, g_film_err)) return 0;
+		std::memcpy(hdr, &hd, sizeof hd);
+		return 1;
+	}
+	catch(...) {}
+	return 0;
 }
 
 void yafaray_abort(yafaray_interface_t *yi) { yi->abort_flag = 1; }

@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <sstream>
 #include <stdexcept>
@@ -553,6 +554,101 @@ static bool load_checked(const std::string &path, Image &img, std::string &err)
 		return load_png(data, img, err);
 	}
 	err = "image format \"" + ext + "\" has no decoder in this build (TGA, HDR and PNG are read; JPEG, TIFF and OpenEXR need libraries this image lacks)";
+	return false;
+}
+
+// ---- film files --------------------------------------------------------------------------------------------------------------
+// The reference's reader (imagefilm.cc:1340-1465) trusts the header: File::read ignores fread's result (file.cc:183-188), so a short
+// file fills the film with whatever the variables held.  Here the file's length must be exactly what its header promises, and that
+// is checked before a byte of the payload is read.
+namespace {
+
+static_assert(__BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__, "film files are little-endian and are read and written as memory images");
+const char kFilmMagic[11] = "YAF_FILMv1";      // ten characters and the terminator File::append(std::string) adds (file.cc:190-194)
+
+struct FileCloser { FILE *f; ~FileCloser() { if(f) std::fclose(f); } };
+
+bool read_film_checked(const std::string &path, FilmHeader &hdr_out, float *film, uint64_t n_floats, std::string &err)
+{
+	FileCloser fc{std::fopen(path.c_str(), "rb")};
+	if(!fc.f) { err = "film file '" + path + "' cannot be opened"; return false; }
+	if(fseeko(fc.f, 0, SEEK_END) != 0) { err = "film file '" + path + "': not a seekable file"; return false; }
+	const off_t end = ftello(fc.f);
+	if(end < 0 || fseeko(fc.f, 0, SEEK_SET) != 0) { err = "film file '" + path + "': not a seekable file"; return false; }
+	const uint64_t size = (uint64_t)end;
+	unsigned char head[kFilmHeaderBytes];
+	const size_t want = (size_t)std::min<uint64_t>(size, kFilmHeaderBytes);
+	if(std::fread(head, 1, want, fc.f) != want) { err = "film file '" + path + "': read error in the header"; return false; }
+	const size_t n_magic = std::min<size_t>(want, 10);
+	if(std::memcmp(head, kFilmMagic, n_magic) != 0) { err = "film file '" + path + "' does not start with \"YAF_FILMv1\" (wrong magic)"; return false; }
+	if(want > 10 && head[10] != 0) { err = "film file '" + path + "': the header string is unterminated"; return false; }
+	if(size < kFilmHeaderBytes)
+	{
+		err = "film file '" + path + "' is truncated: " + std::to_string(size) + " bytes, the header alone has " + std::to_string(kFilmHeaderBytes);
+		return false;
+	}
+	FilmHeader hd;
+	static_assert(sizeof(FilmHeader) == 44, "the eleven header words");
+	std::memcpy(&hd, head + 11, sizeof hd);
+	if(hd.w < 0 || hd.h < 0 || hd.n_passes < 0 || hd.n_aux < 0)
+	{
+		err = "film file '" + path + "': negative count in the header (w " + std::to_string(hd.w) + ", h " + std::to_string(hd.h) + ", passes " +
+		      std::to_string(hd.n_passes) + ", auxiliary passes " + std::to_string(hd.n_aux) + ")";
+		return false;
+	}
+	if(hd.n_passes < 1) { err = "film file '" + path + "' holds no pass"; return false; }
+	// size == header + layers * h * w * 20, by division: no product here can wrap (w * h < 2^62)
+	const uint64_t px = (uint64_t)hd.w * (uint64_t)hd.h, layers = (uint64_t)hd.n_passes + (uint64_t)hd.n_aux;
+	const uint64_t payload = size - kFilmHeaderBytes, cells = payload / 20u;
+	const bool length_ok = payload % 20u == 0 && (px == 0 ? cells == 0 : (cells % px == 0 && cells / px == layers));
+	if(!length_ok)
+	{
+		err = "film file '" + path + "' is " + std::to_string(size) + " bytes long; its header promises " + std::to_string(kFilmHeaderBytes) + " + " +
+		      std::to_string(layers) + " x " + std::to_string(hd.h) + " x " + std::to_string(hd.w) + " x 20 (truncated or trailing bytes)";
+		return false;
+	}
+	if(film)
+	{
+		if(n_floats != px * 5u) { err = "film file '" + path + "': the buffer holds " + std::to_string(n_floats) + " floats, the film has " + std::to_string(px * 5u); return false; }
+		// (px * 20 bytes are in the file: the length check above)
+		if(px && std::fread(film, 20, (size_t)px, fc.f) != (size_t)px) { err = "film file '" + path + "': read error in the payload"; return false; }
+	}
+	hdr_out = hd;
+	return true;
+}
+
+bool write_film_checked(const std::string &path, const FilmHeader &hdr, const float *film, std::string &err)
+{
+	if(hdr.w < 0 || hdr.h < 0) { err = "film file '" + path + "': negative size"; return false; }
+	const uint64_t px = (uint64_t)hdr.w * (uint64_t)hdr.h;
+	if(px && !film) { err = "film file '" + path + "': no film to write"; return false; }
+	if(px > std::numeric_limits<size_t>::max() / 20u) { err = "film file '" + path + "': film too large"; return false; }
+	FileCloser fc{std::fopen(path.c_str(), "wb")};
+	if(!fc.f) { err = "film file '" + path + "' cannot be created"; return false; }
+	FilmHeader hd = hdr;
+	hd.n_passes = 1; hd.n_aux = 0;
+	bool ok = std::fwrite(kFilmMagic, 1, 11, fc.f) == 11 && std::fwrite(&hd, 1, sizeof hd, fc.f) == sizeof hd;
+	if(ok && px) ok = std::fwrite(film, 20, (size_t)px, fc.f) == (size_t)px;
+	FILE *f = fc.f; fc.f = nullptr;
+	if(std::fclose(f) != 0) ok = false;
+	if(!ok) err = "film file '" + path + "': write error";
+	return ok;
+}
+
+} // namespace
+
+bool read_film(const std::string &path, FilmHeader &hdr, float *film_hw5, uint64_t n_floats, std::string &err)
+{
+	try { return read_film_checked(path, hdr, film_hw5, n_floats, err); }
+	catch(...) {}
+	try { err = "out of memory while reading a film file"; } catch(...) {}
+	return false;
+}
+bool write_film(const std::string &path, const FilmHeader &hdr, const float *film_hw5, std::string &err)
+{
+	try { return write_film_checked(path, hdr, film_hw5, err); }
+	catch(...) {}
+	try { err = "out of memory while writing a film file"; } catch(...) {}
 	return false;
 }
 

@@ -21,4 +21,19 @@ struct Image
 // decodes `path` by its extension (tga, hdr, png); false + err for anything else or a damaged file
 bool load(const std::string &path, Image &img, std::string &err);
 
+// ---- film files (ImageFilm::imageFilmSave / imageFilmLoad, imagefilm.cc:1560-1657, :1340-1465), little-endian:
+//   "YAF_FILMv1" 0x00 | the eleven 32-bit words of FilmHeader | (n_passes + n_aux) x h x w x { float r, g, b, a, weight }
+struct FilmHeader
+{
+	uint32_t computer_node = 0, base_sampling_offset = 0, sampling_offset = 0;
+	int32_t w = 0, h = 0, cx0 = 0, cx1 = 0, cy0 = 0, cy1 = 0, n_passes = 1, n_aux = 0;
+};
+constexpr uint64_t kFilmHeaderBytes = 11 + 44;      // the string with its terminator, the header words
+// writes the combined pass alone: n_passes = 1 and n_aux = 0 go into the file whatever hdr says; film = h * w * 5 floats
+bool write_film(const std::string &path, const FilmHeader &hdr, const float *film_hw5, std::string &err);
+// Reads the header and, with film_hw5, pass 0 of the payload into it (n_floats must be h * w * 5); further passes are skipped.
+// False + err, with hdr and the buffer untouched, for: a wrong or unterminated magic, a negative count, no pass at all, a length
+// that is not exactly what the header promises (checked in 64 bits before anything is read or allocated).  Never throws.
+bool read_film(const std::string &path, FilmHeader &hdr, float *film_hw5, uint64_t n_floats, std::string &err);
+
 } // namespace yafimg

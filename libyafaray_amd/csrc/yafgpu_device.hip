@@ -360,6 +360,26 @@ __global__ __launch_bounds__(kBlock) void combine_kernel(const float *planes, fl
 	}
 }
 
+// Film files (ImageFilm::imageFilmLoadAllInFolder, imagefilm.cc:1520-1531): acc += film over the n = h * w * 5 floats of a film, col and
+// weight alike, in float32; the first film is added to the zero film the reference starts from
+__global__ __launch_bounds__(kBlock) void film_add_kernel(float *acc, const float *film, size_t n, int first)
+{
+	for(size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+		acc[i] = (first ? 0.f : acc[i]) + film[i];
+}
+
+// The planes of a resumed render: the loaded film in the own plane, zero in the right, down and diagonal planes, so that combine_kernel
+// gives the film back (x + 0 + 0 + 0) and the passes that follow add to it.  n = h * w * 5, the floats of one plane.
+__global__ __launch_bounds__(kBlock) void seed_planes_kernel(const float *film, float *planes, size_t n)
+{
+	for(size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+	{
+		planes[i] = film[i];
+#pragma unroll
+		for(int k = 1; k < YAFGPU_FILM_PLANES; ++k) planes[(size_t)k * n + i] = 0.f;
+	}
+}
+
 // Component probe: evaluates the device-side restatements of the reference's leaf functions on
 // arrays, so that tests can pin them against the reference's own golden vectors (tests/golden).
 // Integers travel as float bit patterns.  One thread per item; no LDS, no traversal.
@@ -2411,6 +2431,44 @@ __global__ __launch_bounds__(kBlock) void aa_detect_kernel(const float *film, in
 		}
 	}
 }
+// A resumed render's start (yafgpu_aa_schedule::resume_film): the films summed in d_film in the order they are handed out, then the
+// planes seeded from the sum.  One film goes in as it is.
+int seed_resumed_planes(yafgpu_scene *s, const yafgpu_aa_schedule &aa, int w, int h, float *d_planes, float *d_film)
+{
+	const size_t n = (size_t)w * (size_t)h * YAFGPU_FILM_CHANNELS;
+	const uint32_t grid = (uint32_t)std::min<size_t>((n + kBlock - 1) / kBlock, 2048);
+	if(!aa.resume_next) HIP_OK(hipMemcpy(d_film, aa.resume_film, n * sizeof(float), hipMemcpyHostToDevice));
+	else
+	{
+		DevMem<float> d_in;
+		if(d_in.alloc(n) != hipSuccess) return fail(-3, "out of device memory (film merge)");
+		std::vector<float> next;
+		const float *src = aa.resume_film;
+		for(int first = 1;; first = 0)
+		{
+			HIP_OK(hipMemcpy(d_in, src, n * sizeof(float), hipMemcpyHostToDevice));
+			hipLaunchKernelGGL(film_add_kernel, dim3(grid), dim3(kBlock), 0, nullptr, d_film, (const float *)d_in.p, n, first);
+			HIP_OK(hipGetLastError());
+			if(next.empty())
+			{
+				try { next.resize(n); }
+				catch(const std::bad_alloc &) { return fail(-3, "out of host memory (film merge)"); }
+			}
+			const int got = aa.resume_next(aa.resume_user, next.data(), (uint64_t)n);
+			if(got < 0) return fail(-32, "the film source of a resumed render reported a failure");
+			if(got == 0) break;
+			src = next.data();
+		}
+	}
+	hipLaunchKernelGGL(seed_planes_kernel, dim3(grid), dim3(kBlock), 0, nullptr, (const float *)d_film, d_planes, n);
+	HIP_OK(hipGetLastError());
+	// correlative_sample_number_ starts a render at zero (integrator_tiled.cc:192-194); the pass that would reset it does not run
+	s->lc_host_counter = 0u;
+	HIP_OK(s->rp_counter.reserve(1, nullptr));
+	HIP_OK(hipMemsetAsync(s->rp_counter, 0, sizeof(uint32_t), nullptr));
+	HIP_OK(hipDeviceSynchronize());
+	return 0;
+}
 } // namespace
 
 int yafgpu_render_passes_to_host(yafgpu_scene_t *s, const yafgpu_render_params *rp_in, const yafgpu_aa_schedule *aa_in,
@@ -2422,6 +2480,8 @@ int yafgpu_render_passes_to_host(yafgpu_scene_t *s, const yafgpu_render_params *
 	if(aa.passes < 1) aa.passes = 1;
 	const bool exchange = aa.passes > 1 && rp_in->shard_count > 1;
 	if(exchange && !s->exchange) return fail(-16, "multi-pass anti-aliasing on a sharded frame needs an exchange function (yafgpu_scene_set_exchange): the noise detection between passes reads every pixel");
+	const bool resumed = aa.resume_film != nullptr;
+	if(resumed && rp_in->shard_count > 1) return fail(-17, "a resumed render of a sharded frame is not supported: a loaded film is a film of the whole frame");
 	yafgpu_render_params rp = *rp_in;
 	const int w = rp.width, h = rp.height;
 	if(w <= 0 || h <= 0) return fail(-10, "empty image");
@@ -2484,10 +2544,12 @@ int yafgpu_render_passes_to_host(yafgpu_scene_t *s, const yafgpu_render_params *
 		yafgpu_glibc_rand((uint32_t)aa.rand_srand, (int32_t)rand_stream.size(), rand_stream.data());
 		rp.tile_rand = rand_stream.data() + rand_pos; rand_pos += (size_t)n_tiles_frame;
 	}
-	int rc = yafgpu_render_tiles(s, &rp, d_planes, d_cnt, nullptr);
-	if(resampled_out) resampled_out[0] = w * h;
+	// A resumed render skips the first pass (integrator_tiled.cc:198-202: renderPass with 0 samples): no path work, no camera samples;
+	// its tile seeds, taken above, are spent all the same (renderTile's first statement, :319)
+	int rc = resumed ? seed_resumed_planes(s, aa, w, h, d_planes, d_film) : yafgpu_render_tiles(s, &rp, d_planes, d_cnt, nullptr);
+	if(resampled_out) resampled_out[0] = resumed ? 0 : w * h;
 	std::vector<uint8_t> mask;
-	int acum = aa_samples, resampled = 0; bool threshold_changed = true;
+	int acum = resumed ? (int)aa.resume_sampling_offset : aa_samples, resampled = 0; bool threshold_changed = true;
 	for(int i = 1; i < aa.passes && !rc; ++i)
 	{
 		if(s->aborted()) { rc = fail(-30, "aborted"); break; }

@@ -39,6 +39,16 @@ EXCHANGE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)      # yafar
 AREA = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int)
 
 
+class FilmHeader(C.Structure):
+    """yafaray_film_header_t: the eleven words behind a film file's magic"""
+    _fields_ = [("computer_node", C.c_uint32), ("base_sampling_offset", C.c_uint32), ("sampling_offset", C.c_uint32),
+                ("w", C.c_int32), ("h", C.c_int32), ("cx0", C.c_int32), ("cx1", C.c_int32), ("cy0", C.c_int32), ("cy1", C.c_int32),
+                ("n_passes", C.c_int32), ("n_aux", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class Output(C.Structure):
     _fields_ = [("user", C.c_void_p), ("putPixel", PUTPIXEL), ("flush", FLUSH), ("flushArea", AREA), ("highlightArea", AREA)]
 
@@ -69,6 +79,7 @@ C_API_SYMBOLS = [
     "yafaray_renderPassDevice", "yafaray_getRenderSize", "yafaray_loadXml", "yafaray_intersectRays", "yafaray_shadowRays", "yafaray_probe", "yafaray_setProfiling", "yafaray_getKernelProfile", "yafaray_setPassPipelining",
     "yafaray_commGetUniqueId", "yafaray_commCreate", "yafaray_commDestroy", "yafaray_commRank", "yafaray_commWorld", "yafaray_commLastError",
     "yafaray_commBackend", "yafaray_reduceFilm", "yafaray_allReduce", "yafaray_commExchange", "yafaray_setComm",
+    "yafaray_setFilmPath", "yafaray_getFilmPath", "yafaray_getFilmResume", "yafaray_writeFilmFile", "yafaray_readFilmFile", "yafaray_filmLastError",
 ]
 GPU_ABI_SYMBOLS = [
     "yafgpu_last_error", "yafgpu_device_count", "yafgpu_set_device", "yafgpu_scene_create", "yafgpu_scene_destroy",
@@ -147,6 +158,10 @@ def load():
         "yafaray_commRank": (ci, [vp]), "yafaray_commWorld": (ci, [vp]), "yafaray_commLastError": (cp, []), "yafaray_commBackend": (cp, []),
         "yafaray_reduceFilm": (ci, [vp, vp, C.c_uint64, ci, vp]), "yafaray_allReduce": (ci, [vp, vp, C.c_uint64, vp]),
         "yafaray_commExchange": (ci, [vp, vp, C.c_uint64]), "yafaray_setComm": (None, [vp, vp]),
+        "yafaray_setFilmPath": (None, [vp, cp]), "yafaray_getFilmPath": (cp, [vp]),
+        "yafaray_getFilmResume": (None, [vp, C.POINTER(ci), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+        "yafaray_writeFilmFile": (ci, [cp, C.POINTER(FilmHeader), C.POINTER(cf)]),
+        "yafaray_readFilmFile": (ci, [cp, C.POINTER(FilmHeader), C.POINTER(cf), C.c_uint64]), "yafaray_filmLastError": (cp, []),
         "yafgpu_last_error": (cp, []), "yafgpu_device_count": (ci, []), "yafgpu_set_device": (ci, [ci]),
         "yafgpu_planes_bytes": (C.c_uint64, [ci, ci]),
         "yafgpu_film_combine": (ci, [vp, vp, ci, ci, vp]),
@@ -536,6 +551,20 @@ class Interface:
         self._comm = comm
         self._L.yafaray_setComm(self._h, comm.handle if comm is not None else None)
 
+    def setFilmPath(self, path):
+        """the image output path without extension, e.g. "out/frame0007": with it the render parameter film_save_load ("save" |
+        "load-save") writes and loads "<path> - node NNNN.film" (include/yafaray_c_api.h); None or "" detaches it"""
+        self._L.yafaray_setFilmPath(self._h, None if path is None else _b(os.fspath(path)))
+
+    def getFilmPath(self):
+        return self._L.yafaray_getFilmPath(self._h).decode()
+
+    def getFilmResume(self):
+        """what the last render loaded -> (film files loaded, merged sampling_offset, merged base_sampling_offset)"""
+        n, so, bo = C.c_int(0), C.c_uint(0), C.c_uint(0)
+        self._L.yafaray_getFilmResume(self._h, C.byref(n), C.byref(so), C.byref(bo))
+        return n.value, so.value, bo.value
+
     def setSerialReplay(self, on):
         self._L.yafaray_setSerialReplay(self._h, int(bool(on)))
 
@@ -675,6 +704,49 @@ def film_combine(d_planes, d_film, width, height, stream=0):
     rc = load().yafgpu_film_combine(C.c_void_p(d_planes), C.c_void_p(d_film), width, height, C.c_void_p(stream or None))
     if rc:
         raise YafaRayError(load().yafgpu_last_error().decode())
+
+
+FILM_HEADER_FIELDS = tuple(k for k, _ in FilmHeader._fields_)
+
+
+def film_last_error():
+    """why this thread's last read_film_file / write_film_file failed"""
+    return load().yafaray_filmLastError().decode()
+
+
+def write_film_file(path, header, film):
+    """Write `film` ((h, w, 5) float32: r, g, b, a, weight — what getFilm returns) as a film file.  header: a dict with computer_node,
+    base_sampling_offset, sampling_offset, cx0, cx1, cy0, cy1 (absent: 0; cx1 / cy1 absent: cx0 + w / cy0 + h); w and h come from the
+    film.  The file holds the combined pass alone (n_passes 1, n_aux 0).  False on failure (film_last_error())."""
+    px = np.ascontiguousarray(film, dtype=np.float32)
+    if px.ndim != 3 or px.shape[2] != 5:
+        raise ValueError("film must be (height, width, 5)")
+    h = FilmHeader()
+    for k in ("computer_node", "base_sampling_offset", "sampling_offset", "cx0", "cy0"):
+        setattr(h, k, int(header.get(k, 0)))
+    h.h, h.w = px.shape[0], px.shape[1]
+    h.cx1 = int(header.get("cx1", h.cx0 + h.w))
+    h.cy1 = int(header.get("cy1", h.cy0 + h.h))
+    h.n_passes, h.n_aux = 1, 0
+    return bool(load().yafaray_writeFilmFile(_b(os.fspath(path)), C.byref(h), px.ctypes.data_as(C.POINTER(C.c_float))))
+
+
+def read_film_file(path, out=None, header_only=False):
+    """Read a film file -> (header dict, film (h, w, 5) float32), or the header dict alone with header_only; False on failure, with the
+    cause in film_last_error().  Pass 0 is read, further passes are skipped.  out: a C-contiguous float32 array of h * w * 5 values to
+    read into (it is returned in place of a new one, and left untouched on failure)."""
+    L, p, h = load(), _b(os.fspath(path)), FilmHeader()
+    if header_only:
+        return h.as_dict() if L.yafaray_readFilmFile(p, C.byref(h), None, 0) else False
+    if out is None:
+        if not L.yafaray_readFilmFile(p, C.byref(h), None, 0):
+            return False
+        out = np.zeros((h.h, h.w, 5), dtype=np.float32)
+    elif out.dtype != np.float32 or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous float32 array")
+    if not L.yafaray_readFilmFile(p, C.byref(h), out.ctypes.data_as(C.POINTER(C.c_float)), out.size):
+        return False
+    return h.as_dict(), out
 
 
 def film_to_rgba(film):

@@ -223,7 +223,7 @@ def set_render_params(yi, render):
     for k in ("width", "height", "xstart", "ystart", "AA_passes", "AA_minsamples", "filter_type", "tile_size",
               "adv_base_sampling_offset", "adv_computer_node", "adv_auto_shadow_bias_enabled",
               "adv_auto_min_raydist_enabled", "threads", "AA_inc_samples", "AA_detect_color_noise", "AA_dark_detection_type",
-              "AA_variance_edge_size", "AA_variance_pixels"):
+              "AA_variance_edge_size", "AA_variance_pixels", "film_save_load", "film_autosave_interval_type"):
         if k in render:
             rs[k] = render[k]
     for k in ("AA_pixelwidth", "adv_shadow_bias_value", "adv_min_raydist_value", "AA_threshold", "AA_resampled_floor",
