@@ -40,7 +40,8 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 #ifndef YAFGPU_STACK
 #define YAFGPU_STACK 8                // 8 slots: 8 waves/SIMD for the traversal kernels, 0.8 % of rays restart (C2)
 #endif
-constexpr int kStack = YAFGPU_STACK;  // per-lane LDS stack slots (power of two)
+constexpr int kStack = YAFGPU_STACK;  // per-lane LDS stack slots (power of two): wf_trace holds kStack - 1 live entries (its node step writes the slot
+                                      // above the top unconditionally), kd_trace_ts holds kStack; an older far child is overwritten and recovered by a kd-restart
 constexpr int kDepthCap = 48;         // host tree depth cap; deeper pending lists restart
 constexpr float kMinRayDist = (float)0.00005;   // MIN_RAYDIST, CMakeLists.txt:46-48
 constexpr float kShadowBias = (float)0.0005;    // YAF_SHADOW_BIAS, CMakeLists.txt:50-52

@@ -2,7 +2,9 @@
 leaf forced through the escape array (YAFGPU_TREELET_INLINE=0): renders must give the same films and ray counts, bit for bit,
 in both forms, and every ray of a batch (intersectRays / shadowRays run wf_trace) the same answer, bit for bit, as the oracle
 walking the same tree with the reference's traversal.  The scenes include degenerate trees: a one-leaf tree, a tree with only
-empty leaves next to the geometry, and stacks of identical triangles (leaves too large to go inline, kd-restarts)."""
+empty leaves next to the geometry, and stacks of identical triangles (leaves too large to go inline).  The stacked scenes give
+big leaves, not deep lists of pending far children: of these batches' rays under 2 % overflow the short stack and restart
+(test_short_stack_host.py has the soup's count); kd-restarts are covered by test_gpu_short_stack.py."""
 import os
 
 import numpy as np
