@@ -1798,7 +1798,7 @@ __global__ __launch_bounds__(kBlock) void wf_generate(const WfArgs a)
 #endif
 constexpr int kTraceBatch = YAFGPU_TRACE_BATCH;
 #ifndef YAFGPU_REFILL
-#define YAFGPU_REFILL 24               // C2 sweep (voted rounds): 8..32 within 2 %, 48 -> -5 %, 56 -> -12 %
+#define YAFGPU_REFILL 32               // m1 sweep with held answers (profiles/r07_ab_trace_waits.txt): 8 -> -3.4 %, 16 -> -1.0 %, 24 -> -0.5 %, 40 -> -1.0 % against 32
 #endif
 // Postponed leaves.  A lane that reaches a non-empty leaf does not stop there: it notes the leaf as PENDING (its
 // reference range and the exit distance of its cell) and walks on at once, as if the leaf held no terminating hit; only
@@ -1821,6 +1821,23 @@ constexpr int kTraceBatch = YAFGPU_TRACE_BATCH;
 // Per ray the node steps, the leaves and their order are TriKdTree::intersect's; only where a step's operands come from differs.  (The closed
 // alternatives — pair fetch, 64-byte blocks, the tree's top in L1 or LDS, fused rounds, triangle prefetch, leaves apart, non-temporal
 // triangle loads, node windows — are measured in profiles/r02_ab_*.txt and profiles/r03_ab_*.txt.)
+// Answers held in the lane until the wave's next refill (see kAnswer), per launch kind (profiles/r07_ab_trace_waits.txt).
+#ifndef YAFGPU_TRACE_DEFER_ANY
+#define YAFGPU_TRACE_DEFER_ANY 1
+#endif
+#ifndef YAFGPU_TRACE_DEFER_CLOSEST
+#define YAFGPU_TRACE_DEFER_CLOSEST 1
+#endif
+// The visibility word of a triangle record pinned to the record's own fetch.  Left to itself (0: the comparison build) the optimizer
+// narrows r1's load and fetches the word again, behind the test, for the lanes that passed it: a second dependent trip in almost every
+// triangle round.  Pinned, the round has one group of loads (profiles/r07_ab_trace_waits.txt).
+#ifndef YAFGPU_TRACE_VIS_PIN
+#define YAFGPU_TRACE_VIS_PIN 1
+#endif
+// One-off measurement build: the stats kernels count the occluded shadow rays where they count kd-restarts (profiles/r07_ab_trace_waits.txt).
+#ifndef YAFGPU_STATS_OCCLUDED
+#define YAFGPU_STATS_OCCLUDED 0
+#endif
 #ifndef YAFGPU_TRACE_WAVES
 #define YAFGPU_TRACE_WAVES 7     // waves per SIMD the register allocation must leave room for (22.5 KB of LDS per block allow 7): 72 / 70 VGPRs (closest / any); without the bound the any-hit kernel once took 81 (5 waves)
 #endif
@@ -1858,8 +1875,14 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 		const uint32_t bit = 4u * slot + 2u * pair + which;
 		if(occluded) atomicOr(&a.verdict[bit >> 5], 1u << (bit & 31u));
 	};
-	// the walk: at a node or a leaf | at a non-empty leaf, waiting for the pending slot | no node left | no ray
-	enum : uint32_t { kWalk = 0u, kBlocked = 1u, kWalkEnd = 2u, kNoRay = 3u };
+	// the walk: at a node or a leaf | at a non-empty leaf, waiting for the pending slot | no node left | no ray | ray over, its answer
+	// still in the lane's registers (slot / pair / which / hit, or qi / tri / z / bu / bv): idle like kNoRay, written by the next refill
+	enum : uint32_t { kWalk = 0u, kBlocked = 1u, kWalkEnd = 2u, kNoRay = 3u, kAnswer = 4u };
+	constexpr bool kDefer = kAny ? (YAFGPU_TRACE_DEFER_ANY != 0) : (YAFGPU_TRACE_DEFER_CLOSEST != 0);
+	auto answer = [&]() {
+		if(kAny) answer_any(hit);
+		else a.state[2 * c + qi] = make_float4(fbits((uint32_t)(hit ? tri : -1)), z, bu, bv);
+	};
 	constexpr int kVoteNum = YAFGPU_VOTE_NUM, kVoteDen = YAFGPU_VOTE_DEN, kNodeBurst = YAFGPU_NODE_BURST;
 	uint32_t ws = kNoRay;
 	uint32_t p_cur = 0u, p_end = 0u, ti = 0u;       // pending leaf: references [p_cur, p_end) still to test, ti = refs[p_cur] (in flight)
@@ -1870,10 +1893,12 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 	uint32_t rounds_node = 0u, rounds_tri = 0u;     // wave-uniform (kStats)
 	for(;;)
 	{
-		const unsigned long long idle = __ballot(ws == kNoRay);
+		const unsigned long long idle = __ballot(ws >= kNoRay);
 		const int n_idle = __popcll(idle);
 		if(!exhausted && (n_idle >= YAFGPU_REFILL || n_idle == kWave))
 		{
+			// the answers held back since the last refill leave first: one group of stores (any-hit: atomics) per refill, none in the rounds
+			if(kDefer && ws == kAnswer) { answer(); ws = kNoRay; }
 			// the wave owns [w_next, w_end) of the queue; one atomic reserves kTraceBatch entries at a time (a single
 			// counter word sustains only ~90 returning atomics per microsecond: MI355X_MICROARCH.md, row "dequeue")
 			if(w_next >= w_end)
@@ -1951,7 +1976,7 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 				}
 			}
 		}
-		const unsigned long long m_act = __ballot(ws != kNoRay);
+		const unsigned long long m_act = __ballot(ws < kNoRay);
 		if(m_act == 0ull) { if(exhausted) break; else continue; }
 		// The kernel is bound by instruction issue, not by memory, so what counts is how many lanes share each
 		// instruction.  Each round the WAVE does one kind of work, chosen by vote: a round of triangle tests (lanes with a
@@ -1969,7 +1994,7 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 			const bool hit_here = !kAny && hit && z <= tmax;
 			const bool emp = stk.empty();
 			const bool restart = emp && stk.lost() && !(tmax >= t_exit);
-			if(kStats && restart && !hit_here) ++cn.restarts;
+			if(kStats && !YAFGPU_STATS_OCCLUDED && restart && !hit_here) ++cn.restarts;
 			tmin = restart ? restart_from(tmin, tmax) : tmax;                          // see restart_from: progress on degenerate trees
 			link = emp ? root : top.x;
 			tmax = emp ? t_exit : __uint_as_float(top.y);
@@ -1985,7 +2010,13 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 			// Triangle::intersect without its early returns: the same operations in the same order, every lane to the
 			// end (a wave of 30 rays almost never leaves early as a whole), the rejections folded into one predicate
 			const bool ok = tri_test_flat(r0, r1, r2, from, dir, t, u, v);
+#if YAFGPU_TRACE_VIS_PIN
+			uint32_t vis_w = __float_as_uint(r1.w);
+			asm volatile("; visibility word of the record" : "+v"(vis_w));
+			const uint32_t vis = vis_w >> 30;
+#else
 			const uint32_t vis = __float_as_uint(r1.w) >> 30;
+#endif
 			if(kAny)
 			{
 				const bool found = ok && t < dist && t >= ray_tmin && (vis == 0u || vis == 2u);
@@ -2096,9 +2127,11 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 		}
 		if(done || (ws == kWalkEnd && p_cur >= p_end))
 		{
-			if(kAny) answer_any(hit);
-			else a.state[2 * c + qi] = make_float4(fbits((uint32_t)(hit ? tri : -1)), z, bu, bv);
-			ws = kNoRay; done = false; p_cur = p_end = 0u;
+			if(kStats && YAFGPU_STATS_OCCLUDED && kAny && hit) ++cn.restarts;
+			// with the queue exhausted no refill comes: the answer goes out at once (an any-hit ray that is not occluded has nothing to write)
+			const bool hold = kDefer && !exhausted && (!kAny || hit);
+			if(!hold) answer();
+			ws = hold ? kAnswer : kNoRay; done = false; p_cur = p_end = 0u;
 		}
 	}
 	if(a.ra.counters != nullptr)
