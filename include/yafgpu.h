@@ -415,6 +415,13 @@ int yafgpu_render_to_host(yafgpu_scene_t *scene, const yafgpu_render_params *rp,
  * tri (int32, -1 = miss), t, and barycentrics b0,b1,b2 (n*3); any-hit writes 0/1 into shadowed. */
 int yafgpu_trace_closest(yafgpu_scene_t *scene, int32_t n, const float *rays, int32_t *tri, float *t, float *bary);
 int yafgpu_trace_shadow(yafgpu_scene_t *scene, int32_t n, const float *rays, int32_t *shadowed);
+/* The traversal kernels' queue schedule, for tests.  yafgpu_trace_reservation: the entries a wave reserves with `seen` of `n` queue
+ * entries handed out and `waves` waves in the launch, by the rule the library was built with.  yafgpu_trace_schedule: info[0..5] = the
+ * smallest and the largest reservation, the divisor D, whether the sizes shrink, whether a wave's first range is static, and the
+ * waves per workgroup, as built; info[6], info[7] = the workgroups of this process's last closest-hit and any-hit traversal launch,
+ * of a render or of a ray batch (0: none yet), where the switch YAFGPU_TRACE_GRID_CAP shows. */
+uint32_t yafgpu_trace_reservation(uint32_t n, uint32_t seen, uint32_t waves);
+void yafgpu_trace_schedule(uint32_t info[8]);
 
 /* Per-kernel device timing of the NEXT render pass (HIP events around every launch on the pass's own
  * stream; the pass then synchronises after each launch, so it is a measurement mode, not a fast path).

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -1507,6 +1508,7 @@ struct Switches
 	bool record_variant = true;                // YAFGPU_RECORD_VARIANT=0: the record pass on the pass's own kernel (A/B)
 	bool vertex_lds = true;                    // YAFGPU_VERTEX_LDS=0: every vertex record goes through memory and is stored (WfArgs::vtx_lds, vtx_keep)
 	int blocks_per_cu = 8;                     // YAFGPU_BLOCKS_PER_CU: resident workgroups per CU of the persistent kernels (occupancy experiments)
+	int trace_grid_cap = 0;                    // YAFGPU_TRACE_GRID_CAP: at most so many workgroups per traversal launch (tests: only with few waves does a batch of 512 * waves * D rays and more start at the largest reservation and drain through every size); 0: no cap
 	bool stats = false, verbose = false;       // YAFGPU_STATS, YAFGPU_VERBOSE: set at all
 };
 static int env_flag(const char *name)      // 1 / 0: set to a number that is / is not zero; -1: unset
@@ -1528,6 +1530,7 @@ static Switches read_switches()
 	sw.record_variant = env_flag("YAFGPU_RECORD_VARIANT") != 0;
 	sw.vertex_lds = env_flag("YAFGPU_VERTEX_LDS") != 0;
 	if(const char *e = std::getenv("YAFGPU_BLOCKS_PER_CU")) sw.blocks_per_cu = std::max(1, std::atoi(e));
+	if(const char *e = std::getenv("YAFGPU_TRACE_GRID_CAP")) sw.trace_grid_cap = std::max(0, std::atoi(e));
 	sw.stats = std::getenv("YAFGPU_STATS") != nullptr;
 	sw.verbose = std::getenv("YAFGPU_VERBOSE") != nullptr;
 	return sw;
@@ -1544,7 +1547,7 @@ static int device_cus(yafgpu_scene *s)
 	return 0;
 }
 
-static int wf_grid(const void *kernel, int cus, const Switches &sw)
+static int wf_grid(const void *kernel, int cus, const Switches &sw, bool trace = false)      // trace: a wf_trace instantiation (YAFGPU_TRACE_GRID_CAP applies)
 {
 	// (the occupancy of a kernel does not change between passes: asked once per kernel)
 	static std::mutex mu; static std::map<const void *, int> known;
@@ -1559,8 +1562,12 @@ static int wf_grid(const void *kernel, int cus, const Switches &sw)
 			known[kernel] = per_cu;
 		}
 	}
-	return cus * std::min(per_cu, sw.blocks_per_cu);
+	const int grid = cus * std::min(per_cu, sw.blocks_per_cu);
+	return (trace && sw.trace_grid_cap > 0) ? std::min(grid, sw.trace_grid_cap) : grid;
 }
+// workgroups of this process's last closest-hit / any-hit traversal launch, of a render or of a ray batch (yafgpu_trace_schedule: the
+// tests read here that YAFGPU_TRACE_GRID_CAP took effect)
+static std::atomic<int> g_trace_grid[2] = {{0}, {0}};
 
 // Scene-specialised builds of wf_shade (yafgpu_shade_variant.hip), most specialised first.  A variant serves a scene
 // whose material types are a subset of its mask, whose light types are a subset of its light mask (not asked of a record
@@ -2159,8 +2166,9 @@ static int render_wavefront(yafgpu_scene *s, RenderArgs &ra, const Switches &sw,
 	HIP_OK(hipMemcpyAsync(w.pix_prefix, s->h_pix_prefix.data(), s->h_pix_prefix.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
 	if(rpl.replay && (rc = upload_segments(c))) return rc;
 	if((rc = device_cus(s))) return rc;
-	c.g_trace_c = stats ? wf_grid((const void *)wf_trace<false, true>, s->n_cus, sw) : wf_grid((const void *)wf_trace<false, false>, s->n_cus, sw);
-	c.g_trace_s = stats ? wf_grid((const void *)wf_trace<true, true>, s->n_cus, sw) : wf_grid((const void *)wf_trace<true, false>, s->n_cus, sw);
+	c.g_trace_c = stats ? wf_grid((const void *)wf_trace<false, true>, s->n_cus, sw, true) : wf_grid((const void *)wf_trace<false, false>, s->n_cus, sw, true);
+	c.g_trace_s = stats ? wf_grid((const void *)wf_trace<true, true>, s->n_cus, sw, true) : wf_grid((const void *)wf_trace<true, false>, s->n_cus, sw, true);
+	g_trace_grid[0] = c.g_trace_c; g_trace_grid[1] = c.g_trace_s;
 	c.g_shade = wf_grid(p.shade ? p.shade->kernel() : (const void *)wf_shade, s->n_cus, sw);
 	c.g_shade_rec = p.record ? wf_grid(p.record->kernel(), s->n_cus, sw) : c.g_shade;
 	if(p.overlap) { HIP_OK(w.side.create()); HIP_OK(w.fork.create()); HIP_OK(w.join.create()); }
@@ -2614,7 +2622,8 @@ static int trace_batch(yafgpu_scene_t *s, int32_t n, const float *rays, int32_t 
 	a.state = d_state; a.cap = cap;
 	a.cnt_in = d_cnt; a.verdict = d_verdict;
 	const void *kernel = any ? (const void *)wf_trace<true, false> : (const void *)wf_trace<false, false>;
-	const int grid = wf_grid(kernel, s->n_cus, read_switches());
+	const int grid = wf_grid(kernel, s->n_cus, read_switches(), true);
+	g_trace_grid[any ? 1 : 0] = grid;
 	for(uint32_t o = 0; o < (uint32_t)n; o += cap)
 	{
 		const uint32_t m = std::min(cap, (uint32_t)n - o);
@@ -2664,6 +2673,30 @@ int yafgpu_trace_shadow(yafgpu_scene_t *s, int32_t n, const float *rays, int32_t
 	if(!shadowed) return fail(-1, "null output");
 	return trace_batch(s, n, rays, nullptr, nullptr, nullptr, shadowed, true);
 }
+
+uint32_t yafgpu_trace_reservation(uint32_t n, uint32_t seen, uint32_t waves) { return waves ? trace_reservation(n, seen, waves) : 0u; }
+void yafgpu_trace_schedule(uint32_t info[8])
+{
+	info[0] = (uint32_t)YAFGPU_TRACE_BATCH_MIN; info[1] = (uint32_t)YAFGPU_TRACE_BATCH; info[2] = (uint32_t)YAFGPU_TRACE_BATCH_DIV;
+	info[3] = (uint32_t)YAFGPU_TRACE_BATCH_SHRINK; info[4] = (uint32_t)YAFGPU_TRACE_STATIC_FIRST; info[5] = (uint32_t)kWavesPerBlock;
+	info[6] = (uint32_t)g_trace_grid[0].load(); info[7] = (uint32_t)g_trace_grid[1].load();
+}
+
+#if YAFGPU_TRACE_EXIT_LOG
+// (measurement build) the traversal waves' exit records so far: copies up to `cap` of them (8 words each) to `out`, empties the log
+// if `reset`, and returns how many there were
+int yafgpu_exit_log_read(uint32_t *out, uint32_t cap, int reset)
+{
+	uint32_t n = 0u;
+	HIP_OK(hipDeviceSynchronize());
+	HIP_OK(hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_exit_log_n), sizeof n));
+	n = std::min(n, kExitLogCap);
+	if(out && std::min(n, cap)) HIP_OK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_exit_log), (size_t)std::min(n, cap) * 2u * sizeof(uint4)));
+	const uint32_t zero = 0u;
+	if(reset) HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(g_exit_log_n), &zero, sizeof zero));
+	return (int)n;
+}
+#endif
 
 void yafgpu_glibc_rand(uint32_t seed, int32_t count, int32_t *out)
 {	// glibc stdlib/random_r.c, TYPE_3: 31 words seeded by the Lehmer generator 16807 x mod 2^31 - 1 (Schrage's method), then

@@ -18,6 +18,50 @@
 // integrator_montecarlo.cc:78-345, Triangle::intersect); tests/test_gpu_parity.py holds the films to the oracle's.
 #pragma once
 
+// ---- wf_trace's queue reservations: the size rule -----------------------------------------------
+// This part stands on its own: a plain host compiler that defines YAFGPU_TRACE_SCHEDULE_ONLY gets the rule and nothing else
+// of this header (tests/test_trace_schedule_host.py simulates the cursor with it).
+#include <stdint.h>
+#if defined(__HIPCC__)
+#define YAFGPU_HOST_DEVICE __host__ __device__
+#else
+#define YAFGPU_HOST_DEVICE
+#endif
+#ifndef YAFGPU_TRACE_BATCH
+#define YAFGPU_TRACE_BATCH 512         // the largest reservation: queue entries a wave takes with one atomic
+#endif
+// kMin and D, swept on m1 (profiles/r08_ab_trace_schedule.txt): against the parent's rule D 2 -> +1.6 %, 4 -> +5.8 %, 8 -> +8.8 %, 16 -> +8.3 %;
+// kMin 64 and 128 within the noise of each other at every D (256: -0.5 % at D 4), so the larger one, which halves the atomics while a launch drains
+#ifndef YAFGPU_TRACE_BATCH_MIN
+#define YAFGPU_TRACE_BATCH_MIN 128     // the smallest reservation (kMin): bounds the atomics per microsecond on the cursor word while a launch drains
+#endif
+#ifndef YAFGPU_TRACE_BATCH_DIV
+#define YAFGPU_TRACE_BATCH_DIV 8       // D: a reservation is 1 / (waves * D) of what is left
+#endif
+#ifndef YAFGPU_TRACE_BATCH_SHRINK
+#define YAFGPU_TRACE_BATCH_SHRINK 1    // 0: the comparison build, every reservation of a launch sized by the whole queue (with kMin 64 and D 2: the rule before round 8)
+#endif
+#ifndef YAFGPU_TRACE_STATIC_FIRST
+#define YAFGPU_TRACE_STATIC_FIRST 1    // a wave's first range is [w * b0, (w + 1) * b0) without an atomic, the cursor counts from waves * b0 (0: the comparison build; +0.9 % on m1)
+#endif
+
+namespace yafgpu {
+
+// Entries a wave reserves when the last queue position it has seen handed out is `seen` (0 before its first reservation) of `n`,
+// with `waves` waves in the launch: guided self-scheduling, a share 1 / (waves * D) of what is left, a multiple of the wave
+// within [kMin, YAFGPU_TRACE_BATCH].  `seen` may be stale (other waves have reserved since): that only errs towards a larger size.
+YAFGPU_HOST_DEVICE inline uint32_t trace_reservation(uint32_t n, uint32_t seen, uint32_t waves)
+{
+	const uint32_t left = n - (seen < n ? seen : n);
+	const uint32_t share = (left / (waves * (uint32_t)YAFGPU_TRACE_BATCH_DIV)) & ~63u;
+	const uint32_t lo = (uint32_t)YAFGPU_TRACE_BATCH_MIN, hi = (uint32_t)YAFGPU_TRACE_BATCH;
+	return share < lo ? lo : (share > hi ? hi : share);
+}
+
+} // namespace yafgpu
+
+#ifndef YAFGPU_TRACE_SCHEDULE_ONLY
+
 namespace yafgpu {
 
 constexpr int kWfRecs = 32;   // float4 records of parked state per path (512 B; 28..31 hold a SECOND MIS pair parked with the first (WfArgs::multi); 22 and 23 are only touched in textured scenes, 24 and 25 only with bump mapping, 26 and 27 by a path that parks its next segment beside a vertex's last shadow pair)
@@ -1793,10 +1837,7 @@ __global__ __launch_bounds__(kBlock) void wf_generate(const WfArgs a)
 #ifndef YAFGPU_NODE_BURST
 #define YAFGPU_NODE_BURST 2    // treelet fetches per vote, each good for up to two node steps (K sweep: profiles/r04_ab_treelet.txt)
 #endif
-#ifndef YAFGPU_TRACE_BATCH
-#define YAFGPU_TRACE_BATCH 512
-#endif
-constexpr int kTraceBatch = YAFGPU_TRACE_BATCH;
+// (the reservation sizes, YAFGPU_TRACE_BATCH and its kin: trace_reservation at the top of this header)
 #ifndef YAFGPU_REFILL
 #define YAFGPU_REFILL 32               // m1 sweep with held answers (profiles/r07_ab_trace_waits.txt): 8 -> -3.4 %, 16 -> -1.0 %, 24 -> -0.5 %, 40 -> -1.0 % against 32
 #endif
@@ -1838,6 +1879,17 @@ constexpr int kTraceBatch = YAFGPU_TRACE_BATCH;
 #ifndef YAFGPU_STATS_OCCLUDED
 #define YAFGPU_STATS_OCCLUDED 0
 #endif
+// One-off measurement build: every traversal wave leaves a record of how it ended — its start and exit times (wall_clock64, the
+// 100 MHz constant clock), the launch's kind and queue length, its reservations — in a log that yafgpu_exit_log_read hands out
+// (tools/exit_times.py, profiles/r08_ab_trace_schedule.txt).  Off, nothing of it is in any kernel.
+#ifndef YAFGPU_TRACE_EXIT_LOG
+#define YAFGPU_TRACE_EXIT_LOG 0
+#endif
+#if YAFGPU_TRACE_EXIT_LOG
+constexpr uint32_t kExitLogCap = 1u << 20;      // records; later ones are dropped
+static __device__ uint4 g_exit_log[2u * kExitLogCap];      // per record: (exit lo, exit hi, start lo, start hi), (n, any-hit, reservations, wave)
+static __device__ uint32_t g_exit_log_n;
+#endif
 #ifndef YAFGPU_TRACE_WAVES
 #define YAFGPU_TRACE_WAVES 7     // waves per SIMD the register allocation must leave room for (22.5 KB of LDS per block allow 7): 72 / 70 VGPRs (closest / any); without the bound the any-hit kernel once took 81 (5 waves)
 #endif
@@ -1862,8 +1914,25 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 	bool exhausted = (n == 0u);
 	uint32_t slot = 0u, link = 0u, which = 0u, pair = 0u, qi = 0u;      // link: where the walk stands (kdtree_build.h)      // qi: the ray's position in the queue (where a closest-hit answer goes)
 	uint32_t w_next = 0u, w_end = 0u;      // this wave's reserved queue range (wave-uniform)
-	// reservation size: large enough to keep the counter word off the critical path, small enough that a short queue still spreads over all waves
-	const uint32_t batch = min((uint32_t)kTraceBatch, max((uint32_t)kWave, (n / (gridDim.x * (uint32_t)kWavesPerBlock * 2u)) & ~63u));
+	// Reservation sizes (trace_reservation): large enough to keep the counter word off the critical path, small enough that a short queue
+	// still spreads over all waves, and shrinking with what is left of the queue: when the cursor passes n every wave still owns up to one
+	// reservation of its own, and the launch ends only when the slowest of them is through (DESIGN.md §4.1, §9 "Launch tails").
+	const uint32_t n_waves = gridDim.x * (uint32_t)kWavesPerBlock;
+	uint32_t seen = 0u;                    // the last queue position this wave was handed (wave-uniform): what is left is at most n - seen
+	uint32_t first_at = 0u;                // where the cursor's count starts: behind the static first ranges, if there are any
+#if YAFGPU_TRACE_STATIC_FIRST
+	{	// the first range without the atomic: at launch every wave would ask the one counter word at once
+		const uint32_t b0 = trace_reservation(n, 0u, n_waves);
+		const uint32_t w_id = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (uint32_t)kWavesPerBlock + (uint32_t)wave));
+		first_at = n_waves * b0;
+		w_next = min(w_id * b0, n); w_end = min(w_next + b0, n);
+		if(w_next >= n) { exhausted = true; w_next = w_end = 0u; }      // then n <= first_at: nothing is left for the cursor either
+	}
+#endif
+#if YAFGPU_TRACE_EXIT_LOG
+	const unsigned long long log_t0 = wall_clock64();
+	uint32_t log_res = 0u;
+#endif
 	V3 from = mk(0.f, 0.f, 0.f), dir = from;
 	uint32_t dneg = 0u;                    // bit k: direction component k <= 0 (the tie rule at o == split)
 	float ray_tmin = 0.f, dist = 0.f, t_exit = 0.f, tmin = 0.f, tmax = 0.f, z = 0.f, bu = 0.f, bv = 0.f;
@@ -1899,16 +1968,21 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 		{
 			// the answers held back since the last refill leave first: one group of stores (any-hit: atomics) per refill, none in the rounds
 			if(kDefer && ws == kAnswer) { answer(); ws = kNoRay; }
-			// the wave owns [w_next, w_end) of the queue; one atomic reserves kTraceBatch entries at a time (a single
+			// the wave owns [w_next, w_end) of the queue; one atomic reserves `want` entries at a time (a single
 			// counter word sustains only ~90 returning atomics per microsecond: MI355X_MICROARCH.md, row "dequeue")
 			if(w_next >= w_end)
 			{
 				const int leader = __ffsll((long long)idle) - 1;
+				const uint32_t want = trace_reservation(n, YAFGPU_TRACE_BATCH_SHRINK ? seen : 0u, n_waves);
 				uint32_t base = 0u;
-				if(lane == leader) base = atomicAdd(cursor, batch);
-				base = (uint32_t)__shfl((int)base, leader, kWave);
-				w_next = base; w_end = min(base + batch, n);
+				if(lane == leader) base = atomicAdd(cursor, want);
+				base = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)base, leader, kWave)) + first_at;
+				seen = base;
+				w_next = base; w_end = min(base + want, n);
 				if(base >= n) { exhausted = true; w_next = w_end = 0u; }
+#if YAFGPU_TRACE_EXIT_LOG
+				++log_res;
+#endif
 			}
 			const uint32_t avail = w_end - w_next;
 			const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
@@ -2134,6 +2208,21 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 			ws = hold ? kAnswer : kNoRay; done = false; p_cur = p_end = 0u;
 		}
 	}
+#if YAFGPU_TRACE_EXIT_LOG
+	if(n != 0u)
+	{
+		const unsigned long long log_t1 = wall_clock64();
+		if(lane == 0)
+		{
+			const uint32_t at = atomicAdd(&g_exit_log_n, 1u);
+			if(at < kExitLogCap)
+			{
+				g_exit_log[2u * at] = make_uint4((uint32_t)log_t1, (uint32_t)(log_t1 >> 32), (uint32_t)log_t0, (uint32_t)(log_t0 >> 32));
+				g_exit_log[2u * at + 1u] = make_uint4(n, kAny ? 1u : 0u, log_res, blockIdx.x * (uint32_t)kWavesPerBlock + (uint32_t)wave);
+			}
+		}
+	}
+#endif
 	if(a.ra.counters != nullptr)
 	{
 		const uint32_t v0 = wave_sum(cn.closest), v1 = wave_sum(cn.shadow), v2 = wave_sum(cn.interior), v3_ = wave_sum(cn.leaves),
@@ -2600,3 +2689,5 @@ __global__ __launch_bounds__(kWave) void wf_replay_samples(const ReplayArgs r)
 
 #endif // YAFGPU_VARIANT_TU
 } // namespace yafgpu
+
+#endif // YAFGPU_TRACE_SCHEDULE_ONLY

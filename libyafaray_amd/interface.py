@@ -84,7 +84,7 @@ C_API_SYMBOLS = [
 GPU_ABI_SYMBOLS = [
     "yafgpu_last_error", "yafgpu_device_count", "yafgpu_set_device", "yafgpu_scene_create", "yafgpu_scene_destroy",
     "yafgpu_scene_info", "yafgpu_planes_bytes", "yafgpu_render_tiles", "yafgpu_film_combine", "yafgpu_render_to_host", "yafgpu_render_passes_to_host",
-    "yafgpu_trace_closest", "yafgpu_trace_shadow", "yafgpu_scene_get_tree", "yafgpu_probe",
+    "yafgpu_trace_closest", "yafgpu_trace_shadow", "yafgpu_trace_reservation", "yafgpu_trace_schedule", "yafgpu_scene_get_tree", "yafgpu_probe",
     "yafgpu_kdtree_build", "yafgpu_kdtree_build_device", "yafgpu_kdtree_info", "yafgpu_kdtree_get", "yafgpu_kdtree_destroy", "yafgpu_kdtree_treelets",
     "yafgpu_set_profiling", "yafgpu_scene_set_pass_pipelining", "yafgpu_get_profile", "yafgpu_scene_set_abort_flag", "yafgpu_scene_set_exchange", "yafgpu_glibc_rand",
 ]
@@ -694,6 +694,25 @@ def build_treelets(nodes, inline_leaves=True):
     if rc:
         raise YafaRayError(f"treelet layout: {rc}")
     return words[:nw.value].reshape(-1, 8), leaves[:nl.value].reshape(-1, 2), root.value
+
+
+def trace_reservation(n, seen, waves):
+    """the queue entries a traversal wave reserves with `seen` of `n` handed out, by the rule the library was built with"""
+    L = load()
+    L.yafgpu_trace_reservation.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    L.yafgpu_trace_reservation.restype = C.c_uint32
+    return int(L.yafgpu_trace_reservation(n, seen, waves))
+
+
+def trace_schedule():
+    """the traversal kernels' queue schedule as built, and the workgroups of this process's last traversal launches (include/yafgpu.h)"""
+    L = load()
+    info = (C.c_uint32 * 8)()
+    L.yafgpu_trace_schedule.argtypes = [C.POINTER(C.c_uint32)]
+    L.yafgpu_trace_schedule.restype = None
+    L.yafgpu_trace_schedule(info)
+    keys = ("min", "max", "div", "shrink", "static_first", "waves_per_group", "grid_closest", "grid_any")
+    return dict(zip(keys, (int(v) for v in info)))
 
 
 def planes_bytes(width, height):
