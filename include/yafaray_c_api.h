@@ -89,9 +89,29 @@ yafaray_bool_t yafaray_addInstance(yafaray_interface_t *yi, unsigned int base_ob
  * id, has_orco, has_uv, is_smooth, normals_exported (the flags as they stood at the call), then the 16 matrix floats.  Returns the
  * number of instances */
 int yafaray_getInstances(yafaray_interface_t *yi, void *out, int max_instances);
-/* refused with a diagnostic (outside the path's scope): */
+/* Curve meshes (Scene::startCurveMesh / endCurveMesh, scene.cc:133-281): a strand of hair, fur or grass as a poly-line with a root radius
+ * (strand_start), a tip radius (strand_end) and a shape exponent (strand_shape).  The reference extrudes every point into a triangular
+ * cross-section and fills a prism per segment, 6 * (n - 1) + 2 triangles with UVs that run 0 -> 1 along the strand, into an ordinary
+ * TriangleObject (UVs, no orco, visible, no base mesh).  Here the points are kept and the triangles are made on the device at scene set-up,
+ * in the reference's order and arithmetic; the radii are computed at endCurveMesh with the host's libm, as the reference does.
+ *   startCurveMesh  only between startGeometry and endGeometry and outside any open object; opens an object of its own under `id` (a mesh
+ *                   or an instance that had the id is replaced).  `vertices` is a reservation hint.
+ *   in between      addVertex only; addVertexWithOrco, addNormal, addUv, addTriangle*, addTriangles and endTriMesh are refused.
+ *   endCurveMesh    refused, and the object dropped, for a null material, fewer than two points, a non-finite point or parameter, or
+ *                   parameters that give a non-finite radius (a shape below -1 raises 0 to a negative power).
+ * smoothMesh on a curve's id and addInstance with a curve as its base are refused: a curve has no stored faces. */
 yafaray_bool_t yafaray_startCurveMesh(yafaray_interface_t *yi, unsigned int id, int vertices, int obj_pass_index);       /* :62 */
 yafaray_bool_t yafaray_endCurveMesh(yafaray_interface_t *yi, const yafaray_material_t *mat, float strand_start, float strand_end, float strand_shape); /* :65 */
+/* extension: n_curves strands in one call, curve k with n_points[k] points taken in turn from the packed xyz floats of `points`, all with
+ * one material and one set of strand parameters.  Defined as the loop of getNextFreeId / startCurveMesh / addVertex per point /
+ * endCurveMesh, which it stops at the first refusal; ids (NULL or n_curves entries) receives the object ids */
+yafaray_bool_t yafaray_addCurves(yafaray_interface_t *yi, int n_curves, const int *n_points, const float *points, const yafaray_material_t *mat,
+                                 float strand_start, float strand_end, float strand_shape, unsigned int *ids);
+/* extension (test support): what endCurveMesh stored, in object-id order, as a stream of 32-bit words.  Per curve: id, point count n,
+ * material index, then the floats strand_start, strand_end, strand_shape, then per point x y z h s, where h = (float)(0.5 * r) and
+ * s = (float)(1.5 * r / sqrt((double)3.f)) scale the two frame vectors of the extrusion (scene.cc:188-189).  Whole records are written
+ * while they fit into max_words; *n_words (NULL or one int) receives what all of them take.  Returns the number of curves */
+int yafaray_getCurves(yafaray_interface_t *yi, void *out, int max_words, int *n_words);
 /* extension (test support): the per-triangle-corner normals smoothMesh computed, n_tris*9 floats; an all-zero triple = geometric normal */
 yafaray_bool_t yafaray_getMeshCornerNormals(yafaray_interface_t *yi, unsigned int id, float *out, int n_floats);
 /* extension (test support): the scene's enabled lights in Scene::addLight order, as the device gets them: up to max_lights

@@ -231,13 +231,19 @@ typedef struct yafgpu_camera
 	int32_t projection;            /* YAFGPU_ANGULAR_* */
 } yafgpu_camera;
 
-/* Instanced geometry (Scene::addInstance, scene.cc:1105-1130).  The reference has no second tree level: a TriangleObjectInstance's
+/* Instanced geometry (Scene::addInstance, scene.cc:1105-1130) and curve meshes (Scene::endCurveMesh, :154-281): geometry whose triangles are
+ * made on the device at scene set-up.  The reference has no second tree level: a TriangleObjectInstance's
  * TriangleInstance triangles go into the one kd-tree beside every other triangle (scene.cc:797-817), so an instance is more rows of the
  * triangle, shading and texture-coordinate arrays.  With segments, yafgpu_scene_create makes ALL rows of the scene on the device, in segment
  * order (csrc/yafgpu_assemble.hip); only the base meshes and the matrices cross the bus.
  *   plain segment     rows [first, first + count) of the descriptor's own arrays (verts, tri_mat, vnormals, tri_uv, tri_orco), as they are
- *   instance segment  rows [first, first + count) of the base pools below under matrix m (row major, Matrix4 * Point3, matrix4.h:89-94) */
-enum { YAFGPU_SEGMENT_PLAIN = 0, YAFGPU_SEGMENT_INSTANCE = 1 };
+ *   instance segment  rows [first, first + count) of the base pools below under matrix m (row major, Matrix4 * Point3, matrix4.h:89-94)
+ *   curve segment     one strand (Scene::endCurveMesh, scene.cc:154-281): points [first, first + count) of the curve point pool below,
+ *                     count >= 2, extruded into a triangular prism per poly-line segment.  It makes 6 * (count - 1) + 2 rows in the
+ *                     reference's order: the bottom cap, six triangles per segment, the top cap; UVs 0 -> 1 along the strand, no orco,
+ *                     no vertex normals.  `first` = the first point, `count` = the number of points (not of rows), `flags` = the material
+ *                     index of every row; m is not read */
+enum { YAFGPU_SEGMENT_PLAIN = 0, YAFGPU_SEGMENT_INSTANCE = 1, YAFGPU_SEGMENT_CURVE = 2 };
 /* what TriangleObjectInstance copied from its base when it was made (object_geom.cc:104-121) */
 enum { YAFGPU_INSTANCE_SMOOTH = 1,     /* is_smooth_ || normals_exported_: TriangleInstance::getSurface reads vertex normals (triangle.cc:210-222) */
        YAFGPU_INSTANCE_ORCO = 2,       /* has_orco_: the base's orco values (triangle.cc:224-235), else the hit point */
@@ -245,8 +251,8 @@ enum { YAFGPU_INSTANCE_SMOOTH = 1,     /* is_smooth_ || normals_exported_: Trian
 typedef struct yafgpu_segment
 {
 	int32_t kind;                /* YAFGPU_SEGMENT_* */
-	int32_t first, count;
-	uint32_t flags;              /* YAFGPU_INSTANCE_*, instance segments only */
+	int32_t first, count;        /* rows of the plain arrays / the base pools; a curve segment: points of the curve pool */
+	uint32_t flags;              /* instance segments: YAFGPU_INSTANCE_*; curve segments: the material index */
 	float m[16];                 /* obj_to_world, instance segments only */
 } yafgpu_segment;
 typedef struct yafgpu_instancing
@@ -261,6 +267,12 @@ typedef struct yafgpu_instancing
 	const uint8_t *base_vn_index0;       /* with base_vnormals, n_base_tris bytes: bit c set = corner c's normal has index 0 in the base's normal
 	                                        array, which TriangleInstance::getSurface's `index > 0` test sends to the geometric normal */
 	const float *base_uv, *base_orco;    /* NULL or n_base_tris*6 / *9, as tri_uv / tri_orco (first word NaN: none) */
+	/* curve point pool (curve segments), zeroed = none: five floats per point, x y z h s.  h and s are the two extrusion scales of
+	   scene.cc:188-189 for the point's radius r, h = (float)(0.5 * r) along v and s = (float)(1.5 * r / sqrt((double)3.f)) along u.  The
+	   caller computes them: r takes libm's double pow, which the device does not restate.  The tangent frame and everything after it
+	   are made on the device */
+	int32_t n_curve_points;
+	const float *curve_points;   /* n_curve_points*5 */
 } yafgpu_instancing;
 
 typedef struct yafgpu_scene_desc
@@ -286,7 +298,7 @@ typedef struct yafgpu_scene_desc
 	                                The environment variable YAFGPU_BUILD=device|host overrides it. */
 	yafgpu_background background; /* kind 0: none.  A texture background is evaluated per escaping ray (yafgpu_render_params::background is
 	                                the constant case's colour and keeps working without this record) */
-	yafgpu_instancing inst;      /* optional, zeroed = none: then n_tris rows of the arrays above are the scene, made by the host loop as
+	yafgpu_instancing inst;      /* instances and curves; optional, zeroed = none: then n_tris rows of the arrays above are the scene, made by the host loop as
 	                                ever.  With segments the arrays above hold the plain triangles only (n_tris of them) and the scene is
 	                                the segments' rows; yafgpu_tree_info::n_tris counts those */
 } yafgpu_scene_desc;

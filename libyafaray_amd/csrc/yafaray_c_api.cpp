@@ -75,6 +75,16 @@ struct Instance
 	bool has_orco = false, has_uv = false, smooth = false, normals_exported = false;
 };
 
+// A curve (strand) mesh as Scene::startCurveMesh .. endCurveMesh take it (scene.cc:133-281): the poly-line, one material and the three
+// strand parameters.  No triangles are stored: the device extrudes the points at scene set-up (yafgpu_instancing's curve segments).
+struct Curve
+{
+	std::vector<float> points;        // xyz
+	std::vector<float> scales;        // h, s per point (curve_scales), filled by endCurveMesh
+	int mat = -1;
+	float strand_start = 0.f, strand_end = 0.f, strand_shape = 0.f;
+};
+
 struct IntegratorCfg
 {
 	std::string type;
@@ -120,11 +130,15 @@ struct yafaray_interface
 	std::map<std::string, std::unique_ptr<yafaray_camera>> cameras;
 	std::map<std::string, std::unique_ptr<yafaray_background>> backgrounds;
 	std::map<std::string, std::unique_ptr<yafaray_integrator>> integrators;
-	// scene state (scene.cc:110-131): 0 ready, 1 geometry, 2 object
+	// scene state (scene.cc:110-131): 0 ready, 1 geometry, 2 object; 3 is the reference's object state too, with a curve as the open object
 	int state = -1;
 	std::map<unsigned int, Mesh> meshes;
 	std::map<unsigned int, Instance> instances;      // object ids are shared with meshes: the id decides the place in the flattening order
+	std::map<unsigned int, Curve> curves;            // object ids shared with meshes and instances
 	Mesh *cur = nullptr, *last = nullptr;   // last: Scene's cur_obj_ outlives endTriMesh (smoothMesh(0, angle))
+	Curve *cur_curve = nullptr;             // the open curve (state 3)
+	unsigned int cur_curve_id = 0;
+	bool last_is_curve = false;             // Scene's cur_obj_ is a curve: smoothMesh(0, angle) would mean it
 	unsigned int next_id = 1;
 	bool geometry_changed = true;
 	// render
@@ -1112,19 +1126,30 @@ const char *yafaray_getVersion(void) { return "yafgpu-0.1 (MI355X path-tracing c
 yafaray_bool_t yafaray_startScene(yafaray_interface_t *yi, int type)
 {
 	if(type != 0) return fail(yi, "startScene: only scene type 0 (\"triangle\") is supported (import_xml.cc:339-347)");
-	yi->state = 0; yi->meshes.clear(); yi->instances.clear(); yi->cur = nullptr; yi->last = nullptr; yi->geometry_changed = true; yi->prepared = false; yi->scene_dirty = true;
+	yi->state = 0; yi->meshes.clear(); yi->instances.clear(); yi->curves.clear(); yi->cur = nullptr; yi->last = nullptr; yi->cur_curve = nullptr; yi->last_is_curve = false; yi->geometry_changed = true; yi->prepared = false; yi->scene_dirty = true;
 	return 1;
 }
 yafaray_bool_t yafaray_startGeometry(yafaray_interface_t *yi) { if(yi->state != 0) return fail(yi, "startGeometry: wrong state"); yi->state = 1; return 1; }
 yafaray_bool_t yafaray_endGeometry(yafaray_interface_t *yi) { if(yi->state != 1) return fail(yi, "endGeometry: wrong state"); yi->state = 0; return 1; }
-unsigned int yafaray_getNextFreeId(yafaray_interface_t *yi) { while(yi->meshes.count(yi->next_id) || yi->instances.count(yi->next_id)) ++yi->next_id; return yi->next_id++; }
+unsigned int yafaray_getNextFreeId(yafaray_interface_t *yi) { while(yi->meshes.count(yi->next_id) || yi->instances.count(yi->next_id) || yi->curves.count(yi->next_id)) ++yi->next_id; return yi->next_id++; }
+
+// Between startCurveMesh and endCurveMesh only addVertex means something (import_xml.cc:504-509): the reference would push whatever else
+// comes into the TriangleObject that endCurveMesh then indexes by point count.  Refused with the cause.
+static bool in_curve(yafaray_interface_t *yi, const char *call)
+{
+	if(yi->state != 3) return false;
+	fail(yi, std::string(call) + ": a curve mesh is open (startCurveMesh): between it and endCurveMesh only addVertex is accepted");
+	return true;
+}
 
 yafaray_bool_t yafaray_startTriMesh(yafaray_interface_t *yi, unsigned int id, int vertices, int triangles, yafaray_bool_t has_orco, yafaray_bool_t has_uv, int type, int)
 {
+	if(in_curve(yi, "startTriMesh")) return 0;
 	if(yi->state != 1) return fail(yi, "startTriMesh: wrong state");
 	if((type & 0xFF) != 0) return fail(yi, "startTriMesh: only TRIM meshes (type 0) are supported");
 	note_srand(yi, ++g_object_index_auto);          // ObjectGeometric::ObjectGeometric, object_geom.cc:39-43
 	yi->instances.erase(id);                        // meshes_[id] is one slot: a mesh started under an instance's id takes its place
+	yi->curves.erase(id); yi->last_is_curve = false;
 	Mesh &m = yi->meshes[id];
 	m = Mesh();
 	m.visible = !(type & 0x0100); m.base = (type & 0x0200) != 0;
@@ -1136,6 +1161,7 @@ yafaray_bool_t yafaray_startTriMesh(yafaray_interface_t *yi, unsigned int id, in
 yafaray_bool_t yafaray_endTriMesh(yafaray_interface_t *yi)
 {	// Scene::endTriMesh, scene.cc:311-337: "UV-offsets mismatch!" when the triangle and UV-offset counts disagree; the reference never
 	// range-checks the offsets themselves (exporters may list <uv> after the faces), so that check waits until here
+	if(in_curve(yi, "endTriMesh")) return 0;
 	if(yi->state != 2) return fail(yi, "endTriMesh: wrong state");
 	Mesh &m = *yi->cur;
 	if(m.has_uv)
@@ -1149,6 +1175,12 @@ yafaray_bool_t yafaray_endTriMesh(yafaray_interface_t *yi)
 }
 int yafaray_addVertex(yafaray_interface_t *yi, double x, double y, double z)
 {
+	if(yi->state == 3)
+	{	// a point of the open curve's poly-line (startElCurve__, import_xml.cc:504-509)
+		Curve &c = *yi->cur_curve;
+		c.points.push_back((float)x); c.points.push_back((float)y); c.points.push_back((float)z);
+		return (int)(c.points.size() / 3) - 1;
+	}
 	if(yi->state != 2) { fail(yi, "addVertex: wrong state"); return -1; }
 	Mesh &m = *yi->cur;
 	m.points.push_back((float)x); m.points.push_back((float)y); m.points.push_back((float)z);
@@ -1156,6 +1188,7 @@ int yafaray_addVertex(yafaray_interface_t *yi, double x, double y, double z)
 }
 void yafaray_addNormal(yafaray_interface_t *yi, double nx, double ny, double nz)
 {	// Scene::addNormal, scene.cc:592-607: attaches to the last vertex
+	if(in_curve(yi, "addNormal")) return;
 	if(yi->state != 2) { fail(yi, "addNormal: wrong state"); return; }
 	Mesh &m = *yi->cur;
 	const size_t nv = m.points.size() / 3;
@@ -1166,6 +1199,7 @@ void yafaray_addNormal(yafaray_interface_t *yi, double nx, double ny, double nz)
 }
 yafaray_bool_t yafaray_addTriangle(yafaray_interface_t *yi, int a, int b, int c, const yafaray_material_t *mat)
 {
+	if(in_curve(yi, "addTriangle")) return 0;
 	if(yi->state != 2) return fail(yi, "addTriangle: wrong state");
 	if(!mat) return fail(yi, "addTriangle: null material");
 	Mesh &m = *yi->cur;
@@ -1176,6 +1210,7 @@ yafaray_bool_t yafaray_addTriangle(yafaray_interface_t *yi, int a, int b, int c,
 }
 int yafaray_addVertexWithOrco(yafaray_interface_t *yi, double x, double y, double z, double ox, double oy, double oz)
 {	// Interface::addVertex(x, y, z, ox, oy, oz) -> Scene::addVertex(p, orco), scene.cc:567-590
+	if(in_curve(yi, "addVertex")) return -1;        // state_.orco_ is false in a curve (scene.cc:147)
 	if(yi->state != 2) { fail(yi, "addVertex: wrong state"); return -1; }
 	Mesh &m = *yi->cur;
 	if(!m.has_orco) { fail(yi, "addVertex: the mesh was started without orco coordinates"); return -1; }
@@ -1187,6 +1222,7 @@ int yafaray_addVertexWithOrco(yafaray_interface_t *yi, double x, double y, doubl
 }
 int yafaray_addUv(yafaray_interface_t *yi, float u, float v)
 {	// Scene::addUv, scene.cc:672-686
+	if(in_curve(yi, "addUv")) return -1;
 	if(yi->state != 2 || !yi->cur) { fail(yi, "addUv: wrong state"); return -1; }
 	Mesh &m = *yi->cur;
 	m.uv.push_back(u); m.uv.push_back(v);
@@ -1194,6 +1230,7 @@ int yafaray_addUv(yafaray_interface_t *yi, float u, float v)
 }
 yafaray_bool_t yafaray_addTriangleWithUv(yafaray_interface_t *yi, int a, int b, int c, int uv_a, int uv_b, int uv_c, const yafaray_material_t *mat)
 {	// Interface::addTriangle(a, b, c, uv_a, uv_b, uv_c, mat) -> Scene::addTriangle, scene.cc:652-670
+	if(in_curve(yi, "addTriangle")) return 0;
 	if(yi->state != 2) return fail(yi, "addTriangle: wrong state");
 	Mesh &m = *yi->cur;
 	if(!m.has_uv) return fail(yi, "addTriangle: the mesh was started without UV coordinates");
@@ -1207,13 +1244,112 @@ yafaray_bool_t yafaray_startTriMeshPtr(yafaray_interface_t *yi, unsigned int *id
 	*id = yafaray_getNextFreeId(yi);
 	return yafaray_startTriMesh(yi, *id, vertices, triangles, has_orco, has_uv, type, obj_pass_index);
 }
-// outside the hot path's scope: refused with a diagnostic, never routed anywhere else
-yafaray_bool_t yafaray_startCurveMesh(yafaray_interface_t *yi, unsigned int, int, int) { return fail(yi, "startCurveMesh: curve (strand) meshes are outside the GPU path's scope"); }
-yafaray_bool_t yafaray_endCurveMesh(yafaray_interface_t *yi, const yafaray_material_t *, float, float, float) { return fail(yi, "endCurveMesh: curve (strand) meshes are outside the GPU path's scope"); }
+// Scene::startCurveMesh, scene.cc:133-152: an object of its own, a TriangleObject with UVs and without orco, type 0 (visible, no base mesh).
+// `vertices` only sizes the reference's reservations.
+yafaray_bool_t yafaray_startCurveMesh(yafaray_interface_t *yi, unsigned int id, int vertices, int)
+{
+	if(yi->state == 3) return fail(yi, "startCurveMesh: a curve mesh is already open (endCurveMesh closes it)");
+	if(yi->state == 2) return fail(yi, "startCurveMesh: a mesh is open (endTriMesh closes it)");
+	if(yi->state != 1) return fail(yi, "startCurveMesh: wrong state (call it between startGeometry and endGeometry)");
+	note_srand(yi, ++g_object_index_auto);          // the TriangleObject is an ObjectGeometric, object_geom.cc:39-43
+	{	// meshes_[id] is one slot: a curve started under a mesh's or an instance's id takes its place
+		auto it = yi->meshes.find(id);
+		if(it != yi->meshes.end()) { if(yi->last == &it->second) yi->last = nullptr; yi->meshes.erase(it); }
+		yi->instances.erase(id);
+	}
+	Curve &c = yi->curves[id];
+	c = Curve();
+	c.points.reserve((size_t)std::max(vertices, 0) * 3);
+	yi->cur_curve = &c; yi->cur_curve_id = id; yi->last_is_curve = true; yi->state = 3;
+	yi->geometry_changed = true; yi->prepared = false; yi->scene_dirty = true;
+	return 1;
+}
+// The two extrusion scales of point i of n, scene.cc:172-189.  Unqualified pow and sqrt there are the C double functions (<cmath> alone, no
+// using-directive): the ratio and the exponent are floats widened to double, the sum is taken in double and narrowed to `float r`.
+// h scales v and s scales u through operator*(float, Vec3): (float)(0.5 * r) and (float)(1.5 * r / sqrt(3.f)).
+static void curve_scales(int i, int n, float strand_start, float strand_end, float strand_shape, float &h, float &s)
+{
+	float r;
+	if(strand_shape < 0) r = (float)((double)strand_start + ::pow((double)((float)i / (float)(n - 1)), (double)(1 + strand_shape)) * (double)(strand_end - strand_start));
+	else r = (float)((double)strand_start + (1 - ::pow((double)(((float)(n - i - 1)) / (float)(n - 1)), (double)(1 - strand_shape))) * (double)(strand_end - strand_start));
+	h = (float)(0.5 * (double)r);
+	s = (float)(1.5 * (double)r / ::sqrt((double)3.f));
+}
+// Scene::endCurveMesh, scene.cc:154-281.  The points, the material and the three floats are kept, with the scales above per point; the
+// extrusion and the face fill run on the device when the scene is set up.  A refused call closes the block and drops the object.
+yafaray_bool_t yafaray_endCurveMesh(yafaray_interface_t *yi, const yafaray_material_t *mat, float strand_start, float strand_end, float strand_shape)
+{
+	if(yi->state != 3) return fail(yi, "endCurveMesh: no curve mesh is open (startCurveMesh opens one)");
+	Curve &c = *yi->cur_curve;
+	const unsigned int id = yi->cur_curve_id;
+	auto refuse = [&](const std::string &why) { yi->curves.erase(id); yi->cur_curve = nullptr; yi->last_is_curve = false; yi->state = 1; return fail(yi, "endCurveMesh: " + why); };
+	const int n = (int)(c.points.size() / 3);
+	if(!mat) return refuse("null material (the reference stores it in every triangle and dereferences it at the first hit)");
+	if(n < 2) return refuse("a curve needs two or more points, this one has " + std::to_string(n) + " (scene.cc:174 divides by n - 1)");
+	for(size_t k = 0; k < c.points.size(); ++k)
+		if(!std::isfinite(c.points[k])) return refuse("non-finite coordinate in point " + std::to_string(k / 3));
+	if(!std::isfinite(strand_start) || !std::isfinite(strand_end) || !std::isfinite(strand_shape)) return refuse("non-finite strand_start, strand_end or strand_shape");
+	c.scales.resize((size_t)n * 2);
+	for(int i = 0; i < n; ++i)
+	{
+		curve_scales(i, n, strand_start, strand_end, strand_shape, c.scales[2 * (size_t)i], c.scales[2 * (size_t)i + 1]);
+		if(!std::isfinite(c.scales[2 * (size_t)i]) || !std::isfinite(c.scales[2 * (size_t)i + 1]))
+			return refuse("strand_start, strand_end and strand_shape give a non-finite radius at point " + std::to_string(i));
+	}
+	c.mat = mat->index; c.strand_start = strand_start; c.strand_end = strand_end; c.strand_shape = strand_shape;
+	yi->cur_curve = nullptr; yi->state = 1;
+	return 1;
+}
+// extension: n_curves strands in one call, exactly the loop of getNextFreeId / startCurveMesh / addVertex per point / endCurveMesh
+yafaray_bool_t yafaray_addCurves(yafaray_interface_t *yi, int n_curves, const int *n_points, const float *points, const yafaray_material_t *mat,
+                                 float strand_start, float strand_end, float strand_shape, unsigned int *ids)
+{
+	if(n_curves < 0 || (n_curves > 0 && (!n_points || !points))) return fail(yi, "addCurves: bad argument");
+	const float *p = points;
+	for(int k = 0; k < n_curves; ++k)
+	{
+		if(n_points[k] < 0) return fail(yi, "addCurves: negative point count for curve " + std::to_string(k));
+		const unsigned int id = yafaray_getNextFreeId(yi);
+		if(ids) ids[k] = id;
+		if(!yafaray_startCurveMesh(yi, id, n_points[k], 0)) return 0;
+		for(int i = 0; i < n_points[k]; ++i, p += 3) yafaray_addVertex(yi, (double)p[0], (double)p[1], (double)p[2]);
+		if(!yafaray_endCurveMesh(yi, mat, strand_start, strand_end, strand_shape)) return 0;
+	}
+	return 1;
+}
+// what endCurveMesh stored, for tests: per curve, in object-id order, a record of 32-bit words {id, point count n, material index,
+// strand_start, strand_end, strand_shape (floats), then n times x y z h s (floats)}.  Whole records are written while they fit into
+// max_words; *n_words (if given) is what all of them take.  Returns the number of curves.
+int yafaray_getCurves(yafaray_interface_t *yi, void *out, int max_words, int *n_words)
+{
+	size_t at = 0;
+	for(const auto &kv : yi->curves)
+	{
+		const Curve &c = kv.second;
+		const size_t n = c.scales.size() / 2, len = 6 + 5 * n;      // an open curve has no scales yet: it shows with no points
+		if(out && at + len <= (size_t)std::max(max_words, 0))
+		{
+			int32_t *w = (int32_t *)out + at;
+			w[0] = (int32_t)kv.first; w[1] = (int32_t)n; w[2] = c.mat;
+			const float f[3] = {c.strand_start, c.strand_end, c.strand_shape};
+			std::memcpy(w + 3, f, sizeof f);
+			for(size_t i = 0; i < n; ++i)
+			{
+				const float q[5] = {c.points[3 * i], c.points[3 * i + 1], c.points[3 * i + 2], c.scales[2 * i], c.scales[2 * i + 1]};
+				std::memcpy(w + 6 + 5 * i, q, sizeof q);
+			}
+		}
+		at += len;
+	}
+	if(n_words) *n_words = (int)at;
+	return (int)yi->curves.size();
+}
 // Scene::addInstance, scene.cc:1105-1130.  No geometry-state check: the XML loader issues it at document level (import_xml.cc:450-460,
 // :640-671).  Any mesh can be a base, flagged BASEMESH or not.
 yafaray_bool_t yafaray_addInstance(yafaray_interface_t *yi, unsigned int base_object_id, const float *obj_to_world)
 {
+	if(yi->curves.count(base_object_id))
+		return fail(yi, "addInstance: the base object " + std::to_string(base_object_id) + " is a curve mesh: its triangles exist only on the device, after the scene is set up, and there is no base mesh to take them from");
 	if(yi->instances.count(base_object_id))
 		return fail(yi, "addInstance: the base object " + std::to_string(base_object_id) + " is itself an instance; instances of instances are not built (TriangleObjectInstance takes a TriangleObject's own triangles, object_geom.cc:104-121)");
 	auto base = yi->meshes.find(base_object_id);
@@ -1255,6 +1391,7 @@ void *yafaray_createImageHandler(yafaray_interface_t *yi, const char *, yafaray_
 
 yafaray_bool_t yafaray_addTriangles(yafaray_interface_t *yi, int n_verts, const float *verts, int n_tris, const int *indices, const yafaray_material_t *mat)
 {
+	if(in_curve(yi, "addTriangles")) return 0;
 	if(yi->state != 2) return fail(yi, "addTriangles: wrong state");
 	if(!mat || !verts || !indices || n_verts < 0 || n_tris < 0) return fail(yi, "addTriangles: bad argument");
 	Mesh &m = *yi->cur;
@@ -1288,6 +1425,8 @@ yafaray_bool_t yafaray_smoothMesh(yafaray_interface_t *yi, unsigned int id, doub
 {
 	if(yi->state != 1) return fail(yi, "smoothMesh: wrong state (call it between endTriMesh and endGeometry)");
 	Mesh *mp = nullptr;
+	if((id && yi->curves.count(id)) || (!id && yi->last_is_curve))
+		return fail(yi, "smoothMesh: the object is a curve mesh: its triangles are made on the device from the strand's points, and there are no stored faces to smooth");
 	if(id && yi->instances.count(id)) return fail(yi, "smoothMesh: object " + std::to_string(id) + " is an instance: a TriangleObjectInstance has no normals of its own to smooth (it reads its base's)");
 	if(id) { auto it = yi->meshes.find(id); if(it == yi->meshes.end()) return fail(yi, "smoothMesh: no such mesh"); mp = &it->second; }
 	else { mp = yi->last; if(!mp) return fail(yi, "smoothMesh: no current mesh"); }
@@ -1806,7 +1945,7 @@ void yafaray_clearAll(yafaray_interface_t *yi)
 {
 	if(yi->gpu) { yafgpu_scene_destroy(yi->gpu); yi->gpu = nullptr; }
 	yi->materials.clear(); yi->material_order.clear(); yi->textures.clear(); yi->texture_order.clear(); yi->lights.clear(); yi->light_order.clear();
-	yi->cameras.clear(); yi->backgrounds.clear(); yi->integrators.clear(); yi->meshes.clear(); yi->instances.clear();
+	yi->cameras.clear(); yi->backgrounds.clear(); yi->integrators.clear(); yi->meshes.clear(); yi->instances.clear(); yi->curves.clear(); yi->cur_curve = nullptr; yi->last_is_curve = false;
 	yi->params.dicc.clear(); yi->eparams.clear(); yi->cparams = &yi->params;
 	yi->state = -1; yi->prepared = false; yi->scene_dirty = true; yi->geometry_changed = true; yi->film.clear();
 }
@@ -2013,10 +2152,30 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 	std::map<unsigned int, std::pair<int32_t, int32_t>> base_rows;      // base id -> its rows of the pools
 	bool base_normals = false;
 	for(auto &kv : yi->instances) if(kv.second.smooth || kv.second.normals_exported) base_normals = true;
-	auto mesh_it = yi->meshes.begin(); auto inst_it = yi->instances.begin();
-	while(mesh_it != yi->meshes.end() || inst_it != yi->instances.end())
+	// curves (Scene::endCurveMesh, scene.cc:154-281): a segment per strand over the pool of its points and their extrusion scales; the
+	// device extrudes them and fills the prisms
+	std::vector<float> curve_points;
+	auto mesh_it = yi->meshes.begin(); auto inst_it = yi->instances.begin(); auto curve_it = yi->curves.begin();
+	while(mesh_it != yi->meshes.end() || inst_it != yi->instances.end() || curve_it != yi->curves.end())
 	{
-		if(inst_it == yi->instances.end() || (mesh_it != yi->meshes.end() && mesh_it->first < inst_it->first))
+		// the object with the smallest id goes next (an id names one object)
+		const unsigned int none = ~0u;
+		const unsigned int mesh_id = mesh_it != yi->meshes.end() ? mesh_it->first : none, inst_id = inst_it != yi->instances.end() ? inst_it->first : none;
+		const unsigned int curve_id = curve_it != yi->curves.end() ? curve_it->first : none;
+		if(curve_it != yi->curves.end() && curve_id <= mesh_id && curve_id <= inst_id)
+		{
+			const Curve &c = (curve_it++)->second;
+			const size_t n = c.points.size() / 3;
+			yafgpu_segment sg{}; sg.kind = YAFGPU_SEGMENT_CURVE; sg.first = (int32_t)(curve_points.size() / 5); sg.count = (int32_t)n; sg.flags = (uint32_t)c.mat;
+			for(size_t i = 0; i < n; ++i)
+			{
+				curve_points.insert(curve_points.end(), c.points.begin() + 3 * (ptrdiff_t)i, c.points.begin() + 3 * (ptrdiff_t)i + 3);
+				curve_points.push_back(c.scales[2 * i]); curve_points.push_back(c.scales[2 * i + 1]);
+			}
+			segments.push_back(sg);
+			continue;
+		}
+		if(mesh_it != yi->meshes.end() && mesh_id <= inst_id)
 		{
 			const Mesh &m = (mesh_it++)->second;
 			if(!m.visible || m.base) continue;
@@ -2071,8 +2230,9 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 		d.n_textures = (int32_t)textures.size(); d.textures = textures.data();
 		d.n_texels = texels.size() / 4; d.texels = texels.data();
 	}
-	if(!yi->instances.empty())
+	if(!yi->instances.empty() || !yi->curves.empty())
 	{
+		d.inst.n_curve_points = (int32_t)(curve_points.size() / 5); d.inst.curve_points = curve_points.data();
 		d.inst.n_segments = (int32_t)segments.size(); d.inst.segments = segments.data();
 		d.inst.n_base_tris = (int32_t)base_mat.size(); d.inst.base_verts = base_verts.data(); d.inst.base_mat = base_mat.data();
 		if(base_normals) { d.inst.base_vnormals = base_vnormals.data(); d.inst.base_vn_index0 = base_index0.data(); }

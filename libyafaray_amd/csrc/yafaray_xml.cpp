@@ -312,6 +312,45 @@ static yafaray_bool_t load_xml_impl(yafaray_interface_t *yi, const char *path)
 				if(!yafaray_addInstance(yi, (unsigned int)base, m)) { errors.push_back(yafaray_getLastError(yi)); ok = false; }
 			}
 		}
+		else if(el == "curve" && t.kind == Tok::Open)
+		{	// :461-483, startElCurve__ / endElCurve__ :495-546: <curve id=".." vertices=".."> with <p x y z/>, <strand_start>, <strand_end>,
+			// <strand_shape> and <set_material sval="..">; each value is the first attribute's, whatever its name (attrs[1])
+			int vertices = 0, id = -1;
+			for(const auto &kv : t.attrs) { if(kv.first == "vertices") vertices = atoi(kv.second.c_str()); else if(kv.first == "id") id = atoi(kv.second.c_str()); }
+			if(!yafaray_startGeometry(yi)) { errors.push_back(yafaray_getLastError(yi)); ok = false; }
+			const unsigned int cid = id == -1 ? yafaray_getNextFreeId(yi) : (unsigned int)id;
+			const bool started = yafaray_startCurveMesh(yi, cid, vertices, 0) != 0;
+			if(!started) { errors.push_back(yafaray_getLastError(yi)); ok = false; }
+			const yafaray_material_t *mat = nullptr; std::string mat_name; bool mat_set = false;
+			float strand_start = 0.f, strand_end = 0.f, strand_shape = 0.f;      // CurveDat(), :367-373
+			for(;;)
+			{
+				Tok p = lx.next();
+				if(p.kind == Tok::End) { ok = false; break; }
+				if(p.kind == Tok::Close) { if(p.name == "curve") break; continue; }
+				if(p.name == "p")
+				{	// parsePoint__, :214-249; a curve takes the point alone
+					double x = 0, y = 0, z = 0;
+					for(const auto &kv : p.attrs)
+						if(kv.first.size() == 1) { if(kv.first[0] == 'x') x = atof(kv.second.c_str()); else if(kv.first[0] == 'y') y = atof(kv.second.c_str()); else if(kv.first[0] == 'z') z = atof(kv.second.c_str()); }
+					if(started) yafaray_addVertex(yi, x, y, z);
+				}
+				else if(p.attrs.empty()) continue;      // the reference reads attrs[1] of an element without attributes
+				else if(p.name == "strand_start") strand_start = (float)atof(p.attrs[0].second.c_str());
+				else if(p.name == "strand_end") strand_end = (float)atof(p.attrs[0].second.c_str());
+				else if(p.name == "strand_shape") strand_shape = (float)atof(p.attrs[0].second.c_str());
+				else if(p.name == "set_material")
+				{
+					mat_name = p.attrs[0].second; mat_set = true;
+					auto it = materials.find(mat_name);
+					mat = it != materials.end() ? it->second : nullptr;
+				}
+			}
+			// the reference warns "Unknown material!" and goes on with a null pointer that the first hit dereferences
+			if(mat_set && !mat) { errors.push_back("<curve id=\"" + std::to_string(cid) + "\">: unknown material \"" + mat_name + "\""); ok = false; }
+			if(started && !yafaray_endCurveMesh(yi, mat, strand_start, strand_end, strand_shape)) { if(!(mat_set && !mat)) errors.push_back(yafaray_getLastError(yi)); ok = false; }
+			if(!yafaray_endGeometry(yi)) { errors.push_back(yafaray_getLastError(yi)); ok = false; }
+		}
 		else if(el == "smooth")
 		{	// :429-444
 			unsigned int id = 0; double angle = 181;

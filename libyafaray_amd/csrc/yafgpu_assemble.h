@@ -1,5 +1,5 @@
-// Scene rows of instanced geometry, made on the device (yafgpu_assemble.hip): what yafgpu_scene_create launches when its descriptor has
-// segments (include/yafgpu.h, yafgpu_instancing).  Every pointer is a device pointer; an optional array is nullptr.
+// Scene rows of instanced geometry and of curve meshes, made on the device (yafgpu_assemble.hip): what yafgpu_scene_create launches when
+// its descriptor has segments (include/yafgpu.h, yafgpu_instancing).  Every pointer is a device pointer; an optional array is nullptr.
 #ifndef YAFGPU_ASSEMBLE_H
 #define YAFGPU_ASSEMBLE_H
 
@@ -20,6 +20,8 @@ struct AssembleArgs
 	const float *p_verts; const int32_t *p_mat; const float *p_vn, *p_uv, *p_orco;
 	// the base pools (instance segments)
 	const float *b_verts; const int32_t *b_mat; const float *b_vn; const uint8_t *b_vn0; const float *b_uv, *b_orco;
+	// the curve point pool (curve segments): x y z h s per point
+	const float *c_points;
 	const yafgpu_material *mats;     // the scene's material table: a record's visibility rides in its triangles' records
 	// outputs, n_out rows each
 	float4 *rec;                     // 3 per row: (a, eps) (e1, mat | vis << 30) (e2, 0)

@@ -890,13 +890,17 @@ template<typename T> static int upload(yafgpu_scene *s, const T *src, size_t n, 
 	return 0;
 }
 
-// ---- instanced geometry (yafgpu_instancing): the scene's rows are made by yafgpu_assemble.hip -------------------------------
+// ---- instanced geometry and curve meshes (yafgpu_instancing): the scene's rows are made by yafgpu_assemble.hip --------------
 // Every range the kernel will index is checked here, on the host, before anything is launched.
+// the rows a segment makes: a curve of n points is 6 * (n - 1) + 2 triangles (scene.cc:200-275), the other kinds one per source row
+static uint64_t segment_rows(const yafgpu_segment &sg) { return sg.kind == YAFGPU_SEGMENT_CURVE ? 6u * (uint64_t)(sg.count - 1) + 2u : (uint64_t)sg.count; }
+
 static int check_instancing(const yafgpu_scene_desc *d)
 {
 	const yafgpu_instancing &in = d->inst;
 	if(!in.segments) return fail(-1, "instanced geometry: null segment list");
 	if(in.n_base_tris < 0) return fail(-3, "instanced geometry: negative base triangle count");
+	if(in.n_curve_points < 0 || (in.n_curve_points > 0 && !in.curve_points)) return fail(in.n_curve_points < 0 ? -3 : -1, "instanced geometry: curve point pool without points");
 	if(d->n_tris > 0 && (!d->verts || !d->tri_mat)) return fail(-1, "instanced geometry: plain triangles without vertices or materials");
 	if(in.n_base_tris > 0 && (!in.base_verts || !in.base_mat)) return fail(-1, "instanced geometry: base triangles without vertices or materials");
 	if(in.base_vnormals && !in.base_vn_index0) return fail(-1, "instanced geometry: base vertex normals without their index-0 marks");
@@ -904,12 +908,22 @@ static int check_instancing(const yafgpu_scene_desc *d)
 	for(int k = 0; k < in.n_segments; ++k)
 	{
 		const yafgpu_segment &sg = in.segments[k];
-		if(sg.kind != YAFGPU_SEGMENT_PLAIN && sg.kind != YAFGPU_SEGMENT_INSTANCE) return fail(-3, "instanced geometry: segment " + std::to_string(k) + ": unknown kind");
+		if(sg.kind != YAFGPU_SEGMENT_PLAIN && sg.kind != YAFGPU_SEGMENT_INSTANCE && sg.kind != YAFGPU_SEGMENT_CURVE) return fail(-3, "instanced geometry: segment " + std::to_string(k) + ": unknown kind");
+		if(sg.kind == YAFGPU_SEGMENT_CURVE)
+		{	// a strand: points of the curve pool, at least two (scene.cc:174 divides by n - 1), one material for all its rows
+			if(sg.first < 0 || sg.count < 2 || (int64_t)sg.first + (int64_t)sg.count > (int64_t)in.n_curve_points)
+				return fail(-3, "instanced geometry: segment " + std::to_string(k) + ": a curve needs two or more points inside the curve point pool");
+			if(sg.flags >= (uint32_t)d->n_materials) return fail(-3, "instanced geometry: segment " + std::to_string(k) + ": curve material index out of range");
+			total += segment_rows(sg);
+			continue;
+		}
 		const int64_t room = sg.kind == YAFGPU_SEGMENT_INSTANCE ? in.n_base_tris : d->n_tris;
 		if(sg.first < 0 || sg.count < 0 || (int64_t)sg.first + (int64_t)sg.count > room)
 			return fail(-3, "instanced geometry: segment " + std::to_string(k) + ": rows outside the " + (sg.kind == YAFGPU_SEGMENT_INSTANCE ? "base pools" : "plain arrays"));
 		total += (uint64_t)sg.count;
 	}
+	for(size_t k = 0; k < (size_t)std::max(in.n_curve_points, 0) * 5; ++k)
+		if(!std::isfinite(in.curve_points[k])) return fail(-3, "non-finite coordinate or extrusion scale in curve point " + std::to_string(k / 5));
 	if(total > (uint64_t)INT32_MAX / 9u) return fail(-3, "instanced geometry: more than " + std::to_string(INT32_MAX / 9) + " triangles after flattening");
 	for(int i = 0; i < in.n_base_tris; ++i)
 		if(in.base_mat[i] < 0 || in.base_mat[i] >= d->n_materials) return fail(-3, "base triangle material index out of range");
@@ -954,7 +968,7 @@ static int assemble_scene(yafgpu_scene *s, const yafgpu_scene_desc *d, Assembled
 	{
 		const yafgpu_segment &sg = in.segments[k];
 		if(sg.count == 0) continue;
-		first.push_back(out.n); segs.push_back(sg); out.n += (uint32_t)sg.count;
+		first.push_back(out.n); segs.push_back(sg); out.n += (uint32_t)segment_rows(sg);      // check_instancing bounded the sum
 		if(sg.kind == YAFGPU_SEGMENT_INSTANCE && (sg.flags & YAFGPU_INSTANCE_SMOOTH) && in.base_vnormals) smooth_segment = true;
 	}
 	first.push_back(out.n);
@@ -966,13 +980,14 @@ static int assemble_scene(yafgpu_scene *s, const yafgpu_scene_desc *d, Assembled
 	bool bump = false;
 	for(int i = 0; i < d->n_materials && texcoords; ++i) if(d->materials[i].n_bump > 0) bump = true;
 	DevMem<yafgpu_segment> d_segs; DevMem<uint32_t> d_first;
-	DevMem<float> p_verts, p_vn, p_uv, p_orco, b_verts, b_vn, b_uv, b_orco, d_verts; DevMem<int32_t> p_mat, b_mat; DevMem<uint8_t> b_vn0;
+	DevMem<float> p_verts, p_vn, p_uv, p_orco, b_verts, b_vn, b_uv, b_orco, c_points, d_verts; DevMem<int32_t> p_mat, b_mat; DevMem<uint8_t> b_vn0;
 	if((rc = temp_upload(d_segs, segs.data(), segs.size())) || (rc = temp_upload(d_first, first.data(), first.size()))) return rc;
 	if((rc = temp_upload(p_verts, d->verts, np * 9)) || (rc = temp_upload(p_mat, d->tri_mat, np)) || (rc = temp_upload(p_vn, d->vnormals, np * 9))) return rc;
 	if(texcoords && ((rc = temp_upload(p_uv, d->tri_uv, np * 6)) || (rc = temp_upload(p_orco, d->tri_orco, np * 9)))) return rc;
 	if((rc = temp_upload(b_verts, in.base_verts, nb * 9)) || (rc = temp_upload(b_mat, in.base_mat, nb))) return rc;
 	if((rc = temp_upload(b_vn, in.base_vnormals, nb * 9)) || (rc = temp_upload(b_vn0, in.base_vn_index0, in.base_vnormals ? nb : 0))) return rc;
 	if(texcoords && ((rc = temp_upload(b_uv, in.base_uv, nb * 6)) || (rc = temp_upload(b_orco, in.base_orco, nb * 9)))) return rc;
+	if((rc = temp_upload(c_points, in.curve_points, (size_t)in.n_curve_points * 5))) return rc;
 	float4 *rec = nullptr, *ng = nullptr, *vn = nullptr; float *uv = nullptr, *orco = nullptr, *e3 = nullptr;
 	if((rc = scene_alloc(s, 3 * n, &rec)) || (rc = scene_alloc(s, n, &ng))) return rc;
 	if(smooth_segment && (rc = scene_alloc(s, 3 * n, &vn))) return rc;
@@ -983,6 +998,7 @@ static int assemble_scene(yafgpu_scene *s, const yafgpu_scene_desc *d, Assembled
 	a.segs = d_segs.p; a.seg_first = d_first.p; a.n_segs = (int)segs.size(); a.n_out = out.n;
 	a.p_verts = p_verts.p; a.p_mat = p_mat.p; a.p_vn = p_vn.p; a.p_uv = p_uv.p; a.p_orco = p_orco.p;
 	a.b_verts = b_verts.p; a.b_mat = b_mat.p; a.b_vn = b_vn.p; a.b_vn0 = b_vn0.p; a.b_uv = b_uv.p; a.b_orco = b_orco.p;
+	a.c_points = c_points.p;
 	a.mats = out.mats;
 	a.rec = rec; a.ng = ng; a.vn = vn; a.uv = uv; a.orco = orco; a.e3 = e3; a.verts = d_verts.p;
 	HIP_OK(assemble_rows(a));
@@ -1114,6 +1130,7 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 			for(int k = 0; k < d->inst.n_segments; ++k)
 			{	// the rows some segment makes a triangle of
 				const yafgpu_segment &sg = d->inst.segments[k];
+				if(sg.kind == YAFGPU_SEGMENT_CURVE) { used[(size_t)sg.flags] = 1; continue; }
 				const int32_t *mat = sg.kind == YAFGPU_SEGMENT_INSTANCE ? d->inst.base_mat : d->tri_mat;
 				for(int i = sg.first; i < sg.first + sg.count; ++i) used[(size_t)mat[i]] = 1;
 			}

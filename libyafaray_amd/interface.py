@@ -62,7 +62,7 @@ C_API_SYMBOLS = [
     "yafaray_startTriMesh", "yafaray_endTriMesh", "yafaray_addVertex", "yafaray_addNormal", "yafaray_addTriangle",
     "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getCamera", "yafaray_getIntegratorAO", "yafaray_getMaskMaterial", "yafaray_getMaterialTable", "yafaray_addTriangles",
     "yafaray_startTriMeshPtr", "yafaray_addVertexWithOrco", "yafaray_addUv", "yafaray_addTriangleWithUv",
-    "yafaray_startCurveMesh", "yafaray_endCurveMesh", "yafaray_addInstance", "yafaray_getInstances",
+    "yafaray_startCurveMesh", "yafaray_endCurveMesh", "yafaray_addCurves", "yafaray_getCurves", "yafaray_addInstance", "yafaray_getInstances",
     "yafaray_paramsSetColorArray", "yafaray_paramsSetMatrix", "yafaray_paramsSetMatrixD", "yafaray_setInputColorSpace",
     "yafaray_createObject", "yafaray_createVolumeRegion", "yafaray_createImageHandler",
     "yafaray_setLoggingAndBadgeSettings", "yafaray_setupRenderPasses", "yafaray_setInteractive", "yafaray_getRenderParameters",
@@ -121,6 +121,8 @@ def load():
         "yafaray_addVertexWithOrco": (ci, [vp, cd, cd, cd, cd, cd, cd]), "yafaray_addUv": (ci, [vp, cf, cf]),
         "yafaray_addTriangleWithUv": (ci, [vp, ci, ci, ci, ci, ci, ci, vp]),
         "yafaray_startCurveMesh": (ci, [vp, C.c_uint, ci, ci]), "yafaray_endCurveMesh": (ci, [vp, vp, cf, cf, cf]),
+        "yafaray_addCurves": (ci, [vp, ci, C.POINTER(ci), C.POINTER(cf), vp, cf, cf, cf, C.POINTER(C.c_uint)]),
+        "yafaray_getCurves": (ci, [vp, vp, ci, C.POINTER(ci)]),
         "yafaray_addInstance": (ci, [vp, C.c_uint, C.POINTER(cf)]), "yafaray_getInstances": (ci, [vp, vp, ci]),
         "yafaray_paramsSetColorArray": (None, [vp, cp, C.POINTER(cf), ci]), "yafaray_paramsSetMatrix": (None, [vp, cp, C.POINTER(cf), ci]),
         "yafaray_paramsSetMatrixD": (None, [vp, cp, C.POINTER(cd), ci]), "yafaray_setInputColorSpace": (None, [vp, cp, cf]),
@@ -260,10 +262,40 @@ class Interface:
         return self._ok(self._L.yafaray_addTriangleWithUv(self._h, a, b, c, uv_a, uv_b, uv_c, mat), "addTriangle")
 
     def startCurveMesh(self, id, vertices, obj_pass_index=0):
+        """Scene::startCurveMesh: opens a strand under `id`; addVertex gives its points, endCurveMesh closes it"""
         return self._ok(self._L.yafaray_startCurveMesh(self._h, id, vertices, obj_pass_index), "startCurveMesh")
 
     def endCurveMesh(self, mat, strand_start, strand_end, strand_shape):
+        """Scene::endCurveMesh: root radius, tip radius and shape exponent; the 6 * (n - 1) + 2 triangles are made on the device at scene set-up"""
         return self._ok(self._L.yafaray_endCurveMesh(self._h, mat, strand_start, strand_end, strand_shape), "endCurveMesh")
+
+    def addCurves(self, n_points, points, mat, strand_start, strand_end, strand_shape):
+        """many strands in one call (the loop of getNextFreeId / startCurveMesh / addVertex / endCurveMesh): n_points[k] points for curve k,
+        taken in turn from points (sum(n_points), 3).  -> the object ids as uint32, or None when a call of the loop was refused"""
+        cnt = np.ascontiguousarray(n_points, dtype=np.int32).reshape(-1)
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1)
+        if cnt.size and (cnt.min() < 0 or int(cnt.sum()) * 3 != pts.size):
+            raise ValueError("addCurves: points must hold sum(n_points) xyz triples")
+        ids = np.zeros(max(cnt.size, 1), dtype=np.uint32)
+        ok = self._ok(self._L.yafaray_addCurves(self._h, cnt.size, cnt.ctypes.data_as(C.POINTER(C.c_int)), pts.ctypes.data_as(C.POINTER(C.c_float)), mat,
+                                                strand_start, strand_end, strand_shape, ids.ctypes.data_as(C.POINTER(C.c_uint))), "addCurves")
+        return ids[:cnt.size] if ok else None
+
+    def getCurves(self):
+        """what endCurveMesh stored, in object-id order: a list of dicts with the curve's id, material index, the three strand parameters as
+        float32 and `points`, float32 (n, 5): x y z and the two extrusion scales h, s"""
+        need = C.c_int(0)
+        n = self._L.yafaray_getCurves(self._h, None, 0, C.byref(need))
+        w = np.zeros(max(need.value, 1), dtype=np.int32)
+        self._L.yafaray_getCurves(self._h, w.ctypes.data_as(C.c_void_p), need.value, None)
+        out, at = [], 0
+        for _ in range(n):
+            npts = int(w[at + 1])
+            f = w[at + 3:at + 6].view(np.float32)
+            out.append({"id": int(w[at]) & 0xffffffff, "material": int(w[at + 2]), "strand_start": f[0], "strand_end": f[1], "strand_shape": f[2],
+                        "points": w[at + 6:at + 6 + 5 * npts].view(np.float32).reshape(npts, 5).copy()})
+            at += 6 + 5 * npts
+        return out
 
     def addInstance(self, base_object_id, obj_to_world):
         """Scene::addInstance: the base mesh's triangles under obj_to_world (4 x 4, row major) as one more object; None passes a null matrix"""
