@@ -718,6 +718,42 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			o[43] = __uint_as_float(have);
 			break;
 		}
+		case 29:
+		{	// Triangle::intersect on the scene's own 48-byte record: in the triangle index (as bits), from.xyz, dir.xyz -> ok, t, u, v of tri_test
+			// (zeros where it rejects), then ok, t, u, v of tri_test_flat (as computed, also where it rejects: inf / NaN may stand there)
+			if(n_in < 7 || n_out < 8) break;
+			const uint32_t tri = __float_as_uint(x[0]);
+			if(tri >= (uint32_t)sc.n_tris) break;
+			const float4 r0 = sc.tri[3 * (size_t)tri], r1 = sc.tri[3 * (size_t)tri + 1], r2 = sc.tri[3 * (size_t)tri + 2];
+			const V3 from = mk(x[1], x[2], x[3]), dir = mk(x[4], x[5], x[6]);
+			float t = 0.f, u = 0.f, v = 0.f;
+			const bool ok = tri_test(r0, r1, r2, from, dir, t, u, v);
+			o[0] = ok ? 1.f : 0.f; o[1] = ok ? t : 0.f; o[2] = ok ? u : 0.f; o[3] = ok ? v : 0.f;
+			float tf = 0.f, uf = 0.f, vf = 0.f;
+			const bool ok_flat = tri_test_flat(r0, r1, r2, from, dir, tf, uf, vf);
+			o[4] = ok_flat ? 1.f : 0.f; o[5] = tf; o[6] = uf; o[7] = vf;
+			break;
+		}
+		case 30:
+		{	// the surface point the vertex code makes (Triangle::getSurface): in the triangle index (as bits), barycentrics bu, bv, p.xyz ->
+			// get_surface's n, ng, nu, nv [0, 12) and material index (as bits) [12]; tex_point's orco_p, orco_ng [13, 19), u, v [19, 21) and
+			// has_uv (0 / 1) [21]; tex_point_derivatives' ds_du, ds_dv [22, 28) where the scene has bump data, zeros otherwise
+			if(n_in < 6 || n_out < 28) break;
+			const uint32_t tri = __float_as_uint(x[0]);
+			if(tri >= (uint32_t)sc.n_tris) break;
+			SurfPt sp; get_surface(sc, (int)tri, mk(x[3], x[4], x[5]), x[1], x[2], sp);
+			o[0] = sp.n.x; o[1] = sp.n.y; o[2] = sp.n.z; o[3] = sp.ng.x; o[4] = sp.ng.y; o[5] = sp.ng.z;
+			o[6] = sp.nu.x; o[7] = sp.nu.y; o[8] = sp.nu.z; o[9] = sp.nv.x; o[10] = sp.nv.y; o[11] = sp.nv.z;
+			o[12] = __uint_as_float((uint32_t)sp.mat);
+			TexPoint tp; tex_point(sc.tex, (int)tri, x[1], x[2], sp.p, sp.n, sp.ng, tp);
+			o[13] = tp.orco_p.x; o[14] = tp.orco_p.y; o[15] = tp.orco_p.z; o[16] = tp.orco_ng.x; o[17] = tp.orco_ng.y; o[18] = tp.orco_ng.z;
+			o[19] = tp.u; o[20] = tp.v; o[21] = tp.has_uv ? 1.f : 0.f;
+			if(!sc.tex.has_bump) break;
+			const float4 r1 = sc.tri[3 * (size_t)tri + 1], r2 = sc.tri[3 * (size_t)tri + 2];
+			tex_point_derivatives(sc.tex, (int)tri, mk(r1.x, r1.y, r1.z), mk(r2.x, r2.y, r2.z), sp.n, sp.nu, sp.nv, tp);
+			o[22] = tp.ds_du.x; o[23] = tp.ds_du.y; o[24] = tp.ds_du.z; o[25] = tp.ds_dv.x; o[26] = tp.ds_dv.y; o[27] = tp.ds_dv.z;
+			break;
+		}
 		default: break;
 	}
 }
