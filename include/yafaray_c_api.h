@@ -131,8 +131,14 @@ yafaray_bool_t yafaray_getIntegratorAO(yafaray_interface_t *yi, const char *name
  * how many nodes that is, receive_shadows, visibility (0 normal, 1 no_shadows, 2 shadow_only, 3 invisible) and the union of both
  * sub-materials' bsdf flags; false when there is no such material or it is no mask_mat */
 yafaray_bool_t yafaray_getMaskMaterial(yafaray_interface_t *yi, const char *name, void *out8);
+/* extension (test support): what BlendMaterial::factory's restatement parsed for the blend_mat `name`.  out10 receives ten 32-bit words:
+ * the indices of material1 and material2 in creation order, blend_val_ (a float's bits), whether a shader node drives the blend (0 / 1),
+ * that node's slot among the blend's nodes (-1 without one), how many nodes that is, receive_shadows, visibility (0 normal, 1 no_shadows,
+ * 2 shadow_only, 3 invisible), the union of both sub-materials' bsdf flags and additional_depth_, the larger of theirs; false when there
+ * is no such material or it is no blend_mat */
+yafaray_bool_t yafaray_getBlendMaterial(yafaray_interface_t *yi, const char *name, void *out10);
 /* extension (test support): the material table as the device scene would get it: the materials in creation order, then for every
- * mask_mat the two hidden clones of its sub-materials it picks from.  Up to max_materials yafgpu_material records (include/yafgpu.h,
+ * mask_mat the two hidden clones of its sub-materials it picks from, and for every blend_mat the two it mixes.  Up to max_materials yafgpu_material records (include/yafgpu.h,
  * 384 bytes each) into out; returns how many records the table has */
 int yafaray_getMaterialTable(yafaray_interface_t *yi, void *out, int max_materials);
 /* extension (not in the reference): bulk form of addVertex/addTriangle for large meshes;

@@ -41,7 +41,22 @@ enum { YAFGPU_MAT_SHINYDIFFUSE = 0, YAFGPU_MAT_GLOSSY = 1, YAFGPU_MAT_LIGHT = 2,
             is_transparent           isTransparent(): either sub-material's (:86-89)
             bsdf_flags               the union of both sub-materials' flags (:34)
             visibility, receive_shadows   the mask's own (:150-163); flat 0, additional_depth 0, no volume handler: its factory reads none */
-       YAFGPU_MAT_MASKED = 7 };
+       YAFGPU_MAT_MASKED = 7,
+       /* BlendMaterial (material_blend.cc): every material function runs on two other records of the table and mixes the results by
+          val (the constant blend_value, or a shader node's scalar at the hit) and ival = min(1, max(0, 1 - val)).  Unlike a mask it IS
+          the vertex's material: the integrators read its material-level words, and the shading code reaches the two records through it
+          (yafgpu_shading.h, BlendScratch).  Shading units handle it only when bit 8 of YAFGPU_MAT_MASK is set.  The record reads
+            c_index[0], c_index[1]   hidden clones of material1 / material2 (yafaray_c_api.cpp, flatten_materials): the sub-materials as they
+                                     are, nodes included, except flat, which becomes 2 (isFlat() is the blend's, false)
+            transmit_filter          blend_val_, a float (material_blend.cc:45, :483)
+            node_first, n_nodes      the nodes the `mask` shader reaches, in evaluation order; n_nodes 0: the constant blends
+            sh_diffuse               the blend node's index among them (recalc_blend_, :518-526), -1 without one
+            is_transparent           isTransparent(): either sub-material's (:332-335)
+            bsdf_flags               the union of both sub-materials' flags (:42; initBsdf returns the same union, :100)
+            additional_depth         the larger of the two (:48)
+            has_vol_i, beer_sigma    getVolumeHandler(): material1's if both absorb and blend_val_ <= 0.5, else whichever exists (:450-462)
+            visibility, receive_shadows   the blend's own (:485-499, :506); flat 0, no transparent bias: its factory reads neither */
+       YAFGPU_MAT_BLEND = 8 };
 enum { YAFGPU_LIGHT_AREA = 0, YAFGPU_LIGHT_POINT = 1, YAFGPU_LIGHT_DIRECTIONAL = 2, YAFGPU_LIGHT_SUN = 3, YAFGPU_LIGHT_SPHERE = 4,
        YAFGPU_LIGHT_BACKGROUND = 5 /* BackgroundLight (light_background.cc): samples the scene's yafgpu_background through its Pdf1D tables */ };
 enum { YAFGPU_BACKGROUND_NONE = 0, YAFGPU_BACKGROUND_CONSTANT = 1, YAFGPU_BACKGROUND_TEXTURE = 2 };

@@ -30,7 +30,7 @@ cc() {      # cc <object name> <source> [defines...]: compile in the background 
 }
 # the device unit and the scene-specialised shading kernels (yafgpu_shade_variant.hip) compile side by side; every variant is built for
 # area and point lights (YAFGPU_LIGHT_MASK=0x3u): scenes with directional, sun or sphere lights take the device unit's general kernel;
-# none has ambient occlusion (YAFGPU_FEAT_AO=0): a render with do_AO takes the general kernel too
+# none but the blend material's unit has ambient occlusion (YAFGPU_FEAT_AO=0): a render with do_AO takes the general kernel too
 cc yafgpu_device yafgpu_device.hip
 #   diffuse: shinydiffusemat + light_mat, no recursiveRaytrace (BASELINE configs C2, C3)
 cc shade_diffuse yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=diffuse -DYAFGPU_MAT_MASK=0x5u -DYAFGPU_LIGHT_MASK=0x3u -DYAFGPU_FEAT_RECURSE=0 -DYAFGPU_FEAT_TEXTURE=0 -DYAFGPU_FEAT_ANISO=0 -DYAFGPU_FEAT_AO=0 -DYAFGPU_FEAT_MULTI=0
@@ -44,11 +44,14 @@ cc shade_diffuse_rec yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=diffuse_rec 
 cc shade_glossy_rec yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=glossy_rec -DYAFGPU_MAT_MASK=0x7u -DYAFGPU_LIGHT_MASK=0x3u -DYAFGPU_FEAT_RECURSE=0 -DYAFGPU_FEAT_TEXTURE=0 -DYAFGPU_FEAT_ANISO=0 -DYAFGPU_FEAT_AO=0 -DYAFGPU_FEAT_LIGHTS=0
 #   full: every material type and recursiveRaytrace, no shader nodes / textures (the main unit's kernel has those too)
 cc shade_full yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=full -DYAFGPU_MAT_MASK=0x3fu -DYAFGPU_LIGHT_MASK=0x3u -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=0 -DYAFGPU_FEAT_ANISO=0 -DYAFGPU_FEAT_AO=0 -DYAFGPU_FEAT_MULTI=0
+#   blend: the device unit's general kernel (every material type, light type and feature: nothing else is switched off) with BlendMaterial's
+#   code, bit 8 of the material mask; a scene takes it when some triangle uses a blend_mat, for the record pass of a serial-state replay too
+cc shade_blend yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=blend -DYAFGPU_MAT_MASK=0x17fu -DYAFGPU_LIGHT_MASK=0x3fu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1
 # scene set-up for instanced geometry: the rows of the flattened scene, made on the device (same flags: its arithmetic must round like the host loop's)
 cc yafgpu_assemble yafgpu_assemble.hip
 cc kdtree_build kdtree_build.cpp
 cc kdtree_build_device kdtree_build_device.hip
-OBJS="$OBJ/yafgpu_device.o $OBJ/shade_diffuse.o $OBJ/shade_glossy.o $OBJ/shade_diffuse_mp.o $OBJ/shade_glossy_mp.o $OBJ/shade_diffuse_rec.o $OBJ/shade_glossy_rec.o $OBJ/shade_full.o $OBJ/yafgpu_assemble.o $OBJ/kdtree_build.o $OBJ/kdtree_build_device.o"
+OBJS="$OBJ/yafgpu_device.o $OBJ/shade_diffuse.o $OBJ/shade_glossy.o $OBJ/shade_diffuse_mp.o $OBJ/shade_glossy_mp.o $OBJ/shade_diffuse_rec.o $OBJ/shade_glossy_rec.o $OBJ/shade_full.o $OBJ/shade_blend.o $OBJ/yafgpu_assemble.o $OBJ/kdtree_build.o $OBJ/kdtree_build_device.o"
 for f in yafaray_c_api yafaray_xml yafaray_image yafaray_reduce; do
   if [ -f "$HERE/$f.cpp" ]; then cc "$f" "$f.cpp"; OBJS="$OBJS $OBJ/$f.o"; fi
 done

@@ -788,6 +788,7 @@ bool make_mask(yafaray_interface *yi, const ParamMap &p, yafaray_material &out)
 		auto it = yi->materials.find(name);
 		if(it == yi->materials.end()) return fail(yi, "mask_mat: " + key + " \"" + name + "\" names no material defined so far (material_mask.cc:159)");
 		if(it->second->m.type == YAFGPU_MAT_MASKED) return fail(yi, "mask_mat: " + key + " \"" + name + "\" is a mask_mat itself: nesting masks is not built on the GPU path");
+		if(it->second->m.type == YAFGPU_MAT_BLEND) return fail(yi, "mask_mat: " + key + " \"" + name + "\" is a blend_mat: a blend under a mask (nesting) is not built on the GPU path");
 		sub[k] = it->second.get();
 	}
 	p.get("receive_shadows", recv); p.get("visibility", vis);
@@ -821,6 +822,74 @@ bool make_mask(yafaray_interface *yi, const ParamMap &p, yafaray_material &out)
 	return true;
 }
 
+// BlendMaterial::factory + ctor, material_blend.cc:464-544, :38-49.  The record's layout: include/yafgpu.h, YAFGPU_MAT_BLEND.
+// It reads material1, material2, blend_value (a double, kept as a float), receive_shadows, visibility, mat_pass_index and samplingfactor
+// (both read and dropped, as elsewhere), the wireframe parameters (refused unless zero, as for every material), the node list and `mask` —
+// and neither additionaldepth (the ctor takes the larger of the sub-materials'), flat_material nor a bump shader.  Where the reference
+// returns nullptr this refuses with the cause.  A missing `mask` is no error here: the blend then uses the constant (:518, recalc_blend_
+// stays false).  blended_ior_ (:46, getMatIor) is not carried: the integrators read it for ray differentials alone
+// (integrator_montecarlo.cc:908, :945, :1013, under diff_rays_enabled_), which the GPU path does not have.
+bool make_blend(yafaray_interface *yi, const ParamMap &p, yafaray_material &out)
+{
+	yafgpu_material &m = out.m;
+	double blend_val = 0.5; bool recv = true; std::string vis = "normal", name; float wire = 0.f;
+	const yafaray_material *sub[2] = {nullptr, nullptr};
+	for(int k = 0; k < 2; ++k)
+	{	// :479-482, :501
+		const std::string key = k == 0 ? "material1" : "material2";
+		if(!p.get(key, name))
+			return fail(yi, "blend_mat: " + key + " is missing (material_blend.cc:479-482): a blend of fewer than two materials is outside the GPU path's scope, as it is the "
+			                "reference's (createMaterial accepts shinydiffusemat, glossy, coated_glossy, glass, rough_glass, mirror, light_mat, mask_mat, blend_mat)");
+		auto it = yi->materials.find(name);
+		if(it == yi->materials.end()) return fail(yi, "blend_mat: " + key + " \"" + name + "\" names no material defined so far (material_blend.cc:480-482, :501)");
+		if(it->second->m.type == YAFGPU_MAT_MASKED || it->second->m.type == YAFGPU_MAT_BLEND)
+			return fail(yi, "blend_mat: " + key + " \"" + name + "\" is a " + (it->second->m.type == YAFGPU_MAT_BLEND ? "blend_mat" : "mask_mat") + " itself: nesting blends and masks is not built on the GPU path");
+		if(it->second->m.n_bump > 0)
+			return fail(yi, "blend_mat: " + key + " \"" + name + "\" has a bump shader: BlendMaterial::initBsdf blends the two bumped frames (blendSurfacePoints__, surface.cc:137-151), which is not built on the GPU path");
+		sub[k] = it->second.get();
+	}
+	p.get("blend_value", blend_val);
+	p.get("receive_shadows", recv); p.get("visibility", vis); p.get("wireframe_amount", wire);
+	if(wire != 0.f) return fail(yi, "blend_mat: wireframe shading is not supported by the GPU path");
+	// :515-541: the nodes load whether or not `mask` names one
+	LoadedNodes ld;
+	const int rc = load_nodes(yi, yi->eparams, ld);
+	if(rc == 0) return false;
+	if(rc < 0) return fail(yi, "blend_mat: the shader node list failed to load (Blend: loadNodes() failed, material_blend.cc:535-540)");
+	int slot[1] = {-1};
+	out.nodes.clear();
+	if(p.get("mask", name))
+	{
+		auto node = ld.by_name.find(name);
+		if(node == ld.by_name.end()) return fail(yi, "blend_mat: mask shader node \"" + name + "\" does not exist (Blend shader node does not exist, material_blend.cc:527-532)");
+		slot[0] = node->second;
+		if(!sort_nodes(yi, ld, slot, 1, out.nodes)) return false;
+	}
+	// recursiveRaytrace's glossy branch picks its case from the BLEND's flags, the union (integrator_montecarlo.cc:895-919): a glossy lobe
+	// beside a transmitting one takes the reflect + transmit case and BlendMaterial's two-direction sample (material_blend.cc:216-236), which
+	// is not restated — the same pairs a mask refuses, in the same words (rough glass has that union alone)
+	const uint32_t both = sub[0]->m.bsdf_flags | sub[1]->m.bsdf_flags;
+	if((both & 0x2u) && (both & 0x10u) && (both & 0x20u))
+		return fail(yi, "blend_mat: a glossy sub-material beside one that transmits (or rough glass): recursiveRaytrace reads the union of their flags and takes the "
+		                "two-direction sample, which the GPU path does not have for a blend (integrator_montecarlo.cc:895-919)");
+	std::memset(&m, 0, sizeof m);
+	clear_shader_slots(m);
+	m.type = YAFGPU_MAT_BLEND; m.visibility = visibility_from(vis); m.receive_shadows = recv;
+	m.transmit_filter = (float)blend_val;              // blend_val_ (:45)
+	m.bsdf_flags = both;                               // :42
+	m.additional_depth = std::max(sub[0]->m.additional_depth, sub[1]->m.additional_depth);      // :48
+	m.is_transparent = (record_is_transparent(sub[0]->m) || record_is_transparent(sub[1]->m)) ? 1 : 0;      // :332-335
+	m.n_nodes = (int32_t)out.nodes.size(); m.sh_diffuse = slot[0];      // (sort_nodes left the node's place among them)
+	{	// getVolumeHandler, :450-462 (inside: the only handler a material on this path has is glass's vol_i_); by the CONSTANT blend_val_
+		const yafgpu_material *v1 = sub[0]->m.has_vol_i ? &sub[0]->m : nullptr, *v2 = sub[1]->m.has_vol_i ? &sub[1]->m : nullptr;
+		const yafgpu_material *v = (v1 && v2) ? (m.transmit_filter <= 0.5f ? v1 : v2) : (v1 ? v1 : v2);
+		if(v) { m.has_vol_i = 1; for(int k = 0; k < 3; ++k) m.beer_sigma[k] = v->beer_sigma[k]; }
+	}
+	m.c_index[0] = m.c_index[1] = -1;                  // the clones' places in the table: flatten_materials
+	out.mask_sub[0] = sub[0]->index; out.mask_sub[1] = sub[1]->index;
+	return true;
+}
+
 // The material table of the device scene: the materials in creation order, then, for every mask_mat, a clone of each of its two
 // sub-materials, which is what a vertex on the mask gets (yafgpu_wavefront.h wf_mask_hit).  A clone is the sub-material with the
 // material-level values the integrators read off sp.material_, the MASK, in the reference: receive_shadows (integrator_montecarlo.cc:91)
@@ -842,6 +911,19 @@ void flatten_materials(const yafaray_interface *yi, std::vector<yafgpu_material>
 	const size_t n = mats.size();
 	for(size_t i = 0; i < n; ++i)
 	{
+		if(mats[i].type == YAFGPU_MAT_BLEND)
+		{	// a blend_mat's clones, in the same place: the two records its functions run on (yafgpu_shading.h BlendScratch).  The vertex's
+			// material stays the blend, so no material-level word of a clone is ever read; each is the sub-material as it is, nodes shared,
+			// but for flat: isFlat() is the blend's (false), ShinyDiffuseMaterial::eval's own test stays (2)
+			for(int k = 0; k < 2; ++k)
+			{
+				yafgpu_material c = mats[(size_t)yi->material_order[i]->mask_sub[k]];
+				c.flat = c.flat ? 2 : 0;
+				mats[i].c_index[k] = (int32_t)mats.size();
+				mats.push_back(c);
+			}
+			continue;
+		}
 		if(mats[i].type != YAFGPU_MAT_MASKED) continue;
 		for(int k = 0; k < 2; ++k)
 		{
@@ -1572,6 +1654,20 @@ yafaray_bool_t yafaray_getMaskMaterial(yafaray_interface_t *yi, const char *name
 	}
 	return 1;
 }
+yafaray_bool_t yafaray_getBlendMaterial(yafaray_interface_t *yi, const char *name, void *out10)
+{
+	auto it = name ? yi->materials.find(name) : yi->materials.end();
+	if(it == yi->materials.end() || it->second->m.type != YAFGPU_MAT_BLEND) return fail(yi, "getBlendMaterial: no such blend_mat");
+	const yafaray_material &bm = *it->second;
+	if(out10)
+	{
+		int32_t w[10] = {bm.mask_sub[0], bm.mask_sub[1], 0, bm.m.n_nodes > 0 ? 1 : 0, bm.m.sh_diffuse, bm.m.n_nodes, bm.m.receive_shadows, bm.m.visibility,
+		                 (int32_t)bm.m.bsdf_flags, bm.m.additional_depth};
+		std::memcpy(&w[2], &bm.m.transmit_filter, 4);
+		std::memcpy(out10, w, sizeof w);
+	}
+	return 1;
+}
 int yafaray_getMaterialTable(yafaray_interface_t *yi, void *out, int max_materials)
 {
 	std::vector<yafgpu_material> mats; std::vector<yafgpu_node> nodes;
@@ -1661,9 +1757,10 @@ yafaray_material_t *yafaray_createMaterial(yafaray_interface_t *yi, const char *
 	else if(type == "coated_glossy") ok = make_coated_glossy(yi, yi->params, m->m, m->nodes);
 	else if(type == "mirror") ok = make_mirror(yi->params, m->m);
 	else if(type == "mask_mat") ok = make_mask(yi, yi->params, *m);
-	else { fail(yi, "createMaterial: material type \"" + type + "\" is outside the GPU path's scope (shinydiffusemat, glossy, coated_glossy, glass, rough_glass, mirror, light_mat, mask_mat)"); return nullptr; }
+	else if(type == "blend_mat") ok = make_blend(yi, yi->params, *m);
+	else { fail(yi, "createMaterial: material type \"" + type + "\" is outside the GPU path's scope (shinydiffusemat, glossy, coated_glossy, glass, rough_glass, mirror, light_mat, mask_mat, blend_mat)"); return nullptr; }
 	if(!ok) return nullptr;
-	if(type != "shinydiffusemat" && type != "glossy" && type != "coated_glossy" && type != "glass" && type != "mask_mat") clear_shader_slots(m->m);
+	if(type != "shinydiffusemat" && type != "glossy" && type != "coated_glossy" && type != "glass" && type != "mask_mat" && type != "blend_mat") clear_shader_slots(m->m);
 	note_srand(yi, ++g_material_index_auto);        // Material::Material, material.cc:53-57
 	m->index = (int)yi->material_order.size();
 	yafaray_material *raw = m.get();

@@ -242,6 +242,9 @@ YG_DEV void get_surface(const DevScene &sc, int ti, V3 hitp, float bu, float bv,
 // `filtered` — multiplies its transparency into filt; more than max_depth transparent triangles block it too.  The
 // product is taken in visiting order, as there (so its last bits depend on tree topology, there as here).
 constexpr int kTsMaxDepth = 8;
+// kBlend: the walk of a scene in which some triangle uses a blend material (BlendMaterial::getTransparency at a crossing: the blend's node and
+// two resolved records); every other scene's walk is compiled without it and keeps the registers and scratch it had.
+template<bool kBlend>
 YG_DEV bool kd_trace_ts(const DevScene &sc, LaneStack &stk, uint32_t *seen /* [kTsMaxDepth + 1] */, V3 from, V3 dir, float ray_tmin, float dist,
                         int max_depth, Col &filt)
 {
@@ -285,8 +288,9 @@ YG_DEV bool kd_trace_ts(const DevScene &sc, LaneStack &stk, uint32_t *seen /* [k
 			const yafgpu_material *mp = &sc.mats[__float_as_uint(r1.w) & 0x3FFFFFFFu];
 #if YAFGPU_FEAT_TEXTURE
 			const bool masked = sc.tex.nodes != nullptr && mp->type == YAFGPU_MAT_MASKED;
-			// MaskMaterial::isTransparent, material_mask.cc:86-89: either sub-material's
-			if(masked ? !mp->is_transparent : !mat_is_transparent(*mp)) return true;
+			const bool blended = kBlend && mp->type == YAFGPU_MAT_BLEND;
+			// MaskMaterial::isTransparent, material_mask.cc:86-89, BlendMaterial::isTransparent, material_blend.cc:332-335: either sub-material's
+			if((masked || blended) ? !mp->is_transparent : !mat_is_transparent(*mp)) return true;
 #else
 			if(!mat_is_transparent(*mp)) return true;
 #endif
@@ -301,6 +305,15 @@ YG_DEV bool kd_trace_ts(const DevScene &sc, LaneStack &stk, uint32_t *seen /* [k
 			// MaskMaterial::getTransparency, :91-99: the mask's nodes again, against 0.5 and not threshold_; the chosen material's
 			// getTransparency follows, black for one that is opaque (the ray goes on with nothing left to carry)
 			if(masked) mp = &sc.mats[mask_select(sc.tex, sc.cam, *mp, (int)ti, u, v, sp.p, sp.n, sp.ng, true)];
+			if(kBlend && blended)
+			{	// BlendMaterial::getTransparency, material_blend.cc:337-361: both sub-materials' filters (black for an opaque one) mixed by the
+				// blend value at the crossing.  intersectTs calls no initBsdf (kdtree_triangle.cc:1105-1116): the surface point is the triangle's own
+				BlendScratch b;
+				blend_at_hit(sc.tex, sc.cam, sc.mats, *mp, (int)ti, u, v, sp.p, sp.n, sp.ng, b);
+				filt = filt * blend_transparency(b, sp, dir);
+				++depth;
+				continue;
+			}
 #endif
 			const yafgpu_material &m = *mp;
 			if(m.n_nodes > 0 && sc.tex.nodes != nullptr)
@@ -469,6 +482,21 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			SurfPt sp; sp.n = mk(x[1], x[2], x[3]); sp.ng = mk(x[4], x[5], x[6]); sp.p = mk(0.f, 0.f, 0.f); sp.mat = 0;
 			create_cs(sp.n, sp.nu, sp.nv);
 			const V3 wo = mk(x[7], x[8], x[9]), wl = mk(x[10], x[11], x[12]);
+			if(m.type == YAFGPU_MAT_BLEND)
+			{	// a blend's record, with its constant and its sub-materials' records as the table has them (blend_plain): the same outputs from
+				// BlendMaterial's functions, on the surface point as given (initBsdf's lerp of the frame is the vertex code's, wf_mat_hit)
+				BlendScratch b; blend_plain(sc.mats, m, b);
+				const Col e = blend_eval(b, sp, wo, wl, kAll);
+				const float pdf = blend_pdf(b, sp, wo, wl, kGlossy | kDiffuse | kDispersive | kReflect | kTransmit);
+				BsdfSample bs; bs.s_1 = x[13]; bs.s_2 = x[14]; bs.pdf = 0.f; bs.flags = __float_as_uint(x[15]); bs.sampled = kNone;
+				V3 wi = mk(0.f, 0.f, 0.f); float w = 0.f;
+				const Col sc_ = blend_sample(b, sp, wo, wi, bs, w);
+				o[0] = __uint_as_float(m.bsdf_flags); o[1] = e.r; o[2] = e.g; o[3] = e.b; o[4] = pdf; o[5] = __uint_as_float(bs.sampled);
+				o[6] = sc_.r; o[7] = sc_.g; o[8] = sc_.b; o[9] = wi.x; o[10] = wi.y; o[11] = wi.z; o[12] = bs.pdf; o[13] = w;
+				const Col em = blend_emit(b, sp, wo, x[15] != 0.f);
+				o[14] = em.r; o[15] = em.g; o[16] = em.b;
+				break;
+			}
 			BsdfDat d;
 			const uint32_t fl = mat_init_bsdf(m, d);
 			const Col e = mat_eval(m, d, sp, wo, wl, kAll);
@@ -488,6 +516,19 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			SurfPt sp; sp.n = mk(x[1], x[2], x[3]); sp.ng = mk(x[4], x[5], x[6]); sp.p = mk(0.f, 0.f, 0.f); sp.mat = 0;
 			create_cs(sp.n, sp.nu, sp.nv);
 			const V3 wo = mk(x[7], x[8], x[9]);
+			if(m.type == YAFGPU_MAT_BLEND)
+			{	// (a blend's record: as in op 11)
+				BlendScratch b; blend_plain(sc.mats, m, b);
+				bool refl, refr; V3 d0, d1; Col c0, c1;
+				blend_get_specular(b, sp, wo, (n_in >= 11) ? (int)x[10] : 1, refl, refr, d0, c0, d1, c1);
+				o[0] = __uint_as_float((refl ? 1u : 0u) | (refr ? 2u : 0u));
+				o[1] = d0.x; o[2] = d0.y; o[3] = d0.z; o[4] = c0.r; o[5] = c0.g; o[6] = c0.b;
+				o[7] = d1.x; o[8] = d1.y; o[9] = d1.z; o[10] = c1.r; o[11] = c1.g; o[12] = c1.b;
+				o[13] = blend_alpha(b, sp, wo);
+				const Col tr = blend_transparency(b, sp, wo);
+				o[14] = tr.r; o[15] = tr.g; o[16] = tr.b;
+				break;
+			}
 			BsdfDat d;
 			mat_init_bsdf(m, d);
 			bool refl, refr; V3 d0, d1; Col c0, c1;
@@ -754,6 +795,20 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			o[22] = tp.ds_du.x; o[23] = tp.ds_du.y; o[24] = tp.ds_du.z; o[25] = tp.ds_dv.x; o[26] = tp.ds_dv.y; o[27] = tp.ds_dv.z;
 			break;
 		}
+		case 31:
+		{	// the shading frame BlendMaterial::initBsdf leaves (blend_lerp_frame, with the record's constant): in the index of a blend's record
+			// (as bits), n -> n, nu, nv after the lerp [0, 9), create_cs's nu, nv before it [9, 15), val and ival [15, 17)
+			if(n_in < 4 || n_out < 17) break;
+			const uint32_t k = __float_as_uint(x[0]);
+			if(k >= (uint32_t)sc.n_mats || sc.mats[k].type != YAFGPU_MAT_BLEND) break;
+			BlendScratch b; blend_plain(sc.mats, sc.mats[k], b);
+			SurfPt sp; make_sp(mk(0.f, 0.f, 0.f), mk(x[1], x[2], x[3]), mk(x[1], x[2], x[3]), (int)k, sp);
+			o[9] = sp.nu.x; o[10] = sp.nu.y; o[11] = sp.nu.z; o[12] = sp.nv.x; o[13] = sp.nv.y; o[14] = sp.nv.z;
+			blend_lerp_frame(sp, b.ival);
+			o[0] = sp.n.x; o[1] = sp.n.y; o[2] = sp.n.z; o[3] = sp.nu.x; o[4] = sp.nu.y; o[5] = sp.nu.z; o[6] = sp.nv.x; o[7] = sp.nv.y; o[8] = sp.nv.z;
+			o[15] = b.val; o[16] = b.ival;
+			break;
+		}
 		default: break;
 	}
 }
@@ -893,6 +948,7 @@ struct yafgpu_scene
 	bool has_bump = false;               // some material has a bump shader: the shading frame is parked per vertex (records 24 / 25, frame record 12)
 	bool has_textures = false;           // some material in use has shader nodes: the general shading kernel, texture coordinates parked per path
 	bool has_specular = false, has_transparent = false;
+	bool has_blend = false;              // some triangle uses a blend material: the shading kernel built with the blend's code (the "blend" unit), for every pass
 	DevMem<float> d_filter_table;
 	// serial-state replay tables (WfArgs::replay), per scene: a pass that replays is never pipelined
 	DevMem<uint32_t> rp_flags; DevMem<float> rp_p; DevMem<uint8_t> rp_kill, rp_calls; DevMem<uint32_t> rp_base;
@@ -1126,14 +1182,32 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 	{
 		// recursiveRaytrace (integrator_montecarlo.cc:782-1028): the perfect specular branch and both cases of the glossy branch (reflect
 		// only; reflect + transmit, which is rough glass and nothing else) are on the device path; the dispersive branch is not
-		if(d->materials[i].type < 0 || d->materials[i].type > YAFGPU_MAT_MASKED) return fail(-3, "material " + std::to_string(i) + ": unknown type");
+		if(d->materials[i].type < 0 || d->materials[i].type > YAFGPU_MAT_BLEND) return fail(-3, "material " + std::to_string(i) + ": unknown type");
+		if(d->materials[i].type == YAFGPU_MAT_BLEND)
+		{	// a blend runs every material function on two records that are plain materials (neither a mask nor a blend), with or without a
+			// node of its own range for the blend value; like a mask's, its union of flags is no lobe of its own
+			const yafgpu_material &m = d->materials[i];
+			for(int k = 0; k < 2; ++k)
+				if(m.c_index[k] < 0 || m.c_index[k] >= d->n_materials || d->materials[m.c_index[k]].type >= YAFGPU_MAT_MASKED || d->materials[m.c_index[k]].type < 0)
+					return fail(-3, "blend material " + std::to_string(i) + ": a sub-material index outside the table, or a mask or a blend under a blend (nesting is not built)");
+			if(m.n_nodes < 0 || (m.n_nodes > 0 && (!d->nodes || m.sh_diffuse < 0 || m.sh_diffuse >= m.n_nodes)) || m.n_bump != 0)
+				return fail(-24, "blend material " + std::to_string(i) + ": a blend with nodes needs the blend node among them, and has no bump shader");
+			for(int k = 0; k < 2; ++k)
+				if(d->materials[m.c_index[k]].n_bump != 0)
+					return fail(-24, "blend material " + std::to_string(i) + ": a sub-material with a bump shader (BlendMaterial::initBsdf would blend two bumped frames, surface.cc:137-151)");
+			// the same case of recursiveRaytrace's glossy branch as under a mask: BlendMaterial's two-direction sample (material_blend.cc:216-236) is not restated
+			const uint32_t both = d->materials[m.c_index[0]].bsdf_flags | d->materials[m.c_index[1]].bsdf_flags;
+			if((both & kGlossy) && (both & kReflect) && (both & kTransmit))
+				return fail(-4, "blend material " + std::to_string(i) + ": a glossy sub-material beside a transmitting one (recursiveRaytrace reads the union of their flags, integrator_montecarlo.cc:895-919)");
+			continue;
+		}
 		if(d->materials[i].type == YAFGPU_MAT_MASKED)
 		{	// a mask picks between two records that are materials themselves (no nesting), through a node of its own range; the union of flags it
 			// carries (material_mask.cc:34) is no lobe of its own, so the two tests below are its sub-materials' to pass
 			const yafgpu_material &m = d->materials[i];
 			for(int k = 0; k < 2; ++k)
-				if(m.c_index[k] < 0 || m.c_index[k] >= d->n_materials || d->materials[m.c_index[k]].type == YAFGPU_MAT_MASKED)
-					return fail(-3, "mask material " + std::to_string(i) + ": a sub-material index outside the table, or a mask under a mask (nesting is not built)");
+				if(m.c_index[k] < 0 || m.c_index[k] >= d->n_materials || d->materials[m.c_index[k]].type == YAFGPU_MAT_MASKED || d->materials[m.c_index[k]].type == YAFGPU_MAT_BLEND)
+					return fail(-3, "mask material " + std::to_string(i) + ": a sub-material index outside the table, or a mask or a blend under a mask (nesting is not built)");
 			if(!d->nodes || m.n_nodes < 1 || m.sh_diffuse < 0 || m.sh_diffuse >= m.n_nodes || m.n_bump != 0)
 				return fail(-24, "mask material " + std::to_string(i) + ": needs shader nodes and a mask node among them, and has no bump shader");
 			// recursiveRaytrace's glossy branch picks its case from the MASK's flags, the union (integrator_montecarlo.cc:895-919): next to a
@@ -1171,11 +1245,24 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 				for(int i = sg.first; i < sg.first + sg.count; ++i) used[(size_t)mat[i]] = 1;
 			}
 		for(int i = 0; i < d->n_materials; ++i)
-			if(used[(size_t)i] && d->materials[i].type == YAFGPU_MAT_MASKED) used[(size_t)d->materials[i].c_index[0]] = used[(size_t)d->materials[i].c_index[1]] = 1;
+			if(used[(size_t)i] && (d->materials[i].type == YAFGPU_MAT_MASKED || d->materials[i].type == YAFGPU_MAT_BLEND)) used[(size_t)d->materials[i].c_index[0]] = used[(size_t)d->materials[i].c_index[1]] = 1;
 		for(int i = 0; i < d->n_materials; ++i)
 		{
 			if(!used[(size_t)i] || d->materials[i].type == YAFGPU_MAT_MASKED) continue;
 			const yafgpu_material &m = d->materials[i];
+			if(m.type == YAFGPU_MAT_BLEND)
+			{	// A blend in use IS a vertex's material: the scene takes the shading kernel built with the blend's code (pick_shade_variant), and
+				// the blend's own words size what the integrators read off sp.material_ — the union of flags (recursion frames, the glossy loop:
+				// recursiveRaytrace enters on them), the larger additional depth, isTransparent(), the volume handler.  Its two records count
+				// below with their own types and lobes (the anisotropic lobe, rough glass never: that pair is refused).
+				s->has_blend = true;
+				if(m.bsdf_flags & kVolumetric) s->has_volumetric = true;
+				if(m.bsdf_flags & (kSpecular | kFilter)) s->has_specular = true;
+				if(m.bsdf_flags & kGlossy) s->has_glossy = true;
+				s->max_add_depth = std::max(s->max_add_depth, std::min(std::max(m.additional_depth, 0), 15));
+				if(m.is_transparent) s->has_transparent = true;
+				continue;
+			}
 			s->mat_mask |= 1u << (uint32_t)m.type;
 			if(m.bsdf_flags & kVolumetric) s->has_volumetric = true;
 			if(m.bsdf_flags & (kSpecular | kFilter)) s->has_specular = true;
@@ -1321,7 +1408,7 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 			const yafgpu_material &m = d->materials[i];
 			if(m.n_nodes < 0 || m.n_nodes > kMaxNodes || m.node_first < 0 || m.node_first + m.n_nodes > d->n_nodes)
 			{ yafgpu_scene_destroy(s); return fail(-24, "a material's shader nodes: more than " + std::to_string(kMaxNodes) + " nodes, or a range outside the node array"); }
-			if(m.n_nodes > 0 && (m.type != YAFGPU_MAT_MASKED || s->mat_used[(size_t)i])) s->has_textures = true;      // (a mask nothing refers to picks no kernel)
+			if(m.n_nodes > 0 && ((m.type != YAFGPU_MAT_MASKED && m.type != YAFGPU_MAT_BLEND) || s->mat_used[(size_t)i])) s->has_textures = true;      // (a mask or a blend nothing refers to picks no kernel)
 			if(m.n_bump < 0 || m.n_bump > kMaxNodes || (m.n_bump > 0 && (m.bump_first < 0 || m.bump_first + m.n_bump > d->n_nodes || m.sh_bump < 0 || m.sh_bump >= m.n_bump)))
 			{ yafgpu_scene_destroy(s); return fail(-24, "a material's bump shader: more than " + std::to_string(kMaxNodes) + " nodes, or a range outside the node array"); }
 			if(m.n_bump > 0) { s->has_textures = true; s->has_bump = true; }
@@ -1637,6 +1724,7 @@ YG_DECLARE_SHADE_VARIANT(glossy_mp)
 YG_DECLARE_SHADE_VARIANT(diffuse_rec)
 YG_DECLARE_SHADE_VARIANT(glossy_rec)
 YG_DECLARE_SHADE_VARIANT(full)
+YG_DECLARE_SHADE_VARIANT(blend)
 #undef YG_DECLARE_SHADE_VARIANT
 }
 struct ShadeVariant
@@ -1657,8 +1745,15 @@ static const ShadeVariant kShadeVariants[] = {
 	{"glossy_rec", yafgpu_shade_glossy_rec_describe, yafgpu_shade_glossy_rec_kernel, yafgpu_shade_glossy_rec_launch},
 	{"full", yafgpu_shade_full_describe, yafgpu_shade_full_kernel, yafgpu_shade_full_launch},      // everything but shader nodes
 };
+// The general kernel with the blend material's code (YAFGPU_MAT_MASK's bit 8) and every other feature this unit's own wf_shade has: shader
+// nodes, the anisotropic lobe, every light type, ambient occlusion, recursion, a second pair per park, and a record pass's program by
+// WfArgs::replay as in the general kernel.  Not in the list above: no subset of scenes picks it, a blend in use does.
+static const ShadeVariant kBlendVariant = {"blend", yafgpu_shade_blend_describe, yafgpu_shade_blend_kernel, yafgpu_shade_blend_launch};
 static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, const Switches &sw, int frames, bool record_pass, bool want_multi, bool ao)
 {
+	// a blend material some triangle uses: the one kernel that has its code, whatever the switches say (the general kernel has not) and for
+	// the record pass too; a blend nothing uses leaves has_blend clear (yafgpu_scene_create) and the choice below as it was
+	if(s->has_blend) return &kBlendVariant;
 	if(sw.general_shade || (record_pass && !sw.record_variant)) return nullptr;
 	if(ao) return nullptr;                                     // ... and without ambient occlusion (YAFGPU_FEAT_AO)
 	const bool needs_recurse = frames > 0 || s->has_volumetric;
@@ -2078,7 +2173,8 @@ static int run_program(PassCtx &c, WfArgs &a, int n_iters, bool record)
 		{
 			HIP_OK(hipMemsetAsync(w.verdict, 0, ((size_t)4 * a.n_paths + 31) / 32 * sizeof(uint32_t), any_stream));     // occluded rays set their bit
 			if((rc = timed(c, 1, [&] {
-				if(p.transp) hipLaunchKernelGGL(wf_trace_ts, dim3(cus * 8), dim3(kBlock), 0, any_stream, a);
+				if(p.transp && c.s->has_blend) hipLaunchKernelGGL((wf_trace_ts<true>), dim3(cus * 8), dim3(kBlock), 0, any_stream, a);
+				else if(p.transp) hipLaunchKernelGGL((wf_trace_ts<false>), dim3(cus * 8), dim3(kBlock), 0, any_stream, a);
 				else if(p.stats) hipLaunchKernelGGL((wf_trace<true, true>), dim3(c.g_trace_s), dim3(kBlock), 0, any_stream, a);
 				else hipLaunchKernelGGL((wf_trace<true, false>), dim3(c.g_trace_s), dim3(kBlock), 0, any_stream, a); }))) return rc;
 		}

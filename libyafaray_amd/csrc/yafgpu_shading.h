@@ -1018,6 +1018,175 @@ YG_DEV Col mat_emit(const yafgpu_material &m, const SurfPt &sp, V3 wo, bool incl
 	return mkc(0.f, 0.f, 0.f);
 }
 
+// ---- BlendMaterial, material_blend.cc (record layout: yafgpu.h, YAFGPU_MAT_BLEND) ----
+//
+// A vertex on a blend keeps the blend's record as its material, so every material-level word the integrators read off sp.material_
+// (flags, visibility, receive_shadows, isFlat(), additional depth, the volume handler) is the blend's.  The material functions run on
+// both sub-materials and mix: ADD_COLORS(c1, c2, ival, val) = c1 * ival + c2 * val and ADD_PDF(p1, p2) = p1 * ival + p2 * val (:33-36),
+// one float operation each, in that order.  BlendScratch is the vertex's material as those functions see it: the blend's record (the
+// base, so it passes wherever a record does), the two records the functions run on — the table's, or resolved copies in `store`
+// for sub-materials with shader nodes (yafgpu_texture.h blend_at_hit) — and getBlendVal's pair (:57-75).
+// mat_1_flags_ / mat_2_flags_, the members initBsdf writes (:91, :96) and sample reads (:150, :157), are the sub-records' bsdf_flags:
+// initBsdf of every type on this path returns its bsdf_flags_ member at every point (mat_init_bsdf above; material_shiny_diffuse.cc:182,
+// material_glossy.cc:63, material_coated_glossy.cc:79, material_glass.cc:63, material_rough_glass.cc:60, material_glass.h:79 (mirror),
+// material_simple.h:34 (light)).  Without bump mapping (refused on the host) both initBsdf leave their copies of sp alone, and
+// initBsdf's blendSurfacePoints__ (:98, surface.cc:137-151) lerps equal vectors: lerp__(a, a, t) = a * t + a * (1 - t)
+// (util_interpolation.h:31-36, Vec3 * float products) is a only up to roundings, so n_, nu_ and nv_ of the vertex are restated
+// (blend_lerp_frame; the other members it lerps, dp_du_ .. ds_dv_, are read by bump mapping alone).  Each sub-material's BsdfDat is a
+// function of its record (mat_init_bsdf), so it is made again where it is needed and not carried.
+struct BlendScratch : yafgpu_material { const yafgpu_material *sub[2]; float val, ival; yafgpu_material store[2]; };
+YG_DEV void blend_set_val(BlendScratch &b, float val) { b.val = val; b.ival = smin(1.f, smax(0.f, 1.f - val)); }      // :74: val itself is not clamped
+// what initBsdf leaves of the shading frame (:88-98): lerp__(v, v, inv_alpha), alpha a double there and narrowed again by Vec3 * float
+YG_DEV V3 blend_lerp(V3 v, float ival) { return v * ival + v * (float)(1.0 - (double)ival); }
+YG_DEV void blend_lerp_frame(SurfPt &sp, float ival) { sp.n = blend_lerp(sp.n, ival); sp.nu = blend_lerp(sp.nu, ival); sp.nv = blend_lerp(sp.nv, ival); }
+// the blend of table record m with its constant and the table's own sub-records (no shader nodes anywhere)
+YG_DEV void blend_plain(const yafgpu_material *mats, const yafgpu_material &m, BlendScratch &b)
+{
+	static_cast<yafgpu_material &>(b) = m;
+	blend_set_val(b, m.transmit_filter);
+	b.sub[0] = &mats[m.c_index[0]]; b.sub[1] = &mats[m.c_index[1]];
+}
+// eval, :106-129
+YG_DEV Col blend_eval(const BlendScratch &b, const SurfPt &sp, V3 wo, V3 wl, uint32_t bsdfs)
+{
+	Col c[2];
+#pragma unroll 1
+	for(int k = 0; k < 2; ++k) { BsdfDat d; mat_init_bsdf(*b.sub[k], d); c[k] = mat_eval(*b.sub[k], d, sp, wo, wl, bsdfs); }
+	return c[0] * b.ival + c[1] * b.val;
+}
+// pdf, :239-257
+YG_DEV float blend_pdf(const BlendScratch &b, const SurfPt &sp, V3 wo, V3 wi, uint32_t bsdfs)
+{
+	float p[2];
+#pragma unroll 1
+	for(int k = 0; k < 2; ++k) { BsdfDat d; mat_init_bsdf(*b.sub[k], d); p[k] = mat_pdf(*b.sub[k], d, sp, wo, wi, bsdfs); }
+	return p[0] * b.ival + p[1] * b.val;
+}
+// sample, the one-direction form, :131-214.  Both sub-samples start from copies of s with pdf_ zeroed, directions and weights from
+// zero; a sub-material is sampled only where s.flags_ meets its flags; one that was not leaves the other's results as they are
+YG_DEV Col blend_sample(const BlendScratch &b, const SurfPt &sp, V3 wo, V3 &wi, BsdfSample &s, float &w)
+{
+	s.pdf = 0.f;
+	BsdfSample ss[2] = {s, s};
+	Col col[2] = {mkc(0.f, 0.f, 0.f), mkc(0.f, 0.f, 0.f)};
+	V3 wis[2] = {mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f)};
+	float ws[2] = {0.f, 0.f};
+	bool sampled[2];
+#pragma unroll 1
+	for(int k = 0; k < 2; ++k)
+	{
+		sampled[k] = (s.flags & b.sub[k]->bsdf_flags) != 0u;
+		if(sampled[k]) { BsdfDat d; mat_init_bsdf(*b.sub[k], d); col[k] = mat_sample(*b.sub[k], d, sp, wo, wis[k], ss[k], ws[k]); }
+	}
+	if(sampled[0] && sampled[1])
+	{
+		wi = normalize(wis[1] + wis[0]);
+		s.pdf = ss[0].pdf * b.ival + ss[1].pdf * b.val;
+		s.sampled = ss[0].sampled | ss[1].sampled;
+		w = 1.f;
+		return (col[0] * ws[0]) * b.ival + (col[1] * ws[1]) * b.val;
+	}
+	if(sampled[0]) { wi = wis[0]; s.pdf = ss[0].pdf; s.sampled = ss[0].sampled; w = ws[0]; return col[0]; }
+	if(sampled[1]) { wi = wis[1]; s.pdf = ss[1].pdf; s.sampled = ss[1].sampled; w = ws[1]; return col[1]; }
+	return col[0];
+}
+// getSpecular, :259-325: mixed where both reflect (refract), the direction the normalised sum; otherwise material1's scaled by ival, or
+// whatever material2 left scaled by val — also where neither reflects (the asymmetry of the else branches, as it is)
+YG_DEV void blend_get_specular(const BlendScratch &b, const SurfPt &sp, V3 wo, int raylevel, bool &do_reflect, bool &do_refract,
+                               V3 &dir_reflect, Col &col_reflect, V3 &dir_refract, Col &col_refract)
+{
+	bool refl[2], refr[2]; V3 d_refl[2], d_refr[2]; Col c_refl[2], c_refr[2];
+#pragma unroll 1
+	for(int k = 0; k < 2; ++k)
+	{
+		BsdfDat d; mat_init_bsdf(*b.sub[k], d);
+		mat_get_specular(*b.sub[k], d, sp, wo, raylevel, refl[k], refr[k], d_refl[k], c_refl[k], d_refr[k], c_refr[k]);
+	}
+	if(refl[1] && refl[0]) { col_reflect = c_refl[0] * b.ival + c_refl[1] * b.val; dir_reflect = normalize(d_refl[1] + d_refl[0]); }
+	else if(refl[0]) { col_reflect = c_refl[0] * b.ival; dir_reflect = d_refl[0]; }
+	else { col_reflect = c_refl[1] * b.val; dir_reflect = d_refl[1]; }
+	if(refr[1] && refr[0]) { col_refract = c_refr[0] * b.ival + c_refr[1] * b.val; dir_refract = normalize(d_refr[1] + d_refr[0]); }
+	else if(refr[0]) { col_refract = c_refr[0] * b.ival; dir_refract = d_refr[0]; }
+	else { col_refract = c_refr[1] * b.val; dir_refract = d_refr[1]; }
+	do_refract = refr[1] || refr[0];
+	do_reflect = refl[1] || refl[0];
+}
+// getTransparency, :337-361
+YG_DEV Col blend_transparency(const BlendScratch &b, const SurfPt &sp, V3 wo)
+{
+	Col c[2];
+#pragma unroll 1
+	for(int k = 0; k < 2; ++k) c[k] = mat_transparency(*b.sub[k], sp, wo);
+	return c[0] * b.ival + c[1] * b.val;
+}
+// getAlpha, :363-395: the smaller of the two, and only where the blend is transparent
+YG_DEV float blend_alpha(const BlendScratch &b, const SurfPt &sp, V3 wo)
+{
+	if(!b.is_transparent) return 1.f;
+	float al[2];
+#pragma unroll 1
+	for(int k = 0; k < 2; ++k) { BsdfDat d; mat_init_bsdf(*b.sub[k], d); al[k] = mat_alpha(*b.sub[k], d, sp, wo); }
+	return smin(al[0], al[1]);
+}
+// emit, :397-420
+YG_DEV Col blend_emit(const BlendScratch &b, const SurfPt &sp, V3 wo, bool include_lights)
+{
+	Col c[2];
+#pragma unroll 1
+	for(int k = 0; k < 2; ++k) c[k] = mat_emit(*b.sub[k], sp, wo, include_lights);
+	return c[0] * b.ival + c[1] * b.val;
+}
+
+// The material functions as the shading kernels call them.  A unit built with bit 8 of YAFGPU_MAT_MASK sends a blend's record to the
+// functions above — there the record is always the base of a BlendScratch (wf_mat_hit makes it) — and has room for one in the
+// material scratch of every step.  In every other unit the names below ARE the plain functions and the scratch is a record, so that
+// such a unit compiles to what it was before the blend came; it never meets a blend (pick_shade_variant).
+#define YG_HAS_BLEND (((YAFGPU_MAT_MASK) & 0x100u) != 0u)
+#if YG_HAS_BLEND
+typedef BlendScratch MatScratch;
+#define YG_BLEND(m) static_cast<const BlendScratch &>(m)
+YG_DEV Col matb_eval(const yafgpu_material &m, const BsdfDat &d, const SurfPt &sp, V3 wo, V3 wl, uint32_t bsdfs)
+{
+	if(m.type == YAFGPU_MAT_BLEND) return blend_eval(YG_BLEND(m), sp, wo, wl, bsdfs);
+	return mat_eval(m, d, sp, wo, wl, bsdfs);
+}
+YG_DEV float matb_pdf(const yafgpu_material &m, const BsdfDat &d, const SurfPt &sp, V3 wo, V3 wi, uint32_t bsdfs)
+{
+	if(m.type == YAFGPU_MAT_BLEND) return blend_pdf(YG_BLEND(m), sp, wo, wi, bsdfs);
+	return mat_pdf(m, d, sp, wo, wi, bsdfs);
+}
+YG_DEV Col matb_sample(const yafgpu_material &m, const BsdfDat &d, const SurfPt &sp, V3 wo, V3 &wi, BsdfSample &s, float &w)
+{
+	if(m.type == YAFGPU_MAT_BLEND) return blend_sample(YG_BLEND(m), sp, wo, wi, s, w);
+	return mat_sample(m, d, sp, wo, wi, s, w);
+}
+YG_DEV void matb_get_specular(const yafgpu_material &m, const BsdfDat &d, const SurfPt &sp, V3 wo, int raylevel, bool &do_reflect, bool &do_refract,
+                              V3 &dir_reflect, Col &col_reflect, V3 &dir_refract, Col &col_refract)
+{
+	if(m.type == YAFGPU_MAT_BLEND) { blend_get_specular(YG_BLEND(m), sp, wo, raylevel, do_reflect, do_refract, dir_reflect, col_reflect, dir_refract, col_refract); return; }
+	mat_get_specular(m, d, sp, wo, raylevel, do_reflect, do_refract, dir_reflect, col_reflect, dir_refract, col_refract);
+}
+YG_DEV float matb_alpha(const yafgpu_material &m, const BsdfDat &d, const SurfPt &sp, V3 wo)
+{
+	if(m.type == YAFGPU_MAT_BLEND) return blend_alpha(YG_BLEND(m), sp, wo);
+	return mat_alpha(m, d, sp, wo);
+}
+YG_DEV Col matb_emit(const yafgpu_material &m, const SurfPt &sp, V3 wo, bool include_lights)
+{
+	if(m.type == YAFGPU_MAT_BLEND) return blend_emit(YG_BLEND(m), sp, wo, include_lights);
+	return mat_emit(m, sp, wo, include_lights);
+}
+#undef YG_BLEND
+#else
+typedef yafgpu_material MatScratch;
+#define matb_eval mat_eval
+#define matb_pdf mat_pdf
+#define matb_sample mat_sample
+#define matb_get_specular mat_get_specular
+#define matb_alpha mat_alpha
+#define matb_emit mat_emit
+#endif
+
 // AreaLight::illumSample, light_area.cc:67-97
 YG_DEV bool arealight_illum_sample(const yafgpu_light &l, V3 sp_p, float s_1, float s_2, V3 &wi_dir, float &wi_tmax, float &pdf)
 {

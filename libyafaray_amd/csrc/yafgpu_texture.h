@@ -699,6 +699,28 @@ YG_DEV int mask_select(const TexScene &ts, const yafgpu_camera &cam, const yafgp
 	const bool mv = transparency ? val > 0.5f : val > m.transmit_filter;
 	return m.c_index[mv ? 1 : 0];
 }
+// The blend material at a hit (BlendMaterial, material_blend.cc; yafgpu_shading.h BlendScratch): getBlendVal (:57-75) — the constant,
+// or evalNodes over the blend's own nodes and blend_s_->getScalar(stack), the way mask_value reads a mask's — and the two records its
+// functions run on: the table's clones, each resolved at this point if it has shader nodes of its own.  A scene without node data
+// (ts.nodes null) has neither kind of node, and tri / bu / bv are not read.
+YG_DEV void blend_at_hit(const TexScene &ts, const yafgpu_camera &cam, const yafgpu_material *mats, const yafgpu_material &m, int tri, float bu, float bv,
+                         V3 p, V3 n, V3 ng, BlendScratch &b)
+{
+	blend_plain(mats, m, b);
+	if(ts.nodes == nullptr) return;
+	const bool driven = m.n_nodes > 0 && m.sh_diffuse >= 0;
+	if(!driven && b.sub[0]->n_nodes <= 0 && b.sub[1]->n_nodes <= 0) return;
+	TexPoint tp; tex_point(ts, tri, bu, bv, p, n, ng, tp);
+	if(driven)
+	{
+		NodeResult stack[kMaxNodes];
+		nodes_eval(ts, ts.nodes + m.node_first, m.n_nodes < kMaxNodes ? m.n_nodes : kMaxNodes, cam, tp, stack);
+		blend_set_val(b, stack[m.sh_diffuse].f);
+	}
+#pragma unroll 1
+	for(int k = 0; k < 2; ++k)
+		if(b.sub[k]->n_nodes > 0) { mat_resolve(ts, cam, *b.sub[k], tp, b.store[k]); b.sub[k] = &b.store[k]; }
+}
 
 // ---- backgrounds and the background light (image-based lighting) ----
 //

@@ -190,7 +190,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		else if(!pointlight_illuminate(light, sp.p, lcol, r_dir, r_tmax)) return false;
 		r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
 		const float angle = wf_is_flat(mat) ? 1.f : fabsf(dot(sp.n, r_dir));
-		contrib = (mat_eval(mat, dat, sp, wo, r_dir, kAll) * lcol) * angle;
+		contrib = (matb_eval(mat, dat, sp, wo, r_dir, kAll) * lcol) * angle;
 		return true;
 	}
 	if(phase == 0)
@@ -204,7 +204,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
 		if(ls_pdf > 1e-6f)
 		{
-			const Col surf_col = mat_eval(mat, dat, sp, wo, r_dir, kAll);
+			const Col surf_col = matb_eval(mat, dat, sp, wo, r_dir, kAll);
 			const float angle = wf_is_flat(mat) ? 1.f : fabsf(dot(sp.n, r_dir));
 			// the light colour of this half is what illumSample returned (ls.col_, :178-262): col_pdf for the sun, the background in the sampled
 			// direction for the background light, the fixed colour otherwise
@@ -213,7 +213,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 				contrib = ((surf_col * l_col) * angle) / ls_pdf;
 				return true;
 			}
-			const float m_pdf = mat_pdf(mat, dat, sp, wo, r_dir, kMisFlags);
+			const float m_pdf = matb_pdf(mat, dat, sp, wo, r_dir, kMisFlags);
 			const Col ls_col = (YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) || YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) ? l_col : col3(light.color);
 			if(m_pdf > 1e-6f)
 			{
@@ -228,7 +228,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 	r_tmin = ra.rp.min_raydist_auto ? ra.ray_min_dist * smax(1.f, length(sp.p)) : ra.ray_min_dist;
 	float W = 0.f;
 	BsdfSample bs; bs.s_1 = s_1; bs.s_2 = s_2; bs.pdf = 0.f; bs.flags = kMisFlags; bs.sampled = kNone;
-	const Col surf_col = mat_sample(mat, dat, sp, wo, r_dir, bs, W);
+	const Col surf_col = matb_sample(mat, dat, sp, wo, r_dir, bs, W);
 	float light_ipdf;
 	// Light::intersect: the sun's also returns its colour (lcol = col_pdf) and t = -1, an infinite shadow ray; so does the background light's
 	Col l_col = mkc(0.f, 0.f, 0.f);
@@ -278,9 +278,20 @@ YG_DEV uint32_t wf_event(const WfArgs &a, uint32_t slot, uint32_t z19, int path_
 
 // The material at a path vertex: the record itself or, for a material with shader nodes, its resolved copy in `tmp`
 // (yafgpu_texture.h mat_resolve).  wf_mat_hit: triangle and barycentrics at hand; wf_mat_parked: from record 22 / 23.
-YG_DEV const yafgpu_material &wf_mat_hit(const DevScene &sc, const SurfPt &sp, int tri, float bu, float bv, yafgpu_material &tmp)
+// A vertex on a blend material (a unit built with YAFGPU_MAT_MASK's bit 8): the blend's record with its two sub-records behind it
+// (blend_at_hit), whether or not the scene has node data; and sp gets the frame BlendMaterial::initBsdf leaves (blend_lerp_frame).
+// A vertex is parked with the frame it had before (st_after_closest), so every resume that builds its material applies this once.
+YG_DEV const yafgpu_material &wf_mat_hit(const DevScene &sc, SurfPt &sp, int tri, float bu, float bv, MatScratch &tmp)
 {
 	const yafgpu_material &m = sc.mats[sp.mat];
+#if YG_HAS_BLEND
+	if(m.type == YAFGPU_MAT_BLEND)
+	{
+		blend_at_hit(sc.tex, sc.cam, sc.mats, m, tri, bu, bv, sp.p, sp.n, sp.ng, tmp);
+		blend_lerp_frame(sp, tmp.ival);
+		return tmp;
+	}
+#endif
 #if YAFGPU_FEAT_TEXTURE
 	if(m.n_nodes > 0 && sc.tex.nodes != nullptr)
 	{
@@ -339,9 +350,16 @@ YG_DEV void wf_frame_parked(const WfArgs &a, uint32_t slot, int vertex, SurfPt &
 	(void)a; (void)slot; (void)vertex; (void)sp;
 #endif
 }
-YG_DEV const yafgpu_material &wf_mat_parked(const WfArgs &a, uint32_t slot, int vertex, const SurfPt &sp, yafgpu_material &tmp)
+YG_DEV const yafgpu_material &wf_mat_parked(const WfArgs &a, uint32_t slot, int vertex, SurfPt &sp, MatScratch &tmp)
 {
 	const yafgpu_material &m = a.ra.sc.mats[sp.mat];
+#if YG_HAS_BLEND
+	if(m.type == YAFGPU_MAT_BLEND)
+	{	// (record 22 / 23 is written in scenes with node data only; without it blend_at_hit reads neither triangle nor barycentrics)
+		const float4 r = a.ra.sc.tex.nodes != nullptr ? REC(22 + vertex) : make_float4(0.f, 0.f, 0.f, 0.f);
+		return wf_mat_hit(a.ra.sc, sp, (int)ubits(r.x), r.y, r.z, tmp);
+	}
+#endif
 #if YAFGPU_FEAT_TEXTURE
 	if(m.n_nodes > 0 && a.ra.sc.tex.nodes != nullptr)
 	{
@@ -670,7 +688,7 @@ YG_DEV float add_mod_1(float x, float y) { const float t = x + y; return t > 1 ?
 // Ambient occlusion of the direct lighting integrator (integrator_direct_light.cc:145; MonteCarloIntegrator::sampleAmbientOcclusion,
 // integrator_montecarlo.cc:1030-1088).  It rides the light estimate as a pseudo-light at index n_lights, taken after the last real
 // light: one half only, its own sample count and offsets, its samples' contributions added to ccol (record 15) in sample order.  A
-// kernel built with 0 serves renders without it (every unit of yafgpu_shade_variant.hip).
+// kernel built with 0 serves renders without it (every unit of yafgpu_shade_variant.hip but the blend material's, which has it).
 #ifndef YAFGPU_FEAT_AO
 #define YAFGPU_FEAT_AO 1
 #endif
@@ -714,9 +732,9 @@ YG_DEV bool ao_candidate(const AoParams &ao, float s_1, float s_2, const SurfPt 
 	float w = 0.f;
 	BsdfSample bs; bs.s_1 = s_1; bs.s_2 = s_2; bs.pdf = 0.f; bs.flags = kGlossy | kDiffuse | kReflect; bs.sampled = kNone;
 	r_dir = mk(0.f, 0.f, 0.f);
-	const Col surf_col = mat_sample(mat, dat, sp, wo, r_dir, bs, w);
+	const Col surf_col = matb_sample(mat, dat, sp, wo, r_dir, bs, w);
 	emit = mkc(0.f, 0.f, 0.f);
-	if(bsdfs & kEmit) emit = mat_emit(mat, sp, wo, include_lights) * bs.pdf;
+	if(bsdfs & kEmit) emit = matb_emit(mat, sp, wo, include_lights) * bs.pdf;
 	const float cs = fabsf(dot(sp.n, r_dir));
 	contrib = ((ao.col * surf_col) * cs) * w;
 	return !is_black(contrib);
@@ -777,21 +795,22 @@ YG_DEV int st_after_closest(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint
 		get_surface(sc, tri, v3(r0) + dir * ans.y, ans.z, ans.w, sp0);
 		wf_mask_hit(sc, sp0, tri, ans.z, ans.w);
 		if(YAFGPU_FEAT_TEXTURE && sc.tex.has_bump) { const bool bumped = wf_bump_hit(sc, sp0, tri, ans.z, ans.w); REC(24) = f4(sp0.nu, bumped ? 1.f : 0.f); }
-		yafgpu_material m_tmp;
+		MatScratch m_tmp;
+		const V3 n_parked = sp0.n;      // (on a blend wf_mat_hit changes the frame in hand; the records keep the one before it)
 		const yafgpu_material &m = wf_mat_hit(sc, sp0, tri, ans.z, ans.w, m_tmp);
 		if(YAFGPU_FEAT_TEXTURE && sc.tex.nodes != nullptr) REC(22) = make_float4(fbits((uint32_t)tri), ans.z, ans.w, 0.f);
 		BsdfDat dat0;
 		const uint32_t bsdfs0 = mat_init_bsdf(m, dat0);
 		if(YAFGPU_FEAT_RECURSE) c.add = max(c.add, min(m.additional_depth, 15));                 // integrator_path_tracer.cc:149
 		const V3 wo0 = -dir;
-		if(bsdfs0 & kEmit) c.col = c.col + mat_emit(m, sp0, wo0, c.incl != 0);                // :152 (include_lights_ :133)
+		if(bsdfs0 & kEmit) c.col = c.col + matb_emit(m, sp0, wo0, c.incl != 0);                // :152 (include_lights_ :133)
 		alpha = 1.f;
 		if(rp.bg_transp_refract)
 		{
-			const float m_alpha = mat_alpha(m, dat0, sp0, wo0);
+			const float m_alpha = matb_alpha(m, dat0, sp0, wo0);
 			alpha = m_alpha + (1.f - m_alpha) * (rp.bg_transp ? 0.f : 1.f);
 		}
-		VSET(3, f4(sp0.p, fbits((uint32_t)sp0.mat))); VSET(4, f4(sp0.n, 0.f)); VSET(5, f4(sp0.ng, fbits(bsdfs0))); VSET(6, f4(wo0, 0.f));
+		VSET(3, f4(sp0.p, fbits((uint32_t)sp0.mat))); VSET(4, f4(n_parked, 0.f)); VSET(5, f4(sp0.ng, fbits(bsdfs0))); VSET(6, f4(wo0, 0.f));
 		// (throughput, path colour and the roulette stream of this level's path samples: st_start_path, at the first of them)
 		uint32_t z19 = 0u;
 		if(a.ev_m > 1 && c.level > 0) z19 = ubits(REC(19).z) + (1u << 24);      // the next integrate() call of this camera sample
@@ -830,7 +849,8 @@ YG_DEV int st_after_closest(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint
 	get_surface(sc, tri, v3(r0) + dir * ans.y, ans.z, ans.w, hit);
 	wf_mask_hit(sc, hit, tri, ans.z, ans.w);
 	if(YAFGPU_FEAT_TEXTURE && sc.tex.has_bump) { const bool bumped = wf_bump_hit(sc, hit, tri, ans.z, ans.w); REC(25) = f4(hit.nu, bumped ? 1.f : 0.f); }
-	yafgpu_material pm_tmp;
+	MatScratch pm_tmp;
+	const V3 n_parked = hit.n;      // (as at the camera hit)
 	const yafgpu_material &pm = wf_mat_hit(sc, hit, tri, ans.z, ans.w, pm_tmp);
 	if(YAFGPU_FEAT_TEXTURE && sc.tex.nodes != nullptr) REC(23) = make_float4(fbits((uint32_t)tri), ans.z, ans.w, 0.f);
 	BsdfDat dat_n;
@@ -839,7 +859,7 @@ YG_DEV int st_after_closest(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint
 	V3 pwo = -dir;                                                                              // :271
 	if(c.stage == kStFirst && ubits(misc.y) == kNone) pwo = v3(VGET(10));                      // :224: keeps the first segment's pwo
 	// .w of 8..10: p_ray.dir_ of the segment that ended here — what Material::sample leaves in `wi` when it samples nothing
-	VSET(7, f4(hit.p, fbits((uint32_t)hit.mat))); VSET(8, f4(hit.n, dir.x)); VSET(9, f4(hit.ng, dir.y)); VSET(10, f4(pwo, dir.z));
+	VSET(7, f4(hit.p, fbits((uint32_t)hit.mat))); VSET(8, f4(n_parked, dir.x)); VSET(9, f4(hit.ng, dir.y)); VSET(10, f4(pwo, dir.z));
 	if(A_REPLAY != 1) hot_zero_tot(a, slot, h);
 	if(YAFGPU_FEAT_RECURSE && (mb & kVolumetric) && c.stage == kStDepth && pm.has_vol_i && dot(hit.n, pwo) < 0.f)
 	{	// integrator_path_tracer.cc:276-279: the segment ran inside an absorbing material (lcol does not depend on it)
@@ -968,7 +988,7 @@ YG_DEV int st_dl_eval(const WfArgs &a, uint32_t slot, Hot &h, const Ctl &c, uint
 	if(c.dl_on_sp0) { const float4 p = VHELD(3); make_sp(v3(p), v3(VHELD(4)), v3(VHELD(5)), (int)ubits(p.w), sp); wo = v3(VHELD(6)); }
 	else { const float4 p = VHELD(7); make_sp(v3(p), v3(VHELD(8)), v3(VHELD(9)), (int)ubits(p.w), sp); wo = v3(VHELD(10)); }
 	wf_frame_parked(a, slot, c.dl_on_sp0 ? 0 : 1, sp);
-	yafgpu_material mat_tmp;
+	MatScratch mat_tmp;
 	const yafgpu_material &mat = wf_mat_parked(a, slot, c.dl_on_sp0 ? 0 : 1, sp, mat_tmp);
 	BsdfDat dat;
 	const uint32_t bsdfs = mat_init_bsdf(mat, dat); (void)bsdfs;
@@ -1064,11 +1084,23 @@ YG_DEV int st_dl_done(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, bool besid
 	const yafgpu_material &pm_rec = sc.mats[(int)ubits(VGET_W(7))];
 	BsdfDat dat_n;
 	const uint32_t mb = mat_init_bsdf(pm_rec, dat_n);      // the flags do not depend on the nodes
-	yafgpu_material pm_tmp; (void)pm_tmp;
+	MatScratch pm_tmp; (void)pm_tmp;
 	const yafgpu_material *pm_p = &pm_rec;
 	const bool caustic = YAFGPU_FEAT_CAUSTIC && c.stage == kStDepth && rp.trace_caustics && c.incl;      // the segment that ended here: :252
+#if YG_HAS_BLEND
+	const bool on_blend = pm_rec.type == YAFGPU_MAT_BLEND;
+	if((c.stage == kStFirst || caustic) && (mb & kEmit) && on_blend)
+	{	// a blend's emission is its sub-materials' (blend_emit), with or without node data: the material as every other step builds it
+		const float4 p7 = VGET(7);
+		SurfPt hp; make_sp(v3(p7), v3(VGET(8)), v3(VGET(9)), (int)ubits(p7.w), hp);
+		pm_p = &wf_mat_parked(a, slot, 1, hp, pm_tmp);
+	}
+#else
+	const bool on_blend = false;
+#endif
+	(void)on_blend;
 #if YAFGPU_FEAT_TEXTURE
-	if((c.stage == kStFirst || caustic) && (mb & kEmit) && pm_rec.n_nodes > 0 && sc.tex.nodes != nullptr)
+	if((c.stage == kStFirst || caustic) && (mb & kEmit) && pm_rec.n_nodes > 0 && sc.tex.nodes != nullptr && !on_blend)
 	{	// its own emission reads the diffuse shader (emit(), material_shiny_diffuse.cc:295-306)
 		const float4 p7 = VGET(7);
 		SurfPt hp; hp.p = v3(p7); hp.n = v3(VGET(8)); hp.ng = v3(VGET(9)); hp.mat = (int)ubits(p7.w);
@@ -1086,7 +1118,7 @@ YG_DEV int st_dl_done(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, bool besid
 		if(mb & kEmit)
 		{	// :226 — include_lights_ is false here, so only shinydiffuse's own emission can contribute
 			SurfPt dummy; dummy.n = mk(0.f, 0.f, 0.f);
-			lcol = lcol + mat_emit(pm, dummy, mk(0.f, 0.f, 0.f), false);
+			lcol = lcol + matb_emit(pm, dummy, mk(0.f, 0.f, 0.f), false);
 		}
 		path_col = path_col + lcol * throughput;                                                // :228
 		if(!rec) HSET(12, f4(path_col, r12.w));
@@ -1134,7 +1166,10 @@ YG_DEV int st_dl_done(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, bool besid
 		{	// :290 a vertex reached through a caustic lobe adds what it emits, its lights included (include_lights_ is set)
 			const float4 p7 = VGET(7);
 			SurfPt hp; hp.p = v3(p7); hp.n = v3(VGET(8)); hp.ng = v3(VGET(9)); hp.mat = (int)ubits(p7.w);
-			lcol = lcol + mat_emit(pm, hp, v3(VGET(10)), true);
+#if YG_HAS_BLEND
+			if(on_blend) hp.n = blend_lerp(hp.n, static_cast<const BlendScratch &>(pm).ival);      // (the frame initBsdf left, as wf_mat_hit makes it; emit reads the normal alone)
+#endif
+			lcol = lcol + matb_emit(pm, hp, v3(VGET(10)), true);
 		}
 		path_col = path_col + lcol * throughput;                                                // :292
 		++c.depth;
@@ -1163,7 +1198,7 @@ YG_DEV int st_extend(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c)
 	wf_frame_parked(a, slot, 1, hit);
 	const float4 r10 = VGET(10);
 	const V3 pwo = v3(r10);
-	yafgpu_material pm_tmp;
+	MatScratch pm_tmp;
 	const yafgpu_material &pm = wf_mat_parked(a, slot, 1, hit, pm_tmp);
 	BsdfDat dat_n; mat_init_bsdf(pm, dat_n);
 	const uint32_t offs = ubits(REC(19).x);
@@ -1177,7 +1212,7 @@ YG_DEV int st_extend(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c)
 	// through with the previous weight (integrator_path_tracer.cc:243-249).  They live in REC(6).w and in 8..10.w.
 	float w = VGET_W(6);
 	V3 p_dir = mk(VGET(8).w, VGET(9).w, r10.w);
-	const Col scol = mat_sample(pm, dat_n, hit, pwo, p_dir, bs, w) * w;
+	const Col scol = matb_sample(pm, dat_n, hit, pwo, p_dir, bs, w) * w;
 	VSET_W(w);
 	if(is_black(scol)) { ++c.path_i; return W_START_PATH; }                                      // :249 `break`
 	if(A_REPLAY != 1 || ra.rp.bounces - 1 > ra.rp.rr_min_bounces)      // (a record pass without a roulette test to record has no use for the throughput)
@@ -1204,7 +1239,7 @@ YG_DEV int st_start_path(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint32_
 	SurfPt sp0; make_sp(v3(p), v3(VGET(4)), v3(VGET(5)), (int)ubits(p.w), sp0);
 	wf_frame_parked(a, slot, 0, sp0);
 	const V3 wo0 = v3(VGET(6));
-	yafgpu_material m_tmp;
+	MatScratch m_tmp;
 	const yafgpu_material &m = wf_mat_parked(a, slot, 0, sp0, m_tmp);
 	BsdfDat dat0; mat_init_bsdf(m, dat0);
 	const uint32_t offs = (uint32_t)rp.path_samples * pixel_sample + sampling_offs + (uint32_t)c.path_i;
@@ -1217,7 +1252,7 @@ YG_DEV int st_start_path(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint32_
 	const float4 r6 = VGET(6);
 	float w = r6.w;                                   // integrate()'s `w`: 0 at its start, then whatever the last sample() left
 	V3 p_dir = mk(0.f, 0.f, 0.f);
-	const Col scol = mat_sample(m, dat0, sp0, wo0, p_dir, bs, w) * w;
+	const Col scol = matb_sample(m, dat0, sp0, wo0, p_dir, bs, w) * w;
 	VSET_W(w);
 	if(bs.sampled == kNone || !YAFGPU_ACC_ZERO_FLAG) VSET_KEEP(10, f4(wo0, 0.f));      // pwo = wo: only a segment that sampled nothing keeps it (:224, st_after_closest)
 	if(A_REPLAY == 1)
@@ -1267,7 +1302,7 @@ YG_DEV int st_beside(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint32_t pi
 		wf_frame_parked(a, slot, 0, sp0);
 		const float4 r6 = VGET(6);
 		const V3 wo0 = v3(r6);
-		yafgpu_material m_tmp;
+		MatScratch m_tmp;
 		const yafgpu_material &m = wf_mat_parked(a, slot, 0, sp0, m_tmp);
 		BsdfDat dat0; mat_init_bsdf(m, dat0);
 		const uint32_t offs = (uint32_t)rp.path_samples * pixel_sample + sampling_offs;
@@ -1278,7 +1313,7 @@ YG_DEV int st_beside(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint32_t pi
 		bs.flags = path_flags | kDiffuse | kReflect | kTransmit;
 		float w = r6.w;
 		V3 p_dir = mk(0.f, 0.f, 0.f);
-		const Col scol = mat_sample(m, dat0, sp0, wo0, p_dir, bs, w) * w;
+		const Col scol = matb_sample(m, dat0, sp0, wo0, p_dir, bs, w) * w;
 		VSET_W(w);
 		if(bs.sampled == kNone || !YAFGPU_ACC_ZERO_FLAG) VSET_KEEP(10, f4(wo0, 0.f));
 		Mwc rr; rr.init(fnv32a(ordinal) + 123u);
@@ -1305,7 +1340,7 @@ YG_DEV int st_beside(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint32_t pi
 	wf_frame_parked(a, slot, 1, hit);
 	const float4 r10 = VGET(10);
 	const V3 pwo = v3(r10);
-	yafgpu_material pm_tmp;
+	MatScratch pm_tmp;
 	const yafgpu_material &pm = wf_mat_parked(a, slot, 1, hit, pm_tmp);
 	BsdfDat dat_n; mat_init_bsdf(pm, dat_n);
 	const uint32_t offs = ubits(REC(19).x);
@@ -1316,7 +1351,7 @@ YG_DEV int st_beside(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint32_t pi
 	bs.pdf = 0.f; bs.sampled = kNone; bs.flags = kAll;
 	float w = VGET_W(6);
 	V3 p_dir = mk(VGET(8).w, VGET(9).w, r10.w);
-	const Col scol = mat_sample(pm, dat_n, hit, pwo, p_dir, bs, w) * w;
+	const Col scol = matb_sample(pm, dat_n, hit, pwo, p_dir, bs, w) * w;
 	if(is_black(scol)) return W_PARK_SHADOW;          // the path sample ends here (:249): nothing was written, st_extend finds it again
 	VSET_W(w);
 	REC(26) = f4(p_dir, ra.ray_min_dist);
@@ -1355,14 +1390,14 @@ YG_DEV int st_recurse_spec(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c)
 	SurfPt sp0; make_sp(v3(p), v3(VGET(4)), v3(r5), (int)ubits(p.w), sp0);
 	wf_frame_parked(a, slot, 0, sp0);
 	const V3 wo0 = v3(VGET(6));
-	yafgpu_material m_tmp;
+	MatScratch m_tmp;
 	const yafgpu_material &m = wf_mat_parked(a, slot, 0, sp0, m_tmp);
 	BsdfDat dat0; mat_init_bsdf(m, dat0);
 	c.incl = 1;                                                                       // :973
 	bool refl, refr; V3 d_refl, d_refr; Col c_refl, c_refr;
-	mat_get_specular(m, dat0, sp0, wo0, c.level + 1, refl, refr, d_refl, c_refl, d_refr, c_refr);
+	matb_get_specular(m, dat0, sp0, wo0, c.level + 1, refl, refr, d_refl, c_refl, d_refr, c_refr);
 	if(!refl && !refr) return W_RETURN;
-	const float m_alpha = mat_alpha(m, dat0, sp0, wo0);
+	const float m_alpha = matb_alpha(m, dat0, sp0, wo0);
 	const int L = c.level;
 	if(a.has_glossy)
 	{	// the rays below keep this level's trajectory-splitting state
@@ -1420,10 +1455,13 @@ YG_DEV int st_glossy_next(const WfArgs &a, uint32_t slot, Ctl &c, uint32_t pixel
 	SurfPt sp0; make_sp(v3(f2), v3(f6), v3(f7), (int)ubits(FREC(L, 9).w), sp0);
 	if(YAFGPU_FEAT_TEXTURE && sc.tex.has_bump) wf_frame_set(sp0, FREC(L, 12));
 	const V3 wo0 = v3(FREC(L, 8));
-	yafgpu_material m_tmp;
+	MatScratch m_tmp;
 	const yafgpu_material *mp = &sc.mats[sp0.mat];
 #if YAFGPU_FEAT_TEXTURE
 	if(sc.tex.nodes != nullptr) { const float4 t = FREC(L, 11); mp = &wf_mat_hit(sc, sp0, (int)ubits(t.x), t.y, t.z, m_tmp); }
+#endif
+#if YG_HAS_BLEND
+	if(sc.tex.nodes == nullptr && mp->type == YAFGPU_MAT_BLEND) mp = &wf_mat_hit(sc, sp0, 0, 0.f, 0.f, m_tmp);      // (no node data: neither triangle nor barycentrics are read)
 #endif
 	(void)m_tmp;
 	BsdfDat dat0; mat_init_bsdf(*mp, dat0);
@@ -1455,12 +1493,12 @@ YG_DEV int st_glossy_next(const WfArgs &a, uint32_t slot, Ctl &c, uint32_t pixel
 		FREC(L, 10) = f4(mcol, w);
 		FREC(L, 3) = f4(d1, 0.f);
 		FREC(L, 4) = f4(tcol, w1);
-		if(ns == 0) FREC(L, 1) = make_float4(mat_alpha(*mp, dat0, sp0, wo0), 0.f, 0.f, 0.f);
+		if(ns == 0) FREC(L, 1) = make_float4(matb_alpha(*mp, dat0, sp0, wo0), 0.f, 0.f, 0.f);
 		wf_start_level(a, slot, c, sp0.p, wi);      // (sampled_flags_ has Reflect on every way out of the sample: the first ray always goes)
 		c.level = L + 1;
 		return W_PARK_CLOSEST;
 	}
-	const Col mcol = mat_sample(*mp, dat0, sp0, wo0, wi, bs, w);
+	const Col mcol = matb_sample(*mp, dat0, sp0, wo0, wi, bs, w);
 	FREC(L, 10) = f4(mcol, w);
 	wf_start_level(a, slot, c, sp0.p, wi);
 	c.level = L + 1;
@@ -2246,6 +2284,8 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 // Scene::isShadowed with transparent shadows (scene.cc:996-1035) over the shadow queue: one lane per ray, no refill —
 // the feature path for scenes with transparent materials and transpShad, not the benchmark path.
 
+// kBlend: for scenes in which a triangle uses a blend material (kd_trace_ts)
+template<bool kBlend>
 __global__ __launch_bounds__(kBlock) void wf_trace_ts(const WfArgs a)
 {
 	__shared__ uint2 s_stack[kWavesPerBlock][kStack][kWave];
@@ -2273,7 +2313,7 @@ __global__ __launch_bounds__(kBlock) void wf_trace_ts(const WfArgs a)
 		const V3 from = v3(r0) + dir * r0.w;
 		const float dist = (r1.w < 0.f) ? INFINITY : r1.w - 2.f * r0.w;
 		Col filt;
-		const bool sh = kd_trace_ts(sc, stk, seen, from, dir, r0.w, dist, a.ra.rp.shadow_depth, filt);     // sray keeps ray.tmin_ (:998-999)
+		const bool sh = kd_trace_ts<kBlend>(sc, stk, seen, from, dir, r0.w, dist, a.ra.rp.shadow_depth, filt);     // sray keeps ray.tmin_ (:998-999)
 		if(sh) { const uint32_t bit = 4u * slot + which; atomicOr(&a.verdict[bit >> 5], 1u << (bit & 31u)); }      // (a park has one pair under transparent shadows)
 		a.shadow_filt[2u * slot + which] = f4(filt, 0.f);
 		++count;

@@ -60,7 +60,7 @@ C_API_SYMBOLS = [
     "yafaray_createInterface", "yafaray_destroyInterface", "yafaray_getLastError", "yafaray_getVersion",
     "yafaray_startScene", "yafaray_startGeometry", "yafaray_endGeometry", "yafaray_getNextFreeId",
     "yafaray_startTriMesh", "yafaray_endTriMesh", "yafaray_addVertex", "yafaray_addNormal", "yafaray_addTriangle",
-    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getCamera", "yafaray_getIntegratorAO", "yafaray_getMaskMaterial", "yafaray_getMaterialTable", "yafaray_addTriangles",
+    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getCamera", "yafaray_getIntegratorAO", "yafaray_getMaskMaterial", "yafaray_getBlendMaterial", "yafaray_getMaterialTable", "yafaray_addTriangles",
     "yafaray_startTriMeshPtr", "yafaray_addVertexWithOrco", "yafaray_addUv", "yafaray_addTriangleWithUv",
     "yafaray_startCurveMesh", "yafaray_endCurveMesh", "yafaray_addCurves", "yafaray_getCurves", "yafaray_addInstance", "yafaray_getInstances",
     "yafaray_paramsSetColorArray", "yafaray_paramsSetMatrix", "yafaray_paramsSetMatrixD", "yafaray_setInputColorSpace",
@@ -115,6 +115,7 @@ def load():
         "yafaray_getCamera": (ci, [vp, cp, vp]),
         "yafaray_getIntegratorAO": (ci, [vp, cp, C.POINTER(ci), C.POINTER(ci), C.POINTER(cf), C.POINTER(cf)]),
         "yafaray_getMaskMaterial": (ci, [vp, cp, vp]),
+        "yafaray_getBlendMaterial": (ci, [vp, cp, vp]),
         "yafaray_getMaterialTable": (ci, [vp, vp, ci]),
         "yafaray_addTriangles": (ci, [vp, ci, C.POINTER(cf), ci, C.POINTER(ci), vp]),
         "yafaray_startTriMeshPtr": (ci, [vp, C.POINTER(C.c_uint), ci, ci, ci, ci, ci, ci]),
@@ -436,6 +437,16 @@ class Interface:
         return {"material1": int(out[0]), "material2": int(out[1]), "threshold": out.view(np.float32)[2], "mask_slot": int(out[3]), "n_nodes": int(out[4]),
                 "receive_shadows": bool(out[5]), "visibility": int(out[6]), "bsdf_flags": int(out[7]) & 0xffffffff}
 
+    def getBlendMaterial(self, name):
+        """what createMaterial parsed for the blend_mat `name`, as a dict: the indices of material1 / material2 in creation order, blend_value
+        as the float32 it is kept as, whether a shader node drives the blend, that node's slot among the blend's n_nodes nodes (-1 without
+        one), and the material-level fields: the blend's own receive_shadows and visibility, the union of the sub-materials' flags and the
+        larger of their additional depths"""
+        out = np.zeros(10, dtype=np.int32)
+        self._ok(self._L.yafaray_getBlendMaterial(self._h, _b(name), out.ctypes.data_as(C.c_void_p)), "getBlendMaterial")
+        return {"material1": int(out[0]), "material2": int(out[1]), "blend_value": out.view(np.float32)[2], "node_driven": bool(out[3]), "mask_slot": int(out[4]),
+                "n_nodes": int(out[5]), "receive_shadows": bool(out[6]), "visibility": int(out[7]), "bsdf_flags": int(out[8]) & 0xffffffff, "additional_depth": int(out[9])}
+
     MATERIAL_WORDS = 96
     # word offsets of the yafgpu_material fields (include/yafgpu.h) that tests of the material table read
     MATERIAL_FIELDS = {"type": 0, "visibility": 1, "receive_shadows": 2, "flat": 3, "bsdf_flags": 4, "c_index": 10, "transmit_filter": 27, "is_transparent": 30,
@@ -444,7 +455,7 @@ class Interface:
 
     def getMaterialTable(self):
         """the material table as the device scene gets it: one row of the 96 words of a yafgpu_material (include/yafgpu.h) per record, as
-        int32 (view a float field as float32) — the materials in creation order, then two hidden clones per mask_mat"""
+        int32 (view a float field as float32) — the materials in creation order, then two hidden clones per mask_mat and per blend_mat"""
         n = self._L.yafaray_getMaterialTable(self._h, None, 0)
         out = np.zeros((max(n, 0), self.MATERIAL_WORDS), dtype=np.int32)
         if n > 0:
