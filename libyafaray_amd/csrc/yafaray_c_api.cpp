@@ -2072,8 +2072,13 @@ void yafaray_setComm(yafaray_interface_t *yi, yafaray_comm_t *comm)
 }
 void yafaray_setShard(yafaray_interface_t *yi, int shard_index, int shard_count) { yi->shard_index = shard_index; yi->shard_count = std::max(1, shard_count); }
 
+// ---- yafaray_prepareRender: select, read, flatten, describe, adopt --------------------------------------------------------------
 // RenderEnvironment::setupScene (environment.cc:679-813) + createImageFilm (:456-584) + Scene::update (scene.cc:784-894)
-yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
+namespace {
+
+struct Selection { const CameraCfg *cam = nullptr; const IntegratorCfg *inte = nullptr; const BackgroundCfg *bg = nullptr; std::string bg_name; };
+
+bool select_render(yafaray_interface *yi, Selection &sel)
 {
 	const ParamMap &p = yi->params;
 	std::string name;
@@ -2094,17 +2099,32 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 		if(b == yi->backgrounds.end()) return fail(yi, "please specify an _existing_ Background!!");
 		bg = &b->second->b;
 	}
-	{	// One image-based-lighting background per scene, and it is the one in use.  (The reference adds a background's light when the
-		// background is created, selected or not, and two of one kind collide on the light's fixed name.)
-		int n_bg_lights = 0;
-		for(auto *l : yi->light_order) if(l->l.type == YAFGPU_LIGHT_BACKGROUND) ++n_bg_lights;
-		if(n_bg_lights > 1) return fail(yi, "render: more than one background was created with ibl; the GPU path takes one image-based-lighting background per scene");
-		if(n_bg_lights == 1 && !(bg && bg->rec.has_ibl))
-			return fail(yi, "render: a background created with ibl is not the one background_name selects; its light would shine without it");
-		if(bg && bg->rec.has_ibl && bg->rec.kind == YAFGPU_BACKGROUND_CONSTANT && !((bg->rec.color[0] + bg->rec.color[1] + bg->rec.color[2]) * 0.333333f > 0.f))
-			return fail(yi, "render: a constant background with ibl needs a colour with energy; this one is black (its light's distribution would divide by zero)");
-	}
-	const std::string bg_name = bg ? name : std::string();
+	// One image-based-lighting background per scene, and it is the one in use.  (The reference adds a background's light when the
+	// background is created, selected or not, and two of one kind collide on the light's fixed name.)
+	int n_bg_lights = 0;
+	for(auto *l : yi->light_order) if(l->l.type == YAFGPU_LIGHT_BACKGROUND) ++n_bg_lights;
+	if(n_bg_lights > 1) return fail(yi, "render: more than one background was created with ibl; the GPU path takes one image-based-lighting background per scene");
+	if(n_bg_lights == 1 && !(bg && bg->rec.has_ibl))
+		return fail(yi, "render: a background created with ibl is not the one background_name selects; its light would shine without it");
+	if(bg && bg->rec.has_ibl && bg->rec.kind == YAFGPU_BACKGROUND_CONSTANT && !((bg->rec.color[0] + bg->rec.color[1] + bg->rec.color[2]) * 0.333333f > 0.f))
+		return fail(yi, "render: a constant background with ibl needs a colour with energy; this one is black (its light's distribution would divide by zero)");
+	sel.cam = &cam->second->c; sel.inte = &inte->second->c; sel.bg = bg;
+	sel.bg_name = bg ? name : std::string();
+	return true;
+}
+
+// What the parameters say about the render: read into a value of its own, which reaches the interface only when nothing refused it
+struct RenderSetup
+{
+	yafgpu_aa_schedule aa{};
+	yafgpu_render_params rp{};
+	std::string color_space, color_space2 = "Raw_Manual_Gamma"; float gamma = 1.f, gamma2 = 1.f;
+	std::vector<int32_t> tile_rand0;
+};
+
+bool read_render_setup(yafaray_interface *yi, const Selection &sel, RenderSetup &su)
+{
+	const ParamMap &p = yi->params;
 	int aa_passes = 1, aa_samples = 1, tile_size = 32, width = 320, height = 240, xstart = 0, ystart = 0;
 	int base_offset = 0, node = 0;
 	float filt_sz = 1.5f, shadow_bias = (float)0.0005, min_raydist = (float)0.00005, clamp_samples = 0.f, clamp_indirect = 0.f;
@@ -2117,13 +2137,12 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 	p.get("adv_auto_shadow_bias_enabled", auto_bias); p.get("adv_shadow_bias_value", shadow_bias);
 	p.get("adv_auto_min_raydist_enabled", auto_dist); p.get("adv_min_raydist_value", min_raydist);
 	p.get("adv_base_sampling_offset", base_offset); p.get("adv_computer_node", node);
-	p.get("color_space", yi->color_space); p.get("gamma", yi->gamma);
-	yi->color_space2 = "Raw_Manual_Gamma"; yi->gamma2 = 1.f;
-	p.get("color_space2", yi->color_space2); p.get("gamma2", yi->gamma2);
+	su.color_space = yi->color_space; su.gamma = yi->gamma;      // the first colour space stays what an earlier call read
+	p.get("color_space", su.color_space); p.get("gamma", su.gamma);
+	p.get("color_space2", su.color_space2); p.get("gamma2", su.gamma2);
 	// Scene::setAntialiasing (scene.cc:761-778), defaults of RenderEnvironment::setupScene (environment.cc:682-695,747-762)
 	{
-		yafgpu_aa_schedule &aa = yi->aa;
-		aa = yafgpu_aa_schedule{};
+		yafgpu_aa_schedule &aa = su.aa;
 		int inc = aa_samples, var_edge = 10, var_pix = 0; double threshold = 0.05;
 		float floor_pct = 0.f, smf = 1.f, lmf = 1.f, dark_factor = 0.f; bool color_noise = false; std::string dark = "none";
 		p.get("AA_inc_samples", inc); p.get("AA_threshold", threshold); p.get("AA_resampled_floor", floor_pct);
@@ -2145,8 +2164,8 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 	else if(filter == "lanczos") filter_type = YAFGPU_FILTER_LANCZOS;
 	if(premult) return fail(yi, "render: premultiplied alpha is not supported by the GPU path");
 	(void)clamp_indirect;   // only clamps caustic-photon estimates (integrator_path_tracer.cc:160-165), which this path does not have
-	const IntegratorCfg &ic = inte->second->c;
-	yafgpu_render_params &rp = yi->rp;
+	const IntegratorCfg &ic = *sel.inte;
+	yafgpu_render_params &rp = su.rp;
 	std::memset(&rp, 0, sizeof rp);
 	rp.integrator = ic.type == "pathtracing" ? YAFGPU_INTEGRATOR_PATH : YAFGPU_INTEGRATOR_DIRECT;
 	rp.path_samples = ic.path_samples; rp.bounces = ic.bounces; rp.rr_min_bounces = ic.rr_min_bounces;
@@ -2166,41 +2185,29 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 	rp.aa_clamp_samples = clamp_samples;
 	rp.raydepth = ic.raydepth;
 	rp.transp_shad = ic.transp_shad ? 1 : 0; rp.shadow_depth = ic.shadow_depth;
-	if(bg) { rp.has_background = 1; for(int k = 0; k < 3; ++k) rp.background[k] = bg->color[k]; }
+	if(sel.bg) { rp.has_background = 1; for(int k = 0; k < 3; ++k) rp.background[k] = sel.bg->color[k]; }
 	rp.shard_index = yi->shard_index; rp.shard_count = yi->shard_count;
 	rp.serial_replay = yi->serial_replay ? 1 : 0;
-	{	// the first pass's rand() per tile, for callers that run single passes themselves (yafaray_renderPassDevice)
-		const int nt = ((width + tile_size - 1) / std::max(tile_size, 1)) * ((height + tile_size - 1) / std::max(tile_size, 1));
-		yi->tile_rand0.assign((size_t)std::max(nt, 0), 0);
-		if(yi->aa.rand_srand >= 0 && nt > 0)
-		{
-			std::vector<int32_t> v((size_t)yi->aa.rand_skip + (size_t)nt);
-			yafgpu_glibc_rand((uint32_t)yi->aa.rand_srand, (int32_t)v.size(), v.data());
-			std::copy(v.begin() + yi->aa.rand_skip, v.end(), yi->tile_rand0.begin());
-		}
-	}
-
-	// Scene::update: flatten visible non-base meshes in object-id order (scene.cc:797-817)
-	if(yi->state != 0) return fail(yi, "render: scene is not in the ready state (missing endGeometry?)");
-	int threads = -1; p.get("threads", threads);
-	if(yi->gpu && !yi->scene_dirty && std::memcmp(&yi->scene_cam, &cam->second->c.cam, sizeof yi->scene_cam) == 0 && yi->scene_threads == threads && yi->scene_background == bg_name)
-	{	// nothing the device scene is made of changed: keep it, tree and all (Scene::update rebuilds only on changes, scene.cc:784-790)
-		yafgpu_scene_set_exchange(yi->gpu, yi->exchange, yi->exchange_user);
-		yi->prepared = true;
-		return 1;
-	}
-	if(yi->gpu) { yafgpu_scene_destroy(yi->gpu); yi->gpu = nullptr; }
-	std::vector<float> verts; std::vector<int32_t> tri_mat; std::vector<float> vnormals; bool any_normals = false;
-	for(auto &kv : yi->meshes) if(kv.second.normals_exported || (kv.second.smooth && !kv.second.smooth_normals.empty())) any_normals = true;
-	// texture coordinates, only when some material evaluates shader nodes: per triangle corner UVs and orcos (yafgpu_scene_desc)
-	bool any_nodes = false;
-	for(auto *m : yi->material_order) if(!m->nodes.empty()) any_nodes = true;
-	std::vector<float> tri_uv, tri_orco;
-	const float kNoOrco = std::numeric_limits<float>::quiet_NaN();
-	// one mesh's rows: corner vertices, materials, vertex normals and texture coordinates per triangle corner
-	auto append_rows = [&](const Mesh &m, bool with_normals, std::vector<float> &verts, std::vector<int32_t> &tri_mat, std::vector<float> &vnormals,
-	                       std::vector<float> &tri_uv, std::vector<float> &tri_orco, std::vector<uint8_t> *index0)
+	// the first pass's rand() per tile, for callers that run single passes themselves (yafaray_renderPassDevice)
+	const int nt = ((width + tile_size - 1) / std::max(tile_size, 1)) * ((height + tile_size - 1) / std::max(tile_size, 1));
+	su.tile_rand0.assign((size_t)std::max(nt, 0), 0);
+	if(su.aa.rand_srand >= 0 && nt > 0)
 	{
+		std::vector<int32_t> v((size_t)su.aa.rand_skip + (size_t)nt);
+		yafgpu_glibc_rand((uint32_t)su.aa.rand_srand, (int32_t)v.size(), v.data());
+		std::copy(v.begin() + su.aa.rand_skip, v.end(), su.tile_rand0.begin());
+	}
+	return true;
+}
+
+// One set of rows: corner vertices, materials, vertex normals and texture coordinates per triangle corner.  The plain arrays are one,
+// the base pools of the instances another, which marks the corners whose normal has index 0 as well.
+struct RowPool
+{
+	std::vector<float> verts, vnormals, uv, orco; std::vector<int32_t> mat; std::vector<uint8_t> index0;
+	void append(const Mesh &m, bool with_normals, bool with_texcoords, bool mark_index0)
+	{
+		const float kNoOrco = std::numeric_limits<float>::quiet_NaN();
 		const size_t nt = m.tri_mat.size();
 		for(size_t t = 0; t < nt; ++t)
 		{
@@ -2225,33 +2232,49 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 					else { vnormals.push_back(0.f); vnormals.push_back(0.f); vnormals.push_back(0.f); }
 				}
 			}
-			if(with_normals && index0) index0->push_back(zero_marks);
-			tri_mat.push_back(m.tri_mat[t]);
-			if(any_nodes)
+			if(with_normals && mark_index0) index0.push_back(zero_marks);
+			mat.push_back(m.tri_mat[t]);
+			if(with_texcoords)
 			{
 				for(int c = 0; c < 3; ++c)
 				{
 					const size_t vi = (size_t)m.tri[3 * t + (size_t)c];
 					if(m.has_uv && m.tri_uv.size() >= 3 * (t + 1))
-					{ const size_t ui = (size_t)m.tri_uv[3 * t + (size_t)c]; tri_uv.push_back(m.uv[2 * ui]); tri_uv.push_back(m.uv[2 * ui + 1]); }
-					else { tri_uv.push_back(c == 0 ? kNoOrco : 0.f); tri_uv.push_back(0.f); }            // has_uv_ false (NaN marker): sp.u_ = sp.v_ = 0, implicit dPdU / dPdV, triangle.cc:103-111
+					{ const size_t ui = (size_t)m.tri_uv[3 * t + (size_t)c]; uv.push_back(m.uv[2 * ui]); uv.push_back(m.uv[2 * ui + 1]); }
+					else { uv.push_back(c == 0 ? kNoOrco : 0.f); uv.push_back(0.f); }            // has_uv_ false (NaN marker): sp.u_ = sp.v_ = 0, implicit dPdU / dPdV, triangle.cc:103-111
 					if(m.has_orco && m.orco.size() >= 3 * (vi + 1))
-					{ tri_orco.push_back(m.orco[3 * vi]); tri_orco.push_back(m.orco[3 * vi + 1]); tri_orco.push_back(m.orco[3 * vi + 2]); }
-					else { tri_orco.push_back(c == 0 ? kNoOrco : 0.f); tri_orco.push_back(0.f); tri_orco.push_back(0.f); }   // has_orco_ false: orco = the hit point
+					{ orco.push_back(m.orco[3 * vi]); orco.push_back(m.orco[3 * vi + 1]); orco.push_back(m.orco[3 * vi + 2]); }
+					else { orco.push_back(c == 0 ? kNoOrco : 0.f); orco.push_back(0.f); orco.push_back(0.f); }   // has_orco_ false: orco = the hit point
 				}
 			}
 		}
-	};
+	}
+};
+
+// Everything the scene descriptor points into
+struct FlatScene
+{
+	RowPool plain, base;                        // Scene::update's flattened meshes, and the base meshes of the instances
+	std::vector<yafgpu_segment> segments;       // the flattened scene in object-id order (yafgpu_instancing)
+	std::vector<float> curve_points;            // xyz and the two extrusion scales per point
+	std::vector<yafgpu_material> mats; std::vector<yafgpu_node> nodes;
+	std::vector<yafgpu_texture> textures; std::vector<float> texels;
+	std::vector<yafgpu_light> lights;
+	bool any_normals = false, base_normals = false, any_nodes = false, with_textures = false, instanced = false;
+};
+
+// Scene::update: flatten visible non-base meshes in object-id order (scene.cc:797-817)
+bool flatten_scene(yafaray_interface *yi, const Selection &sel, FlatScene &f)
+{
+	for(auto &kv : yi->meshes) if(kv.second.normals_exported || (kv.second.smooth && !kv.second.smooth_normals.empty())) f.any_normals = true;
+	// texture coordinates, only when some material evaluates shader nodes: per triangle corner UVs and orcos (yafgpu_scene_desc)
+	for(auto *m : yi->material_order) if(!m->nodes.empty()) f.any_nodes = true;
 	// instances (Scene::addInstance, scene.cc:1105-1130): the flattened scene becomes a list of segments in object-id order, plain meshes as
-	// rows of the arrays above, instances as rows of the base pools under their matrix; the device makes the triangles (yafgpu_instancing)
-	std::vector<yafgpu_segment> segments;
-	std::vector<float> base_verts, base_vnormals, base_uv, base_orco; std::vector<int32_t> base_mat; std::vector<uint8_t> base_index0;
+	// rows of the plain arrays, instances as rows of the base pools under their matrix; the device makes the triangles (yafgpu_instancing)
 	std::map<unsigned int, std::pair<int32_t, int32_t>> base_rows;      // base id -> its rows of the pools
-	bool base_normals = false;
-	for(auto &kv : yi->instances) if(kv.second.smooth || kv.second.normals_exported) base_normals = true;
+	for(auto &kv : yi->instances) if(kv.second.smooth || kv.second.normals_exported) f.base_normals = true;
 	// curves (Scene::endCurveMesh, scene.cc:154-281): a segment per strand over the pool of its points and their extrusion scales; the
 	// device extrudes them and fills the prisms
-	std::vector<float> curve_points;
 	auto mesh_it = yi->meshes.begin(); auto inst_it = yi->instances.begin(); auto curve_it = yi->curves.begin();
 	while(mesh_it != yi->meshes.end() || inst_it != yi->instances.end() || curve_it != yi->curves.end())
 	{
@@ -2263,23 +2286,23 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 		{
 			const Curve &c = (curve_it++)->second;
 			const size_t n = c.points.size() / 3;
-			yafgpu_segment sg{}; sg.kind = YAFGPU_SEGMENT_CURVE; sg.first = (int32_t)(curve_points.size() / 5); sg.count = (int32_t)n; sg.flags = (uint32_t)c.mat;
+			yafgpu_segment sg{}; sg.kind = YAFGPU_SEGMENT_CURVE; sg.first = (int32_t)(f.curve_points.size() / 5); sg.count = (int32_t)n; sg.flags = (uint32_t)c.mat;
 			for(size_t i = 0; i < n; ++i)
 			{
-				curve_points.insert(curve_points.end(), c.points.begin() + 3 * (ptrdiff_t)i, c.points.begin() + 3 * (ptrdiff_t)i + 3);
-				curve_points.push_back(c.scales[2 * i]); curve_points.push_back(c.scales[2 * i + 1]);
+				f.curve_points.insert(f.curve_points.end(), c.points.begin() + 3 * (ptrdiff_t)i, c.points.begin() + 3 * (ptrdiff_t)i + 3);
+				f.curve_points.push_back(c.scales[2 * i]); f.curve_points.push_back(c.scales[2 * i + 1]);
 			}
-			segments.push_back(sg);
+			f.segments.push_back(sg);
 			continue;
 		}
 		if(mesh_it != yi->meshes.end() && mesh_id <= inst_id)
 		{
 			const Mesh &m = (mesh_it++)->second;
 			if(!m.visible || m.base) continue;
-			yafgpu_segment sg{}; sg.kind = YAFGPU_SEGMENT_PLAIN; sg.first = (int32_t)tri_mat.size();
-			append_rows(m, any_normals, verts, tri_mat, vnormals, tri_uv, tri_orco, nullptr);
-			sg.count = (int32_t)tri_mat.size() - sg.first;
-			segments.push_back(sg);
+			yafgpu_segment sg{}; sg.kind = YAFGPU_SEGMENT_PLAIN; sg.first = (int32_t)f.plain.mat.size();
+			f.plain.append(m, f.any_normals, f.any_nodes, false);
+			sg.count = (int32_t)f.plain.mat.size() - sg.first;
+			f.segments.push_back(sg);
 			continue;
 		}
 		const Instance &in = (inst_it++)->second;      // visible_ is true whatever the base's visibility (object_geom.cc:112)
@@ -2288,59 +2311,88 @@ yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
 		auto rows = base_rows.find(in.base);
 		if(rows == base_rows.end())
 		{
-			const int32_t first = (int32_t)base_mat.size();
-			append_rows(base->second, base_normals, base_verts, base_mat, base_vnormals, base_uv, base_orco, &base_index0);
-			rows = base_rows.emplace(in.base, std::make_pair(first, (int32_t)base_mat.size() - first)).first;
+			const int32_t first = (int32_t)f.base.mat.size();
+			f.base.append(base->second, f.base_normals, f.any_nodes, true);
+			rows = base_rows.emplace(in.base, std::make_pair(first, (int32_t)f.base.mat.size() - first)).first;
 		}
 		yafgpu_segment sg{}; sg.kind = YAFGPU_SEGMENT_INSTANCE; sg.first = rows->second.first; sg.count = rows->second.second;
 		sg.flags = ((in.smooth || in.normals_exported) ? (uint32_t)YAFGPU_INSTANCE_SMOOTH : 0u) | (in.has_orco ? (uint32_t)YAFGPU_INSTANCE_ORCO : 0u) | (in.has_uv ? (uint32_t)YAFGPU_INSTANCE_UV : 0u);
 		std::memcpy(sg.m, in.m, sizeof sg.m);
-		segments.push_back(sg);
+		f.segments.push_back(sg);
 	}
+	f.instanced = !yi->instances.empty() || !yi->curves.empty();
 	if(yi->material_order.empty()) return fail(yi, "render: no materials defined");
-	std::vector<yafgpu_material> mats; std::vector<yafgpu_node> nodes;
-	flatten_materials(yi, mats, nodes);
-	std::vector<yafgpu_texture> textures; std::vector<float> texels;
-	const bool bg_texture = bg && bg->rec.kind == YAFGPU_BACKGROUND_TEXTURE;
-	if(any_nodes || bg_texture)
+	flatten_materials(yi, f.mats, f.nodes);
+	f.with_textures = f.any_nodes || (sel.bg && sel.bg->rec.kind == YAFGPU_BACKGROUND_TEXTURE);
+	if(f.with_textures)
 		for(auto *t : yi->texture_order)
 		{
-			if((texels.size() + t->texels.size()) / 4 > 0xffffffffull) return fail(yi, "render: more than 2^32 texels in the scene's image textures");
+			if((f.texels.size() + t->texels.size()) / 4 > 0xffffffffull) return fail(yi, "render: more than 2^32 texels in the scene's image textures");
 			yafgpu_texture rec = t->t;
-			rec.texel_first = (uint32_t)(texels.size() / 4);
-			texels.insert(texels.end(), t->texels.begin(), t->texels.end());
-			textures.push_back(rec);
+			rec.texel_first = (uint32_t)(f.texels.size() / 4);
+			f.texels.insert(f.texels.end(), t->texels.begin(), t->texels.end());
+			f.textures.push_back(rec);
 		}
-	std::vector<yafgpu_light> lights; for(auto *l : yi->light_order) lights.push_back(l->l);
+	for(auto *l : yi->light_order) f.lights.push_back(l->l);
+	return true;
+}
+
+yafgpu_scene_desc describe_scene(const FlatScene &f, const Selection &sel, int threads)
+{
 	yafgpu_scene_desc d{};
-	d.n_tris = (int32_t)tri_mat.size(); d.verts = verts.data(); d.tri_mat = tri_mat.data();
-	d.vnormals = any_normals ? vnormals.data() : nullptr;
-	d.n_materials = (int32_t)mats.size(); d.materials = mats.data();
-	d.n_lights = (int32_t)lights.size(); d.lights = lights.data();
-	if(any_nodes)
+	d.n_tris = (int32_t)f.plain.mat.size(); d.verts = f.plain.verts.data(); d.tri_mat = f.plain.mat.data();
+	d.vnormals = f.any_normals ? f.plain.vnormals.data() : nullptr;
+	d.n_materials = (int32_t)f.mats.size(); d.materials = f.mats.data();
+	d.n_lights = (int32_t)f.lights.size(); d.lights = f.lights.data();
+	if(f.any_nodes)
 	{
-		d.tri_uv = tri_uv.data(); d.tri_orco = tri_orco.data();
-		d.n_nodes = (int32_t)nodes.size(); d.nodes = nodes.data();
+		d.tri_uv = f.plain.uv.data(); d.tri_orco = f.plain.orco.data();
+		d.n_nodes = (int32_t)f.nodes.size(); d.nodes = f.nodes.data();
 	}
-	if(any_nodes || bg_texture)
+	if(f.with_textures)
 	{
-		d.n_textures = (int32_t)textures.size(); d.textures = textures.data();
-		d.n_texels = texels.size() / 4; d.texels = texels.data();
+		d.n_textures = (int32_t)f.textures.size(); d.textures = f.textures.data();
+		d.n_texels = f.texels.size() / 4; d.texels = f.texels.data();
 	}
-	if(!yi->instances.empty() || !yi->curves.empty())
+	if(f.instanced)
 	{
-		d.inst.n_curve_points = (int32_t)(curve_points.size() / 5); d.inst.curve_points = curve_points.data();
-		d.inst.n_segments = (int32_t)segments.size(); d.inst.segments = segments.data();
-		d.inst.n_base_tris = (int32_t)base_mat.size(); d.inst.base_verts = base_verts.data(); d.inst.base_mat = base_mat.data();
-		if(base_normals) { d.inst.base_vnormals = base_vnormals.data(); d.inst.base_vn_index0 = base_index0.data(); }
-		if(any_nodes) { d.inst.base_uv = base_uv.data(); d.inst.base_orco = base_orco.data(); }
+		d.inst.n_curve_points = (int32_t)(f.curve_points.size() / 5); d.inst.curve_points = f.curve_points.data();
+		d.inst.n_segments = (int32_t)f.segments.size(); d.inst.segments = f.segments.data();
+		d.inst.n_base_tris = (int32_t)f.base.mat.size(); d.inst.base_verts = f.base.verts.data(); d.inst.base_mat = f.base.mat.data();
+		if(f.base_normals) { d.inst.base_vnormals = f.base.vnormals.data(); d.inst.base_vn_index0 = f.base.index0.data(); }
+		if(f.any_nodes) { d.inst.base_uv = f.base.uv.data(); d.inst.base_orco = f.base.orco.data(); }
 	}
-	if(bg) d.background = bg->rec;
-	d.camera = cam->second->c.cam;
+	if(sel.bg) d.background = sel.bg->rec;
+	d.camera = sel.cam->cam;
 	d.build_threads = 0;
 	if(threads > 0) d.build_threads = threads;
+	return d;
+}
+
+} // namespace
+
+// A call that fails leaves the interface unprepared, whatever an earlier call prepared.
+yafaray_bool_t yafaray_prepareRender(yafaray_interface_t *yi)
+{
+	yi->prepared = false;
+	Selection sel; RenderSetup su;
+	if(!select_render(yi, sel) || !read_render_setup(yi, sel, su)) return 0;
+	yi->aa = su.aa; yi->rp = su.rp; yi->tile_rand0 = std::move(su.tile_rand0);
+	yi->color_space = su.color_space; yi->gamma = su.gamma; yi->color_space2 = su.color_space2; yi->gamma2 = su.gamma2;
+	if(yi->state != 0) return fail(yi, "render: scene is not in the ready state (missing endGeometry?)");
+	int threads = -1; yi->params.get("threads", threads);
+	if(yi->gpu && !yi->scene_dirty && std::memcmp(&yi->scene_cam, &sel.cam->cam, sizeof yi->scene_cam) == 0 && yi->scene_threads == threads && yi->scene_background == sel.bg_name)
+	{	// nothing the device scene is made of changed: keep it, tree and all (Scene::update rebuilds only on changes, scene.cc:784-790)
+		yafgpu_scene_set_exchange(yi->gpu, yi->exchange, yi->exchange_user);
+		yi->prepared = true;
+		return 1;
+	}
+	if(yi->gpu) { yafgpu_scene_destroy(yi->gpu); yi->gpu = nullptr; }
+	FlatScene flat;
+	if(!flatten_scene(yi, sel, flat)) return 0;
+	const yafgpu_scene_desc d = describe_scene(flat, sel, threads);
 	if(yafgpu_scene_create(&d, &yi->gpu)) return fail(yi, std::string("scene upload: ") + yafgpu_last_error());
-	yi->scene_dirty = false; yi->scene_cam = cam->second->c.cam; yi->scene_threads = threads; yi->scene_background = bg_name;
+	yi->scene_dirty = false; yi->scene_cam = sel.cam->cam; yi->scene_threads = threads; yi->scene_background = sel.bg_name;
 	yafgpu_scene_set_pass_pipelining(yi->gpu, yi->pass_pipelining);
 	yafgpu_scene_set_abort_flag(yi->gpu, &yi->abort_flag);
 	yafgpu_scene_set_exchange(yi->gpu, yi->exchange, yi->exchange_user);

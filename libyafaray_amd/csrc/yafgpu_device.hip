@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 #include <map>
+#include <memory>
 #include <mutex>
 
 #include "../../include/yafgpu.h"
@@ -918,8 +919,11 @@ struct WfSet
 
 struct yafgpu_scene
 {
+	yafgpu_scene() = default;
+	yafgpu_scene(const yafgpu_scene &) = delete; yafgpu_scene &operator=(const yafgpu_scene &) = delete;
+	~yafgpu_scene() { for(void *p : allocs) (void)hipFree(p); }      // the scene's device arrays first; then the members go, whatever their order
 	DevScene dev{};
-	std::vector<void *> allocs;
+	std::vector<void *> allocs;          // the scene's device arrays (upload, scene_alloc)
 	KdTree tree;
 	yafgpu_tree_info info{};
 	std::vector<yafgpu_material> mats;
@@ -1024,12 +1028,190 @@ static int check_instancing(const yafgpu_scene_desc *d)
 	return 0;
 }
 
-struct AssembledRows      // device arrays owned by the scene (yafgpu_scene::allocs)
+// A mask picks between, and a blend mixes, two records that are plain materials themselves (neither a mask nor a blend: no nesting); the
+// union of flags either carries (material_mask.cc:34) is no lobe of its own, so check_desc's lobe tests are its sub-materials' to pass.
+static int check_mask_or_blend(const yafgpu_scene_desc *d, int i)
+{
+	const yafgpu_material &m = d->materials[i];
+	const bool blend = m.type == YAFGPU_MAT_BLEND;
+	const std::string kind = blend ? "blend" : "mask", who = kind + " material " + std::to_string(i);
+	for(int k = 0; k < 2; ++k)
+	{
+		const int sub = m.c_index[k];
+		const int type = sub < 0 || sub >= d->n_materials ? YAFGPU_MAT_MASKED : d->materials[sub].type;
+		if(blend ? (type >= YAFGPU_MAT_MASKED || type < 0) : (type == YAFGPU_MAT_MASKED || type == YAFGPU_MAT_BLEND))
+			return fail(-3, who + ": a sub-material index outside the table, or a mask or a blend under a " + kind + " (nesting is not built)");
+	}
+	// a mask needs its node, of its own range; a blend takes its value from a node or from a constant
+	if(blend && (m.n_nodes < 0 || (m.n_nodes > 0 && (!d->nodes || m.sh_diffuse < 0 || m.sh_diffuse >= m.n_nodes)) || m.n_bump != 0))
+		return fail(-24, who + ": a blend with nodes needs the blend node among them, and has no bump shader");
+	if(!blend && (!d->nodes || m.n_nodes < 1 || m.sh_diffuse < 0 || m.sh_diffuse >= m.n_nodes || m.n_bump != 0))
+		return fail(-24, who + ": needs shader nodes and a mask node among them, and has no bump shader");
+	for(int k = 0; k < 2 && blend; ++k)
+		if(d->materials[m.c_index[k]].n_bump != 0)
+			return fail(-24, who + ": a sub-material with a bump shader (BlendMaterial::initBsdf would blend two bumped frames, surface.cc:137-151)");
+	// recursiveRaytrace's glossy branch picks its case from the mask's or blend's flags, the union (integrator_montecarlo.cc:895-919): next to a
+	// transmitting partner a glossy sub-material lands in the reflect + transmit case, whose two-direction sample MaskMaterial leaves at
+	// Material's empty default and BlendMaterial's (material_blend.cc:216-236) is not restated
+	const uint32_t both = d->materials[m.c_index[0]].bsdf_flags | d->materials[m.c_index[1]].bsdf_flags;
+	if((both & kGlossy) && (both & kReflect) && (both & kTransmit))
+		return fail(-4, who + ": a glossy sub-material beside a transmitting one (recursiveRaytrace reads the union of their flags, integrator_montecarlo.cc:895-919)");
+	return 0;
+}
+
+// every reference inside a node range is -1 or names a node BEFORE the one that reads it (evaluation order): the device indexes a per-lane
+// result stack with them (nodes_eval, mat_resolve, nodes_eval_derivative)
+static bool node_range_ok(const yafgpu_node *nodes, int first, int count)
+{
+	for(int k = 0; k < count; ++k)
+	{
+		const yafgpu_node &n = nodes[first + k];
+		auto ref_ok = [&](int r) { return r >= -1 && r < k; };
+		if(n.type == YAFGPU_NODE_MIX && !(ref_ok(n.input1) && ref_ok(n.input2) && ref_ok(n.factor))) return false;
+		if(n.type == YAFGPU_NODE_LAYER && !(n.input >= 0 && n.input < k && ref_ok(n.upper))) return false;
+		if(n.type < YAFGPU_NODE_TEXTURE_MAPPER || n.type > YAFGPU_NODE_LAYER) return false;
+	}
+	return true;
+}
+
+// Every refusal that depends on the descriptor alone, on the host, before a scene object or any device memory exists.  (One refusal is left
+// for later: a coordinate that an instance's matrix overflows, which only the device finds, assemble_scene.)
+static int check_desc(const yafgpu_scene_desc *d)
+{
+	if(!d) return fail(-1, "null argument");
+	if(d->n_tris < 0 || d->n_materials <= 0) return fail(-2, "scene needs at least one material");
+	// the light-estimate bookkeeping of a parked path packs the light index and the end of its light range in 8 bits each
+	// (pack_dlc, yafgpu_wavefront.h)
+	if(d->n_lights < 0 || d->n_lights > 255) return fail(-2, "more than 255 lights: the device path indexes lights with 8 bits");
+	{	// a NaN or infinite coordinate poisons the scene bound and with it every ray's clip against it: refuse it here
+		const size_t nf = (size_t)d->n_tris * 9;
+		for(size_t k = 0; k < nf; ++k)
+			if(!std::isfinite(d->verts[k])) return fail(-3, "non-finite vertex coordinate in triangle " + std::to_string(k / 9));
+	}
+	for(int i = 0; i < d->n_tris; ++i)
+		if(d->tri_mat[i] < 0 || d->tri_mat[i] >= d->n_materials) return fail(-3, "triangle material index out of range");
+	for(int i = 0; i < d->n_lights; ++i)
+		if(d->lights[i].type < YAFGPU_LIGHT_AREA || d->lights[i].type > YAFGPU_LIGHT_BACKGROUND) return fail(-2, "light " + std::to_string(i) + ": unknown type");
+	{	// the background and its light: one record, at most one light, and the light only with a background that asks for it
+		const yafgpu_background &b = d->background;
+		int n_bg_lights = 0;
+		for(int i = 0; i < d->n_lights; ++i) if(d->lights[i].type == YAFGPU_LIGHT_BACKGROUND) ++n_bg_lights;
+		if(b.kind < YAFGPU_BACKGROUND_NONE || b.kind > YAFGPU_BACKGROUND_TEXTURE) return fail(-2, "background: unknown kind");
+		if(n_bg_lights > 1) return fail(-2, "more than one background light");
+		if(n_bg_lights != ((b.kind != YAFGPU_BACKGROUND_NONE && b.has_ibl) ? 1 : 0)) return fail(-2, "a background light needs a background with has_ibl, and such a background its light");
+		if(b.kind == YAFGPU_BACKGROUND_TEXTURE)
+		{
+			if(!d->textures || b.texture < 0 || b.texture >= d->n_textures) return fail(-24, "the background's texture does not exist");
+			if(b.projection != 0 && b.projection != 1) return fail(-2, "background: unknown projection");
+		}
+		if(b.kind == YAFGPU_BACKGROUND_CONSTANT && b.has_ibl && !((b.color[0] + b.color[1] + b.color[2]) * 0.333333f > 0.f))
+			return fail(-2, "a constant background with a light needs a colour with energy (Pdf1D would divide by zero)");
+	}
+	for(int i = 0; i < d->n_materials; ++i)
+	{
+		// recursiveRaytrace (integrator_montecarlo.cc:782-1028): the perfect specular branch and both cases of the glossy branch (reflect
+		// only; reflect + transmit, which is rough glass and nothing else) are on the device path; the dispersive branch is not
+		const yafgpu_material &m = d->materials[i];
+		if(m.type < 0 || m.type > YAFGPU_MAT_BLEND) return fail(-3, "material " + std::to_string(i) + ": unknown type");
+		if(m.type == YAFGPU_MAT_BLEND || m.type == YAFGPU_MAT_MASKED)
+		{
+			const int rc = check_mask_or_blend(d, i);
+			if(rc) return rc;
+			continue;
+		}
+		if(m.bsdf_flags & kDispersive)
+			return fail(-4, "material with a dispersive lobe needs recursiveRaytrace's dispersive branch, which the GPU path does not implement");
+		if((m.bsdf_flags & kGlossy) && (m.bsdf_flags & kTransmit) && m.type != YAFGPU_MAT_ROUGH_GLASS)
+			return fail(-4, "a glossy transmission lobe on a material that is not rough glass: the reflect + transmit case of recursiveRaytrace's glossy branch takes RoughGlassMaterial's two-direction sample");
+		if(m.type == YAFGPU_MAT_ROUGH_GLASS && !(m.rg_a2 > 0.f))
+			return fail(-3, "rough glass material " + std::to_string(i) + ": rg_a2 (alpha squared) must be positive");
+	}
+	if(d->inst.n_segments > 0) { const int rc = check_instancing(d); if(rc) return rc; }
+	const bool with_nodes = d->n_nodes > 0 && d->nodes;
+	if(with_nodes || d->background.kind == YAFGPU_BACKGROUND_TEXTURE)      // image textures: what the shader nodes and a texture background look up
+		for(int i = 0; i < d->n_textures; ++i)
+		{
+			const yafgpu_texture &t = d->textures[i];
+			if(t.width <= 0 || t.height <= 0 || (uint64_t)t.texel_first + (uint64_t)t.width * (uint64_t)t.height > d->n_texels) return fail(-24, "a texture's texel range lies outside the texel array");
+		}
+	if(!with_nodes) return 0;
+	for(int i = 0; i < d->n_materials; ++i)
+	{
+		const yafgpu_material &m = d->materials[i];
+		if(m.n_nodes < 0 || m.n_nodes > kMaxNodes || m.node_first < 0 || m.node_first + m.n_nodes > d->n_nodes)
+			return fail(-24, "a material's shader nodes: more than " + std::to_string(kMaxNodes) + " nodes, or a range outside the node array");
+		if(m.n_bump < 0 || m.n_bump > kMaxNodes || (m.n_bump > 0 && (m.bump_first < 0 || m.bump_first + m.n_bump > d->n_nodes || m.sh_bump < 0 || m.sh_bump >= m.n_bump)))
+			return fail(-24, "a material's bump shader: more than " + std::to_string(kMaxNodes) + " nodes, or a range outside the node array");
+		const int slots[] = {m.sh_diffuse, m.sh_mirror_color, m.sh_mirror, m.sh_transparency, m.sh_translucency, m.sh_sigma_oren, m.sh_diffuse_refl, m.sh_ior,
+		                     m.sh_glossy, m.sh_glossy_reflect, m.sh_exponent, m.sh_filter_color};
+		for(int sl : slots)
+			if(m.n_nodes > 0 && (sl < -1 || sl >= m.n_nodes)) return fail(-24, "a material's shader slot names a node outside its node range");
+		if(!node_range_ok(d->nodes, m.node_first, m.n_nodes) || (m.n_bump > 0 && !node_range_ok(d->nodes, m.bump_first, m.n_bump)))
+			return fail(-24, "a shader node refers to a node that is not evaluated before it (or has an unknown type; a layer needs an input)");
+	}
+	for(int i = 0; i < d->n_nodes; ++i)
+		if(d->nodes[i].type == YAFGPU_NODE_TEXTURE_MAPPER && (d->nodes[i].texture < 0 || d->nodes[i].texture >= d->n_textures)) return fail(-24, "a texture_mapper node refers to a texture that does not exist");
+	return 0;
+}
+
+// What the scene's materials ask of the pipeline — recursion frames, the glossy loop's wider frames, extra depth, the transparent-shadow
+// kernel, the kernel variant — is taken from the materials some triangle actually USES: a definition nothing refers to can never be
+// hit, and must not cost frames, a kernel variant or (through the size of the replay's event tables) the exactness of the serial state.
+// A mask material in use stands for the two records it picks from: those count, the mask's own type and union of flags do not (it is
+// never a vertex's material).  A mask nothing refers to sizes nothing either, and neither do its records.
+static void classify_materials(yafgpu_scene *s, const yafgpu_scene_desc *d)
+{
+	std::vector<char> &used = s->mat_used;
+	used.assign((size_t)d->n_materials, 0);
+	if(d->inst.n_segments <= 0) for(int i = 0; i < d->n_tris; ++i) used[(size_t)d->tri_mat[i]] = 1;
+	for(int k = 0; k < d->inst.n_segments; ++k)
+	{	// the rows some segment makes a triangle of
+		const yafgpu_segment &sg = d->inst.segments[k];
+		if(sg.kind == YAFGPU_SEGMENT_CURVE) { used[(size_t)sg.flags] = 1; continue; }
+		const int32_t *mat = sg.kind == YAFGPU_SEGMENT_INSTANCE ? d->inst.base_mat : d->tri_mat;
+		for(int i = sg.first; i < sg.first + sg.count; ++i) used[(size_t)mat[i]] = 1;
+	}
+	for(int i = 0; i < d->n_materials; ++i)
+		if(used[(size_t)i] && (d->materials[i].type == YAFGPU_MAT_MASKED || d->materials[i].type == YAFGPU_MAT_BLEND)) used[(size_t)d->materials[i].c_index[0]] = used[(size_t)d->materials[i].c_index[1]] = 1;
+	for(int i = 0; i < d->n_materials; ++i)
+	{
+		if(!used[(size_t)i] || d->materials[i].type == YAFGPU_MAT_MASKED) continue;
+		const yafgpu_material &m = d->materials[i];
+		// A blend in use IS a vertex's material: the scene takes the shading kernel built with the blend's code (pick_shade_variant), and
+		// the blend's own words size what the integrators read off sp.material_ — the union of flags (recursion frames, the glossy loop:
+		// recursiveRaytrace enters on them), the larger additional depth, isTransparent(), the volume handler.  Its two records count
+		// with their own types and lobes (the anisotropic lobe, rough glass never: that pair is refused).
+		const bool blend = m.type == YAFGPU_MAT_BLEND;
+		if(m.bsdf_flags & kVolumetric) s->has_volumetric = true;
+		if(m.bsdf_flags & (kSpecular | kFilter)) s->has_specular = true;
+		if(m.bsdf_flags & kGlossy) s->has_glossy = true;
+		s->max_add_depth = std::max(s->max_add_depth, std::min(std::max(m.additional_depth, 0), 15));
+		if(blend) { s->has_blend = true; if(m.is_transparent) s->has_transparent = true; continue; }
+		s->mat_mask |= 1u << (uint32_t)m.type;
+		if(m.anisotropic) s->has_aniso = true;
+		if(m.type == YAFGPU_MAT_ROUGH_GLASS) s->has_glossy_two = true;
+		if((m.type == YAFGPU_MAT_SHINYDIFFUSE && m.is_transparent) || ((m.type == YAFGPU_MAT_GLASS || m.type == YAFGPU_MAT_ROUGH_GLASS) && m.fake_shadow)) s->has_transparent = true;
+	}
+	if(!(d->n_nodes > 0 && d->nodes)) return;
+	for(int i = 0; i < d->n_materials; ++i)
+	{	// shader nodes: the general shading kernel; a bump shader parks the shading frame too
+		const yafgpu_material &m = d->materials[i];
+		if(m.n_nodes > 0 && ((m.type != YAFGPU_MAT_MASKED && m.type != YAFGPU_MAT_BLEND) || used[(size_t)i])) s->has_textures = true;      // (a mask or a blend nothing refers to picks no kernel)
+		if(m.n_bump > 0) { s->has_textures = true; s->has_bump = true; }
+	}
+}
+
+// The flattened scene's rows, made by host_rows (plain arrays) or assemble_scene (instanced geometry and curves): device arrays owned by the
+// scene (yafgpu_scene::allocs), and the corner vertices on the host for the tree builders
+struct AssembledRows
 {
 	uint32_t n = 0;
 	const float4 *rec = nullptr, *ng = nullptr, *vn = nullptr;
 	const float *uv = nullptr, *orco = nullptr, *e3 = nullptr;
 	const yafgpu_material *mats = nullptr;
+	const float *verts = nullptr;      // 9 per row: the descriptor's own, or `made`
+	std::vector<float> made;           // what came back from the device (assemble_scene)
+	std::vector<float4> h_rec, h_ng, h_vn;      // what host_rows made: on the device after upload_rows, behind the tree
 };
 
 template<typename T> static int scene_alloc(yafgpu_scene *s, size_t n, T **dst)
@@ -1050,10 +1232,11 @@ template<typename T> static int temp_upload(DevMem<T> &m, const T *src, size_t n
 	return 0;
 }
 
-// h_verts: the flattened scene's corner vertices, the only output that comes back (the tree builders and the non-finite check read them)
-static int assemble_scene(yafgpu_scene *s, const yafgpu_scene_desc *d, AssembledRows &out, std::vector<float> &h_verts)
+// out.made: the flattened scene's corner vertices, the only output that comes back (the tree builders and the non-finite check read them)
+static int assemble_scene(yafgpu_scene *s, const yafgpu_scene_desc *d, AssembledRows &out)
 {
 	const yafgpu_instancing &in = d->inst;
+	std::vector<float> &h_verts = out.made;
 	std::vector<yafgpu_segment> segs; std::vector<uint32_t> first;
 	bool smooth_segment = d->vnormals != nullptr;
 	for(int k = 0; k < in.n_segments; ++k)
@@ -1099,221 +1282,19 @@ static int assemble_scene(yafgpu_scene *s, const yafgpu_scene_desc *d, Assembled
 	// a matrix that overflows a coordinate is refused as a bad vertex is
 	for(size_t k = 0; k < h_verts.size(); ++k)
 		if(!std::isfinite(h_verts[k])) return fail(-3, "non-finite vertex coordinate in triangle " + std::to_string(k / 9));
-	out.rec = rec; out.ng = ng; out.vn = vn; out.uv = uv; out.orco = orco; out.e3 = e3;
+	out.rec = rec; out.ng = ng; out.vn = vn; out.uv = uv; out.orco = orco; out.e3 = e3; out.verts = h_verts.data();
 	return 0;
 }
 
-// Faure permutations (the reference ships them as a table, src/common/faure_tables.cc; they are
-// the standard construction of Faure 1992 and are regenerated here rather than copied)
-static void faure_perm(int b, std::vector<int> &out)
+// The same rows from the plain arrays, on the host.  Triangle records: Triangle::updateIntersectionCachedValues (triangle.h:197-207),
+// recNormal (:295-302); yafgpu_assemble.hip makes them by these expressions.
+static void host_rows(const yafgpu_scene_desc *d, AssembledRows &out)
 {
-	if(b == 2) { out = {0, 1}; return; }
-	if(b % 2 == 0)
-	{
-		std::vector<int> half; faure_perm(b / 2, half);
-		out.resize((size_t)b);
-		for(int i = 0; i < b / 2; ++i) { out[(size_t)i] = 2 * half[(size_t)i]; out[(size_t)(b / 2 + i)] = 2 * half[(size_t)i] + 1; }
-	}
-	else
-	{
-		std::vector<int> prev; faure_perm(b - 1, prev);
-		const int m = (b - 1) / 2;
-		for(int &v : prev) if(v >= m) ++v;
-		out.assign(prev.begin(), prev.begin() + m);
-		out.push_back(m);
-		out.insert(out.end(), prev.begin() + m, prev.end());
-	}
-}
-
-static const int kPrimsHost[50] = {1, 2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, 41, 43, 47, 53, 59, 61, 67,
-                                   71, 73, 79, 83, 89, 97, 101, 103, 107, 109, 113, 127, 131, 137, 139, 149, 151, 157, 163, 167,
-                                   173, 179, 181, 191, 193, 197, 199, 211, 223, 227};
-
-extern "C" {
-
-const char *yafgpu_last_error(void) { return g_err.c_str(); }
-extern "C" void yafgpu_internal_set_error(const char *msg) { g_err = msg ? msg : ""; }
-
-int yafgpu_device_count(void)
-{
-	int n = 0;
-	if(hipGetDeviceCount(&n) != hipSuccess) return 0;
-	return n;
-}
-int yafgpu_set_device(int device) { HIP_OK(hipSetDevice(device)); return 0; }
-
-uint64_t yafgpu_planes_bytes(int32_t width, int32_t height)
-{
-	return (uint64_t)YAFGPU_FILM_PLANES * (uint64_t)width * (uint64_t)height * YAFGPU_FILM_CHANNELS * sizeof(float);
-}
-
-int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
-{
-	if(!d || !out) return fail(-1, "null argument");
-	if(d->n_tris < 0 || d->n_materials <= 0) return fail(-2, "scene needs at least one material");
-	// the light-estimate bookkeeping of a parked path packs the light index and the end of its light range in 8 bits each
-	// (pack_dlc, yafgpu_wavefront.h)
-	if(d->n_lights < 0 || d->n_lights > 255) return fail(-2, "more than 255 lights: the device path indexes lights with 8 bits");
-	{	// a NaN or infinite coordinate poisons the scene bound and with it every ray's clip against it: refuse it here
-		const size_t nf = (size_t)d->n_tris * 9;
-		for(size_t k = 0; k < nf; ++k)
-			if(!std::isfinite(d->verts[k])) return fail(-3, "non-finite vertex coordinate in triangle " + std::to_string(k / 9));
-	}
-	for(int i = 0; i < d->n_tris; ++i)
-		if(d->tri_mat[i] < 0 || d->tri_mat[i] >= d->n_materials) return fail(-3, "triangle material index out of range");
-	for(int i = 0; i < d->n_lights; ++i)
-		if(d->lights[i].type < YAFGPU_LIGHT_AREA || d->lights[i].type > YAFGPU_LIGHT_BACKGROUND) return fail(-2, "light " + std::to_string(i) + ": unknown type");
-	{	// the background and its light: one record, at most one light, and the light only with a background that asks for it
-		const yafgpu_background &b = d->background;
-		int n_bg_lights = 0;
-		for(int i = 0; i < d->n_lights; ++i) if(d->lights[i].type == YAFGPU_LIGHT_BACKGROUND) ++n_bg_lights;
-		if(b.kind < YAFGPU_BACKGROUND_NONE || b.kind > YAFGPU_BACKGROUND_TEXTURE) return fail(-2, "background: unknown kind");
-		if(n_bg_lights > 1) return fail(-2, "more than one background light");
-		if(n_bg_lights != ((b.kind != YAFGPU_BACKGROUND_NONE && b.has_ibl) ? 1 : 0)) return fail(-2, "a background light needs a background with has_ibl, and such a background its light");
-		if(b.kind == YAFGPU_BACKGROUND_TEXTURE)
-		{
-			if(!d->textures || b.texture < 0 || b.texture >= d->n_textures) return fail(-24, "the background's texture does not exist");
-			if(b.projection != 0 && b.projection != 1) return fail(-2, "background: unknown projection");
-		}
-		if(b.kind == YAFGPU_BACKGROUND_CONSTANT && b.has_ibl && !((b.color[0] + b.color[1] + b.color[2]) * 0.333333f > 0.f))
-			return fail(-2, "a constant background with a light needs a colour with energy (Pdf1D would divide by zero)");
-	}
-	for(int i = 0; i < d->n_materials; ++i)
-	{
-		// recursiveRaytrace (integrator_montecarlo.cc:782-1028): the perfect specular branch and both cases of the glossy branch (reflect
-		// only; reflect + transmit, which is rough glass and nothing else) are on the device path; the dispersive branch is not
-		if(d->materials[i].type < 0 || d->materials[i].type > YAFGPU_MAT_BLEND) return fail(-3, "material " + std::to_string(i) + ": unknown type");
-		if(d->materials[i].type == YAFGPU_MAT_BLEND)
-		{	// a blend runs every material function on two records that are plain materials (neither a mask nor a blend), with or without a
-			// node of its own range for the blend value; like a mask's, its union of flags is no lobe of its own
-			const yafgpu_material &m = d->materials[i];
-			for(int k = 0; k < 2; ++k)
-				if(m.c_index[k] < 0 || m.c_index[k] >= d->n_materials || d->materials[m.c_index[k]].type >= YAFGPU_MAT_MASKED || d->materials[m.c_index[k]].type < 0)
-					return fail(-3, "blend material " + std::to_string(i) + ": a sub-material index outside the table, or a mask or a blend under a blend (nesting is not built)");
-			if(m.n_nodes < 0 || (m.n_nodes > 0 && (!d->nodes || m.sh_diffuse < 0 || m.sh_diffuse >= m.n_nodes)) || m.n_bump != 0)
-				return fail(-24, "blend material " + std::to_string(i) + ": a blend with nodes needs the blend node among them, and has no bump shader");
-			for(int k = 0; k < 2; ++k)
-				if(d->materials[m.c_index[k]].n_bump != 0)
-					return fail(-24, "blend material " + std::to_string(i) + ": a sub-material with a bump shader (BlendMaterial::initBsdf would blend two bumped frames, surface.cc:137-151)");
-			// the same case of recursiveRaytrace's glossy branch as under a mask: BlendMaterial's two-direction sample (material_blend.cc:216-236) is not restated
-			const uint32_t both = d->materials[m.c_index[0]].bsdf_flags | d->materials[m.c_index[1]].bsdf_flags;
-			if((both & kGlossy) && (both & kReflect) && (both & kTransmit))
-				return fail(-4, "blend material " + std::to_string(i) + ": a glossy sub-material beside a transmitting one (recursiveRaytrace reads the union of their flags, integrator_montecarlo.cc:895-919)");
-			continue;
-		}
-		if(d->materials[i].type == YAFGPU_MAT_MASKED)
-		{	// a mask picks between two records that are materials themselves (no nesting), through a node of its own range; the union of flags it
-			// carries (material_mask.cc:34) is no lobe of its own, so the two tests below are its sub-materials' to pass
-			const yafgpu_material &m = d->materials[i];
-			for(int k = 0; k < 2; ++k)
-				if(m.c_index[k] < 0 || m.c_index[k] >= d->n_materials || d->materials[m.c_index[k]].type == YAFGPU_MAT_MASKED || d->materials[m.c_index[k]].type == YAFGPU_MAT_BLEND)
-					return fail(-3, "mask material " + std::to_string(i) + ": a sub-material index outside the table, or a mask or a blend under a mask (nesting is not built)");
-			if(!d->nodes || m.n_nodes < 1 || m.sh_diffuse < 0 || m.sh_diffuse >= m.n_nodes || m.n_bump != 0)
-				return fail(-24, "mask material " + std::to_string(i) + ": needs shader nodes and a mask node among them, and has no bump shader");
-			// recursiveRaytrace's glossy branch picks its case from the MASK's flags, the union (integrator_montecarlo.cc:895-919): next to a
-			// transmitting partner a glossy sub-material lands in the reflect + transmit case, whose two-direction sample MaskMaterial leaves
-			// at Material's empty default
-			const uint32_t both = d->materials[m.c_index[0]].bsdf_flags | d->materials[m.c_index[1]].bsdf_flags;
-			if((both & kGlossy) && (both & kReflect) && (both & kTransmit))
-				return fail(-4, "mask material " + std::to_string(i) + ": a glossy sub-material beside a transmitting one (recursiveRaytrace reads the union of their flags, integrator_montecarlo.cc:895-919)");
-			continue;
-		}
-		if(d->materials[i].bsdf_flags & kDispersive)
-			return fail(-4, "material with a dispersive lobe needs recursiveRaytrace's dispersive branch, which the GPU path does not implement");
-		if((d->materials[i].bsdf_flags & kGlossy) && (d->materials[i].bsdf_flags & kTransmit) && d->materials[i].type != YAFGPU_MAT_ROUGH_GLASS)
-			return fail(-4, "a glossy transmission lobe on a material that is not rough glass: the reflect + transmit case of recursiveRaytrace's glossy branch takes RoughGlassMaterial's two-direction sample");
-		if(d->materials[i].type == YAFGPU_MAT_ROUGH_GLASS && !(d->materials[i].rg_a2 > 0.f))
-			return fail(-3, "rough glass material " + std::to_string(i) + ": rg_a2 (alpha squared) must be positive");
-	}
-	const bool instanced = d->inst.n_segments > 0;
-	if(instanced) { const int irc = check_instancing(d); if(irc) return irc; }
-	auto *s = new yafgpu_scene();
-	{	// What the scene's materials ask of the pipeline — recursion frames, the glossy loop's wider frames, extra depth, the transparent-shadow
-		// kernel, the kernel variant — is taken from the materials some triangle actually USES: a definition nothing refers to can never be
-		// hit, and must not cost frames, a kernel variant or (through the size of the replay's event tables) the exactness of the serial state
-		// A mask material in use stands for the two records it picks from: those count, the mask's own type and union of flags do not (it is
-		// never a vertex's material).  A mask nothing refers to sizes nothing either, and neither do its records.
-		std::vector<char> &used = s->mat_used;
-		used.assign((size_t)d->n_materials, 0);
-		if(!instanced) for(int i = 0; i < d->n_tris; ++i) used[(size_t)d->tri_mat[i]] = 1;
-		else
-			for(int k = 0; k < d->inst.n_segments; ++k)
-			{	// the rows some segment makes a triangle of
-				const yafgpu_segment &sg = d->inst.segments[k];
-				if(sg.kind == YAFGPU_SEGMENT_CURVE) { used[(size_t)sg.flags] = 1; continue; }
-				const int32_t *mat = sg.kind == YAFGPU_SEGMENT_INSTANCE ? d->inst.base_mat : d->tri_mat;
-				for(int i = sg.first; i < sg.first + sg.count; ++i) used[(size_t)mat[i]] = 1;
-			}
-		for(int i = 0; i < d->n_materials; ++i)
-			if(used[(size_t)i] && (d->materials[i].type == YAFGPU_MAT_MASKED || d->materials[i].type == YAFGPU_MAT_BLEND)) used[(size_t)d->materials[i].c_index[0]] = used[(size_t)d->materials[i].c_index[1]] = 1;
-		for(int i = 0; i < d->n_materials; ++i)
-		{
-			if(!used[(size_t)i] || d->materials[i].type == YAFGPU_MAT_MASKED) continue;
-			const yafgpu_material &m = d->materials[i];
-			if(m.type == YAFGPU_MAT_BLEND)
-			{	// A blend in use IS a vertex's material: the scene takes the shading kernel built with the blend's code (pick_shade_variant), and
-				// the blend's own words size what the integrators read off sp.material_ — the union of flags (recursion frames, the glossy loop:
-				// recursiveRaytrace enters on them), the larger additional depth, isTransparent(), the volume handler.  Its two records count
-				// below with their own types and lobes (the anisotropic lobe, rough glass never: that pair is refused).
-				s->has_blend = true;
-				if(m.bsdf_flags & kVolumetric) s->has_volumetric = true;
-				if(m.bsdf_flags & (kSpecular | kFilter)) s->has_specular = true;
-				if(m.bsdf_flags & kGlossy) s->has_glossy = true;
-				s->max_add_depth = std::max(s->max_add_depth, std::min(std::max(m.additional_depth, 0), 15));
-				if(m.is_transparent) s->has_transparent = true;
-				continue;
-			}
-			s->mat_mask |= 1u << (uint32_t)m.type;
-			if(m.bsdf_flags & kVolumetric) s->has_volumetric = true;
-			if(m.bsdf_flags & (kSpecular | kFilter)) s->has_specular = true;
-			if(m.anisotropic) s->has_aniso = true;
-			s->max_add_depth = std::max(s->max_add_depth, std::min(std::max(m.additional_depth, 0), 15));
-			if(m.bsdf_flags & kGlossy) s->has_glossy = true;
-			if(m.type == YAFGPU_MAT_ROUGH_GLASS) s->has_glossy_two = true;
-			if((m.type == YAFGPU_MAT_SHINYDIFFUSE && m.is_transparent) || ((m.type == YAFGPU_MAT_GLASS || m.type == YAFGPU_MAT_ROUGH_GLASS) && m.fake_shadow)) s->has_transparent = true;
-		}
-	}
-	// instanced geometry: every row of the scene is made on the device, and the vertices come back for the tree builders
-	AssembledRows rows; std::vector<float> rows_verts;
-	double assemble_seconds = 0.0;
-	if(instanced)
-	{
-		const auto ta = std::chrono::steady_clock::now();
-		const int arc = assemble_scene(s, d, rows, rows_verts);
-		if(arc) { yafgpu_scene_destroy(s); return arc; }
-		assemble_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
-	}
-	const float *verts = instanced ? rows_verts.data() : d->verts;
-	const int n_tris = instanced ? (int)rows.n : d->n_tris;
-	const auto t0 = std::chrono::steady_clock::now();
-	{
-		// 0: by size -- the device builder wins from a few ten thousand triangles on (1 M: 0.07 s against 0.33 s)
-		bool on_device = d->build_on_device > 0 || (d->build_on_device == 0 && n_tris >= 65536);
-		if(const char *e = std::getenv("YAFGPU_BUILD")) on_device = std::strcmp(e, "device") == 0;
-		if(on_device)
-		{
-			std::string err;
-			// heavily overlapping geometry can outgrow the builder's arrays: more room, and past that the host builder
-			// (same format, same cost model) rather than no tree
-			const int brc = build_kdtree_device_retry(verts, n_tris, kDepthCap, s->tree, &err);
-			if(brc == -2 || brc == -3) build_kdtree(verts, n_tris, kDepthCap, d->build_threads, s->tree);     // arrays outgrown / no device memory for them
-			else if(brc) { yafgpu_scene_destroy(s); return fail(-20, err); }
-		}
-		else build_kdtree(verts, n_tris, kDepthCap, d->build_threads, s->tree);
-	}
-	s->info.build_seconds = s->tree.build_seconds;
-	s->info.n_nodes = (uint32_t)s->tree.nodes.size();
-	s->info.n_leaf_refs = (uint32_t)s->tree.refs.size();
-	s->info.max_depth = (uint32_t)s->tree.max_depth;
-	s->info.n_tris = (uint32_t)n_tris;
-	const auto t1 = std::chrono::steady_clock::now();
-
-	// triangle records: Triangle::updateIntersectionCachedValues (triangle.h:197-207), recNormal (:295-302)
-	// (with instanced geometry yafgpu_assemble.hip has made them, by these expressions)
-	const size_t nt = (size_t)n_tris;
-	std::vector<float4> rec(instanced ? 0 : 3 * nt), ng(instanced ? 0 : nt), vn;
+	const size_t nt = (size_t)d->n_tris;
+	std::vector<float4> &rec = out.h_rec, &ng = out.h_ng, &vn = out.h_vn;
+	rec.resize(3 * nt); ng.resize(nt);
 	bool any_smooth = false;
-	for(size_t i = 0; i < nt && !instanced; ++i)
+	for(size_t i = 0; i < nt; ++i)
 	{
 		const float *v = d->verts + 9 * i;
 		const float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]}, e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
@@ -1353,7 +1334,143 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 			}
 		}
 	}
-	// QMC tables
+	out.n = (uint32_t)nt; out.verts = d->verts;
+}
+
+// What host_rows made goes to the device once the tree is built (the device builder has the memory to itself, and a process's first HIP
+// call is the builder's); rows that assemble_scene made are there already.
+static int upload_rows(yafgpu_scene *s, const yafgpu_scene_desc *d, AssembledRows &out)
+{
+	if(out.rec) return 0;
+	const size_t nt = out.n;
+	int rc = 0;
+	if((rc = upload(s, out.h_rec.data(), out.h_rec.size(), &out.rec)) || (rc = upload(s, out.h_ng.data(), out.h_ng.size(), &out.ng))) return rc;
+	if(!out.h_vn.empty() && (rc = upload(s, out.h_vn.data(), out.h_vn.size(), &out.vn))) return rc;
+	if((rc = upload(s, d->materials, (size_t)d->n_materials, &out.mats))) return rc;
+	if(!(d->n_nodes > 0 && d->nodes)) return 0;
+	// the per-triangle texture coordinates the shader nodes read
+	if(d->tri_uv && (rc = upload(s, d->tri_uv, nt * 6, &out.uv))) return rc;
+	if(d->tri_orco && (rc = upload(s, d->tri_orco, nt * 9, &out.orco))) return rc;
+	if(s->has_bump)
+	{	// the third edge of Triangle::getSurface's dPdU / dPdV (triangle.cc:80-111): c - b, rounded once like e1 and e2 of the record
+		std::vector<float> e3(nt * 3);
+		for(size_t i = 0; i < nt; ++i) for(int k = 0; k < 3; ++k) e3[3 * i + k] = d->verts[9 * i + 6 + k] - d->verts[9 * i + 3 + k];
+		if((rc = upload(s, e3.data(), e3.size(), &out.e3))) return rc;
+	}
+	return 0;
+}
+
+// Faure permutations (the reference ships them as a table, src/common/faure_tables.cc; they are
+// the standard construction of Faure 1992 and are regenerated here rather than copied)
+static void faure_perm(int b, std::vector<int> &out)
+{
+	if(b == 2) { out = {0, 1}; return; }
+	if(b % 2 == 0)
+	{
+		std::vector<int> half; faure_perm(b / 2, half);
+		out.resize((size_t)b);
+		for(int i = 0; i < b / 2; ++i) { out[(size_t)i] = 2 * half[(size_t)i]; out[(size_t)(b / 2 + i)] = 2 * half[(size_t)i] + 1; }
+	}
+	else
+	{
+		std::vector<int> prev; faure_perm(b - 1, prev);
+		const int m = (b - 1) / 2;
+		for(int &v : prev) if(v >= m) ++v;
+		out.assign(prev.begin(), prev.begin() + m);
+		out.push_back(m);
+		out.insert(out.end(), prev.begin() + m, prev.end());
+	}
+}
+
+static const int kPrimsHost[50] = {1, 2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, 41, 43, 47, 53, 59, 61, 67,
+                                   71, 73, 79, 83, 89, 97, 101, 103, 107, 109, 113, 127, 131, 137, 139, 149, 151, 157, 163, 167,
+                                   173, 179, 181, 191, 193, 197, 199, 211, 223, 227};
+
+// ---- the steps of yafgpu_scene_create, in its order ---------------------------------------------------------------------------
+static int build_tree(yafgpu_scene *s, const yafgpu_scene_desc *d, const AssembledRows &rows)
+{
+	const int n_tris = (int)rows.n;
+	// 0: by size -- the device builder wins from a few ten thousand triangles on (1 M: 0.07 s against 0.33 s)
+	bool on_device = d->build_on_device > 0 || (d->build_on_device == 0 && n_tris >= 65536);
+	if(const char *e = std::getenv("YAFGPU_BUILD")) on_device = std::strcmp(e, "device") == 0;
+	if(on_device)
+	{
+		std::string err;
+		// heavily overlapping geometry can outgrow the builder's arrays: more room, and past that the host builder
+		// (same format, same cost model) rather than no tree
+		const int brc = build_kdtree_device_retry(rows.verts, n_tris, kDepthCap, s->tree, &err);
+		if(brc == -2 || brc == -3) build_kdtree(rows.verts, n_tris, kDepthCap, d->build_threads, s->tree);     // arrays outgrown / no device memory for them
+		else if(brc) return fail(-20, err);
+	}
+	else build_kdtree(rows.verts, n_tris, kDepthCap, d->build_threads, s->tree);
+	s->info.build_seconds = s->tree.build_seconds;
+	s->info.n_nodes = (uint32_t)s->tree.nodes.size();
+	s->info.n_leaf_refs = (uint32_t)s->tree.refs.size();
+	s->info.max_depth = (uint32_t)s->tree.max_depth;
+	s->info.n_tris = (uint32_t)n_tris;
+	return 0;
+}
+
+static int upload_tree(yafgpu_scene *s)
+{
+	DevScene &dv = s->dev;
+	int rc = 0;
+	if((rc = upload(s, (const uint2 *)s->tree.nodes.data(), s->tree.nodes.size(), &dv.nodes))) return rc;
+	// the treelet layout for wf_trace; YAFGPU_TREELET_INLINE=0 sends every non-empty leaf through the escape array (a test aid)
+	const char *e = std::getenv("YAFGPU_TREELET_INLINE");
+	TreeletLayout tl;
+	if(build_treelets(s->tree.nodes, !(e && std::atoi(e) == 0), tl)) return fail(-2, "kd-tree too large for the treelet layout");
+	dv.tl_root = tl.root;
+	if((rc = upload(s, (const uint4 *)tl.words.data(), tl.words.size() / 4, &dv.treelets))) return rc;
+	if((rc = upload(s, (const uint2 *)tl.leaves.data(), tl.leaves.size() / 2, &dv.tl_leaves))) return rc;
+	if((rc = upload(s, s->tree.refs.data(), s->tree.refs.size(), &dv.refs))) return rc;
+	dv.n_nodes = (uint32_t)s->tree.nodes.size();
+	for(int k = 0; k < 3; ++k) { dv.blo[k] = s->tree.bound_lo[k]; dv.bhi[k] = s->tree.bound_hi[k]; }
+	return 0;
+}
+
+static int upload_lights(yafgpu_scene *s, const yafgpu_scene_desc *d)
+{
+	const int rc = upload(s, d->lights, (size_t)d->n_lights, &s->dev.lights);
+	if(rc) return rc;
+	s->dev.n_lights = s->n_lights = d->n_lights;
+	s->h_lights.assign(d->lights, d->lights + d->n_lights);
+	for(const yafgpu_light &l : s->h_lights) s->light_mask |= 1u << (uint32_t)l.type;
+	// a texture background is evaluated per escaping ray by the code that comes with the background light: such a scene asks for a
+	// kernel built with that light's bit whether or not the light is there
+	if(d->background.kind == YAFGPU_BACKGROUND_TEXTURE) s->light_mask |= 1u << (uint32_t)YAFGPU_LIGHT_BACKGROUND;
+	return 0;
+}
+
+// image textures: what the shader nodes and a texture background look up
+static int upload_textures(yafgpu_scene *s, const yafgpu_scene_desc *d)
+{
+	DevScene &dv = s->dev;
+	std::memset(&dv.tex, 0, sizeof dv.tex);
+	if(!((d->n_nodes > 0 && d->nodes) || d->background.kind == YAFGPU_BACKGROUND_TEXTURE)) return 0;
+	int rc = 0;
+	const float4 *texels = nullptr;
+	if((rc = upload(s, d->textures, (size_t)std::max(d->n_textures, 0), &dv.tex.textures))) return rc;
+	if((rc = upload(s, (const float4 *)d->texels, (size_t)d->n_texels, &texels))) return rc;
+	dv.tex.texels = texels; dv.tex.n_textures = d->n_textures;
+	return 0;
+}
+
+// shader nodes and the per-triangle texture coordinates they read
+static int upload_nodes(yafgpu_scene *s, const yafgpu_scene_desc *d, const AssembledRows &rows)
+{
+	DevScene &dv = s->dev;
+	if(!(d->n_nodes > 0 && d->nodes)) return 0;
+	const int rc = upload(s, d->nodes, (size_t)d->n_nodes, &dv.tex.nodes);
+	if(rc) return rc;
+	dv.tex.tri_uv = rows.uv; dv.tex.tri_orco = rows.orco;
+	if(s->has_bump) { dv.tex.tri_e3 = rows.e3; dv.tex.has_bump = 1; }
+	return 0;
+}
+
+static int upload_qmc_tables(yafgpu_scene *s)
+{
+	DevScene &dv = s->dev;
 	std::vector<int> faure; std::vector<int> foff(50); std::vector<double> invp(50);
 	for(int dim = 0; dim < 50; ++dim)
 	{
@@ -1367,149 +1484,103 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 		invp[(size_t)dim] = std::strtod(buf, nullptr);
 	}
 	int rc = 0;
-	DevScene &dv = s->dev;
-	if((rc = upload(s, (const uint2 *)s->tree.nodes.data(), s->tree.nodes.size(), &dv.nodes))) { yafgpu_scene_destroy(s); return rc; }
-	{	// the treelet layout for wf_trace; YAFGPU_TREELET_INLINE=0 sends every non-empty leaf through the escape array (a test aid)
-		const char *e = std::getenv("YAFGPU_TREELET_INLINE");
-		TreeletLayout tl;
-		if(build_treelets(s->tree.nodes, !(e && std::atoi(e) == 0), tl)) { yafgpu_scene_destroy(s); return fail(-2, "kd-tree too large for the treelet layout"); }
-		dv.tl_root = tl.root;
-		if((rc = upload(s, (const uint4 *)tl.words.data(), tl.words.size() / 4, &dv.treelets))) { yafgpu_scene_destroy(s); return rc; }
-		if((rc = upload(s, (const uint2 *)tl.leaves.data(), tl.leaves.size() / 2, &dv.tl_leaves))) { yafgpu_scene_destroy(s); return rc; }
-	}
-	if((rc = upload(s, s->tree.refs.data(), s->tree.refs.size(), &dv.refs))) { yafgpu_scene_destroy(s); return rc; }
-	if(instanced) { dv.tri = rows.rec; dv.tri_ng = rows.ng; dv.tri_vn = rows.vn; dv.mats = rows.mats; }      // already where the kernels read them
-	else
-	{
-		if((rc = upload(s, rec.data(), rec.size(), &dv.tri))) { yafgpu_scene_destroy(s); return rc; }
-		if((rc = upload(s, ng.data(), ng.size(), &dv.tri_ng))) { yafgpu_scene_destroy(s); return rc; }
-		dv.tri_vn = nullptr;
-		if(any_smooth && (rc = upload(s, vn.data(), vn.size(), &dv.tri_vn))) { yafgpu_scene_destroy(s); return rc; }
-		if((rc = upload(s, d->materials, (size_t)d->n_materials, &dv.mats))) { yafgpu_scene_destroy(s); return rc; }
-	}
-	if((rc = upload(s, d->lights, (size_t)d->n_lights, &dv.lights))) { yafgpu_scene_destroy(s); return rc; }
-	std::memset(&dv.tex, 0, sizeof dv.tex);
-	if((d->n_nodes > 0 && d->nodes) || d->background.kind == YAFGPU_BACKGROUND_TEXTURE)
-	{	// image textures: what the shader nodes and a texture background look up
-		for(int i = 0; i < d->n_textures; ++i)
-		{
-			const yafgpu_texture &t = d->textures[i];
-			if(t.width <= 0 || t.height <= 0 || (uint64_t)t.texel_first + (uint64_t)t.width * (uint64_t)t.height > d->n_texels) { yafgpu_scene_destroy(s); return fail(-24, "a texture's texel range lies outside the texel array"); }
-		}
-		const float4 *texels = nullptr;
-		if((rc = upload(s, d->textures, (size_t)std::max(d->n_textures, 0), &dv.tex.textures))) { yafgpu_scene_destroy(s); return rc; }
-		if((rc = upload(s, (const float4 *)d->texels, (size_t)d->n_texels, &texels))) { yafgpu_scene_destroy(s); return rc; }
-		dv.tex.texels = texels; dv.tex.n_textures = d->n_textures;
-	}
-	if(d->n_nodes > 0 && d->nodes)
-	{	// shader nodes and the per-triangle texture coordinates they read
-		for(int i = 0; i < d->n_materials; ++i)
-		{
-			const yafgpu_material &m = d->materials[i];
-			if(m.n_nodes < 0 || m.n_nodes > kMaxNodes || m.node_first < 0 || m.node_first + m.n_nodes > d->n_nodes)
-			{ yafgpu_scene_destroy(s); return fail(-24, "a material's shader nodes: more than " + std::to_string(kMaxNodes) + " nodes, or a range outside the node array"); }
-			if(m.n_nodes > 0 && ((m.type != YAFGPU_MAT_MASKED && m.type != YAFGPU_MAT_BLEND) || s->mat_used[(size_t)i])) s->has_textures = true;      // (a mask or a blend nothing refers to picks no kernel)
-			if(m.n_bump < 0 || m.n_bump > kMaxNodes || (m.n_bump > 0 && (m.bump_first < 0 || m.bump_first + m.n_bump > d->n_nodes || m.sh_bump < 0 || m.sh_bump >= m.n_bump)))
-			{ yafgpu_scene_destroy(s); return fail(-24, "a material's bump shader: more than " + std::to_string(kMaxNodes) + " nodes, or a range outside the node array"); }
-			if(m.n_bump > 0) { s->has_textures = true; s->has_bump = true; }
-			// every reference inside the material — a shader slot, a node's inputs — is -1 or names a node BEFORE the one that reads it
-			// (evaluation order): the device indexes a per-lane result stack with them (nodes_eval, mat_resolve, nodes_eval_derivative)
-			const int slots[] = {m.sh_diffuse, m.sh_mirror_color, m.sh_mirror, m.sh_transparency, m.sh_translucency, m.sh_sigma_oren, m.sh_diffuse_refl, m.sh_ior,
-			                     m.sh_glossy, m.sh_glossy_reflect, m.sh_exponent, m.sh_filter_color};
-			for(int sl : slots)
-				if(m.n_nodes > 0 && (sl < -1 || sl >= m.n_nodes)) { yafgpu_scene_destroy(s); return fail(-24, "a material's shader slot names a node outside its node range"); }
-			auto range_ok = [&](int first, int count) {
-				for(int k = 0; k < count; ++k)
-				{
-					const yafgpu_node &n = d->nodes[first + k];
-					auto ref_ok = [&](int r) { return r >= -1 && r < k; };
-					if(n.type == YAFGPU_NODE_MIX && !(ref_ok(n.input1) && ref_ok(n.input2) && ref_ok(n.factor))) return false;
-					if(n.type == YAFGPU_NODE_LAYER && !(n.input >= 0 && n.input < k && ref_ok(n.upper))) return false;
-					if(n.type < YAFGPU_NODE_TEXTURE_MAPPER || n.type > YAFGPU_NODE_LAYER) return false;
-				}
-				return true;
-			};
-			if(!range_ok(m.node_first, m.n_nodes) || (m.n_bump > 0 && !range_ok(m.bump_first, m.n_bump)))
-			{ yafgpu_scene_destroy(s); return fail(-24, "a shader node refers to a node that is not evaluated before it (or has an unknown type; a layer needs an input)"); }
-		}
-		for(int i = 0; i < d->n_nodes; ++i)
-		{
-			const yafgpu_node &n = d->nodes[i];
-			if(n.type == YAFGPU_NODE_TEXTURE_MAPPER && (n.texture < 0 || n.texture >= d->n_textures)) { yafgpu_scene_destroy(s); return fail(-24, "a texture_mapper node refers to a texture that does not exist"); }
-		}
-		if((rc = upload(s, d->nodes, (size_t)d->n_nodes, &dv.tex.nodes))) { yafgpu_scene_destroy(s); return rc; }
-		if(instanced) { dv.tex.tri_uv = rows.uv; dv.tex.tri_orco = rows.orco; if(s->has_bump) { dv.tex.tri_e3 = rows.e3; dv.tex.has_bump = 1; } }
-		if(!instanced && d->tri_uv && (rc = upload(s, d->tri_uv, nt * 6, &dv.tex.tri_uv))) { yafgpu_scene_destroy(s); return rc; }
-		if(!instanced && d->tri_orco && (rc = upload(s, d->tri_orco, nt * 9, &dv.tex.tri_orco))) { yafgpu_scene_destroy(s); return rc; }
-		if(s->has_bump && !instanced)
-		{	// the third edge of Triangle::getSurface's dPdU / dPdV (triangle.cc:80-111): c - b, rounded once like e1 and e2 of the record
-			std::vector<float> e3(nt * 3);
-			for(size_t i = 0; i < nt; ++i) for(int k = 0; k < 3; ++k) e3[3 * i + k] = d->verts[9 * i + 6 + k] - d->verts[9 * i + 3 + k];
-			if((rc = upload(s, e3.data(), e3.size(), &dv.tex.tri_e3))) { yafgpu_scene_destroy(s); return rc; }
-			dv.tex.has_bump = 1;
-		}
-	}
-	if((rc = upload(s, faure.data(), faure.size(), &dv.faure))) { yafgpu_scene_destroy(s); return rc; }
+	if((rc = upload(s, faure.data(), faure.size(), &dv.faure))) return rc;
 	dv.n_faure = (int)faure.size(); dv.faure_far = dv.faure; dv.faure_near = dv.n_faure;
-	if((rc = upload(s, foff.data(), foff.size(), &dv.faure_off))) { yafgpu_scene_destroy(s); return rc; }
-	if((rc = upload(s, invp.data(), invp.size(), &dv.inv_prims))) { yafgpu_scene_destroy(s); return rc; }
-	dv.n_lights = d->n_lights; dv.n_tris = n_tris; dv.n_mats = d->n_materials; dv.n_nodes = (uint32_t)s->tree.nodes.size();
-	for(int k = 0; k < 3; ++k) { dv.blo[k] = s->tree.bound_lo[k]; dv.bhi[k] = s->tree.bound_hi[k]; }
-	dv.cam = d->camera;
-	{	// PerspectiveCamera ctor, camera_perspective.cc:42-54: corner table of the polygonal bokeh shapes
-		for(float &v : dv.cam.ls) v = 0.f;
-		int ns = dv.cam.bokeh_type;
-		if(ns >= 3 && ns <= 6)
-		{
-			float w = (float)((double)dv.cam.bokeh_rotation * 0.01745329251994329576922);
-			const float wi = (float)(6.28318530717958647692 / (double)(float)ns);
-			ns = (ns + 2) * 2;
-			for(int i = 0; i < ns; i += 2)
-			{
-				dv.cam.ls[i] = host_fsin(w + (float)1.57079632679489661923);     // fCos__
-				dv.cam.ls[i + 1] = host_fsin(w);
-				w += wi;
-			}
-		}
+	if((rc = upload(s, foff.data(), foff.size(), &dv.faure_off))) return rc;
+	return upload(s, invp.data(), invp.size(), &dv.inv_prims);
+}
+
+// PerspectiveCamera ctor, camera_perspective.cc:42-54: corner table of the polygonal bokeh shapes
+static void bokeh_table(yafgpu_camera &cam)
+{
+	for(float &v : cam.ls) v = 0.f;
+	int ns = cam.bokeh_type;
+	if(ns < 3 || ns > 6) return;
+	float w = (float)((double)cam.bokeh_rotation * 0.01745329251994329576922);
+	const float wi = (float)(6.28318530717958647692 / (double)(float)ns);
+	ns = (ns + 2) * 2;
+	for(int i = 0; i < ns; i += 2)
+	{
+		cam.ls[i] = host_fsin(w + (float)1.57079632679489661923);     // fCos__
+		cam.ls[i + 1] = host_fsin(w);
+		w += wi;
 	}
-	s->mats.assign(d->materials, d->materials + d->n_materials);
-	s->n_lights = d->n_lights;
-	s->h_lights.assign(d->lights, d->lights + d->n_lights);
-	for(const yafgpu_light &l : s->h_lights) s->light_mask |= 1u << (uint32_t)l.type;
+}
+
+// BackgroundLight::init: the tables are built where the texture evaluator is, once per scene, from the finished DevScene
+static int background_tables(yafgpu_scene *s, const yafgpu_scene_desc *d)
+{
+	DevScene &dv = s->dev;
 	dv.bg.rec = d->background; dv.bg.tab = nullptr;
-	// a texture background is evaluated per escaping ray by the code that comes with the background light: such a scene asks for a
-	// kernel built with that light's bit whether or not the light is there
-	if(d->background.kind == YAFGPU_BACKGROUND_TEXTURE) s->light_mask |= 1u << (uint32_t)YAFGPU_LIGHT_BACKGROUND;
-	if(d->background.kind != YAFGPU_BACKGROUND_NONE && d->background.has_ibl)
-	{	// BackgroundLight::init: the tables are built where the texture evaluator is, once per scene
-		float *tab = nullptr;
-		const size_t n_tab = (size_t)(kBgRows + 1) * kBgRowStride;
-		if(hipMalloc((void **)&tab, n_tab * sizeof(float)) != hipSuccess) { yafgpu_scene_destroy(s); return fail(-100, "no device memory for the background light's tables"); }
-		s->allocs.push_back(tab);
-		s->info.device_bytes += n_tab * sizeof(float);
-		hipError_t e = hipMemset(tab, 0, n_tab * sizeof(float));
-		if(e == hipSuccess)
-		{
-			hipLaunchKernelGGL(bg_rows_kernel, dim3((uint32_t)kBgRows), dim3(kBlock), 0, nullptr, dv, tab);
-			hipLaunchKernelGGL(bg_vdist_kernel, dim3(1), dim3(kBlock), 0, nullptr, tab);
-			e = hipGetLastError();
-		}
-		if(e == hipSuccess) e = hipDeviceSynchronize();
-		if(e != hipSuccess) { yafgpu_scene_destroy(s); return fail(-100, std::string("background light tables: ") + hipGetErrorString(e)); }
-		dv.bg.tab = tab;
+	if(d->background.kind == YAFGPU_BACKGROUND_NONE || !d->background.has_ibl) return 0;
+	float *tab = nullptr;
+	const size_t n_tab = (size_t)(kBgRows + 1) * kBgRowStride;
+	if(hipMalloc((void **)&tab, n_tab * sizeof(float)) != hipSuccess) return fail(-100, "no device memory for the background light's tables");
+	s->allocs.push_back(tab);
+	s->info.device_bytes += n_tab * sizeof(float);
+	hipError_t e = hipMemset(tab, 0, n_tab * sizeof(float));
+	if(e == hipSuccess)
+	{
+		hipLaunchKernelGGL(bg_rows_kernel, dim3((uint32_t)kBgRows), dim3(kBlock), 0, nullptr, dv, tab);
+		hipLaunchKernelGGL(bg_vdist_kernel, dim3(1), dim3(kBlock), 0, nullptr, tab);
+		e = hipGetLastError();
 	}
-	s->info.upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count() + assemble_seconds;
-	(void)t0;
-	*out = s;
+	if(e == hipSuccess) e = hipDeviceSynchronize();
+	if(e != hipSuccess) return fail(-100, std::string("background light tables: ") + hipGetErrorString(e));
+	dv.bg.tab = tab;
 	return 0;
 }
 
-void yafgpu_scene_destroy(yafgpu_scene_t *s)
+extern "C" {
+
+const char *yafgpu_last_error(void) { return g_err.c_str(); }
+extern "C" void yafgpu_internal_set_error(const char *msg) { g_err = msg ? msg : ""; }
+
+int yafgpu_device_count(void)
 {
-	if(!s) return;
-	for(void *p : s->allocs) (void)hipFree(p);
-	delete s;      // (buffers, streams and events go with their owners)
+	int n = 0;
+	if(hipGetDeviceCount(&n) != hipSuccess) return 0;
+	return n;
 }
+int yafgpu_set_device(int device) { HIP_OK(hipSetDevice(device)); return 0; }
+
+uint64_t yafgpu_planes_bytes(int32_t width, int32_t height)
+{
+	return (uint64_t)YAFGPU_FILM_PLANES * (uint64_t)width * (uint64_t)height * YAFGPU_FILM_CHANNELS * sizeof(float);
+}
+
+// check, classify, make the rows, build the tree, upload: a scene that fails on the way goes with everything it allocated
+int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
+{
+	if(!out) return fail(-1, "null argument");
+	int rc = check_desc(d);
+	if(rc) return rc;
+	std::unique_ptr<yafgpu_scene> owner(new yafgpu_scene());
+	yafgpu_scene *s = owner.get();
+	classify_materials(s, d);
+	// instanced geometry: every row of the scene is made on the device, and the vertices come back for the tree builders
+	AssembledRows rows;
+	const auto tr = std::chrono::steady_clock::now();
+	if(d->inst.n_segments <= 0) host_rows(d, rows);
+	else if((rc = assemble_scene(s, d, rows))) return rc;
+	const double rows_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tr).count();
+	if((rc = build_tree(s, d, rows))) return rc;
+	const auto t1 = std::chrono::steady_clock::now();
+	DevScene &dv = s->dev;
+	if((rc = upload_tree(s)) || (rc = upload_rows(s, d, rows))) return rc;
+	dv.tri = rows.rec; dv.tri_ng = rows.ng; dv.tri_vn = rows.vn; dv.mats = rows.mats;
+	dv.n_tris = (int)rows.n; dv.n_mats = d->n_materials;
+	if((rc = upload_lights(s, d)) || (rc = upload_textures(s, d)) || (rc = upload_nodes(s, d, rows)) || (rc = upload_qmc_tables(s))) return rc;
+	dv.cam = d->camera;
+	bokeh_table(dv.cam);
+	s->mats.assign(d->materials, d->materials + d->n_materials);
+	if((rc = background_tables(s, d))) return rc;
+	s->info.upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count() + rows_seconds;
+	*out = owner.release();
+	return 0;
+}
+
+void yafgpu_scene_destroy(yafgpu_scene_t *s) { delete s; }      // (device arrays, buffers, streams and events go with their owners)
 
 int yafgpu_scene_info(const yafgpu_scene_t *s, yafgpu_tree_info *info)
 {

@@ -98,6 +98,41 @@ def test_default_mode_pipelines_small_frames_and_a_frame_change_in_between_is_or
             assert torch.equal(a.view(torch.int32), b.view(torch.int32)), f"shard {shards}"
 
 
+def test_a_failed_prepare_leaves_the_interface_unprepared():
+    """prepareRender that refuses its parameters after an earlier success: nothing renders with the half-read set-up until a call
+    succeeds again, and that one renders what the first did"""
+    import torch
+    from libyafaray_amd.interface import YafaRayError
+    sc = scenes.cornell_soup(12, seed=7, res=(8, 8))
+    rd = scenes.render_settings(8, 8, 2, bounces=2)
+    yi = Interface()
+    scenes.load_scene(yi, sc, rd)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def one_pass():
+        yi.prepareRender()
+        assert yi.getRenderSize() == (8, 8)
+        p = torch.zeros((4, 8, 8, 5), dtype=torch.float32, device=dev)
+        yi.renderPassDevice(p.data_ptr(), 0, stream)
+        torch.cuda.synchronize()
+        return p.cpu().numpy()
+
+    first = one_pass()
+    assert np.any(first != 0)
+    scenes.set_render_params(yi, dict(rd, AA_passes=0))
+    with pytest.raises(YafaRayError, match="AA_passes must be at least 1"):
+        yi.prepareRender()
+    with pytest.raises(YafaRayError, match="call prepareRender first"):
+        yi.getRenderSize()
+    p = torch.zeros((4, 8, 8, 5), dtype=torch.float32, device=dev)
+    with pytest.raises(YafaRayError, match="call prepareRender first"):
+        yi.renderPassDevice(p.data_ptr(), 0, stream)
+    scenes.set_render_params(yi, dict(rd, AA_passes=1))
+    again = one_pass()
+    assert np.array_equal(first.view(np.uint32), again.view(np.uint32))
+
+
 def test_accumulating_passes_add_up_in_call_order():
     """rp.accumulate passes (yafaray_render's later passes) add into the same planes: the float sums depend on the order, which is the
     caller's stream's — compared with the host-driven multi-pass render of the same settings, pipelining off"""
