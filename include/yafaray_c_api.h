@@ -169,7 +169,13 @@ void yafaray_paramsEndList(yafaray_interface_t *yi);                            
  * Camera::factory (src/camera/camera.cc:34-44), Integrator::factory (src/integrator/integrator.cc:36-57) */
 /* createLight: arealight, pointlight, directionallight, sunlight and spherelight (light_area.cc, light_point.cc, light_directional.cc,
  * light_sun.cc, light_sphere.cc factories); every other type, and photon_only lights, are refused with a diagnostic.  A sphere light's
- * `object` is accepted and changes nothing: the mesh it names renders as the light-material geometry it is. */
+ * `object` is accepted and changes nothing: the mesh it names renders as the light-material geometry it is.
+ * meshlight (light_meshlight.cc): object, color, power, samples, double_sided, light_enabled, cast_shadows; with_caustic / with_diffuse are
+ * read and dropped.  Without an `object` it is refused here.  The mesh is looked up at prepareRender (MeshLight::init runs at scene update),
+ * so the light may be created before or after its mesh; prepareRender refuses an object that names no mesh, a curve mesh or an instance
+ * (their triangles exist on the device only), a mesh that is not rendered, one with no triangles and one whose total area is zero or not
+ * finite.  The mesh stays ordinary scene geometry with the material it has.  yafaray_getLights then shows the rows the light resolved to and
+ * its area_. */
 yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name);            /* :92 */
 yafaray_texture_t *yafaray_createTexture(yafaray_interface_t *yi, const char *name);        /* :93: type "image" (TGA, HDR and PNG files; none /
                                                                                                bilinear interpolation); procedural types are refused */

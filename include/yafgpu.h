@@ -58,7 +58,11 @@ enum { YAFGPU_MAT_SHINYDIFFUSE = 0, YAFGPU_MAT_GLOSSY = 1, YAFGPU_MAT_LIGHT = 2,
             visibility, receive_shadows   the blend's own (:485-499, :506); flat 0, no transparent bias: its factory reads neither */
        YAFGPU_MAT_BLEND = 8 };
 enum { YAFGPU_LIGHT_AREA = 0, YAFGPU_LIGHT_POINT = 1, YAFGPU_LIGHT_DIRECTIONAL = 2, YAFGPU_LIGHT_SUN = 3, YAFGPU_LIGHT_SPHERE = 4,
-       YAFGPU_LIGHT_BACKGROUND = 5 /* BackgroundLight (light_background.cc): samples the scene's yafgpu_background through its Pdf1D tables */ };
+       YAFGPU_LIGHT_BACKGROUND = 5, /* BackgroundLight (light_background.cc): samples the scene's yafgpu_background through its Pdf1D tables */
+       /* MeshLight (light_meshlight.cc): a mesh of the scene sampled by area; its triangles and its Pdf1D row are in the light-geometry pool
+          (yafgpu_scene_desc::light_verts).  Not 6: YAFGPU_LIGHT_BACKGROUND + 1 is the type that tests/scene_desc_cases.cpp hands
+          yafgpu_scene_create as an unknown one, and it stays unknown */
+       YAFGPU_LIGHT_MESH = 7 };
 enum { YAFGPU_BACKGROUND_NONE = 0, YAFGPU_BACKGROUND_CONSTANT = 1, YAFGPU_BACKGROUND_TEXTURE = 2 };
 enum { YAFGPU_INTEGRATOR_PATH = 0, YAFGPU_INTEGRATOR_DIRECT = 1 };
 enum { YAFGPU_FILTER_BOX = 0, YAFGPU_FILTER_MITCHELL = 1, YAFGPU_FILTER_GAUSS = 2, YAFGPU_FILTER_LANCZOS = 3 };
@@ -172,7 +176,9 @@ typedef struct yafgpu_node
  *   sun          samples, direction (normalised), du / dv (createCs__ of the direction AS GIVEN, sic light_sun.cc:36), cos_angle,
  *                invpdf, pdf, col_pdf (color * pdf); color (col * power) is kept for reference only
  *   sphere       samples, position (center), radius, square_radius, square_radius_epsilon, color (col * power)
- *   background   samples, clamp_intersect (0 = no clamp), abs_intersect; what it emits is the scene's yafgpu_background */
+ *   background   samples, clamp_intersect (0 = no clamp), abs_intersect; what it emits is the scene's yafgpu_background
+ *   mesh         samples, mesh_first, mesh_count, mesh_pool, double_sided, color (col * (float)power * pi); yafgpu_scene_create computes
+ *                mesh_row and area (MeshLight::initIs, light_meshlight.cc:55-73) for the scene's own copy, whatever the caller wrote there */
 typedef struct yafgpu_light
 {
 	int32_t type, samples, cast_shadows;
@@ -188,9 +194,18 @@ typedef struct yafgpu_light
 			float radius, square_radius, square_radius_epsilon;
 			float pad2[2];
 		};
+		struct
+		{	/* mesh: words 4-8 of the record */
+			int32_t mesh_first;        /* the scene row of the mesh's first triangle: its rows (a, eps)(e1)(e2) are contiguous from there */
+			int32_t mesh_count;        /* n_tris_: its triangles, at least one */
+			int32_t mesh_pool;         /* its first triangle in the light-geometry pool (yafgpu_scene_desc::light_verts) */
+			int32_t double_sided;
+			int32_t mesh_row;          /* filled by yafgpu_scene_create: the float at which its Pdf1D row starts in the scene's row pool,
+			                              integral_, inv_integral_, func_[mesh_count], cdf_[mesh_count + 1] */
+		};
 	};
 	float color[3];
-	float area;
+	float area;                    /* mesh: area_, the double sum of the float triangle areas, narrowed (light_meshlight.cc:61-68) */
 	float position[3];
 	float clamp_intersect;         /* background: clamp_intersect_ (Light::setClampIntersect, light_background.cc:182) */
 	int32_t abs_intersect;         /* background: abs_inter_ (:178); the background factories always pass false */
@@ -316,6 +331,12 @@ typedef struct yafgpu_scene_desc
 	yafgpu_instancing inst;      /* instances and curves; optional, zeroed = none: then n_tris rows of the arrays above are the scene, made by the host loop as
 	                                ever.  With segments the arrays above hold the plain triangles only (n_tris of them) and the scene is
 	                                the segments' rows; yafgpu_tree_info::n_tris counts those */
+	/* The light-geometry pool: per triangle of a mesh light the corners a, b, c as the mesh stores them (Triangle::sample reads them; the
+	   scene rows hold a and the edges, and a + e1 is not bit-equal to b).  A mesh light's triangles are
+	   light_verts[9 * mesh_pool .. 9 * (mesh_pool + mesh_count)), in the order of its scene rows.  yafgpu_scene_create computes the triangle
+	   areas and every light's Pdf1D row from them on the device.  Zeroed = no mesh light */
+	int32_t n_light_tris;
+	const float *light_verts;    /* n_light_tris*9 */
 } yafgpu_scene_desc;
 
 typedef struct yafgpu_render_params

@@ -15,6 +15,7 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -108,7 +109,7 @@ struct BackgroundCfg { float color[3]; yafgpu_background rec; };      // color: 
 struct yafaray_material { yafgpu_material m; int index; std::vector<yafgpu_node> nodes; int mask_sub[2] = {-1, -1}; };   // nodes: evaluation order, `texture` = index into texture_order; mask_sub: a mask_mat's material1 / material2 (their `index`)
 static_assert(sizeof(yafgpu_material) == 384, "yafaray_getMaterialTable hands out 96-word records");
 struct yafaray_texture { yafgpu_texture t; int index; std::vector<float> texels; };            // texels: height * width * 4, as ImageHandler::getPixel returns them
-struct yafaray_light { yafgpu_light l; };
+struct yafaray_light { yafgpu_light l; unsigned int object = 0; };      // object: a mesh light's mesh (obj_id_), resolved at prepareRender
 struct yafaray_camera { CameraCfg c; };
 struct yafaray_background { BackgroundCfg b; };
 struct yafaray_integrator { IntegratorCfg c; };
@@ -1064,6 +1065,21 @@ bool make_spherelight(const ParamMap &p, yafgpu_light &l)
 	l.square_radius_epsilon = (float)((double)l.square_radius * 1.000003815);    // ~0.2 % larger radius squared
 	return enabled;
 }
+// MeshLight::factory + ctor, light_meshlight.cc:231-262, :34-43.  The mesh is looked up when the scene is made (MeshLight::init, :75-86;
+// flatten_scene here): until then the record names no rows (mesh_first -1) and has no area
+bool make_meshlight(const ParamMap &p, yafgpu_light &l, unsigned int &object_id)
+{
+	float color[3] = {1, 1, 1};
+	double power = 1.0; int samples = 4, object = 0; bool double_s = false, enabled = true, cast = true;
+	p.get("object", object); p.getColor("color", color); p.get("power", power); p.get("samples", samples); p.get("double_sided", double_s);
+	p.get("light_enabled", enabled); p.get("cast_shadows", cast);
+	std::memset(&l, 0, sizeof l);
+	l.type = YAFGPU_LIGHT_MESH; l.samples = samples; l.cast_shadows = cast; l.double_sided = double_s;
+	l.mesh_first = -1;
+	for(int k = 0; k < 3; ++k) l.color[k] = (color[k] * (float)power) * (float)kPi;   // color * (float)power * M_PI (:255): Rgb * float twice (color.h:266 narrows M_PI)
+	object_id = (unsigned int)object;
+	return enabled;
+}
 
 // PerspectiveCamera::factory, Camera::Camera, setAxis — camera_perspective.cc:198-243, camera.cc:46-66, :60-74
 bool make_camera(yafaray_interface *yi, const ParamMap &p, yafgpu_camera &c)
@@ -1887,7 +1903,7 @@ yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name)
 	if(yi->lights.count(name)) { fail(yi, std::string("createLight: \"") + name + "\" already defined"); return nullptr; }
 	if(!yi->params.get("type", type)) { fail(yi, "createLight: type of light not specified"); return nullptr; }
 	auto l = std::make_unique<yafaray_light>();
-	bool enabled, photon_only = false;
+	bool enabled, photon_only = false; int object = 0;
 	// light_area.cc:69, light_point.cc:40,60 (and light_directional.cc:62, light_sun.cc:55, light_sphere.cc:73): a photon-only light gives illumSample / illuminate nothing (and still counts among the lights the
 	// one-light estimator picks from): a photon-mapping setting, not taken over
 	if(yi->params.get("photon_only", photon_only) && photon_only) { fail(yi, "createLight: photon_only lights are outside the GPU path's scope (photon mapping)"); return nullptr; }
@@ -1896,7 +1912,12 @@ yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name)
 	else if(type == "directionallight") enabled = make_directionallight(yi->params, l->l);
 	else if(type == "sunlight") enabled = make_sunlight(yi->params, l->l);
 	else if(type == "spherelight") enabled = make_spherelight(yi->params, l->l);
-	else { fail(yi, "createLight: light type \"" + type + "\" is outside the GPU path's scope (arealight, pointlight, directionallight, sunlight, spherelight)"); return nullptr; }
+	else if(type == "meshlight" && yi->params.get("object", object)) enabled = make_meshlight(yi->params, l->l, l->object);
+	else
+	{	// (a meshlight without an object has no mesh at all: the reference's dereferences a null distribution at its first sample)
+		fail(yi, "createLight: light type \"" + type + "\" is outside the GPU path's scope (arealight, pointlight, directionallight, sunlight, spherelight, and meshlight with the object it lights from)");
+		return nullptr;
+	}
 	yafaray_light *raw = l.get();
 	if(enabled) yi->light_order.push_back(raw);   // Scene::addLight only sees enabled lights (environment.cc:230-233)
 	yi->lights[name] = std::move(l);
@@ -2260,8 +2281,41 @@ struct FlatScene
 	std::vector<yafgpu_material> mats; std::vector<yafgpu_node> nodes;
 	std::vector<yafgpu_texture> textures; std::vector<float> texels;
 	std::vector<yafgpu_light> lights;
+	std::vector<float> light_verts;             // the light-geometry pool: the corners of every mesh light's triangles (yafgpu_scene_desc::light_verts)
 	bool any_normals = false, base_normals = false, any_nodes = false, with_textures = false, instanced = false;
 };
+
+// MeshLight::init (light_meshlight.cc:75-86): the light's mesh, by now part of the flattened scene.  plain_first / scene_first: the mesh's rows
+// in the plain arrays and in the scene; the corners go to the light-geometry pool.  The areas are summed here as the device will sum them
+// (initIs, :60-68: float areas, a double sum), to refuse a mesh that has none before anything is allocated and to show area_ in getLights.
+bool resolve_mesh_light(yafaray_interface *yi, const FlatScene &f, const std::map<unsigned int, std::array<int32_t, 3>> &mesh_rows, const yafaray_light &light,
+                        yafgpu_light &rec, std::vector<float> &pool)
+{
+	const std::string who = "render: meshlight object " + std::to_string(light.object);
+	auto rows = mesh_rows.find(light.object);
+	if(rows == mesh_rows.end())
+	{
+		if(yi->curves.count(light.object) || yi->instances.count(light.object))
+			return fail(yi, who + " is a curve mesh or an instance: their triangles exist on the device only, a mesh light needs a plain mesh");
+		if(yi->meshes.count(light.object)) return fail(yi, who + " is a mesh that is not rendered (invisible, or the base of instances): it has no rows for the light to be hit on");
+		return fail(yi, who + " names no mesh");
+	}
+	const int32_t plain_first = rows->second[0], scene_first = rows->second[1], count = rows->second[2];
+	if(count <= 0) return fail(yi, who + " is a mesh with no triangles");
+	const float *v = f.plain.verts.data() + 9 * (size_t)plain_first;
+	double total_area = 0.0;
+	for(int32_t i = 0; i < count; ++i, v += 9)
+	{
+		const float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]}, e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
+		float n[3]; cross3(e1, e2, n);
+		total_area += (double)(float)(0.5 * (double)std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]));
+	}
+	if(!((float)total_area > 0.f && std::isfinite((float)total_area))) return fail(yi, who + " is a mesh whose total area is zero or not finite: nothing to sample by area");
+	rec.mesh_first = scene_first; rec.mesh_count = count; rec.mesh_pool = (int32_t)(pool.size() / 9);
+	rec.area = (float)total_area;      // area_, for getLights: the device computes its own, bit-equal one (the expressions are IEEE operations on both sides)
+	pool.insert(pool.end(), f.plain.verts.begin() + 9 * (ptrdiff_t)plain_first, f.plain.verts.begin() + 9 * ((ptrdiff_t)plain_first + count));
+	return true;
+}
 
 // Scene::update: flatten visible non-base meshes in object-id order (scene.cc:797-817)
 bool flatten_scene(yafaray_interface *yi, const Selection &sel, FlatScene &f)
@@ -2276,6 +2330,8 @@ bool flatten_scene(yafaray_interface *yi, const Selection &sel, FlatScene &f)
 	// curves (Scene::endCurveMesh, scene.cc:154-281): a segment per strand over the pool of its points and their extrusion scales; the
 	// device extrudes them and fills the prisms
 	auto mesh_it = yi->meshes.begin(); auto inst_it = yi->instances.begin(); auto curve_it = yi->curves.begin();
+	std::map<unsigned int, std::array<int32_t, 3>> mesh_rows;      // flattened mesh id -> its first row of the plain arrays, its first row of the scene, its rows
+	int64_t scene_rows = 0;
 	while(mesh_it != yi->meshes.end() || inst_it != yi->instances.end() || curve_it != yi->curves.end())
 	{
 		// the object with the smallest id goes next (an id names one object)
@@ -2293,16 +2349,20 @@ bool flatten_scene(yafaray_interface *yi, const Selection &sel, FlatScene &f)
 				f.curve_points.push_back(c.scales[2 * i]); f.curve_points.push_back(c.scales[2 * i + 1]);
 			}
 			f.segments.push_back(sg);
+			scene_rows += 6 * ((int64_t)n - 1) + 2;
 			continue;
 		}
 		if(mesh_it != yi->meshes.end() && mesh_id <= inst_id)
 		{
-			const Mesh &m = (mesh_it++)->second;
+			const Mesh &m = mesh_it->second;
+			const unsigned int id = (mesh_it++)->first;
 			if(!m.visible || m.base) continue;
 			yafgpu_segment sg{}; sg.kind = YAFGPU_SEGMENT_PLAIN; sg.first = (int32_t)f.plain.mat.size();
 			f.plain.append(m, f.any_normals, f.any_nodes, false);
 			sg.count = (int32_t)f.plain.mat.size() - sg.first;
 			f.segments.push_back(sg);
+			mesh_rows[id] = {sg.first, (int32_t)scene_rows, sg.count};
+			scene_rows += sg.count;
 			continue;
 		}
 		const Instance &in = (inst_it++)->second;      // visible_ is true whatever the base's visibility (object_geom.cc:112)
@@ -2319,6 +2379,7 @@ bool flatten_scene(yafaray_interface *yi, const Selection &sel, FlatScene &f)
 		sg.flags = ((in.smooth || in.normals_exported) ? (uint32_t)YAFGPU_INSTANCE_SMOOTH : 0u) | (in.has_orco ? (uint32_t)YAFGPU_INSTANCE_ORCO : 0u) | (in.has_uv ? (uint32_t)YAFGPU_INSTANCE_UV : 0u);
 		std::memcpy(sg.m, in.m, sizeof sg.m);
 		f.segments.push_back(sg);
+		scene_rows += sg.count;
 	}
 	f.instanced = !yi->instances.empty() || !yi->curves.empty();
 	if(yi->material_order.empty()) return fail(yi, "render: no materials defined");
@@ -2333,7 +2394,13 @@ bool flatten_scene(yafaray_interface *yi, const Selection &sel, FlatScene &f)
 			f.texels.insert(f.texels.end(), t->texels.begin(), t->texels.end());
 			f.textures.push_back(rec);
 		}
-	for(auto *l : yi->light_order) f.lights.push_back(l->l);
+	for(auto *l : yi->light_order)
+	{
+		f.lights.push_back(l->l);
+		if(l->l.type != YAFGPU_LIGHT_MESH) continue;
+		if(!resolve_mesh_light(yi, f, mesh_rows, *l, f.lights.back(), f.light_verts)) return false;
+		l->l = f.lights.back();      // getLights shows the rows the light resolved to
+	}
 	return true;
 }
 
@@ -2362,6 +2429,7 @@ yafgpu_scene_desc describe_scene(const FlatScene &f, const Selection &sel, int t
 		if(f.base_normals) { d.inst.base_vnormals = f.base.vnormals.data(); d.inst.base_vn_index0 = f.base.index0.data(); }
 		if(f.any_nodes) { d.inst.base_uv = f.base.uv.data(); d.inst.base_orco = f.base.orco.data(); }
 	}
+	d.n_light_tris = (int32_t)(f.light_verts.size() / 9); d.light_verts = f.light_verts.data();
 	if(sel.bg) d.background = sel.bg->rec;
 	d.camera = sel.cam->cam;
 	d.build_threads = 0;

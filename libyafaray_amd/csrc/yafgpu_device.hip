@@ -73,6 +73,8 @@ struct DevScene
 	yafgpu_camera cam;
 	TexScene tex;                // textures, texels, shader nodes, per-triangle texture coordinates (nodes == nullptr: none)
 	BgScene bg;                  // the background record and the background light's tables (kind 0: none; tab == nullptr: no light)
+	const float *lgeo;           // the light-geometry pool of the mesh lights (nullptr: none): 9 floats per triangle (a, b, c) from 9 * mesh_pool on,
+	                             // and behind the triangles every light's Pdf1D row from mesh_row on (integral_, inv_integral_, func_, cdf_)
 };
 
 struct RenderArgs
@@ -810,6 +812,41 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			o[15] = b.val; o[16] = b.ival;
 			break;
 		}
+		// the mesh light (ops 32-34): the light is sc.lights[k], k the last input word (a uint's bits); a k that is out of range or names a
+		// light of another type leaves the outputs at zero
+		case 32:
+		{	// MeshLight::illumSample: in p.xyz, s_1, s_2, k -> ok, wi.dir, wi.tmax, pdf, ls.col (zeros where it refuses)
+			if(n_in < 6 || n_out < 9) break;
+			const uint32_t k = __float_as_uint(x[5]);
+			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_MESH) break;
+			const yafgpu_light &l = sc.lights[k];
+			V3 d = mk(0.f, 0.f, 0.f); float tmax = 0.f, pdf = 0.f;
+			if(!meshlight_illum_sample(sc, l, mk(x[0], x[1], x[2]), x[3], x[4], d, tmax, pdf)) break;
+			o[0] = 1.f; o[1] = d.x; o[2] = d.y; o[3] = d.z; o[4] = tmax; o[5] = pdf; o[6] = l.color[0]; o[7] = l.color[1]; o[8] = l.color[2];
+			break;
+		}
+		case 33:
+		{	// MeshLight::intersect: in from.xyz, dir.xyz, tmin, k -> ok, t, ipdf, col (zeros where it refuses)
+			if(n_in < 8 || n_out < 6) break;
+			const uint32_t k = __float_as_uint(x[7]);
+			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_MESH) break;
+			const yafgpu_light &l = sc.lights[k];
+			float t = 0.f, ipdf = 0.f;
+			if(!meshlight_intersect(sc, l, mk(x[0], x[1], x[2]), mk(x[3], x[4], x[5]), x[6], t, ipdf)) break;
+			o[0] = 1.f; o[1] = t; o[2] = ipdf; o[3] = l.color[0]; o[4] = l.color[1]; o[5] = l.color[2];
+			break;
+		}
+		case 34:
+		{	// a mesh light's stored row: in k -> count (as bits), area_, integral_, inv_integral_, then func_ (count) and cdf_ (count + 1), as far as n_out reaches
+			if(n_in < 1 || n_out < 4) break;
+			const uint32_t k = __float_as_uint(x[0]);
+			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_MESH) break;
+			const yafgpu_light &l = sc.lights[k];
+			const float *row = sc.lgeo + l.mesh_row;
+			o[0] = __uint_as_float((uint32_t)l.mesh_count); o[1] = l.area; o[2] = row[0]; o[3] = row[1];
+			for(int j = 0; j < min(n_out - 4, 2 * l.mesh_count + 1); ++j) o[4 + j] = row[kLgeoFunc + j];
+			break;
+		}
 		default: break;
 	}
 }
@@ -843,6 +880,31 @@ __global__ __launch_bounds__(kBlock) void bg_vdist_kernel(float *tab)
 	for(int y = (int)threadIdx.x; y < kBgRows; y += (int)blockDim.x) row[kBgFunc + y] = tab[(size_t)y * kBgRowStride + 1];
 	__syncthreads();
 	if(threadIdx.x == 0 && blockIdx.x == 0) pdf1d_build(row, kBgRows);
+}
+
+// MeshLight::initIs (light_meshlight.cc:55-73), one workgroup per light of the scene; those of other types have nothing to do.  The threads
+// compute the triangles' areas into func_ (Triangle::surfaceArea, triangle.cc:169-179: the 0.5 is a double); one thread then builds cdf_
+// over them in index order (Pdf1D's constructor) and sums area_, a double sum of the float areas in the same order.  `lights` is the
+// scene's own array: the light's area is written there.
+__global__ __launch_bounds__(kBlock) void meshlight_rows_kernel(yafgpu_light *lights, int n_lights, float *lgeo)
+{
+	const int k = (int)blockIdx.x;
+	if(k >= n_lights || lights[k].type != YAFGPU_LIGHT_MESH) return;
+	const int n = lights[k].mesh_count;
+	float *row = lgeo + lights[k].mesh_row, *func = row + kLgeoFunc;
+	for(int i = (int)threadIdx.x; i < n; i += (int)blockDim.x)
+	{
+		const float *q = lgeo + 9 * (size_t)(lights[k].mesh_pool + i);
+		const V3 a = vec3(q), edge_1 = vec3(q + 3) - a, edge_2 = vec3(q + 6) - a;
+		func[i] = (float)(0.5 * (double)length(cross(edge_1, edge_2)));
+	}
+	__syncthreads();
+	if(threadIdx.x != 0) return;
+	double total_area = 0.0;
+	for(int i = 0; i < n; ++i) total_area += (double)func[i];
+	const float integral = pdf1d_cumulate(func, n, func + n);
+	row[0] = integral; row[1] = 1.f / integral;
+	lights[k].area = (float)total_area;
 }
 
 } // namespace yafgpu
@@ -944,6 +1006,7 @@ struct yafgpu_scene
 	uint32_t mat_mask = 0u;              // bit per YAFGPU_MAT_* present; picks the shading kernel variant
 	std::vector<char> mat_used;          // per material record: some triangle refers to it, or a mask in use picks it
 	uint32_t light_mask = 0u;            // bit per YAFGPU_LIGHT_* present; a variant must have been built for all of them
+	size_t lgeo_floats = 0;              // floats of the light-geometry pool: the mesh lights' triangles and rows (upload_lights, mesh_light_rows)
 	bool has_volumetric = false;
 	int max_add_depth = 0;               // the largest Material::additional_depth_ of the scene: recursion frames beyond raydepth
 	bool has_glossy_two = false;         // rough glass: a glossy trajectory sends two rays (the replay's call count)
@@ -1059,6 +1122,30 @@ static int check_mask_or_blend(const yafgpu_scene_desc *d, int i)
 	return 0;
 }
 
+// Mesh lights: every range the kernels will index — the light's scene rows, its triangles in the light-geometry pool — lies inside its
+// array, and the pool's corners are finite.  (After check_instancing: the scene's row count is the segments'.)
+static int check_mesh_lights(const yafgpu_scene_desc *d)
+{
+	int64_t rows = d->n_tris;
+	if(d->inst.n_segments > 0) { rows = 0; for(int k = 0; k < d->inst.n_segments; ++k) rows += (int64_t)segment_rows(d->inst.segments[k]); }
+	bool any = false;
+	for(int i = 0; i < d->n_lights; ++i)
+	{
+		const yafgpu_light &l = d->lights[i];
+		if(l.type != YAFGPU_LIGHT_MESH) continue;
+		const std::string who = "mesh light " + std::to_string(i);
+		any = true;
+		if(l.mesh_count < 1) return fail(-2, who + ": a mesh with no triangles");
+		if(l.mesh_first < 0 || (int64_t)l.mesh_first + (int64_t)l.mesh_count > rows) return fail(-3, who + ": its rows lie outside the scene's triangles");
+		if(!d->light_verts || l.mesh_pool < 0 || (int64_t)l.mesh_pool + (int64_t)l.mesh_count > (int64_t)d->n_light_tris)
+			return fail(-3, who + ": its triangles lie outside the light-geometry pool");
+	}
+	if(!any) return 0;
+	for(size_t k = 0; k < (size_t)d->n_light_tris * 9; ++k)
+		if(!std::isfinite(d->light_verts[k])) return fail(-3, "non-finite vertex coordinate in triangle " + std::to_string(k / 9) + " of the light-geometry pool");
+	return 0;
+}
+
 // every reference inside a node range is -1 or names a node BEFORE the one that reads it (evaluation order): the device indexes a per-lane
 // result stack with them (nodes_eval, mat_resolve, nodes_eval_derivative)
 static bool node_range_ok(const yafgpu_node *nodes, int first, int count)
@@ -1091,7 +1178,7 @@ static int check_desc(const yafgpu_scene_desc *d)
 	for(int i = 0; i < d->n_tris; ++i)
 		if(d->tri_mat[i] < 0 || d->tri_mat[i] >= d->n_materials) return fail(-3, "triangle material index out of range");
 	for(int i = 0; i < d->n_lights; ++i)
-		if(d->lights[i].type < YAFGPU_LIGHT_AREA || d->lights[i].type > YAFGPU_LIGHT_BACKGROUND) return fail(-2, "light " + std::to_string(i) + ": unknown type");
+		if(d->lights[i].type < YAFGPU_LIGHT_AREA || (d->lights[i].type > YAFGPU_LIGHT_BACKGROUND && d->lights[i].type != YAFGPU_LIGHT_MESH)) return fail(-2, "light " + std::to_string(i) + ": unknown type");
 	{	// the background and its light: one record, at most one light, and the light only with a background that asks for it
 		const yafgpu_background &b = d->background;
 		int n_bg_lights = 0;
@@ -1127,6 +1214,7 @@ static int check_desc(const yafgpu_scene_desc *d)
 			return fail(-3, "rough glass material " + std::to_string(i) + ": rg_a2 (alpha squared) must be positive");
 	}
 	if(d->inst.n_segments > 0) { const int rc = check_instancing(d); if(rc) return rc; }
+	{ const int rc = check_mesh_lights(d); if(rc) return rc; }
 	const bool with_nodes = d->n_nodes > 0 && d->nodes;
 	if(with_nodes || d->background.kind == YAFGPU_BACKGROUND_TEXTURE)      // image textures: what the shader nodes and a texture background look up
 		for(int i = 0; i < d->n_textures; ++i)
@@ -1431,10 +1519,16 @@ static int upload_tree(yafgpu_scene *s)
 
 static int upload_lights(yafgpu_scene *s, const yafgpu_scene_desc *d)
 {
-	const int rc = upload(s, d->lights, (size_t)d->n_lights, &s->dev.lights);
+	s->h_lights.assign(d->lights, d->lights + d->n_lights);
+	// a mesh light's Pdf1D row (2 + n + n + 1 floats) follows the triangles of the light-geometry pool, in light order (mesh_light_rows)
+	size_t row = (size_t)std::max(d->n_light_tris, 0) * 9;
+	for(yafgpu_light &l : s->h_lights)
+		if(l.type == YAFGPU_LIGHT_MESH) { l.mesh_row = (int32_t)row; row += 2 * (size_t)l.mesh_count + 3; }
+	if(row > (size_t)INT32_MAX) return fail(-3, "the light-geometry pool outgrows 2^31 floats");
+	s->lgeo_floats = row;
+	const int rc = upload(s, s->h_lights.data(), s->h_lights.size(), &s->dev.lights);
 	if(rc) return rc;
 	s->dev.n_lights = s->n_lights = d->n_lights;
-	s->h_lights.assign(d->lights, d->lights + d->n_lights);
 	for(const yafgpu_light &l : s->h_lights) s->light_mask |= 1u << (uint32_t)l.type;
 	// a texture background is evaluated per escaping ray by the code that comes with the background light: such a scene asks for a
 	// kernel built with that light's bit whether or not the light is there
@@ -1531,6 +1625,28 @@ static int background_tables(yafgpu_scene *s, const yafgpu_scene_desc *d)
 	return 0;
 }
 
+// MeshLight::init: the light-geometry pool (the corners of every mesh light's triangles, then a Pdf1D row per light) and each light's area_,
+// computed on the device from the corners.  The scene's light records come back with their areas: a light whose mesh has none is refused.
+static int mesh_light_rows(yafgpu_scene *s, const yafgpu_scene_desc *d)
+{
+	DevScene &dv = s->dev;
+	dv.lgeo = nullptr;
+	if(!(s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_MESH))) return 0;
+	float *lgeo = nullptr;
+	int rc = scene_alloc(s, s->lgeo_floats, &lgeo);
+	if(rc) return rc;
+	HIP_OK(hipMemcpy(lgeo, d->light_verts, (size_t)d->n_light_tris * 9 * sizeof(float), hipMemcpyHostToDevice));
+	hipLaunchKernelGGL(meshlight_rows_kernel, dim3((uint32_t)s->n_lights), dim3(kBlock), 0, nullptr, const_cast<yafgpu_light *>(dv.lights), s->n_lights, lgeo);
+	HIP_OK(hipGetLastError());
+	HIP_OK(hipDeviceSynchronize());
+	HIP_OK(hipMemcpy(s->h_lights.data(), dv.lights, s->h_lights.size() * sizeof(yafgpu_light), hipMemcpyDeviceToHost));
+	for(size_t i = 0; i < s->h_lights.size(); ++i)
+		if(s->h_lights[i].type == YAFGPU_LIGHT_MESH && !(s->h_lights[i].area > 0.f && std::isfinite(s->h_lights[i].area)))
+			return fail(-3, "mesh light " + std::to_string(i) + ": the mesh's total area is zero or not finite (Pdf1D would divide by zero)");
+	dv.lgeo = lgeo;
+	return 0;
+}
+
 extern "C" {
 
 const char *yafgpu_last_error(void) { return g_err.c_str(); }
@@ -1574,7 +1690,7 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 	dv.cam = d->camera;
 	bokeh_table(dv.cam);
 	s->mats.assign(d->materials, d->materials + d->n_materials);
-	if((rc = background_tables(s, d))) return rc;
+	if((rc = background_tables(s, d)) || (rc = mesh_light_rows(s, d))) return rc;
 	s->info.upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count() + rows_seconds;
 	*out = owner.release();
 	return 0;
@@ -1796,6 +1912,8 @@ YG_DECLARE_SHADE_VARIANT(diffuse_rec)
 YG_DECLARE_SHADE_VARIANT(glossy_rec)
 YG_DECLARE_SHADE_VARIANT(full)
 YG_DECLARE_SHADE_VARIANT(blend)
+YG_DECLARE_SHADE_VARIANT(meshlight)
+YG_DECLARE_SHADE_VARIANT(blend_meshlight)
 #undef YG_DECLARE_SHADE_VARIANT
 }
 struct ShadeVariant
@@ -1820,8 +1938,14 @@ static const ShadeVariant kShadeVariants[] = {
 // nodes, the anisotropic lobe, every light type, ambient occlusion, recursion, a second pair per park, and a record pass's program by
 // WfArgs::replay as in the general kernel.  Not in the list above: no subset of scenes picks it, a blend in use does.
 static const ShadeVariant kBlendVariant = {"blend", yafgpu_shade_blend_describe, yafgpu_shade_blend_kernel, yafgpu_shade_blend_launch};
+// The general kernel, and the blend's, with the mesh light's code (YAFGPU_LIGHT_MASK's bit YAFGPU_LIGHT_MESH) and every other feature as well.
+// Not in the list either: a mesh light in the scene picks one of them, by whether a blend is in use.
+static const ShadeVariant kMeshLightVariant = {"meshlight", yafgpu_shade_meshlight_describe, yafgpu_shade_meshlight_kernel, yafgpu_shade_meshlight_launch};
+static const ShadeVariant kBlendMeshLightVariant = {"blend_meshlight", yafgpu_shade_blend_meshlight_describe, yafgpu_shade_blend_meshlight_kernel, yafgpu_shade_blend_meshlight_launch};
 static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, const Switches &sw, int frames, bool record_pass, bool want_multi, bool ao)
 {
+	// a mesh light: the kernels that have its code, for the same reasons as the blend's below
+	if(s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_MESH)) return s->has_blend ? &kBlendMeshLightVariant : &kMeshLightVariant;
 	// a blend material some triangle uses: the one kernel that has its code, whatever the switches say (the general kernel has not) and for
 	// the record pass too; a blend nothing uses leaves has_blend clear (yafgpu_scene_create) and the choice below as it was
 	if(s->has_blend) return &kBlendVariant;

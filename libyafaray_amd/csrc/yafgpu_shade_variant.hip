@@ -12,7 +12,8 @@
 // the flag is 0 here whether or not the command line says so; asking for 1 is an error)
 // (the exception is the unit built with the blend material's bit, YAFGPU_MAT_MASK & 0x100: the general kernel with BlendMaterial's code, which
 // keeps every feature of the main unit's wf_shade — shader nodes, the anisotropic lobe, every light type, ambient occlusion — and is picked by
-// a blend in use and nothing else, pick_shade_variant)
+// a blend in use and nothing else, pick_shade_variant; and the two units built with the mesh light's bit, YAFGPU_LIGHT_MASK & 0x80, which are
+// the general kernel and the blend's with that light's code, picked by a mesh light in the scene)
 //
 // and includes the main unit with everything but wf_shade and what it calls compiled out.  All of its symbols live in
 // their own namespace (the macro below renames `yafgpu`), so the variants and the main unit link into one library; the
@@ -25,7 +26,7 @@
 #endif
 #ifndef YAFGPU_FEAT_AO
 #define YAFGPU_FEAT_AO 0
-#elif YAFGPU_FEAT_AO && !((YAFGPU_MAT_MASK) & 0x100u)
+#elif YAFGPU_FEAT_AO && !((YAFGPU_MAT_MASK) & 0x100u) && !((YAFGPU_LIGHT_MASK) & 0x80u)
 #error "a shade variant with ambient occlusion: pick_shade_variant (yafgpu_device.hip) assumes that none has it"
 #endif
 #define YAFGPU_VARIANT_TU 1

@@ -802,11 +802,10 @@ YG_DEV Col bg_eval(const BgScene &bg, const TexScene &ts, V3 dir)
 	return ret * bg.rec.power;
 }
 
-// Pdf1D's constructor over the n values already in the row's func_ (cumulateStep1DDf__: the running sum in double, in index order)
-YG_DEV void pdf1d_build(float *row, int n)
+// cumulateStep1DDf__, util_sample.h:89-102: cdf_ (n + 1 entries) over the n values of func_, the running sum in double, in index order;
+// returns integral_
+YG_DEV float pdf1d_cumulate(const float *f, int n, float *cdf)
 {
-	const float *f = row + kBgFunc;
-	float *cdf = row + kBgCdf;
 	double c = 0.0;
 	const double delta = 1.0 / (double)n;
 	cdf[0] = 0.f;
@@ -817,6 +816,12 @@ YG_DEV void pdf1d_build(float *row, int n)
 	}
 	const float integral = (float)c;
 	for(int i = 1; i < n + 1; ++i) cdf[i] /= integral;
+	return integral;
+}
+// Pdf1D's constructor over the n values already in the row's func_
+YG_DEV void pdf1d_build(float *row, int n)
+{
+	const float integral = pdf1d_cumulate(row + kBgFunc, n, row + kBgCdf);
 	row[0] = (float)n; row[1] = integral; row[2] = 1.f / integral; row[3] = 1.f / (float)n;
 }
 // Pdf1D::sample.  std::lower_bound over the n + 1 cdf entries as a search of fixed length: ten halvings empty a range of 721, and a

@@ -170,6 +170,104 @@ YG_DEV void dl_samples(const RenderArgs &ra, const yafgpu_light &light, int li, 
 	for(int k = 0; k <= is; ++k) { s_1 = hal_2.next(); s_2 = hal_3.next(); }   // the incremental sequence, replayed
 }
 
+// ---- MeshLight, light_meshlight.cc: a mesh of the scene sampled by area.  Its corners and its Pdf1D row are in DevScene::lgeo, its scene
+// rows (the triangle records and normals every ray sees) are mesh_count rows from mesh_first on.
+constexpr int kLgeoFunc = 2;      // a light's row: integral_, inv_integral_, func_[mesh_count], cdf_[mesh_count + 1]
+YG_DEV const float *meshlight_cdf(const DevScene &sc, const yafgpu_light &l) { return sc.lgeo + l.mesh_row + kLgeoFunc + l.mesh_count; }
+// Pdf1D::dSample, util_sample.h:144-160, without the pdf (sampleSurface drops it).  std::lower_bound over the n + 1 cdf entries as a search
+// of fixed length without a branch: every step at least halves the range, so the bit length of n + 1 steps empty it (nine for 300 triangles)
+YG_DEV int pdf1d_dsample(const float *cdf, int n, float u)
+{
+	if(u == 0.f) return 0;
+	int first = 0, len = n + 1;
+	const int steps = 32 - __clz(n + 1);
+#pragma unroll 1
+	for(int k = 0; k < steps; ++k)
+	{
+		const int half = len >> 1, mid = first + half;
+		const bool right = len > 0 && cdf[min(mid, n)] < u;      // (len > 0: mid <= n already; the clamp keeps the emptied range's read inside the row)
+		first = right ? mid + 1 : first;
+		len = right ? len - half - 1 : half;
+	}
+	return max(first - 1, 0);
+}
+// MeshLight::illumSample, light_meshlight.cc:110-148, with sampleSurface (:88-106) and Triangle::sample (triangle.cc:181-192)
+YG_DEV bool meshlight_illum_sample(const DevScene &sc, const yafgpu_light &l, V3 sp_p, float s_1, float s_2, V3 &wi_dir, float &wi_tmax, float &pdf)
+{
+	const float *cdf = meshlight_cdf(sc, l);
+	const int prim_num = pdf1d_dsample(cdf, l.mesh_count, s_1);
+	if(prim_num >= l.mesh_count) return false;      // "Sampling error!" (:92-96): s_1 above cdf_[n] = 1, which no sampler hands out; the reference goes on with an unset point
+	float ss_1, delta = cdf[prim_num + 1];
+	if(prim_num > 0)
+	{
+		delta -= cdf[prim_num];
+		ss_1 = (s_1 - cdf[prim_num]) / delta;
+	}
+	else ss_1 = s_1 / delta;
+	const float *q = sc.lgeo + 9 * (size_t)(l.mesh_pool + prim_num);
+	const float su_1 = f_sqrt(ss_1);
+	const float u = 1.f - su_1;
+	const float v = s_2 * su_1;
+	const V3 p = vec3(q) * u + vec3(q + 3) * v + vec3(q + 6) * (1.f - u - v);
+	const float4 g = sc.tri_ng[l.mesh_first + prim_num];      // getNormal()
+	const V3 n = mk(g.x, g.y, g.z);
+	V3 ldir = p - sp_p;
+	const float dist_sqr = ldir.x * ldir.x + ldir.y * ldir.y + ldir.z * ldir.z;
+	const float dist = f_sqrt(dist_sqr);
+	if(dist <= 0.f) return false;
+	const float inv = 1.f / dist;
+	ldir.x *= inv; ldir.y *= inv; ldir.z *= inv;
+	float cos_angle = -dot(ldir, n);
+	if(cos_angle <= 0.f)
+	{	// no light behind a single-sided mesh
+		if(l.double_sided) cos_angle = -cos_angle;
+		else return false;
+	}
+	wi_tmax = dist;
+	wi_dir = ldir;
+	const float area_mul_cosangle = l.area * cos_angle;
+	pdf = (float)((double)dist_sqr * kPi / (double)((area_mul_cosangle == 0.f) ? 1e-8f : area_mul_cosangle));
+	return true;
+}
+// MeshLight::intersect, :190-213 (returns the INVERSE pdf).  The reference asks a kd-tree of the light's own triangles for the closest hit
+// with tmin <= t < infinity among those of a visible material (TriKdTree::intersect, kdtree_triangle.cc:780-817); a scan of the light's scene
+// rows with the same triangle test finds the same t.  The lanes of a wave take turns by light, so that the rows of the light whose turn it is
+// are read at wave-uniform addresses.
+YG_DEV bool meshlight_intersect(const DevScene &sc, const yafgpu_light &l, V3 from, V3 dir, float tmin, float &t, float &ipdf)
+{
+	float z = __builtin_inff();
+	int hit = -1;
+	const int my_first = l.mesh_first, my_count = l.mesh_count;
+	bool pending = true;
+	while(pending)
+	{
+		const int first = __builtin_amdgcn_readfirstlane(my_first), count = __builtin_amdgcn_readfirstlane(my_count);
+		if(my_first == first && my_count == count)
+		{
+			for(int k = 0; k < count; ++k)
+			{
+				const float4 r0 = sc.tri[3 * (first + k)], r1 = sc.tri[3 * (first + k) + 1], r2 = sc.tri[3 * (first + k) + 2];
+				const uint32_t vis = __float_as_uint(r1.w) >> 30;
+				float t_hit, bu, bv;
+				if(tri_test(r0, r1, r2, from, dir, t_hit, bu, bv) && t_hit < z && t_hit >= tmin && (vis == 0u || vis == 1u)) { z = t_hit; hit = k; }
+			}
+			pending = false;
+		}
+	}
+	if(hit < 0) return false;
+	const float4 g = sc.tri_ng[my_first + hit];
+	float cos_angle = dot(dir, -mk(g.x, g.y, g.z));
+	if(cos_angle <= 0.f)
+	{
+		if(l.double_sided) cos_angle = fabsf(cos_angle);
+		else return false;
+	}
+	const float idist_sqr = 1.f / (z * z);
+	ipdf = (float)((double)((idist_sqr * l.area) * cos_angle) * k1Pi);
+	t = z;
+	return true;
+}
+
 // Material::isFlat() as doLightEstimation reads it (:105, :189).  Off sp.material_: under a mask that is the mask's, false, while the chosen
 // material's own eval keeps its flag (yafgpu_material::flat 2).  Masks live in kernels with textures only; the others test the word as before.
 YG_DEV bool wf_is_flat(const yafgpu_material &mat) { return YAFGPU_FEAT_TEXTURE ? (mat.flat & 1) != 0 : mat.flat != 0; }
@@ -200,6 +298,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN)) sunlight_illum_sample(light, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col);
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) bglight_illum_sample(ra.sc.bg, ra.sc.tex, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col);
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPHERE)) { if(!spherelight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col)) return false; }
+		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_MESH)) { if(!meshlight_illum_sample(ra.sc, light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf)) return false; }
 		else if(!arealight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf)) return false;
 		r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
 		if(ls_pdf > 1e-6f)
@@ -235,6 +334,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 	if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN)) { if(!(bs.pdf > 1e-6f && sunlight_intersect(light, r_dir, r_tmax, l_col, light_ipdf))) return false; }
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) { if(!(bs.pdf > 1e-6f && bglight_intersect(light, ra.sc.bg, ra.sc.tex, r_dir, r_tmax, l_col, light_ipdf))) return false; }
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPHERE)) return false;      // (canIntersect() is false: st_dl_eval never asks)
+	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_MESH)) { if(!(bs.pdf > 1e-6f && meshlight_intersect(ra.sc, light, sp.p, r_dir, r_tmin, r_tmax, light_ipdf))) return false; }
 	else if(!(bs.pdf > 1e-6f && arealight_intersect(light, sp.p, r_dir, r_tmax, light_ipdf))) return false;
 	if(light_ipdf > 1e-6f)
 	{
