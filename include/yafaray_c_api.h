@@ -175,7 +175,13 @@ void yafaray_paramsEndList(yafaray_interface_t *yi);                            
  * so the light may be created before or after its mesh; prepareRender refuses an object that names no mesh, a curve mesh or an instance
  * (their triangles exist on the device only), a mesh that is not rendered, one with no triangles and one whose total area is zero or not
  * finite.  The mesh stays ordinary scene geometry with the material it has.  yafaray_getLights then shows the rows the light resolved to and
- * its area_. */
+ * its area_.
+ * bgPortalLight (light_background_portal.cc): object, samples, power (a float), light_enabled, cast_shadows; with_caustic / with_diffuse are
+ * read and dropped; no color and no double_sided.  Without an `object` it is refused here.  Its mesh must be a plain triangle mesh created
+ * invisible (startTriMesh type bit 0x0100): BackgroundPortalLight::init hides the mesh, so its triangles are no scene geometry and live
+ * with the light.  prepareRender refuses a scene with no background, an object that names no mesh, a curve mesh or an instance, the base of
+ * instances, a visible mesh, one with no triangles and one whose total area is zero or not finite.  yafaray_getLights then shows the
+ * light's triangles in the light-geometry pool and its area_. */
 yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name);            /* :92 */
 yafaray_texture_t *yafaray_createTexture(yafaray_interface_t *yi, const char *name);        /* :93: type "image" (TGA, HDR and PNG files; none /
                                                                                                bilinear interpolation); procedural types are refused */

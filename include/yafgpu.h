@@ -62,7 +62,10 @@ enum { YAFGPU_LIGHT_AREA = 0, YAFGPU_LIGHT_POINT = 1, YAFGPU_LIGHT_DIRECTIONAL =
        /* MeshLight (light_meshlight.cc): a mesh of the scene sampled by area; its triangles and its Pdf1D row are in the light-geometry pool
           (yafgpu_scene_desc::light_verts).  Not 6: YAFGPU_LIGHT_BACKGROUND + 1 is the type that tests/scene_desc_cases.cpp hands
           yafgpu_scene_create as an unknown one, and it stays unknown */
-       YAFGPU_LIGHT_MESH = 7 };
+       YAFGPU_LIGHT_MESH = 7,
+       /* BackgroundPortalLight (light_background_portal.cc): a hidden mesh sampled by area that asks the scene's yafgpu_background for its
+          colour.  Its triangles have no scene rows: corners, triangle records, normals and the Pdf1D row are all in the light-geometry pool */
+       YAFGPU_LIGHT_PORTAL = 8 };
 enum { YAFGPU_BACKGROUND_NONE = 0, YAFGPU_BACKGROUND_CONSTANT = 1, YAFGPU_BACKGROUND_TEXTURE = 2 };
 enum { YAFGPU_INTEGRATOR_PATH = 0, YAFGPU_INTEGRATOR_DIRECT = 1 };
 enum { YAFGPU_FILTER_BOX = 0, YAFGPU_FILTER_MITCHELL = 1, YAFGPU_FILTER_GAUSS = 2, YAFGPU_FILTER_LANCZOS = 3 };
@@ -178,7 +181,10 @@ typedef struct yafgpu_node
  *   sphere       samples, position (center), radius, square_radius, square_radius_epsilon, color (col * power)
  *   background   samples, clamp_intersect (0 = no clamp), abs_intersect; what it emits is the scene's yafgpu_background
  *   mesh         samples, mesh_first, mesh_count, mesh_pool, double_sided, color (col * (float)power * pi); yafgpu_scene_create computes
- *                mesh_row and area (MeshLight::initIs, light_meshlight.cc:55-73) for the scene's own copy, whatever the caller wrote there */
+ *                mesh_row and area (MeshLight::initIs, light_meshlight.cc:55-73) for the scene's own copy, whatever the caller wrote there
+ *   portal       samples, mesh_count, mesh_pool, portal_power; yafgpu_scene_create computes mesh_first (here: where the light's triangle
+ *                records start in the pool), mesh_row and area (BackgroundPortalLight::initIs, light_background_portal.cc:58-77).  No
+ *                color: what it emits is the scene's yafgpu_background times portal_power; single-sided, so double_sided stays 0 */
 typedef struct yafgpu_light
 {
 	int32_t type, samples, cast_shadows;
@@ -202,10 +208,15 @@ typedef struct yafgpu_light
 			int32_t double_sided;
 			int32_t mesh_row;          /* filled by yafgpu_scene_create: the float at which its Pdf1D row starts in the scene's row pool,
 			                              integral_, inv_integral_, func_[mesh_count], cdf_[mesh_count + 1] */
+			/* portal only (word 9; a mesh light leaves it 0): power_.  For a portal mesh_first is not a scene row (its mesh has none) but,
+			   filled by yafgpu_scene_create, the float (a multiple of 4) at which its triangles' records start in the scene's row pool: three
+			   float4 per triangle as a scene row has them, (a, eps)(e1, material | visibility << 30)(e2, 0), then one float4 per triangle, the
+			   geometric normal */
+			float portal_power;
 		};
 	};
 	float color[3];
-	float area;                    /* mesh: area_, the double sum of the float triangle areas, narrowed (light_meshlight.cc:61-68) */
+	float area;                    /* mesh, portal: area_, the double sum of the float triangle areas, narrowed (light_meshlight.cc:61-68) */
 	float position[3];
 	float clamp_intersect;         /* background: clamp_intersect_ (Light::setClampIntersect, light_background.cc:182) */
 	int32_t abs_intersect;         /* background: abs_inter_ (:178); the background factories always pass false */
@@ -337,6 +348,10 @@ typedef struct yafgpu_scene_desc
 	   areas and every light's Pdf1D row from them on the device.  Zeroed = no mesh light */
 	int32_t n_light_tris;
 	const float *light_verts;    /* n_light_tris*9 */
+	/* A portal light's triangles have no scene row to take a material from: per triangle of the pool its material index (of `materials`),
+	   which a portal's triangle records carry with that material's visibility.  Read for the portals' ranges only; null when the scene has
+	   no portal light */
+	const int32_t *light_tri_mat; /* n_light_tris */
 } yafgpu_scene_desc;
 
 typedef struct yafgpu_render_params

@@ -51,11 +51,15 @@ cc shade_blend yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=blend -DYAFGPU_MAT
 #   one of them when it has a mesh light, so that every other scene's kernels stay what they were
 cc shade_meshlight yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=meshlight -DYAFGPU_MAT_MASK=0x7fu -DYAFGPU_LIGHT_MASK=0xbfu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1
 cc shade_blend_meshlight yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=blend_meshlight -DYAFGPU_MAT_MASK=0x17fu -DYAFGPU_LIGHT_MASK=0xbfu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1
+#   portal, blend_portal: the same two with BackgroundPortalLight's code as well, bit 8 of the light mask (YAFGPU_LIGHT_PORTAL); a scene takes one of
+#   them when it has a portal light, with or without a mesh light beside it
+cc shade_portal yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=portal -DYAFGPU_MAT_MASK=0x7fu -DYAFGPU_LIGHT_MASK=0x1bfu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1
+cc shade_blend_portal yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=blend_portal -DYAFGPU_MAT_MASK=0x17fu -DYAFGPU_LIGHT_MASK=0x1bfu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1
 # scene set-up for instanced geometry: the rows of the flattened scene, made on the device (same flags: its arithmetic must round like the host loop's)
 cc yafgpu_assemble yafgpu_assemble.hip
 cc kdtree_build kdtree_build.cpp
 cc kdtree_build_device kdtree_build_device.hip
-OBJS="$OBJ/yafgpu_device.o $OBJ/shade_diffuse.o $OBJ/shade_glossy.o $OBJ/shade_diffuse_mp.o $OBJ/shade_glossy_mp.o $OBJ/shade_diffuse_rec.o $OBJ/shade_glossy_rec.o $OBJ/shade_full.o $OBJ/shade_blend.o $OBJ/shade_meshlight.o $OBJ/shade_blend_meshlight.o $OBJ/yafgpu_assemble.o $OBJ/kdtree_build.o $OBJ/kdtree_build_device.o"
+OBJS="$OBJ/yafgpu_device.o $OBJ/shade_diffuse.o $OBJ/shade_glossy.o $OBJ/shade_diffuse_mp.o $OBJ/shade_glossy_mp.o $OBJ/shade_diffuse_rec.o $OBJ/shade_glossy_rec.o $OBJ/shade_full.o $OBJ/shade_blend.o $OBJ/shade_meshlight.o $OBJ/shade_blend_meshlight.o $OBJ/shade_portal.o $OBJ/shade_blend_portal.o $OBJ/yafgpu_assemble.o $OBJ/kdtree_build.o $OBJ/kdtree_build_device.o"
 for f in yafaray_c_api yafaray_xml yafaray_image yafaray_reduce; do
   if [ -f "$HERE/$f.cpp" ]; then cc "$f" "$f.cpp"; OBJS="$OBJS $OBJ/$f.o"; fi
 done

@@ -109,7 +109,7 @@ struct BackgroundCfg { float color[3]; yafgpu_background rec; };      // color: 
 struct yafaray_material { yafgpu_material m; int index; std::vector<yafgpu_node> nodes; int mask_sub[2] = {-1, -1}; };   // nodes: evaluation order, `texture` = index into texture_order; mask_sub: a mask_mat's material1 / material2 (their `index`)
 static_assert(sizeof(yafgpu_material) == 384, "yafaray_getMaterialTable hands out 96-word records");
 struct yafaray_texture { yafgpu_texture t; int index; std::vector<float> texels; };            // texels: height * width * 4, as ImageHandler::getPixel returns them
-struct yafaray_light { yafgpu_light l; unsigned int object = 0; };      // object: a mesh light's mesh (obj_id_), resolved at prepareRender
+struct yafaray_light { yafgpu_light l; unsigned int object = 0; };      // object: a mesh light's or a portal's mesh (obj_id_ / object_id_), resolved at prepareRender
 struct yafaray_camera { CameraCfg c; };
 struct yafaray_background { BackgroundCfg b; };
 struct yafaray_integrator { IntegratorCfg c; };
@@ -1080,6 +1080,20 @@ bool make_meshlight(const ParamMap &p, yafgpu_light &l, unsigned int &object_id)
 	object_id = (unsigned int)object;
 	return enabled;
 }
+// BackgroundPortalLight::factory + ctor, light_background_portal.cc:237-264, :34-43.  power is a float here (:241); no color and no
+// double_sided.  The mesh is looked up when the scene is made (init, :79-96; flatten_scene here): until then the record has no
+// triangles (mesh_pool -1) and no area.  clamp_intersect stays 0: only the background's own factory sets it, on its own light
+bool make_portallight(const ParamMap &p, yafgpu_light &l, unsigned int &object_id)
+{
+	float power = 1.0f; int samples = 4, object = 0; bool enabled = true, cast = true;
+	p.get("object", object); p.get("samples", samples); p.get("power", power); p.get("light_enabled", enabled); p.get("cast_shadows", cast);
+	std::memset(&l, 0, sizeof l);
+	l.type = YAFGPU_LIGHT_PORTAL; l.samples = samples; l.cast_shadows = cast;
+	l.mesh_first = -1; l.mesh_pool = -1;
+	l.portal_power = power;
+	object_id = (unsigned int)object;
+	return enabled;
+}
 
 // PerspectiveCamera::factory, Camera::Camera, setAxis — camera_perspective.cc:198-243, camera.cc:46-66, :60-74
 bool make_camera(yafaray_interface *yi, const ParamMap &p, yafgpu_camera &c)
@@ -1913,9 +1927,10 @@ yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name)
 	else if(type == "sunlight") enabled = make_sunlight(yi->params, l->l);
 	else if(type == "spherelight") enabled = make_spherelight(yi->params, l->l);
 	else if(type == "meshlight" && yi->params.get("object", object)) enabled = make_meshlight(yi->params, l->l, l->object);
+	else if(type == "bgPortalLight" && yi->params.get("object", object)) enabled = make_portallight(yi->params, l->l, l->object);
 	else
-	{	// (a meshlight without an object has no mesh at all: the reference's dereferences a null distribution at its first sample)
-		fail(yi, "createLight: light type \"" + type + "\" is outside the GPU path's scope (arealight, pointlight, directionallight, sunlight, spherelight, and meshlight with the object it lights from)");
+	{	// (a meshlight or a bgPortalLight without an object has no mesh at all: the reference's dereferences a null distribution at its first sample)
+		fail(yi, "createLight: light type \"" + type + "\" is outside the GPU path's scope (arealight, pointlight, directionallight, sunlight, spherelight, and meshlight or bgPortalLight with the object it lights from)");
 		return nullptr;
 	}
 	yafaray_light *raw = l.get();
@@ -2281,7 +2296,8 @@ struct FlatScene
 	std::vector<yafgpu_material> mats; std::vector<yafgpu_node> nodes;
 	std::vector<yafgpu_texture> textures; std::vector<float> texels;
 	std::vector<yafgpu_light> lights;
-	std::vector<float> light_verts;             // the light-geometry pool: the corners of every mesh light's triangles (yafgpu_scene_desc::light_verts)
+	std::vector<float> light_verts;             // the light-geometry pool: the corners of every mesh light's and portal's triangles (yafgpu_scene_desc::light_verts)
+	std::vector<int32_t> light_tri_mat;         // per triangle of the pool its material, filled once a portal is there (yafgpu_scene_desc::light_tri_mat)
 	bool any_normals = false, base_normals = false, any_nodes = false, with_textures = false, instanced = false;
 };
 
@@ -2314,6 +2330,48 @@ bool resolve_mesh_light(yafaray_interface *yi, const FlatScene &f, const std::ma
 	rec.mesh_first = scene_first; rec.mesh_count = count; rec.mesh_pool = (int32_t)(pool.size() / 9);
 	rec.area = (float)total_area;      // area_, for getLights: the device computes its own, bit-equal one (the expressions are IEEE operations on both sides)
 	pool.insert(pool.end(), f.plain.verts.begin() + 9 * (ptrdiff_t)plain_first, f.plain.verts.begin() + 9 * ((ptrdiff_t)plain_first + count));
+	return true;
+}
+
+// BackgroundPortalLight::init (light_background_portal.cc:79-96): the light's mesh, from the interface's meshes and not from the flattened
+// scene: init hides the mesh, so its triangles have no scene rows and live in the light-geometry pool alone, corners and materials.  Only a
+// mesh that was created invisible has one meaning: Scene::update (scene.cc:788-874) builds the tree before it runs Light::init, so a visible
+// portal mesh is in the tree for the first render, stops its own shadow rays, and is gone after the next geometry update.
+// The areas are summed as the device will sum them (initIs, :63-71), to refuse early and to show area_ in getLights.
+bool resolve_portal_light(yafaray_interface *yi, const Selection &sel, const yafaray_light &light, yafgpu_light &rec, std::vector<float> &pool, std::vector<int32_t> &pool_mat)
+{
+	const std::string who = "render: bgPortalLight object " + std::to_string(light.object);
+	if(!sel.bg) return fail(yi, "render: a bgPortalLight needs a background to take its colour from, and the scene has none (the reference dereferences a null background at the first sample)");
+	auto it = yi->meshes.find(light.object);
+	if(it == yi->meshes.end())
+	{
+		if(yi->curves.count(light.object) || yi->instances.count(light.object))
+			return fail(yi, who + " is a curve mesh or an instance: their triangles exist on the device only, a portal needs a plain mesh");
+		return fail(yi, who + " names no mesh");
+	}
+	const Mesh &m = it->second;
+	if(m.base) return fail(yi, who + " is the base of instances: a portal needs a plain mesh of its own");
+	if(m.visible)
+		return fail(yi, who + " is a visible mesh: the reference hides a portal's mesh only after the first tree is built, so it would block its own shadow rays in the first render and be gone from the next; create the mesh invisible (startTriMesh type bit 0x0100), as exporters do");
+	const size_t count = m.tri_mat.size();
+	if(count == 0) return fail(yi, who + " is a mesh with no triangles");
+	if(pool.size() / 9 + count > (size_t)INT32_MAX) return fail(yi, who + ": the light-geometry pool outgrows 2^31 triangles");
+	RowPool rows;
+	rows.append(m, false, false, false);
+	const float *v = rows.verts.data();
+	double total_area = 0.0;
+	for(size_t i = 0; i < count; ++i, v += 9)
+	{
+		const float e1[3] = {v[3] - v[0], v[4] - v[1], v[5] - v[2]}, e2[3] = {v[6] - v[0], v[7] - v[1], v[8] - v[2]};
+		float n[3]; cross3(e1, e2, n);
+		total_area += (double)(float)(0.5 * (double)std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]));
+	}
+	if(!((float)total_area > 0.f && std::isfinite((float)total_area))) return fail(yi, who + " is a mesh whose total area is zero or not finite: nothing to sample by area");
+	rec.mesh_count = (int32_t)count; rec.mesh_pool = (int32_t)(pool.size() / 9);
+	rec.area = (float)total_area;
+	pool_mat.resize(pool.size() / 9, 0);      // (the mesh lights' entries before this one: read by nothing)
+	pool.insert(pool.end(), rows.verts.begin(), rows.verts.end());
+	pool_mat.insert(pool_mat.end(), rows.mat.begin(), rows.mat.end());
 	return true;
 }
 
@@ -2397,10 +2455,15 @@ bool flatten_scene(yafaray_interface *yi, const Selection &sel, FlatScene &f)
 	for(auto *l : yi->light_order)
 	{
 		f.lights.push_back(l->l);
-		if(l->l.type != YAFGPU_LIGHT_MESH) continue;
-		if(!resolve_mesh_light(yi, f, mesh_rows, *l, f.lights.back(), f.light_verts)) return false;
+		if(l->l.type == YAFGPU_LIGHT_PORTAL)
+		{
+			if(!resolve_portal_light(yi, sel, *l, f.lights.back(), f.light_verts, f.light_tri_mat)) return false;
+		}
+		else if(l->l.type != YAFGPU_LIGHT_MESH) continue;
+		else if(!resolve_mesh_light(yi, f, mesh_rows, *l, f.lights.back(), f.light_verts)) return false;
 		l->l = f.lights.back();      // getLights shows the rows the light resolved to
 	}
+	if(!f.light_tri_mat.empty()) f.light_tri_mat.resize(f.light_verts.size() / 9, 0);
 	return true;
 }
 
@@ -2430,6 +2493,7 @@ yafgpu_scene_desc describe_scene(const FlatScene &f, const Selection &sel, int t
 		if(f.any_nodes) { d.inst.base_uv = f.base.uv.data(); d.inst.base_orco = f.base.orco.data(); }
 	}
 	d.n_light_tris = (int32_t)(f.light_verts.size() / 9); d.light_verts = f.light_verts.data();
+	d.light_tri_mat = f.light_tri_mat.empty() ? nullptr : f.light_tri_mat.data();
 	if(sel.bg) d.background = sel.bg->rec;
 	d.camera = sel.cam->cam;
 	d.build_threads = 0;

@@ -73,8 +73,9 @@ struct DevScene
 	yafgpu_camera cam;
 	TexScene tex;                // textures, texels, shader nodes, per-triangle texture coordinates (nodes == nullptr: none)
 	BgScene bg;                  // the background record and the background light's tables (kind 0: none; tab == nullptr: no light)
-	const float *lgeo;           // the light-geometry pool of the mesh lights (nullptr: none): 9 floats per triangle (a, b, c) from 9 * mesh_pool on,
-	                             // and behind the triangles every light's Pdf1D row from mesh_row on (integral_, inv_integral_, func_, cdf_)
+	const float *lgeo;           // the light-geometry pool of the mesh lights and the portals (nullptr: none): 9 floats per triangle (a, b, c) from
+	                             // 9 * mesh_pool on, behind the triangles every light's Pdf1D row from mesh_row on (integral_, inv_integral_, func_,
+	                             // cdf_), and behind the rows every portal's triangle records and normals from mesh_first on
 };
 
 struct RenderArgs
@@ -847,6 +848,43 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			for(int j = 0; j < min(n_out - 4, 2 * l.mesh_count + 1); ++j) o[4 + j] = row[kLgeoFunc + j];
 			break;
 		}
+		// the portal light (ops 35-37), addressed like the mesh light
+		case 35:
+		{	// BackgroundPortalLight::illumSample: in p.xyz, s_1, s_2, k -> ok, wi.dir, wi.tmax, pdf, ls.col (zeros where it refuses)
+			if(n_in < 6 || n_out < 9) break;
+			const uint32_t k = __float_as_uint(x[5]);
+			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_PORTAL) break;
+			V3 d = mk(0.f, 0.f, 0.f); float tmax = 0.f, pdf = 0.f; Col c = mkc(0.f, 0.f, 0.f);
+			if(!portallight_illum_sample(sc, sc.lights[k], mk(x[0], x[1], x[2]), x[3], x[4], d, tmax, pdf, c)) break;
+			o[0] = 1.f; o[1] = d.x; o[2] = d.y; o[3] = d.z; o[4] = tmax; o[5] = pdf; o[6] = c.r; o[7] = c.g; o[8] = c.b;
+			break;
+		}
+		case 36:
+		{	// BackgroundPortalLight::intersect: in from.xyz, dir.xyz, tmin, k -> ok, t, ipdf, col (zeros where it refuses)
+			if(n_in < 8 || n_out < 6) break;
+			const uint32_t k = __float_as_uint(x[7]);
+			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_PORTAL) break;
+			float t = 0.f, ipdf = 0.f; Col c = mkc(0.f, 0.f, 0.f);
+			if(!portallight_intersect(sc, sc.lights[k], mk(x[0], x[1], x[2]), mk(x[3], x[4], x[5]), x[6], t, ipdf, c)) break;
+			o[0] = 1.f; o[1] = t; o[2] = ipdf; o[3] = c.r; o[4] = c.g; o[5] = c.b;
+			break;
+		}
+		case 37:
+		{	// a portal's stored row: in k -> count (as bits), area_, integral_, inv_integral_, then func_ (count), cdf_ (count + 1), the
+			// triangles' normals (4 * count: x y z and the smooth word) and their records (12 * count), as far as n_out reaches
+			if(n_in < 1 || n_out < 4) break;
+			const uint32_t k = __float_as_uint(x[0]);
+			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_PORTAL) break;
+			const yafgpu_light &l = sc.lights[k];
+			const float *row = sc.lgeo + l.mesh_row, *rec = sc.lgeo + l.mesh_first;
+			const int n = l.mesh_count;
+			o[0] = __uint_as_float((uint32_t)n); o[1] = l.area; o[2] = row[0]; o[3] = row[1];
+			const int64_t n_row = 2 * (int64_t)n + 1, n_ng = 4 * (int64_t)n, n_rec = 12 * (int64_t)n;
+			const int64_t n_all = n_row + n_ng + n_rec, n_copy = (int64_t)n_out - 4 < n_all ? (int64_t)n_out - 4 : n_all;
+			for(int64_t j = 0; j < n_copy; ++j)
+				o[4 + j] = j < n_row ? row[kLgeoFunc + j] : j < n_row + n_ng ? rec[n_rec + (j - n_row)] : rec[j - n_row - n_ng];
+			break;
+		}
 		default: break;
 	}
 }
@@ -886,10 +924,10 @@ __global__ __launch_bounds__(kBlock) void bg_vdist_kernel(float *tab)
 // compute the triangles' areas into func_ (Triangle::surfaceArea, triangle.cc:169-179: the 0.5 is a double); one thread then builds cdf_
 // over them in index order (Pdf1D's constructor) and sums area_, a double sum of the float areas in the same order.  `lights` is the
 // scene's own array: the light's area is written there.
-__global__ __launch_bounds__(kBlock) void meshlight_rows_kernel(yafgpu_light *lights, int n_lights, float *lgeo)
+// BackgroundPortalLight::initIs (light_background_portal.cc:58-77) is the same statement for the same members, so the portal's kernel below
+// runs the same body.
+YG_DEV void lgeo_rows(yafgpu_light *lights, int k, float *lgeo)
 {
-	const int k = (int)blockIdx.x;
-	if(k >= n_lights || lights[k].type != YAFGPU_LIGHT_MESH) return;
 	const int n = lights[k].mesh_count;
 	float *row = lgeo + lights[k].mesh_row, *func = row + kLgeoFunc;
 	for(int i = (int)threadIdx.x; i < n; i += (int)blockDim.x)
@@ -905,6 +943,18 @@ __global__ __launch_bounds__(kBlock) void meshlight_rows_kernel(yafgpu_light *li
 	const float integral = pdf1d_cumulate(func, n, func + n);
 	row[0] = integral; row[1] = 1.f / integral;
 	lights[k].area = (float)total_area;
+}
+__global__ __launch_bounds__(kBlock) void meshlight_rows_kernel(yafgpu_light *lights, int n_lights, float *lgeo)
+{
+	const int k = (int)blockIdx.x;
+	if(k >= n_lights || lights[k].type != YAFGPU_LIGHT_MESH) return;
+	lgeo_rows(lights, k, lgeo);
+}
+__global__ __launch_bounds__(kBlock) void portallight_rows_kernel(yafgpu_light *lights, int n_lights, float *lgeo)
+{
+	const int k = (int)blockIdx.x;
+	if(k >= n_lights || lights[k].type != YAFGPU_LIGHT_PORTAL) return;
+	lgeo_rows(lights, k, lgeo);
 }
 
 } // namespace yafgpu
@@ -1006,7 +1056,7 @@ struct yafgpu_scene
 	uint32_t mat_mask = 0u;              // bit per YAFGPU_MAT_* present; picks the shading kernel variant
 	std::vector<char> mat_used;          // per material record: some triangle refers to it, or a mask in use picks it
 	uint32_t light_mask = 0u;            // bit per YAFGPU_LIGHT_* present; a variant must have been built for all of them
-	size_t lgeo_floats = 0;              // floats of the light-geometry pool: the mesh lights' triangles and rows (upload_lights, mesh_light_rows)
+	size_t lgeo_floats = 0;              // floats of the light-geometry pool: the mesh lights' and portals' triangles and rows, the portals' records (upload_lights, mesh_light_rows)
 	bool has_volumetric = false;
 	int max_add_depth = 0;               // the largest Material::additional_depth_ of the scene: recursion frames beyond raydepth
 	bool has_glossy_two = false;         // rough glass: a glossy trajectory sends two rays (the replay's call count)
@@ -1132,13 +1182,20 @@ static int check_mesh_lights(const yafgpu_scene_desc *d)
 	for(int i = 0; i < d->n_lights; ++i)
 	{
 		const yafgpu_light &l = d->lights[i];
-		if(l.type != YAFGPU_LIGHT_MESH) continue;
-		const std::string who = "mesh light " + std::to_string(i);
+		if(l.type != YAFGPU_LIGHT_MESH && l.type != YAFGPU_LIGHT_PORTAL) continue;
+		const bool portal = l.type == YAFGPU_LIGHT_PORTAL;
+		const std::string who = (portal ? "portal light " : "mesh light ") + std::to_string(i);
 		any = true;
 		if(l.mesh_count < 1) return fail(-2, who + ": a mesh with no triangles");
-		if(l.mesh_first < 0 || (int64_t)l.mesh_first + (int64_t)l.mesh_count > rows) return fail(-3, who + ": its rows lie outside the scene's triangles");
+		// a portal's triangles have no scene rows; what it asks instead is a background and a material for each of its triangles
+		if(portal && d->background.kind == YAFGPU_BACKGROUND_NONE) return fail(-2, who + ": a portal needs a background to take its colour from");
+		if(!portal && (l.mesh_first < 0 || (int64_t)l.mesh_first + (int64_t)l.mesh_count > rows)) return fail(-3, who + ": its rows lie outside the scene's triangles");
 		if(!d->light_verts || l.mesh_pool < 0 || (int64_t)l.mesh_pool + (int64_t)l.mesh_count > (int64_t)d->n_light_tris)
 			return fail(-3, who + ": its triangles lie outside the light-geometry pool");
+		if(!portal) continue;
+		if(!d->light_tri_mat) return fail(-3, who + ": no materials for the triangles of the light-geometry pool (light_tri_mat)");
+		for(int32_t k = l.mesh_pool; k < l.mesh_pool + l.mesh_count; ++k)
+			if(d->light_tri_mat[k] < 0 || d->light_tri_mat[k] >= d->n_materials) return fail(-3, who + ": triangle material index out of range");
 	}
 	if(!any) return 0;
 	for(size_t k = 0; k < (size_t)d->n_light_tris * 9; ++k)
@@ -1178,7 +1235,7 @@ static int check_desc(const yafgpu_scene_desc *d)
 	for(int i = 0; i < d->n_tris; ++i)
 		if(d->tri_mat[i] < 0 || d->tri_mat[i] >= d->n_materials) return fail(-3, "triangle material index out of range");
 	for(int i = 0; i < d->n_lights; ++i)
-		if(d->lights[i].type < YAFGPU_LIGHT_AREA || (d->lights[i].type > YAFGPU_LIGHT_BACKGROUND && d->lights[i].type != YAFGPU_LIGHT_MESH)) return fail(-2, "light " + std::to_string(i) + ": unknown type");
+		if(d->lights[i].type < YAFGPU_LIGHT_AREA || (d->lights[i].type > YAFGPU_LIGHT_BACKGROUND && d->lights[i].type != YAFGPU_LIGHT_MESH && d->lights[i].type != YAFGPU_LIGHT_PORTAL)) return fail(-2, "light " + std::to_string(i) + ": unknown type");
 	{	// the background and its light: one record, at most one light, and the light only with a background that asks for it
 		const yafgpu_background &b = d->background;
 		int n_bg_lights = 0;
@@ -1523,7 +1580,11 @@ static int upload_lights(yafgpu_scene *s, const yafgpu_scene_desc *d)
 	// a mesh light's Pdf1D row (2 + n + n + 1 floats) follows the triangles of the light-geometry pool, in light order (mesh_light_rows)
 	size_t row = (size_t)std::max(d->n_light_tris, 0) * 9;
 	for(yafgpu_light &l : s->h_lights)
-		if(l.type == YAFGPU_LIGHT_MESH) { l.mesh_row = (int32_t)row; row += 2 * (size_t)l.mesh_count + 3; }
+		if(l.type == YAFGPU_LIGHT_MESH || l.type == YAFGPU_LIGHT_PORTAL) { l.mesh_row = (int32_t)row; row += 2 * (size_t)l.mesh_count + 3; }
+	// a portal's triangle records and normals (16 floats per triangle, read as float4) follow the rows
+	row = (row + 3) & ~(size_t)3;
+	for(yafgpu_light &l : s->h_lights)
+		if(l.type == YAFGPU_LIGHT_PORTAL) { l.mesh_first = row <= (size_t)INT32_MAX ? (int32_t)row : 0; row += 16 * (size_t)l.mesh_count; }
 	if(row > (size_t)INT32_MAX) return fail(-3, "the light-geometry pool outgrows 2^31 floats");
 	s->lgeo_floats = row;
 	const int rc = upload(s, s->h_lights.data(), s->h_lights.size(), &s->dev.lights);
@@ -1625,24 +1686,57 @@ static int background_tables(yafgpu_scene *s, const yafgpu_scene_desc *d)
 	return 0;
 }
 
+// A portal's triangles have no scene rows, so the triangle records and normals its two leaf functions read are made here, by the kernel that
+// makes the scene's rows (assemble_rows: updateIntersectionCachedValues and recNormal), from the corners and the materials of the pool: one
+// plain segment per portal, its records to mesh_first, its normals behind them.  Temporaries go when this returns.
+static int portal_records(yafgpu_scene *s, const yafgpu_scene_desc *d, float *lgeo)
+{
+	DevMem<int32_t> p_mat;
+	int rc = temp_upload(p_mat, d->light_tri_mat, (size_t)d->n_light_tris);
+	if(rc) return rc;
+	for(const yafgpu_light &l : s->h_lights)
+	{
+		if(l.type != YAFGPU_LIGHT_PORTAL) continue;
+		yafgpu_segment sg{}; sg.kind = YAFGPU_SEGMENT_PLAIN; sg.first = l.mesh_pool; sg.count = l.mesh_count;
+		const uint32_t first[2] = {0u, (uint32_t)l.mesh_count};
+		DevMem<yafgpu_segment> d_seg; DevMem<uint32_t> d_first; DevMem<float> d_verts;
+		if((rc = temp_upload(d_seg, &sg, 1)) || (rc = temp_upload(d_first, first, 2))) return rc;
+		HIP_OK(d_verts.alloc(9 * (size_t)l.mesh_count));
+		AssembleArgs a{};
+		a.segs = d_seg.p; a.seg_first = d_first.p; a.n_segs = 1; a.n_out = (uint32_t)l.mesh_count;
+		a.p_verts = lgeo; a.p_mat = p_mat.p; a.mats = s->dev.mats;
+		a.rec = (float4 *)(lgeo + l.mesh_first); a.ng = a.rec + 3 * (size_t)l.mesh_count; a.verts = d_verts.p;
+		HIP_OK(assemble_rows(a));
+		HIP_OK(hipDeviceSynchronize());
+	}
+	return 0;
+}
+
 // MeshLight::init: the light-geometry pool (the corners of every mesh light's triangles, then a Pdf1D row per light) and each light's area_,
 // computed on the device from the corners.  The scene's light records come back with their areas: a light whose mesh has none is refused.
 static int mesh_light_rows(yafgpu_scene *s, const yafgpu_scene_desc *d)
 {
 	DevScene &dv = s->dev;
 	dv.lgeo = nullptr;
-	if(!(s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_MESH))) return 0;
+	const bool portals = (s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_PORTAL)) != 0u;
+	if(!(s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_MESH)) && !portals) return 0;
 	float *lgeo = nullptr;
 	int rc = scene_alloc(s, s->lgeo_floats, &lgeo);
 	if(rc) return rc;
 	HIP_OK(hipMemcpy(lgeo, d->light_verts, (size_t)d->n_light_tris * 9 * sizeof(float), hipMemcpyHostToDevice));
 	hipLaunchKernelGGL(meshlight_rows_kernel, dim3((uint32_t)s->n_lights), dim3(kBlock), 0, nullptr, const_cast<yafgpu_light *>(dv.lights), s->n_lights, lgeo);
 	HIP_OK(hipGetLastError());
+	if(portals)
+	{
+		hipLaunchKernelGGL(portallight_rows_kernel, dim3((uint32_t)s->n_lights), dim3(kBlock), 0, nullptr, const_cast<yafgpu_light *>(dv.lights), s->n_lights, lgeo);
+		HIP_OK(hipGetLastError());
+		if((rc = portal_records(s, d, lgeo))) return rc;
+	}
 	HIP_OK(hipDeviceSynchronize());
 	HIP_OK(hipMemcpy(s->h_lights.data(), dv.lights, s->h_lights.size() * sizeof(yafgpu_light), hipMemcpyDeviceToHost));
 	for(size_t i = 0; i < s->h_lights.size(); ++i)
-		if(s->h_lights[i].type == YAFGPU_LIGHT_MESH && !(s->h_lights[i].area > 0.f && std::isfinite(s->h_lights[i].area)))
-			return fail(-3, "mesh light " + std::to_string(i) + ": the mesh's total area is zero or not finite (Pdf1D would divide by zero)");
+		if((s->h_lights[i].type == YAFGPU_LIGHT_MESH || s->h_lights[i].type == YAFGPU_LIGHT_PORTAL) && !(s->h_lights[i].area > 0.f && std::isfinite(s->h_lights[i].area)))
+			return fail(-3, std::string(s->h_lights[i].type == YAFGPU_LIGHT_PORTAL ? "portal" : "mesh") + " light " + std::to_string(i) + ": the mesh's total area is zero or not finite (Pdf1D would divide by zero)");
 	dv.lgeo = lgeo;
 	return 0;
 }
@@ -1914,6 +2008,8 @@ YG_DECLARE_SHADE_VARIANT(full)
 YG_DECLARE_SHADE_VARIANT(blend)
 YG_DECLARE_SHADE_VARIANT(meshlight)
 YG_DECLARE_SHADE_VARIANT(blend_meshlight)
+YG_DECLARE_SHADE_VARIANT(portal)
+YG_DECLARE_SHADE_VARIANT(blend_portal)
 #undef YG_DECLARE_SHADE_VARIANT
 }
 struct ShadeVariant
@@ -1942,8 +2038,13 @@ static const ShadeVariant kBlendVariant = {"blend", yafgpu_shade_blend_describe,
 // Not in the list either: a mesh light in the scene picks one of them, by whether a blend is in use.
 static const ShadeVariant kMeshLightVariant = {"meshlight", yafgpu_shade_meshlight_describe, yafgpu_shade_meshlight_kernel, yafgpu_shade_meshlight_launch};
 static const ShadeVariant kBlendMeshLightVariant = {"blend_meshlight", yafgpu_shade_blend_meshlight_describe, yafgpu_shade_blend_meshlight_kernel, yafgpu_shade_blend_meshlight_launch};
+// The same two with the portal light's code as well (bits YAFGPU_LIGHT_MESH and YAFGPU_LIGHT_PORTAL): a portal in the scene picks one of them, with or
+// without a mesh light beside it.
+static const ShadeVariant kPortalVariant = {"portal", yafgpu_shade_portal_describe, yafgpu_shade_portal_kernel, yafgpu_shade_portal_launch};
+static const ShadeVariant kBlendPortalVariant = {"blend_portal", yafgpu_shade_blend_portal_describe, yafgpu_shade_blend_portal_kernel, yafgpu_shade_blend_portal_launch};
 static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, const Switches &sw, int frames, bool record_pass, bool want_multi, bool ao)
 {
+	if(s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_PORTAL)) return s->has_blend ? &kBlendPortalVariant : &kPortalVariant;
 	// a mesh light: the kernels that have its code, for the same reasons as the blend's below
 	if(s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_MESH)) return s->has_blend ? &kBlendMeshLightVariant : &kMeshLightVariant;
 	// a blend material some triangle uses: the one kernel that has its code, whatever the switches say (the general kernel has not) and for

@@ -28,7 +28,8 @@ namespace yafgpu {
 // Light types this compilation of the light estimate handles (YAFGPU_LIGHT_MASK, one bit per YAFGPU_LIGHT_*), in the same way: the
 // shade variants are built for area and point lights (0x3) and keep the code they had before the other types came; the main unit has all
 // but the mesh light (bit YAFGPU_LIGHT_MESH, 0x80), whose code lives in the two units built with 0xbf (csrc/build.sh: meshlight,
-// blend_meshlight), so that the general kernel stays the kernel it was for every scene without one
+// blend_meshlight), so that the general kernel stays the kernel it was for every scene without one; the portal light (bit
+// YAFGPU_LIGHT_PORTAL, 0x100) lives in two more built with 0x1bf (portal, blend_portal) for the same reason
 #ifndef YAFGPU_LIGHT_MASK
 #define YAFGPU_LIGHT_MASK 0x3fu
 #endif
@@ -37,7 +38,8 @@ namespace yafgpu {
 // Light::diracLight (light_point.h, light_directional.h:44): one illuminate() and no samples.
 // Light::canIntersect (light_area.h, light_sun.h:46, light_background.h; light_sphere.h:56 says no): the sampled lights that take the BSDF half
 // of the MIS pair.  The background light is sampled and intersectable: neither Dirac nor a sphere, so both answers below already hold for it,
-// and for the mesh light (light_meshlight.h: diracLight() false, canIntersect() true), in a unit with or without its code.
+// and for the mesh light and the portal (light_meshlight.h, light_background_portal.h: diracLight() false, canIntersect() true), in a unit
+// with or without their code.
 // A build for area | point lights sees exactly the tests it had before these types came (type == point, type != point).
 // The answers hold only for the types inside YAFGPU_LIGHT_MASK: in such a build light_can_intersect(YAFGPU_LIGHT_SPHERE) is true.
 // Code in a masked unit never sees other types (pick_shade_variant does not hand it such a scene); host code asks the main unit's

@@ -268,6 +268,83 @@ YG_DEV bool meshlight_intersect(const DevScene &sc, const yafgpu_light &l, V3 fr
 	return true;
 }
 
+// ---- BackgroundPortalLight, light_background_portal.cc: a hidden mesh sampled by area whose colour is the background's in the sampled
+// direction.  Its mesh has no scene rows (init hides it, :90): corners, Pdf1D row, triangle records and normals are all in DevScene::lgeo,
+// the records (three float4 per triangle, as a scene row) from float mesh_first on and the normals (one float4 per triangle) behind them.
+YG_DEV const float4 *portallight_records(const DevScene &sc, const yafgpu_light &l) { return (const float4 *)(sc.lgeo + l.mesh_first); }
+// BackgroundPortalLight::illumSample, :136-168.  Single-sided; no guard on area_ * cos_angle, unlike the mesh light's (:160).
+// sampleSurface (:98-115) is the mesh light's word for word and shares meshlight_cdf and pdf1d_dsample with it; its few lines stand here a
+// second time because moving them out of meshlight_illum_sample changed the code of the mesh light's own shading units
+YG_DEV bool portallight_illum_sample(const DevScene &sc, const yafgpu_light &l, V3 sp_p, float s_1, float s_2, V3 &wi_dir, float &wi_tmax, float &pdf, Col &col)
+{
+	const float *cdf = meshlight_cdf(sc, l);
+	const int prim_num = pdf1d_dsample(cdf, l.mesh_count, s_1);
+	if(prim_num >= l.mesh_count) return false;      // "Sampling error!" (:102-106)
+	float ss_1, delta = cdf[prim_num + 1];
+	if(prim_num > 0)
+	{
+		delta -= cdf[prim_num];
+		ss_1 = (s_1 - cdf[prim_num]) / delta;
+	}
+	else ss_1 = s_1 / delta;
+	const float *q = sc.lgeo + 9 * (size_t)(l.mesh_pool + prim_num);
+	const float su_1 = f_sqrt(ss_1);
+	const float u = 1.f - su_1;
+	const float v = s_2 * su_1;
+	const V3 p = vec3(q) * u + vec3(q + 3) * v + vec3(q + 6) * (1.f - u - v);      // Triangle::sample, triangle.cc:181-192
+	const float4 g = portallight_records(sc, l)[3 * l.mesh_count + prim_num];      // getNormal()
+	const V3 n = mk(g.x, g.y, g.z);
+	V3 ldir = p - sp_p;
+	const float dist_sqr = ldir.x * ldir.x + ldir.y * ldir.y + ldir.z * ldir.z;
+	const float dist = f_sqrt(dist_sqr);
+	if(dist <= 0.f) return false;
+	const float inv = 1.f / dist;
+	ldir.x *= inv; ldir.y *= inv; ldir.z *= inv;
+	const float cos_angle = -dot(ldir, n);
+	if(cos_angle <= 0.f) return false;      // no light behind the portal
+	wi_tmax = dist;
+	wi_dir = ldir;
+	col = bg_eval(sc.bg, sc.tex, ldir) * l.portal_power;
+	pdf = (float)((double)dist_sqr * kPi / (double)(l.area * cos_angle));
+	return true;
+}
+// BackgroundPortalLight::intersect, :198-219 (returns the INVERSE pdf; clamp_intersect_ is 0 for this light, so :216 does nothing).  The
+// reference asks a kd-tree of the light's triangles for the closest hit with tmin <= t < infinity among those of a visible material
+// (TriKdTree::intersect, kdtree_triangle.cc:782-786); a scan of the light's records with the same triangle test finds the same t.  The lanes
+// of a wave take turns by light, as in meshlight_intersect.
+YG_DEV bool portallight_intersect(const DevScene &sc, const yafgpu_light &l, V3 from, V3 dir, float tmin, float &t, float &ipdf, Col &col)
+{
+	float z = __builtin_inff();
+	int hit = -1;
+	const int my_first = l.mesh_first, my_count = l.mesh_count;
+	bool pending = true;
+	while(pending)
+	{
+		const int first = __builtin_amdgcn_readfirstlane(my_first), count = __builtin_amdgcn_readfirstlane(my_count);
+		if(my_first == first && my_count == count)
+		{
+			const float4 *rec = (const float4 *)(sc.lgeo + first);
+			for(int k = 0; k < count; ++k)
+			{
+				const float4 r0 = rec[3 * k], r1 = rec[3 * k + 1], r2 = rec[3 * k + 2];
+				const uint32_t vis = __float_as_uint(r1.w) >> 30;
+				float t_hit, bu, bv;
+				if(tri_test(r0, r1, r2, from, dir, t_hit, bu, bv) && t_hit < z && t_hit >= tmin && (vis == 0u || vis == 1u)) { z = t_hit; hit = k; }
+			}
+			pending = false;
+		}
+	}
+	if(hit < 0) return false;
+	const float4 g = portallight_records(sc, l)[3 * my_count + hit];
+	const float cos_angle = dot(dir, -mk(g.x, g.y, g.z));
+	if(cos_angle <= 0.f) return false;
+	const float idist_sqr = 1.f / (z * z);
+	ipdf = (float)((double)((idist_sqr * l.area) * cos_angle) * k1Pi);
+	col = bg_eval(sc.bg, sc.tex, dir) * l.portal_power;
+	t = z;
+	return true;
+}
+
 // Material::isFlat() as doLightEstimation reads it (:105, :189).  Off sp.material_: under a mask that is the mask's, false, while the chosen
 // material's own eval keeps its flag (yafgpu_material::flat 2).  Masks live in kernels with textures only; the others test the word as before.
 YG_DEV bool wf_is_flat(const yafgpu_material &mat) { return YAFGPU_FEAT_TEXTURE ? (mat.flat & 1) != 0 : mat.flat != 0; }
@@ -299,6 +376,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) bglight_illum_sample(ra.sc.bg, ra.sc.tex, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col);
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPHERE)) { if(!spherelight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col)) return false; }
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_MESH)) { if(!meshlight_illum_sample(ra.sc, light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf)) return false; }
+		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_PORTAL)) { if(!portallight_illum_sample(ra.sc, light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col)) return false; }
 		else if(!arealight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf)) return false;
 		r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
 		if(ls_pdf > 1e-6f)
@@ -306,14 +384,14 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 			const Col surf_col = matb_eval(mat, dat, sp, wo, r_dir, kAll);
 			const float angle = wf_is_flat(mat) ? 1.f : fabsf(dot(sp.n, r_dir));
 			// the light colour of this half is what illumSample returned (ls.col_, :178-262): col_pdf for the sun, the background in the sampled
-			// direction for the background light, the fixed colour otherwise
+			// direction for the background light and the portal, the fixed colour otherwise
 			if(YG_LIGHT_HAS(YAFGPU_LIGHT_SPHERE) && !light_can_intersect(light.type))
 			{	// a light the BSDF half cannot hit takes no MIS weight (:244-258)
 				contrib = ((surf_col * l_col) * angle) / ls_pdf;
 				return true;
 			}
 			const float m_pdf = matb_pdf(mat, dat, sp, wo, r_dir, kMisFlags);
-			const Col ls_col = (YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) || YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) ? l_col : col3(light.color);
+			const Col ls_col = (YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) || YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND) || YG_LIGHT_IS(light, YAFGPU_LIGHT_PORTAL)) ? l_col : col3(light.color);
 			if(m_pdf > 1e-6f)
 			{
 				const float l_2 = ls_pdf * ls_pdf, m_2 = m_pdf * m_pdf;
@@ -335,13 +413,14 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) { if(!(bs.pdf > 1e-6f && bglight_intersect(light, ra.sc.bg, ra.sc.tex, r_dir, r_tmax, l_col, light_ipdf))) return false; }
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPHERE)) return false;      // (canIntersect() is false: st_dl_eval never asks)
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_MESH)) { if(!(bs.pdf > 1e-6f && meshlight_intersect(ra.sc, light, sp.p, r_dir, r_tmin, r_tmax, light_ipdf))) return false; }
+	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_PORTAL)) { if(!(bs.pdf > 1e-6f && portallight_intersect(ra.sc, light, sp.p, r_dir, r_tmin, r_tmax, light_ipdf, l_col))) return false; }
 	else if(!(bs.pdf > 1e-6f && arealight_intersect(light, sp.p, r_dir, r_tmax, light_ipdf))) return false;
 	if(light_ipdf > 1e-6f)
 	{
 		const float l_pdf = 1.f / light_ipdf;
 		const float l_2 = l_pdf * l_pdf, m_2 = bs.pdf * bs.pdf;
 		const float w = m_2 / (l_2 + m_2);
-		contrib = ((surf_col * ((YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) || YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) ? l_col : col3(light.color))) * w) * W;
+		contrib = ((surf_col * ((YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) || YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND) || YG_LIGHT_IS(light, YAFGPU_LIGHT_PORTAL)) ? l_col : col3(light.color))) * w) * W;
 	}
 	return true;
 }

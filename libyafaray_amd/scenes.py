@@ -209,11 +209,17 @@ def load_scene(yi, scene, render):
     if scene.get("smooth_angle") is not None:
         yi.smoothMesh(0, float(scene["smooth_angle"]))      # Interface::smoothMesh on the mesh just closed
     for m in scene.get("extra_meshes") or []:
-        # further meshes of their own, after the main one: {"verts": (n, 3, 3), "material": index[, "id": object id]}.  A meshlight's
-        # `object` names one of them; without "id" they take the next free ids, 2, 3, ... after the main mesh's 1
+        # further meshes of their own, after the main one: {"verts": (n, 3, 3), "material": index[, "id": object id][, "type": bits]}.  A
+        # meshlight's or a bgPortalLight's `object` names one of them; without "id" they take the next free ids, 2, 3, ... after the main
+        # mesh's 1.  "type" is startTriMesh's (0x0100: invisible, as exporters create a portal's mesh); "material" may be a list, one index
+        # per triangle
         mv = np.asarray(m["verts"], dtype=np.float32).reshape(-1, 3)
-        yi.startTriMesh(int(m["id"]) if "id" in m else yi.getNextFreeId(), mv.shape[0], mv.shape[0] // 3, False, False, 0)
-        yi.addTriangles(mv, np.arange(mv.shape[0], dtype=np.int32), handles[int(m["material"])])
+        yi.startTriMesh(int(m["id"]) if "id" in m else yi.getNextFreeId(), mv.shape[0], mv.shape[0] // 3, False, False, int(m.get("type", 0)))
+        if np.ndim(m["material"]) == 0:
+            yi.addTriangles(mv, np.arange(mv.shape[0], dtype=np.int32), handles[int(m["material"])])
+        else:
+            for t, mi in enumerate(m["material"]):
+                yi.addTriangles(mv[3 * t:3 * t + 3], np.arange(3, dtype=np.int32), handles[int(mi)])
         yi.endTriMesh()
     yi.endGeometry()
     set_render_params(yi, render)
