@@ -131,6 +131,10 @@ yafaray_bool_t yafaray_getIntegratorAO(yafaray_interface_t *yi, const char *name
  * how many nodes that is, receive_shadows, visibility (0 normal, 1 no_shadows, 2 shadow_only, 3 invisible) and the union of both
  * sub-materials' bsdf flags; false when there is no such material or it is no mask_mat */
 yafaray_bool_t yafaray_getMaskMaterial(yafaray_interface_t *yi, const char *name, void *out8);
+/* An ieslight's parsed file (a test hook for the parser): the photometric type, the counts of horizontal and vertical angles (after a
+ * single horizontal angle was doubled), max_rad_ and the largest vertical angle in radians; then up to n_floats floats of the horizontal
+ * map, the vertical map and the table, row-major by horizontal angle.  Any pointer may be null. */
+yafaray_bool_t yafaray_getIesLight(yafaray_interface_t *yi, const char *name, int *type, int *n_hor, int *n_vert, float *max_rad, float *max_v_angle, float *out, int n_floats);
 /* extension (test support): what BlendMaterial::factory's restatement parsed for the blend_mat `name`.  out10 receives ten 32-bit words:
  * the indices of material1 and material2 in creation order, blend_val_ (a float's bits), whether a shader node drives the blend (0 / 1),
  * that node's slot among the blend's nodes (-1 without one), how many nodes that is, receive_shadows, visibility (0 normal, 1 no_shadows,
@@ -181,7 +185,12 @@ void yafaray_paramsEndList(yafaray_interface_t *yi);                            
  * invisible (startTriMesh type bit 0x0100): BackgroundPortalLight::init hides the mesh, so its triangles are no scene geometry and live
  * with the light.  prepareRender refuses a scene with no background, an object that names no mesh, a curve mesh or an instance, the base of
  * instances, a visible mesh, one with no triangles and one whose total area is zero or not finite.  yafaray_getLights then shows the
- * light's triangles in the light-geometry pool and its area_. */
+ * light's triangles in the light-geometry pool and its area_.
+ * ieslight (light_ies.cc): from, to, color, power, file, samples (16), soft_shadows (false), light_enabled, cast_shadows; cone_angle,
+ * with_caustic and with_diffuse are read and dropped.  `file` is an IES photometric file, looked up like a texture's filename; it is parsed
+ * here, and a file that is missing, cut off, malformed or larger than 4096 angles a side is refused with its cause.  Without soft_shadows
+ * the light is a Dirac light with a table lookup, with it a sampled light of `samples` samples that cannot be intersected.  Without a
+ * `file` it is refused. */
 yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name);            /* :92 */
 yafaray_texture_t *yafaray_createTexture(yafaray_interface_t *yi, const char *name);        /* :93: type "image" (TGA, HDR and PNG files; none /
                                                                                                bilinear interpolation); procedural types are refused */

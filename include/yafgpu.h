@@ -65,7 +65,11 @@ enum { YAFGPU_LIGHT_AREA = 0, YAFGPU_LIGHT_POINT = 1, YAFGPU_LIGHT_DIRECTIONAL =
        YAFGPU_LIGHT_MESH = 7,
        /* BackgroundPortalLight (light_background_portal.cc): a hidden mesh sampled by area that asks the scene's yafgpu_background for its
           colour.  Its triangles have no scene rows: corners, triangle records, normals and the Pdf1D row are all in the light-geometry pool */
-       YAFGPU_LIGHT_PORTAL = 8 };
+       YAFGPU_LIGHT_PORTAL = 8,
+       /* IesLight (light_ies.cc): a point with a measured distribution, a table looked up by two angles (yafgpu_scene_desc::ies_tables).
+          Two types for its two behaviours, split by soft_shadows_: IES is a Dirac light (illuminate), IES_SOFT a sampled one that cannot be
+          intersected (illumSample alone, the light half of the MIS pair, as the sphere light) */
+       YAFGPU_LIGHT_IES = 9, YAFGPU_LIGHT_IES_SOFT = 10 };
 enum { YAFGPU_BACKGROUND_NONE = 0, YAFGPU_BACKGROUND_CONSTANT = 1, YAFGPU_BACKGROUND_TEXTURE = 2 };
 enum { YAFGPU_INTEGRATOR_PATH = 0, YAFGPU_INTEGRATOR_DIRECT = 1 };
 enum { YAFGPU_FILTER_BOX = 0, YAFGPU_FILTER_MITCHELL = 1, YAFGPU_FILTER_GAUSS = 2, YAFGPU_FILTER_LANCZOS = 3 };
@@ -184,7 +188,10 @@ typedef struct yafgpu_node
  *                mesh_row and area (MeshLight::initIs, light_meshlight.cc:55-73) for the scene's own copy, whatever the caller wrote there
  *   portal       samples, mesh_count, mesh_pool, portal_power; yafgpu_scene_create computes mesh_first (here: where the light's triangle
  *                records start in the pool), mesh_row and area (BackgroundPortalLight::initIs, light_background_portal.cc:58-77).  No
- *                color: what it emits is the scene's yafgpu_background times portal_power; single-sided, so double_sided stays 0 */
+ *                color: what it emits is the scene's yafgpu_background times portal_power; single-sided, so double_sided stays 0
+ *   ies, ies_soft  samples (1 for ies), position (from), direction (ndir_ = normalize(from - to)), du / dv (createCs__ of dir_ = -ndir_),
+ *                cos_angle (cos_end_ = fCos__ of the largest vertical angle), color (col * power), ies_first, ies_n_hor, ies_n_vert,
+ *                ies_type, ies_max_rad */
 typedef struct yafgpu_light
 {
 	int32_t type, samples, cast_shadows;
@@ -213,6 +220,16 @@ typedef struct yafgpu_light
 			   float4 per triangle as a scene row has them, (a, eps)(e1, material | visibility << 30)(e2, 0), then one float4 per triangle, the
 			   geometric normal */
 			float portal_power;
+		};
+		struct
+		{	/* ies, ies_soft: words 14-18 of the record, behind direction, du, dv and cos_angle, which they share with the sun */
+			float ies_pad[10];
+			int32_t ies_first;         /* the first float of the light's tables in yafgpu_scene_desc::ies_tables: the horizontal map (ies_n_hor), the
+			                              vertical map (ies_n_vert), then the table, ies_n_hor rows of ies_n_vert values.  In the scene's own copy
+			                              yafgpu_scene_create moves it to where the tables lie in the scene's light-geometry pool */
+			int32_t ies_n_hor, ies_n_vert;      /* at least 2 each */
+			int32_t ies_type;          /* the file's photometric type: 1 C, 2 B, anything else is read like 3, A (util_ies.h:72-86) */
+			float ies_max_rad;         /* max_rad_: 1 / the table's largest value, applied at lookup (util_ies.h:130) */
 		};
 	};
 	float color[3];
@@ -352,6 +369,10 @@ typedef struct yafgpu_scene_desc
 	   which a portal's triangle records carry with that material's visibility.  Read for the portals' ranges only; null when the scene has
 	   no portal light */
 	const int32_t *light_tri_mat; /* n_light_tris */
+	/* The measured tables of the IES lights (yafgpu_light::ies_first), one float pool: per light its horizontal map, its vertical map (both
+	   strictly increasing, in degrees) and its table, row-major by horizontal angle.  Zeroed = no IES light */
+	int32_t n_ies_floats;
+	const float *ies_tables;     /* n_ies_floats */
 } yafgpu_scene_desc;
 
 typedef struct yafgpu_render_params

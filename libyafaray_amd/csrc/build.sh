@@ -12,7 +12,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function"
 EXTRA="${YAFGPU_EXTRA_FLAGS:-}"
 mkdir -p "$OBJ"
-HEADERS=("$HERE"/*.h "$HERE"/../../include/*.h "$HERE/build.sh")
+HEADERS=("$HERE"/*.h "$HERE"/../../include/*.h "$HERE/yafaray_ies.cpp" "$HERE/build.sh")
 STAMP="$OBJ/.flags"
 if [ ! -f "$STAMP" ] || [ "$(cat "$STAMP")" != "$FLAGS $EXTRA" ] || [ "${YAFGPU_FORCE:-0}" = "1" ]; then rm -f "$OBJ"/*.o; echo "$FLAGS $EXTRA" > "$STAMP"; fi
 
@@ -55,11 +55,16 @@ cc shade_blend_meshlight yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=blend_me
 #   them when it has a portal light, with or without a mesh light beside it
 cc shade_portal yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=portal -DYAFGPU_MAT_MASK=0x7fu -DYAFGPU_LIGHT_MASK=0x1bfu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1
 cc shade_blend_portal yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=blend_portal -DYAFGPU_MAT_MASK=0x17fu -DYAFGPU_LIGHT_MASK=0x1bfu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1
+#   ies, blend_ies: the same two with IesLight's two types as well, bits 9 and 10 of the light mask (YAFGPU_LIGHT_IES, YAFGPU_LIGHT_IES_SOFT): every
+#   light type's code; a scene takes one of them when it has an IES light of either kind, whatever other lights it has
+cc shade_ies yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=ies -DYAFGPU_MAT_MASK=0x7fu -DYAFGPU_LIGHT_MASK=0x7bfu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1
+cc shade_blend_ies yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=blend_ies -DYAFGPU_MAT_MASK=0x17fu -DYAFGPU_LIGHT_MASK=0x7bfu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1
 # scene set-up for instanced geometry: the rows of the flattened scene, made on the device (same flags: its arithmetic must round like the host loop's)
 cc yafgpu_assemble yafgpu_assemble.hip
 cc kdtree_build kdtree_build.cpp
 cc kdtree_build_device kdtree_build_device.hip
-OBJS="$OBJ/yafgpu_device.o $OBJ/shade_diffuse.o $OBJ/shade_glossy.o $OBJ/shade_diffuse_mp.o $OBJ/shade_glossy_mp.o $OBJ/shade_diffuse_rec.o $OBJ/shade_glossy_rec.o $OBJ/shade_full.o $OBJ/shade_blend.o $OBJ/shade_meshlight.o $OBJ/shade_blend_meshlight.o $OBJ/shade_portal.o $OBJ/shade_blend_portal.o $OBJ/yafgpu_assemble.o $OBJ/kdtree_build.o $OBJ/kdtree_build_device.o"
+OBJS="$OBJ/yafgpu_device.o $OBJ/shade_diffuse.o $OBJ/shade_glossy.o $OBJ/shade_diffuse_mp.o $OBJ/shade_glossy_mp.o $OBJ/shade_diffuse_rec.o $OBJ/shade_glossy_rec.o $OBJ/shade_full.o $OBJ/shade_blend.o $OBJ/shade_meshlight.o $OBJ/shade_blend_meshlight.o $OBJ/shade_portal.o $OBJ/shade_blend_portal.o $OBJ/shade_ies.o $OBJ/shade_blend_ies.o $OBJ/yafgpu_assemble.o $OBJ/kdtree_build.o $OBJ/kdtree_build_device.o"
+# (yafaray_ies.cpp, the IES file parser, is part of yafaray_c_api's unit: it is included there)
 for f in yafaray_c_api yafaray_xml yafaray_image yafaray_reduce; do
   if [ -f "$HERE/$f.cpp" ]; then cc "$f" "$f.cpp"; OBJS="$OBJS $OBJ/$f.o"; fi
 done

@@ -8,6 +8,9 @@
 #include "../../include/yafaray_c_api.h"
 #include "../../include/yafgpu.h"
 #include "yafaray_image.h"
+// The IES parser is a source file of its own, with no HIP and nothing of the interface in it, so that tests/ies_parse_cases.cpp builds it
+// alone; the library takes it in here and not as an object of its own, so that every build of the interface's host side has it
+#include "yafaray_ies.cpp"
 
 #include <hip/hip_runtime.h>
 
@@ -109,7 +112,7 @@ struct BackgroundCfg { float color[3]; yafgpu_background rec; };      // color: 
 struct yafaray_material { yafgpu_material m; int index; std::vector<yafgpu_node> nodes; int mask_sub[2] = {-1, -1}; };   // nodes: evaluation order, `texture` = index into texture_order; mask_sub: a mask_mat's material1 / material2 (their `index`)
 static_assert(sizeof(yafgpu_material) == 384, "yafaray_getMaterialTable hands out 96-word records");
 struct yafaray_texture { yafgpu_texture t; int index; std::vector<float> texels; };            // texels: height * width * 4, as ImageHandler::getPixel returns them
-struct yafaray_light { yafgpu_light l; unsigned int object = 0; };      // object: a mesh light's or a portal's mesh (obj_id_ / object_id_), resolved at prepareRender
+struct yafaray_light { yafgpu_light l; unsigned int object = 0; yafies::Data ies; };      // object: a mesh light's or a portal's mesh (obj_id_ / object_id_), resolved at prepareRender; ies: an ieslight's parsed file
 struct yafaray_camera { CameraCfg c; };
 struct yafaray_background { BackgroundCfg b; };
 struct yafaray_integrator { IntegratorCfg c; };
@@ -1094,6 +1097,36 @@ bool make_portallight(const ParamMap &p, yafgpu_light &l, unsigned int &object_i
 	object_id = (unsigned int)object;
 	return enabled;
 }
+// IesLight::factory + ctor, light_ies.cc:190-233, :30-49.  cone_angle is read and unused, as there; tot_energy_ serves photon emission only.
+// ies_first is filled when the scene is made (flatten_scene), where the lights' tables meet in one pool.
+// Returns whether the light was made; `enabled` is then light_enabled.
+bool make_ieslight(yafaray_interface *yi, const ParamMap &p, yafgpu_light &l, yafies::Data &ies, bool &enabled)
+{
+	float from[3] = {0, 0, 0}, to[3] = {0, 0, -1}, color[3] = {1, 1, 1};
+	float power = 1.f, ang = 180.f; int samples = 16; bool soft = false, cast = true;
+	std::string file;
+	enabled = true;
+	p.getPoint("from", from); p.getPoint("to", to); p.getColor("color", color); p.get("power", power); p.get("file", file); p.get("samples", samples);
+	p.get("soft_shadows", soft); p.get("cone_angle", ang); p.get("light_enabled", enabled); p.get("cast_shadows", cast);
+	(void)ang;
+	std::string err, path = file;
+	{	// the name as given first, then beside the XML file, as createTexture resolves `filename`
+		FILE *f = std::fopen(path.c_str(), "rb");
+		if(f) std::fclose(f);
+		else if(!yi->base_dir.empty() && !file.empty() && file[0] != '/') path = yi->base_dir + "/" + file;
+	}
+	if(!yafies::parse_file(path, ies, err)) { fail(yi, "createLight: " + err); return false; }
+	std::memset(&l, 0, sizeof l);
+	l.type = soft ? YAFGPU_LIGHT_IES_SOFT : YAFGPU_LIGHT_IES; l.samples = soft ? samples : 1; l.cast_shadows = cast;
+	float dir[3];
+	for(int k = 0; k < 3; ++k) { l.position[k] = from[k]; l.direction[k] = from[k] - to[k]; l.color[k] = color[k] * power; }
+	ref_normalize(l.direction);
+	for(int k = 0; k < 3; ++k) dir[k] = -l.direction[k];
+	ref_create_cs(dir, l.du, l.dv);
+	l.cos_angle = host_fsin_poly(ies.max_v_angle + (float)1.57079632679489661923);      // fCos__(getMaxVAngle())
+	l.ies_first = -1; l.ies_n_hor = ies.n_hor; l.ies_n_vert = ies.n_vert; l.ies_type = ies.type; l.ies_max_rad = ies.max_rad;
+	return true;
+}
 
 // PerspectiveCamera::factory, Camera::Camera, setAxis — camera_perspective.cc:198-243, camera.cc:46-66, :60-74
 bool make_camera(yafaray_interface *yi, const ParamMap &p, yafgpu_camera &c)
@@ -1684,6 +1717,26 @@ yafaray_bool_t yafaray_getMaskMaterial(yafaray_interface_t *yi, const char *name
 	}
 	return 1;
 }
+// an ieslight's parsed file (test hook for the parser): type, counts, max_rad_ and the largest vertical angle in radians, then up to n_floats
+// of its pool layout: the horizontal map, the vertical map, the table row-major by horizontal angle
+yafaray_bool_t yafaray_getIesLight(yafaray_interface_t *yi, const char *name, int *type, int *n_hor, int *n_vert, float *max_rad, float *max_v_angle, float *out, int n_floats)
+{
+	auto it = name ? yi->lights.find(name) : yi->lights.end();
+	if(it == yi->lights.end() || (it->second->l.type != YAFGPU_LIGHT_IES && it->second->l.type != YAFGPU_LIGHT_IES_SOFT)) return fail(yi, "getIesLight: no such ieslight");
+	const yafies::Data &d = it->second->ies;
+	if(type) *type = d.type;
+	if(n_hor) *n_hor = d.n_hor;
+	if(n_vert) *n_vert = d.n_vert;
+	if(max_rad) *max_rad = d.max_rad;
+	if(max_v_angle) *max_v_angle = d.max_v_angle;
+	if(out && n_floats > 0)
+	{
+		std::vector<float> all(d.hor);
+		all.insert(all.end(), d.vert.begin(), d.vert.end()); all.insert(all.end(), d.table.begin(), d.table.end());
+		std::memcpy(out, all.data(), sizeof(float) * std::min((size_t)n_floats, all.size()));
+	}
+	return 1;
+}
 yafaray_bool_t yafaray_getBlendMaterial(yafaray_interface_t *yi, const char *name, void *out10)
 {
 	auto it = name ? yi->materials.find(name) : yi->materials.end();
@@ -1917,7 +1970,7 @@ yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name)
 	if(yi->lights.count(name)) { fail(yi, std::string("createLight: \"") + name + "\" already defined"); return nullptr; }
 	if(!yi->params.get("type", type)) { fail(yi, "createLight: type of light not specified"); return nullptr; }
 	auto l = std::make_unique<yafaray_light>();
-	bool enabled, photon_only = false; int object = 0;
+	bool enabled, photon_only = false; int object = 0; std::string file;
 	// light_area.cc:69, light_point.cc:40,60 (and light_directional.cc:62, light_sun.cc:55, light_sphere.cc:73): a photon-only light gives illumSample / illuminate nothing (and still counts among the lights the
 	// one-light estimator picks from): a photon-mapping setting, not taken over
 	if(yi->params.get("photon_only", photon_only) && photon_only) { fail(yi, "createLight: photon_only lights are outside the GPU path's scope (photon mapping)"); return nullptr; }
@@ -1928,9 +1981,11 @@ yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name)
 	else if(type == "spherelight") enabled = make_spherelight(yi->params, l->l);
 	else if(type == "meshlight" && yi->params.get("object", object)) enabled = make_meshlight(yi->params, l->l, l->object);
 	else if(type == "bgPortalLight" && yi->params.get("object", object)) enabled = make_portallight(yi->params, l->l, l->object);
+	else if(type == "ieslight" && yi->params.get("file", file)) { if(!make_ieslight(yi, yi->params, l->l, l->ies, enabled)) return nullptr; }
 	else
-	{	// (a meshlight or a bgPortalLight without an object has no mesh at all: the reference's dereferences a null distribution at its first sample)
-		fail(yi, "createLight: light type \"" + type + "\" is outside the GPU path's scope (arealight, pointlight, directionallight, sunlight, spherelight, and meshlight or bgPortalLight with the object it lights from)");
+	{	// (a meshlight or a bgPortalLight without an object has no mesh at all: the reference's dereferences a null distribution at its first sample;
+		// an ieslight without a file has nothing to parse, and the reference's factory returns no light either)
+		fail(yi, "createLight: " + std::string(type == "ieslight" ? "no file given: " : "") + "light type \"" + type + "\" is outside the GPU path's scope (arealight, pointlight, directionallight, sunlight, spherelight, meshlight or bgPortalLight with the object it lights from, and ieslight with the file it reads)");
 		return nullptr;
 	}
 	yafaray_light *raw = l.get();
@@ -2297,6 +2352,7 @@ struct FlatScene
 	std::vector<yafgpu_texture> textures; std::vector<float> texels;
 	std::vector<yafgpu_light> lights;
 	std::vector<float> light_verts;             // the light-geometry pool: the corners of every mesh light's and portal's triangles (yafgpu_scene_desc::light_verts)
+	std::vector<float> ies_tables;              // the IES lights' maps and tables (yafgpu_scene_desc::ies_tables)
 	std::vector<int32_t> light_tri_mat;         // per triangle of the pool its material, filled once a portal is there (yafgpu_scene_desc::light_tri_mat)
 	bool any_normals = false, base_normals = false, any_nodes = false, with_textures = false, instanced = false;
 };
@@ -2455,7 +2511,12 @@ bool flatten_scene(yafaray_interface *yi, const Selection &sel, FlatScene &f)
 	for(auto *l : yi->light_order)
 	{
 		f.lights.push_back(l->l);
-		if(l->l.type == YAFGPU_LIGHT_PORTAL)
+		if(l->l.type == YAFGPU_LIGHT_IES || l->l.type == YAFGPU_LIGHT_IES_SOFT)
+		{	// the light's maps and table join the pool (the parser bounds one light's; 255 lights of the largest size stay below 2^31 floats)
+			f.lights.back().ies_first = (int32_t)f.ies_tables.size();
+			for(const std::vector<float> *v : {&l->ies.hor, &l->ies.vert, &l->ies.table}) f.ies_tables.insert(f.ies_tables.end(), v->begin(), v->end());
+		}
+		else if(l->l.type == YAFGPU_LIGHT_PORTAL)
 		{
 			if(!resolve_portal_light(yi, sel, *l, f.lights.back(), f.light_verts, f.light_tri_mat)) return false;
 		}
@@ -2494,6 +2555,7 @@ yafgpu_scene_desc describe_scene(const FlatScene &f, const Selection &sel, int t
 	}
 	d.n_light_tris = (int32_t)(f.light_verts.size() / 9); d.light_verts = f.light_verts.data();
 	d.light_tri_mat = f.light_tri_mat.empty() ? nullptr : f.light_tri_mat.data();
+	d.n_ies_floats = (int32_t)f.ies_tables.size(); d.ies_tables = f.ies_tables.empty() ? nullptr : f.ies_tables.data();
 	if(sel.bg) d.background = sel.bg->rec;
 	d.camera = sel.cam->cam;
 	d.build_threads = 0;

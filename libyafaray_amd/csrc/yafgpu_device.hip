@@ -885,6 +885,35 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 				o[4 + j] = j < n_row ? row[kLgeoFunc + j] : j < n_row + n_ng ? rec[n_rec + (j - n_row)] : rec[j - n_row - n_ng];
 			break;
 		}
+		// the IES light (ops 38-40), addressed like the others; either of its two types answers each op
+		case 38:
+		{	// IesData::getRadiance: in h_ang, v_ang (degrees), k -> ok, the radiance
+			if(n_in < 3 || n_out < 2) break;
+			const uint32_t k = __float_as_uint(x[2]);
+			if(k >= (uint32_t)sc.n_lights || (sc.lights[k].type != YAFGPU_LIGHT_IES && sc.lights[k].type != YAFGPU_LIGHT_IES_SOFT)) break;
+			o[0] = 1.f; o[1] = ies_radiance(sc.lights[k], sc.lgeo + sc.lights[k].ies_first, x[0], x[1]);
+			break;
+		}
+		case 39:
+		{	// IesLight::illuminate: in p.xyz, k -> ok, wi.dir, wi.tmax, col (zeros where it refuses)
+			if(n_in < 4 || n_out < 8) break;
+			const uint32_t k = __float_as_uint(x[3]);
+			if(k >= (uint32_t)sc.n_lights || (sc.lights[k].type != YAFGPU_LIGHT_IES && sc.lights[k].type != YAFGPU_LIGHT_IES_SOFT)) break;
+			Col c = mkc(0.f, 0.f, 0.f); V3 d = mk(0.f, 0.f, 0.f); float tmax = 0.f;
+			if(!ieslight_illuminate(sc, sc.lights[k], mk(x[0], x[1], x[2]), c, d, tmax)) break;
+			o[0] = 1.f; o[1] = d.x; o[2] = d.y; o[3] = d.z; o[4] = tmax; o[5] = c.r; o[6] = c.g; o[7] = c.b;
+			break;
+		}
+		case 40:
+		{	// IesLight::illumSample: in p.xyz, s_1, s_2, k -> ok, wi.dir, wi.tmax, pdf, ls.col (zeros where it refuses)
+			if(n_in < 6 || n_out < 9) break;
+			const uint32_t k = __float_as_uint(x[5]);
+			if(k >= (uint32_t)sc.n_lights || (sc.lights[k].type != YAFGPU_LIGHT_IES && sc.lights[k].type != YAFGPU_LIGHT_IES_SOFT)) break;
+			V3 d = mk(0.f, 0.f, 0.f); float tmax = 0.f, pdf = 0.f; Col c = mkc(0.f, 0.f, 0.f);
+			if(!ieslight_illum_sample(sc, sc.lights[k], mk(x[0], x[1], x[2]), x[3], x[4], d, tmax, pdf, c)) break;
+			o[0] = 1.f; o[1] = d.x; o[2] = d.y; o[3] = d.z; o[4] = tmax; o[5] = pdf; o[6] = c.r; o[7] = c.g; o[8] = c.b;
+			break;
+		}
 		default: break;
 	}
 }
@@ -1056,7 +1085,9 @@ struct yafgpu_scene
 	uint32_t mat_mask = 0u;              // bit per YAFGPU_MAT_* present; picks the shading kernel variant
 	std::vector<char> mat_used;          // per material record: some triangle refers to it, or a mask in use picks it
 	uint32_t light_mask = 0u;            // bit per YAFGPU_LIGHT_* present; a variant must have been built for all of them
-	size_t lgeo_floats = 0;              // floats of the light-geometry pool: the mesh lights' and portals' triangles and rows, the portals' records (upload_lights, mesh_light_rows)
+	size_t lgeo_floats = 0;              // floats of the light-geometry pool: the mesh lights' and portals' triangles and rows, the portals' records, the IES lights' tables (upload_lights, mesh_light_rows)
+	size_t ies_base = 0;                 // where the IES lights' tables start in that pool
+	bool has_ies = false;                // some light is an IES light: its tables are in the pool
 	bool has_volumetric = false;
 	int max_add_depth = 0;               // the largest Material::additional_depth_ of the scene: recursion frames beyond raydepth
 	bool has_glossy_two = false;         // rough glass: a glossy trajectory sends two rays (the replay's call count)
@@ -1203,6 +1234,27 @@ static int check_mesh_lights(const yafgpu_scene_desc *d)
 	return 0;
 }
 
+// IES lights: the light's two maps and its table lie inside the table pool, the maps are strictly increasing (the lookup divides by their
+// steps and bisects them) and max_rad_ is a number to multiply by.
+static int check_ies_lights(const yafgpu_scene_desc *d)
+{
+	for(int i = 0; i < d->n_lights; ++i)
+	{
+		const yafgpu_light &l = d->lights[i];
+		if(l.type != YAFGPU_LIGHT_IES && l.type != YAFGPU_LIGHT_IES_SOFT) continue;
+		const std::string who = "IES light " + std::to_string(i);
+		if(l.ies_n_hor < 2 || l.ies_n_vert < 2) return fail(-2, who + ": fewer than 2 horizontal or 2 vertical angles");
+		const int64_t floats = (int64_t)l.ies_n_hor + (int64_t)l.ies_n_vert + (int64_t)l.ies_n_hor * (int64_t)l.ies_n_vert;
+		if(!d->ies_tables || d->n_ies_floats <= 0 || l.ies_first < 0 || (int64_t)l.ies_first + floats > (int64_t)d->n_ies_floats)
+			return fail(-3, who + ": its maps and table lie outside the IES table pool");
+		const float *hor = d->ies_tables + l.ies_first, *vert = hor + l.ies_n_hor;
+		for(int k = 1; k < l.ies_n_hor; ++k) if(!(hor[k] > hor[k - 1])) return fail(-3, who + ": its horizontal angles are not strictly increasing");
+		for(int k = 1; k < l.ies_n_vert; ++k) if(!(vert[k] > vert[k - 1])) return fail(-3, who + ": its vertical angles are not strictly increasing");
+		if(!(l.ies_max_rad > 0.f && std::isfinite(l.ies_max_rad))) return fail(-3, who + ": max_rad is not finite and positive");
+	}
+	return 0;
+}
+
 // every reference inside a node range is -1 or names a node BEFORE the one that reads it (evaluation order): the device indexes a per-lane
 // result stack with them (nodes_eval, mat_resolve, nodes_eval_derivative)
 static bool node_range_ok(const yafgpu_node *nodes, int first, int count)
@@ -1235,7 +1287,7 @@ static int check_desc(const yafgpu_scene_desc *d)
 	for(int i = 0; i < d->n_tris; ++i)
 		if(d->tri_mat[i] < 0 || d->tri_mat[i] >= d->n_materials) return fail(-3, "triangle material index out of range");
 	for(int i = 0; i < d->n_lights; ++i)
-		if(d->lights[i].type < YAFGPU_LIGHT_AREA || (d->lights[i].type > YAFGPU_LIGHT_BACKGROUND && d->lights[i].type != YAFGPU_LIGHT_MESH && d->lights[i].type != YAFGPU_LIGHT_PORTAL)) return fail(-2, "light " + std::to_string(i) + ": unknown type");
+		if(d->lights[i].type < YAFGPU_LIGHT_AREA || (d->lights[i].type > YAFGPU_LIGHT_BACKGROUND && d->lights[i].type != YAFGPU_LIGHT_MESH && d->lights[i].type != YAFGPU_LIGHT_PORTAL && d->lights[i].type != YAFGPU_LIGHT_IES && d->lights[i].type != YAFGPU_LIGHT_IES_SOFT)) return fail(-2, "light " + std::to_string(i) + ": unknown type");
 	{	// the background and its light: one record, at most one light, and the light only with a background that asks for it
 		const yafgpu_background &b = d->background;
 		int n_bg_lights = 0;
@@ -1272,6 +1324,7 @@ static int check_desc(const yafgpu_scene_desc *d)
 	}
 	if(d->inst.n_segments > 0) { const int rc = check_instancing(d); if(rc) return rc; }
 	{ const int rc = check_mesh_lights(d); if(rc) return rc; }
+	{ const int rc = check_ies_lights(d); if(rc) return rc; }
 	const bool with_nodes = d->n_nodes > 0 && d->nodes;
 	if(with_nodes || d->background.kind == YAFGPU_BACKGROUND_TEXTURE)      // image textures: what the shader nodes and a texture background look up
 		for(int i = 0; i < d->n_textures; ++i)
@@ -1578,13 +1631,22 @@ static int upload_lights(yafgpu_scene *s, const yafgpu_scene_desc *d)
 {
 	s->h_lights.assign(d->lights, d->lights + d->n_lights);
 	// a mesh light's Pdf1D row (2 + n + n + 1 floats) follows the triangles of the light-geometry pool, in light order (mesh_light_rows)
-	size_t row = (size_t)std::max(d->n_light_tris, 0) * 9;
+	// (the pool's triangles are there for the mesh lights and the portals: without one of them nothing reads, checks or copies them)
+	bool with_tris = false;
+	for(const yafgpu_light &l : s->h_lights) with_tris = with_tris || l.type == YAFGPU_LIGHT_MESH || l.type == YAFGPU_LIGHT_PORTAL;
+	size_t row = with_tris ? (size_t)std::max(d->n_light_tris, 0) * 9 : 0;
 	for(yafgpu_light &l : s->h_lights)
 		if(l.type == YAFGPU_LIGHT_MESH || l.type == YAFGPU_LIGHT_PORTAL) { l.mesh_row = (int32_t)row; row += 2 * (size_t)l.mesh_count + 3; }
 	// a portal's triangle records and normals (16 floats per triangle, read as float4) follow the rows
 	row = (row + 3) & ~(size_t)3;
 	for(yafgpu_light &l : s->h_lights)
 		if(l.type == YAFGPU_LIGHT_PORTAL) { l.mesh_first = row <= (size_t)INT32_MAX ? (int32_t)row : 0; row += 16 * (size_t)l.mesh_count; }
+	// the IES lights' tables follow, the whole of the descriptor's pool: a light's ies_first moves by where the pool lands
+	s->ies_base = row;
+	for(const yafgpu_light &l : s->h_lights) s->has_ies = s->has_ies || l.type == YAFGPU_LIGHT_IES || l.type == YAFGPU_LIGHT_IES_SOFT;
+	if(s->has_ies) row += (size_t)d->n_ies_floats;
+	for(yafgpu_light &l : s->h_lights)
+		if(l.type == YAFGPU_LIGHT_IES || l.type == YAFGPU_LIGHT_IES_SOFT) l.ies_first = row <= (size_t)INT32_MAX ? (int32_t)(s->ies_base + (size_t)l.ies_first) : 0;
 	if(row > (size_t)INT32_MAX) return fail(-3, "the light-geometry pool outgrows 2^31 floats");
 	s->lgeo_floats = row;
 	const int rc = upload(s, s->h_lights.data(), s->h_lights.size(), &s->dev.lights);
@@ -1719,10 +1781,14 @@ static int mesh_light_rows(yafgpu_scene *s, const yafgpu_scene_desc *d)
 	DevScene &dv = s->dev;
 	dv.lgeo = nullptr;
 	const bool portals = (s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_PORTAL)) != 0u;
-	if(!(s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_MESH)) && !portals) return 0;
+	const bool with_tris = (s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_MESH)) != 0u || portals;
+	if(!with_tris && !s->has_ies) return 0;
 	float *lgeo = nullptr;
 	int rc = scene_alloc(s, s->lgeo_floats, &lgeo);
 	if(rc) return rc;
+	// the IES lights' tables, as the descriptor has them, behind everything else (upload_lights moved the lights' ies_first there)
+	if(s->has_ies) HIP_OK(hipMemcpy(lgeo + s->ies_base, d->ies_tables, (size_t)d->n_ies_floats * sizeof(float), hipMemcpyHostToDevice));
+	if(!with_tris) { dv.lgeo = lgeo; return 0; }
 	HIP_OK(hipMemcpy(lgeo, d->light_verts, (size_t)d->n_light_tris * 9 * sizeof(float), hipMemcpyHostToDevice));
 	hipLaunchKernelGGL(meshlight_rows_kernel, dim3((uint32_t)s->n_lights), dim3(kBlock), 0, nullptr, const_cast<yafgpu_light *>(dv.lights), s->n_lights, lgeo);
 	HIP_OK(hipGetLastError());
@@ -1877,7 +1943,7 @@ static void host_filter_table(int type, float table[256])
 static_assert(sizeof(yafgpu_light) == 136, "yafgpu_light: the directional / sun / sphere fields overlay the area light's, the record keeps its size");
 static int light_pairs(const yafgpu_light &l, float aa_light_sample_multiplier)
 {
-	return light_is_dirac(l.type) ? 1 : (int)std::ceil((float)l.samples * aa_light_sample_multiplier);
+	return light_type_is_dirac(l.type) ? 1 : (int)std::ceil((float)l.samples * aa_light_sample_multiplier);
 }
 
 static int validate(const yafgpu_scene *s, const yafgpu_render_params *rp)
@@ -1892,7 +1958,7 @@ static int validate(const yafgpu_scene *s, const yafgpu_render_params *rp)
 	// the sample index of a light estimate in flight is packed in 12 bits (pack_dlc); validate() runs for every pass, so a
 	// light-sample multiplier that grows over the passes of an adaptive render is caught when it gets there
 	for(const yafgpu_light &l : s->h_lights)
-		if(!light_is_dirac(l.type) && std::ceil((float)l.samples * rp->aa_light_sample_multiplier) > 4095.f)
+		if(!light_type_is_dirac(l.type) && std::ceil((float)l.samples * rp->aa_light_sample_multiplier) > 4095.f)
 			return fail(-19, "a sampled light (area, sun, sphere) with more than 4095 samples per estimate (samples x AA light-sample multiplier): the device path counts them in 12 bits");
 	if(rp->do_ao && rp->integrator == YAFGPU_INTEGRATOR_DIRECT)
 	{	// ambient occlusion rides the light estimate as the light after the last one (yafgpu_wavefront.h, ao_candidate)
@@ -2010,6 +2076,8 @@ YG_DECLARE_SHADE_VARIANT(meshlight)
 YG_DECLARE_SHADE_VARIANT(blend_meshlight)
 YG_DECLARE_SHADE_VARIANT(portal)
 YG_DECLARE_SHADE_VARIANT(blend_portal)
+YG_DECLARE_SHADE_VARIANT(ies)
+YG_DECLARE_SHADE_VARIANT(blend_ies)
 #undef YG_DECLARE_SHADE_VARIANT
 }
 struct ShadeVariant
@@ -2042,8 +2110,13 @@ static const ShadeVariant kBlendMeshLightVariant = {"blend_meshlight", yafgpu_sh
 // without a mesh light beside it.
 static const ShadeVariant kPortalVariant = {"portal", yafgpu_shade_portal_describe, yafgpu_shade_portal_kernel, yafgpu_shade_portal_launch};
 static const ShadeVariant kBlendPortalVariant = {"blend_portal", yafgpu_shade_blend_portal_describe, yafgpu_shade_blend_portal_kernel, yafgpu_shade_blend_portal_launch};
+// And the same two once more with the IES light's two types (bits YAFGPU_LIGHT_IES and YAFGPU_LIGHT_IES_SOFT): every light type's code.  An IES
+// light of either kind picks one of them, whatever other lights stand beside it.
+static const ShadeVariant kIesVariant = {"ies", yafgpu_shade_ies_describe, yafgpu_shade_ies_kernel, yafgpu_shade_ies_launch};
+static const ShadeVariant kBlendIesVariant = {"blend_ies", yafgpu_shade_blend_ies_describe, yafgpu_shade_blend_ies_kernel, yafgpu_shade_blend_ies_launch};
 static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, const Switches &sw, int frames, bool record_pass, bool want_multi, bool ao)
 {
+	if(s->has_ies) return s->has_blend ? &kBlendIesVariant : &kIesVariant;
 	if(s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_PORTAL)) return s->has_blend ? &kBlendPortalVariant : &kPortalVariant;
 	// a mesh light: the kernels that have its code, for the same reasons as the blend's below
 	if(s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_MESH)) return s->has_blend ? &kBlendMeshLightVariant : &kMeshLightVariant;

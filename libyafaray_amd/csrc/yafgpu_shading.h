@@ -29,7 +29,8 @@ namespace yafgpu {
 // shade variants are built for area and point lights (0x3) and keep the code they had before the other types came; the main unit has all
 // but the mesh light (bit YAFGPU_LIGHT_MESH, 0x80), whose code lives in the two units built with 0xbf (csrc/build.sh: meshlight,
 // blend_meshlight), so that the general kernel stays the kernel it was for every scene without one; the portal light (bit
-// YAFGPU_LIGHT_PORTAL, 0x100) lives in two more built with 0x1bf (portal, blend_portal) for the same reason
+// YAFGPU_LIGHT_PORTAL, 0x100) lives in two more built with 0x1bf (portal, blend_portal) for the same reason, and the IES light's two types
+// (bits YAFGPU_LIGHT_IES and YAFGPU_LIGHT_IES_SOFT, 0x600) in two built with 0x7bf (ies, blend_ies)
 #ifndef YAFGPU_LIGHT_MASK
 #define YAFGPU_LIGHT_MASK 0x3fu
 #endif
@@ -44,12 +45,20 @@ namespace yafgpu {
 // The answers hold only for the types inside YAFGPU_LIGHT_MASK: in such a build light_can_intersect(YAFGPU_LIGHT_SPHERE) is true.
 // Code in a masked unit never sees other types (pick_shade_variant does not hand it such a scene); host code asks the main unit's
 // definitions, which know every type.
-#if (YAFGPU_LIGHT_MASK) & 0x4u          /* YAFGPU_LIGHT_DIRECTIONAL */
+// The IES light's two types (light_ies.cc: diracLight() is !soft_shadow_, canIntersect() false) are the exception: Dirac (YAFGPU_LIGHT_IES)
+// or sampled and not intersectable (YAFGPU_LIGHT_IES_SOFT), which only the units built with their bits (0x600: ies, blend_ies) answer, so
+// that every other unit keeps its code.  Host code asks light_type_is_dirac below, which is no unit's.
+__host__ inline bool light_type_is_dirac(int type) { return type == YAFGPU_LIGHT_POINT || type == YAFGPU_LIGHT_DIRECTIONAL || type == YAFGPU_LIGHT_IES; }
+#if (YAFGPU_LIGHT_MASK) & 0x600u        /* YAFGPU_LIGHT_IES, YAFGPU_LIGHT_IES_SOFT */
+__host__ __device__ __forceinline__ bool light_is_dirac(int type) { return type == YAFGPU_LIGHT_POINT || type == YAFGPU_LIGHT_DIRECTIONAL || type == YAFGPU_LIGHT_IES; }
+#elif (YAFGPU_LIGHT_MASK) & 0x4u        /* YAFGPU_LIGHT_DIRECTIONAL */
 __host__ __device__ __forceinline__ bool light_is_dirac(int type) { return type == YAFGPU_LIGHT_POINT || type == YAFGPU_LIGHT_DIRECTIONAL; }
 #else
 __host__ __device__ __forceinline__ bool light_is_dirac(int type) { return type == YAFGPU_LIGHT_POINT; }
 #endif
-#if (YAFGPU_LIGHT_MASK) & 0x10u         /* YAFGPU_LIGHT_SPHERE */
+#if (YAFGPU_LIGHT_MASK) & 0x600u
+__host__ __device__ __forceinline__ bool light_can_intersect(int type) { return !light_is_dirac(type) && type != YAFGPU_LIGHT_SPHERE && type != YAFGPU_LIGHT_IES_SOFT; }
+#elif (YAFGPU_LIGHT_MASK) & 0x10u       /* YAFGPU_LIGHT_SPHERE */
 __host__ __device__ __forceinline__ bool light_can_intersect(int type) { return !light_is_dirac(type) && type != YAFGPU_LIGHT_SPHERE; }
 #else
 __host__ __device__ __forceinline__ bool light_can_intersect(int type) { return !light_is_dirac(type); }

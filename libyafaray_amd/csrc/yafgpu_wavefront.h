@@ -345,6 +345,105 @@ YG_DEV bool portallight_intersect(const DevScene &sc, const yafgpu_light &l, V3 
 	return true;
 }
 
+// ---- IesLight, light_ies.cc: a point light whose intensity is a measured table over two angles (IesData, util_ies.h).  The light's tables
+// are in DevScene::lgeo from float ies_first on: the horizontal map, the vertical map, the table row-major by horizontal angle.
+// The interval i of a strictly increasing map with map[i] <= ang < map[i + 1], by bisection; 0 where there is none (an angle below the first
+// entry, at or beyond the last one, or a NaN).  The reference's linear scans (util_ies.h:93-108) find the same interval; they also read
+// map[n] at their last step, one past the array, which is left out here: unless that stray value lies above the angle they leave 0 too.
+YG_DEV int ies_cell(const float *map, int n, float ang)
+{
+	if(!(map[0] <= ang && ang < map[n - 1])) return 0;
+	int lo = 0, hi = n - 1;
+	while(hi - lo > 1)
+	{
+		const int mid = (lo + hi) >> 1;
+		if(map[mid] <= ang) lo = mid; else hi = mid;
+	}
+	return lo;
+}
+// IesData::getRadiance, util_ies.h:65-131; h_ang and v_ang in degrees
+YG_DEV float ies_radiance(const yafgpu_light &l, const float *pool, float h_ang, float v_ang)
+{
+	const int n_hor = l.ies_n_hor, n_vert = l.ies_n_vert;
+	const float *hor = pool, *vert = pool + n_hor, *tab = vert + n_vert;
+	float ang_1, ang_2;
+	if(l.ies_type == 1) { ang_1 = h_ang; ang_2 = v_ang; }
+	else
+	{
+		ang_1 = v_ang; ang_2 = h_ang;
+		if(l.ies_type == 2)
+		{
+			ang_1 += 90.f;
+			if(ang_1 > 360.f) ang_1 -= 360.f;
+		}
+	}
+	if(ang_1 > 180.f && hor[n_hor - 1] <= 180.f) ang_1 = 360.f - ang_1;
+	if(ang_1 > 90.f && hor[n_hor - 1] <= 90.f) ang_1 -= 90.f;
+	if(ang_2 > 90.f && vert[n_vert - 1] <= 90.f) ang_2 -= 90.f;
+	const int x = ies_cell(hor, n_hor, ang_1), y = ies_cell(vert, n_vert, ang_2);
+	float rad;
+	if(ang_1 == hor[x] && ang_2 == vert[y]) rad = tab[x * n_vert + y];
+	else
+	{
+		const float *r_1 = tab + x * n_vert + y, *r_2 = r_1 + n_vert;
+		const float d_x = (ang_1 - hor[x]) / (hor[x + 1] - hor[x]);
+		const float d_y = (ang_2 - vert[y]) / (vert[y + 1] - vert[y]);
+		const float rx_1 = ((1.f - d_x) * r_1[0]) + (d_x * r_2[0]);
+		const float rx_2 = ((1.f - d_x) * r_1[1]) + (d_x * r_2[1]);
+		rad = ((1.f - d_y) * rx_1) + (d_y * rx_2);
+	}
+	return rad * l.ies_max_rad;
+}
+// IesLight::getAngles, :51-61: the WORLD z and y of the direction, not the light's frame (sic); RAD_TO_DEG is a double constant
+YG_DEV void ies_angles(V3 dir, float costheta, float &u, float &v)
+{
+	u = (dir.z >= 1.f) ? 0.f : (float)((double)f_acos(dir.z) * 57.29577951308232087684636);
+	if(dir.y < 0.f) u = 360.f - u;
+	v = (costheta >= 1.f) ? 0.f : (float)((double)f_acos(costheta) * 57.29577951308232087684636);
+}
+// IesLight::illuminate, :63-89 (YAFGPU_LIGHT_IES)
+YG_DEV bool ieslight_illuminate(const DevScene &sc, const yafgpu_light &l, V3 sp_p, Col &col, V3 &wi_dir, float &wi_tmax)
+{
+	V3 ldir = vec3(l.position) - sp_p;
+	const float dist_sqr = ldir.x * ldir.x + ldir.y * ldir.y + ldir.z * ldir.z;
+	const float dist = f_sqrt(dist_sqr);
+	const float idist_sqr = 1.f / dist_sqr;
+	if(dist == 0.f) return false;
+	const float inv = 1.f / dist;
+	ldir.x *= inv; ldir.y *= inv; ldir.z *= inv;
+	const float cosa = dot(vec3(l.direction), ldir);
+	if(cosa < l.cos_angle) return false;
+	float u, v;
+	ies_angles(ldir, cosa, u, v);
+	col = (col3(l.color) * ies_radiance(l, sc.lgeo + l.ies_first, u, v)) * idist_sqr;
+	wi_tmax = dist;
+	wi_dir = ldir;
+	return true;
+}
+// IesLight::illumSample, :91-121 (YAFGPU_LIGHT_IES_SOFT): a direction in the cone around the direction to the light whose opening is the
+// angle to the light's axis; the angles are the sampled direction's with the UNSAMPLED cosine (sic), the pdf is 1 / the table's value
+YG_DEV bool ieslight_illum_sample(const DevScene &sc, const yafgpu_light &l, V3 sp_p, float s_1, float s_2, V3 &wi_dir, float &wi_tmax, float &pdf, Col &col)
+{
+	V3 ldir = vec3(l.position) - sp_p;
+	const float dist_sqr = ldir.x * ldir.x + ldir.y * ldir.y + ldir.z * ldir.z;
+	const float dist = f_sqrt(dist_sqr);
+	const float idist_sqr = 1.f / dist_sqr;
+	if(dist == 0.f) return false;
+	const float inv = 1.f / dist;
+	ldir.x *= inv; ldir.y *= inv; ldir.z *= inv;
+	const float cosa = dot(vec3(l.direction), ldir);
+	if(cosa < l.cos_angle) return false;
+	wi_tmax = dist;
+	wi_dir = sample_cone(ldir, vec3(l.du), vec3(l.dv), cosa, s_1, s_2);
+	float u, v;
+	ies_angles(wi_dir, cosa, u, v);
+	const float rad = ies_radiance(l, sc.lgeo + l.ies_first, u, v);
+	if(rad == 0.f) return false;
+	col = col3(l.color) * idist_sqr;
+	pdf = 1.f / rad;
+	return true;
+}
+
 // Material::isFlat() as doLightEstimation reads it (:105, :189).  Off sp.material_: under a mask that is the mask's, false, while the chosen
 // material's own eval keeps its flag (yafgpu_material::flat 2).  Masks live in kernels with textures only; the others test the word as before.
 YG_DEV bool wf_is_flat(const yafgpu_material &mat) { return YAFGPU_FEAT_TEXTURE ? (mat.flat & 1) != 0 : mat.flat != 0; }
@@ -362,6 +461,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 	{
 		Col lcol;
 		if(YG_LIGHT_IS(light, YAFGPU_LIGHT_DIRECTIONAL)) { if(!directionallight_illuminate(light, sp.p, lcol, r_dir, r_tmax)) return false; }
+		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_IES)) { if(!ieslight_illuminate(ra.sc, light, sp.p, lcol, r_dir, r_tmax)) return false; }
 		else if(!pointlight_illuminate(light, sp.p, lcol, r_dir, r_tmax)) return false;
 		r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
 		const float angle = wf_is_flat(mat) ? 1.f : fabsf(dot(sp.n, r_dir));
@@ -377,6 +477,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPHERE)) { if(!spherelight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col)) return false; }
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_MESH)) { if(!meshlight_illum_sample(ra.sc, light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf)) return false; }
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_PORTAL)) { if(!portallight_illum_sample(ra.sc, light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col)) return false; }
+		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_IES_SOFT)) { if(!ieslight_illum_sample(ra.sc, light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col)) return false; }
 		else if(!arealight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf)) return false;
 		r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
 		if(ls_pdf > 1e-6f)
@@ -412,6 +513,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 	if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN)) { if(!(bs.pdf > 1e-6f && sunlight_intersect(light, r_dir, r_tmax, l_col, light_ipdf))) return false; }
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) { if(!(bs.pdf > 1e-6f && bglight_intersect(light, ra.sc.bg, ra.sc.tex, r_dir, r_tmax, l_col, light_ipdf))) return false; }
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPHERE)) return false;      // (canIntersect() is false: st_dl_eval never asks)
+	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_IES_SOFT)) return false;    // (the same)
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_MESH)) { if(!(bs.pdf > 1e-6f && meshlight_intersect(ra.sc, light, sp.p, r_dir, r_tmin, r_tmax, light_ipdf))) return false; }
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_PORTAL)) { if(!(bs.pdf > 1e-6f && portallight_intersect(ra.sc, light, sp.p, r_dir, r_tmin, r_tmax, light_ipdf, l_col))) return false; }
 	else if(!(bs.pdf > 1e-6f && arealight_intersect(light, sp.p, r_dir, r_tmax, light_ipdf))) return false;

@@ -60,7 +60,7 @@ C_API_SYMBOLS = [
     "yafaray_createInterface", "yafaray_destroyInterface", "yafaray_getLastError", "yafaray_getVersion",
     "yafaray_startScene", "yafaray_startGeometry", "yafaray_endGeometry", "yafaray_getNextFreeId",
     "yafaray_startTriMesh", "yafaray_endTriMesh", "yafaray_addVertex", "yafaray_addNormal", "yafaray_addTriangle",
-    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getCamera", "yafaray_getIntegratorAO", "yafaray_getMaskMaterial", "yafaray_getBlendMaterial", "yafaray_getMaterialTable", "yafaray_addTriangles",
+    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getCamera", "yafaray_getIntegratorAO", "yafaray_getMaskMaterial", "yafaray_getIesLight", "yafaray_getBlendMaterial", "yafaray_getMaterialTable", "yafaray_addTriangles",
     "yafaray_startTriMeshPtr", "yafaray_addVertexWithOrco", "yafaray_addUv", "yafaray_addTriangleWithUv",
     "yafaray_startCurveMesh", "yafaray_endCurveMesh", "yafaray_addCurves", "yafaray_getCurves", "yafaray_addInstance", "yafaray_getInstances",
     "yafaray_paramsSetColorArray", "yafaray_paramsSetMatrix", "yafaray_paramsSetMatrixD", "yafaray_setInputColorSpace",
@@ -116,6 +116,7 @@ def load():
         "yafaray_getIntegratorAO": (ci, [vp, cp, C.POINTER(ci), C.POINTER(ci), C.POINTER(cf), C.POINTER(cf)]),
         "yafaray_getMaskMaterial": (ci, [vp, cp, vp]),
         "yafaray_getBlendMaterial": (ci, [vp, cp, vp]),
+        "yafaray_getIesLight": (ci, [vp, cp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(cf), C.POINTER(cf), C.POINTER(cf), ci]),
         "yafaray_getMaterialTable": (ci, [vp, vp, ci]),
         "yafaray_addTriangles": (ci, [vp, ci, C.POINTER(cf), ci, C.POINTER(ci), vp]),
         "yafaray_startTriMeshPtr": (ci, [vp, C.POINTER(C.c_uint), ci, ci, ci, ci, ci, ci]),
@@ -436,6 +437,17 @@ class Interface:
         self._ok(self._L.yafaray_getMaskMaterial(self._h, _b(name), out.ctypes.data_as(C.c_void_p)), "getMaskMaterial")
         return {"material1": int(out[0]), "material2": int(out[1]), "threshold": out.view(np.float32)[2], "mask_slot": int(out[3]), "n_nodes": int(out[4]),
                 "receive_shadows": bool(out[5]), "visibility": int(out[6]), "bsdf_flags": int(out[7]) & 0xffffffff}
+
+    def getIesLight(self, name):
+        """what createLight parsed from the file of the ieslight `name`, as a dict: the photometric type, the two angle maps in degrees, the
+        table (n_hor, n_vert) as read, max_rad (1 / its largest value) and the largest vertical angle in radians, all float32"""
+        t, nh, nv, mr, mv = C.c_int(0), C.c_int(0), C.c_int(0), C.c_float(0), C.c_float(0)
+        self._ok(self._L.yafaray_getIesLight(self._h, _b(name), C.byref(t), C.byref(nh), C.byref(nv), C.byref(mr), C.byref(mv), None, 0), "getIesLight")
+        n_hor, n_vert = nh.value, nv.value
+        out = np.zeros(n_hor + n_vert + n_hor * n_vert, dtype=np.float32)
+        self._ok(self._L.yafaray_getIesLight(self._h, _b(name), None, None, None, None, None, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "getIesLight")
+        return {"type": t.value, "hor": out[:n_hor].copy(), "vert": out[n_hor:n_hor + n_vert].copy(),
+                "table": out[n_hor + n_vert:].reshape(n_hor, n_vert).copy(), "max_rad": np.float32(mr.value), "max_v_angle": np.float32(mv.value)}
 
     def getBlendMaterial(self, name):
         """what createMaterial parsed for the blend_mat `name`, as a dict: the indices of material1 / material2 in creation order, blend_value
