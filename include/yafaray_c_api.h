@@ -11,7 +11,8 @@
  *
  * Scope: scenes of type "triangle"; materials shinydiffusemat / glossy(as_diffuse) /
  * coated_glossy(as_diffuse) / glass / mirror / light_mat; lights arealight / pointlight; camera perspective (with depth of
- * field); background constant; integrators pathtracing / directlighting; volume integrator none.  Every method of
+ * field); background constant; integrators pathtracing / directlighting; volume integrator none; image files tga / hdr / png written
+ * from the device film (createImageHandler + createImageOutput).  Every method of
  * Interface has a function here: what lies outside the scope fails loudly (0 / NULL + yafaray_getLastError) at the call
  * or at render time — nothing falls back to a CPU path, and nothing is silently dropped.
  */
@@ -207,7 +208,41 @@ yafaray_bool_t yafaray_getTextureImage(yafaray_interface_t *yi, const char *name
 /* refused with a diagnostic (NULL / 0 and yafaray_getLastError): */
 unsigned int yafaray_createObject(yafaray_interface_t *yi, const char *name);               /* :100 */
 void *yafaray_createVolumeRegion(yafaray_interface_t *yi, const char *name);                /* :98 */
-void *yafaray_createImageHandler(yafaray_interface_t *yi, const char *name, yafaray_bool_t add_to_table); /* :99 */
+/* ---- image file output: createImageHandler + ImageOutput + render, the sequence an exporter writes for a file render ----
+ * createImageHandler (:99; TgaHandler::factory, imagehandler_tga.cc:525-556, and its siblings) reads from the current ParamMap: type "tga",
+ * "hdr" / "pic" or "png"; width and height; alpha_channel (false); for_output (true).  The handler is the buffer an image output fills
+ * and the encoder that saves it: 8-bit RGB[A] for tga and png, RGBE for hdr (which has no alpha).  Refused, each with its cause: no type
+ * (so the bare call stays refused); jpg / jpeg / tif / tiff / exr (no encoder in this build); any other type; width or height below 1;
+ * denoiseEnabled (OpenCV); img_grayscale; with add_to_table, a name that is taken.  for_output = false is accepted and yields a handler
+ * without a buffer, which createImageOutput refuses.  No badge is drawn and the height is not extended for one.  The handler is owned by
+ * the interface until clearAll; an image output made from it keeps it alive. */
+typedef struct yafaray_image_handler yafaray_image_handler_t;
+typedef struct yafaray_image_output yafaray_image_output_t;
+yafaray_image_handler_t *yafaray_createImageHandler(yafaray_interface_t *yi, const char *name, yafaray_bool_t add_to_table); /* :99 */
+/* ImageOutput (common/output_image.cc): the render window goes into the handler's image at (border_x, border_y) and flush writes ONE file
+ * under `path` as it is given, as ImageOutput::flush:106-114 does for the combined pass with one view; no log, HTML or statistics file.
+ * Owned by the caller; destroy it after the interface's last render with it.  NULL for a null argument, a handler made with for_output =
+ * false or a negative border.  yafaray_imageOutputLastError: why the output's last flush failed ("" when it did not). */
+yafaray_image_output_t *yafaray_createImageOutput(yafaray_interface_t *yi, yafaray_image_handler_t *handler, const char *path, int border_x, int border_y);
+void yafaray_destroyImageOutput(yafaray_image_output_t *image_output);
+const char *yafaray_imageOutputLastError(const yafaray_image_output_t *image_output);
+/* The image output as a ColorOutput: `user` is the image output, putPixel and flush are the library's own functions, the table lives as long
+ * as the image output.  yafaray_render, yafaray_setOutput2 and yafaray_getRenderedImage recognise the table by its putPixel pointer and
+ * then do not call it per pixel: one kernel converts the device film into the handler's packed pixels (include/yafgpu.h,
+ * yafgpu_scene_film_to_image), one download brings them into the handler's buffer, and flush writes the file.  As output 2 it gets
+ * color_space2 / gamma2.  A caller that drives the table itself, pixel by pixel, gets the same file: putPixel stores at (x + border_x,
+ * y + border_y), dropping what falls outside the image, and flush packs on the host and saves.
+ * yafaray_render refuses, before anything is launched: a render window plus border that does not fit the handler's size (both are named),
+ * and images_autosave_interval_type other than "none".  A file that cannot be written fails the render with the path and the cause. */
+const yafaray_output_t *yafaray_imageOutputCallbacks(yafaray_image_output_t *image_output);
+/* Two functions that need no interface (the cause of a failure: yafaray_filmLastError, per thread).
+ * filmToImage: a film [h][w][5] as yafaray_getFilm / yafaray_readFilmFile return it is uploaded, converted by the output stage and
+ * downloaded into `out`: w * h pixels of `format` (the YAFGPU_IMAGE_* of include/yafgpu.h: 0 four floats, 1 RGBA8, 2 RGBE).  color_space is
+ * "sRGB" | "XYZ" | "LinearRGB" | "Raw_Manual_Gamma".  A merged film file becomes a picture without a render.  Needs a GPU.
+ * writeImageFile: host only.  file_type "tga" | "png" (packed_pixels: w * h RGBA8; without alpha the fourth byte is not written) or
+ * "hdr" | "pic" (w * h RGBE; alpha is ignored). */
+yafaray_bool_t yafaray_filmToImage(const float *film_hw5, int w, int h, const char *color_space, float gamma, yafaray_bool_t alpha, int format, void *out);
+yafaray_bool_t yafaray_writeImageFile(const char *path, const char *file_type, int w, int h, yafaray_bool_t alpha, const void *packed_pixels);
 /* the calls exporters make around a render besides render() itself */
 yafaray_bool_t yafaray_setLoggingAndBadgeSettings(yafaray_interface_t *yi);                 /* :104: accepted; no badge is drawn, no log file written */
 yafaray_bool_t yafaray_setupRenderPasses(yafaray_interface_t *yi);                          /* :105: accepted for the combined pass alone; any other enabled pass is refused */

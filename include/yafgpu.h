@@ -486,6 +486,37 @@ int yafgpu_render_tiles(yafgpu_scene_t *scene, const yafgpu_render_params *rp, f
 /* d_film[h][w][5] = own + right(x-1) + down(y-1) + diag(x-1,y-1), in that fixed order */
 int yafgpu_film_combine(const float *d_planes, float *d_film, int32_t width, int32_t height, void *stream);
 
+/* The output stage (yafgpu_output.hip): a film [height][width][5] becomes the packed pixels of an image, one pixel per lane.  Per
+ * pixel, in ImageFilm::flush's order for the combined pass (imagefilm.cc:737-772): Pixel::normalized, clampRgb0,
+ * colorSpaceFromLinearRgb, alpha clamped to [0, 1]; then one of three packings:
+ *   YAFGPU_IMAGE_FLOAT  four floats r g b a, what a ColorOutput's putPixel receives (16 bytes a pixel)
+ *   YAFGPU_IMAGE_RGBA8  clampRgba01 and (uint8_t)(c * 255.f), a truncation, bytes r g b a; alpha = 0 makes the alpha byte 255
+ *   YAFGPU_IMAGE_RGBE   RgbePixel::operator=(const Rgb &) (imagehandler_util_hdr.h:52-71), bytes r g b e
+ * The image is image_width x image_height pixels, rows outermost; the film lands at (border_x, border_y) and every other pixel is zero.
+ * What the reference's casts leave undefined is defined: a NaN channel packs to the byte 0, and a pixel whose largest colour channel is
+ * not finite packs to four zero bytes in RGBE. */
+#define YAFGPU_IMAGE_FLOAT 0
+#define YAFGPU_IMAGE_RGBA8 1
+#define YAFGPU_IMAGE_RGBE 2
+typedef struct yafgpu_image_desc
+{
+	int32_t width, height;         /* the film: the render window */
+	int32_t color_space;           /* 0 sRGB, 1 XYZ, 2 LinearRGB, 3 Raw_Manual_Gamma */
+	float gamma;                   /* Raw_Manual_Gamma alone reads it */
+	int32_t alpha;                 /* YAFGPU_IMAGE_RGBA8 alone reads it */
+	int32_t format;                /* YAFGPU_IMAGE_* */
+	int32_t image_width, image_height, border_x, border_y;
+} yafgpu_image_desc;
+/* bytes of an image of that format and size; 0 for a size or a format out of range */
+uint64_t yafgpu_image_bytes(int32_t format, int32_t width, int32_t height);
+/* d_film and d_image are device pointers (d_image: yafgpu_image_bytes of the image's size, aligned to 16 bytes); one launch,
+ * asynchronous on `stream`.  Sizes and the border are checked before anything is launched. */
+int yafgpu_film_to_image(const float *d_film, const yafgpu_image_desc *desc, void *d_image, void *stream);
+/* The same for the film the scene's render targets hold after yafgpu_render_to_host / yafgpu_render_passes_to_host (desc->width and
+ * height must be that render's), with no upload: converted on the device, downloaded into h_image (host memory), synchronised.
+ * -13 when the scene holds no finished film of that size (nothing rendered yet, or a render that failed). */
+int yafgpu_scene_film_to_image(yafgpu_scene_t *scene, const yafgpu_image_desc *desc, void *h_image);
+
 /* Convenience: allocate, render, combine, copy the film to host memory, synchronise. */
 /* TiledIntegrator::render (integrator_tiled.cc:116-258): pass 0 with rp->aa_minsamples samples, then aa->passes - 1
    adaptive passes; between passes ImageFilm::nextPass (imagefilm.cc:270-480) picks the pixels to resample from the

@@ -5,7 +5,7 @@ The package is a thin host-side mirror of the reference's `yafaray4::Interface`
 happens in hand-written HIP kernels (csrc/yafgpu_device.hip); there is no CPU fallback: loading
 fails loudly when the HIP library is missing, rendering fails loudly without a GPU.
 """
-from .interface import Interface, YafaRayError, lib_path  # noqa: F401
+from .interface import Interface, ImageOutput, YafaRayError, lib_path  # noqa: F401
 from . import scenes  # noqa: F401
 
-__all__ = ["Interface", "YafaRayError", "lib_path", "scenes"]
+__all__ = ["Interface", "ImageOutput", "YafaRayError", "lib_path", "scenes"]

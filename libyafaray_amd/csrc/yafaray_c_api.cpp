@@ -28,6 +28,7 @@
 #include <list>
 #include <map>
 #include <memory>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -113,6 +114,29 @@ struct yafaray_material { yafgpu_material m; int index; std::vector<yafgpu_node>
 static_assert(sizeof(yafgpu_material) == 384, "yafaray_getMaterialTable hands out 96-word records");
 struct yafaray_texture { yafgpu_texture t; int index; std::vector<float> texels; };            // texels: height * width * 4, as ImageHandler::getPixel returns them
 struct yafaray_light { yafgpu_light l; unsigned int object = 0; yafies::Data ies; };      // object: a mesh light's or a portal's mesh (obj_id_ / object_id_), resolved at prepareRender; ies: an ieslight's parsed file
+// An image handler made for output (TgaHandler / HdrHandler / PngHandler after initForOutput): the image an output fills and the encoder
+// that saves it.  `packed` is what the encoder takes, four bytes a pixel (RGBA8 for tga and png, RGBE for hdr): the device's output stage
+// writes it whole; a caller that delivers pixel by pixel fills `rgba` instead, which flush packs on the host (`driven`)
+struct yafaray_image_handler
+{
+	enum Type { Tga, Hdr, Png } type = Tga;
+	int width = 0, height = 0; bool alpha = false, for_output = true;
+	std::vector<uint8_t> packed;       // height * width * 4
+	std::vector<float> rgba;           // height * width * 4, made at the first putPixel
+	bool driven = false;
+};
+// ImageOutput (common/output_image.cc): a handler, the file name and the border; `table` is what yafaray_imageOutputCallbacks hands out
+struct yafaray_image_output
+{
+	std::shared_ptr<yafaray_image_handler> ih;
+	std::string path, err;
+	int bx = 0, by = 0;
+	yafaray_output_t table{};
+};
+// The device's output stage (yafgpu_output.hip, and the scene's half of it in the device unit).  Weak: a build of the host side without the
+// device unit (the sanitizer build's stub) still links and loads, and an image output then fails with "no device unit"
+extern "C" int yafgpu_film_to_image(const float *d_film, const yafgpu_image_desc *desc, void *d_image, void *stream) __attribute__((weak));
+extern "C" int yafgpu_scene_film_to_image(yafgpu_scene_t *scene, const yafgpu_image_desc *desc, void *h_image) __attribute__((weak));
 struct yafaray_camera { CameraCfg c; };
 struct yafaray_background { BackgroundCfg b; };
 struct yafaray_integrator { IntegratorCfg c; };
@@ -134,6 +158,8 @@ struct yafaray_interface
 	std::map<std::string, std::unique_ptr<yafaray_camera>> cameras;
 	std::map<std::string, std::unique_ptr<yafaray_background>> backgrounds;
 	std::map<std::string, std::unique_ptr<yafaray_integrator>> integrators;
+	std::map<std::string, std::shared_ptr<yafaray_image_handler>> image_handlers;      // shared with the image outputs made from them
+	std::vector<std::shared_ptr<yafaray_image_handler>> loose_image_handlers;          // createImageHandler with add_to_table = false
 	// scene state (scene.cc:110-131): 0 ready, 1 geometry, 2 object; 3 is the reference's object state too, with a curve as the open object
 	int state = -1;
 	std::map<unsigned int, Mesh> meshes;
@@ -1532,7 +1558,123 @@ int yafaray_getInstances(yafaray_interface_t *yi, void *out, int max_instances)
 }
 unsigned int yafaray_createObject(yafaray_interface_t *yi, const char *) { fail(yi, "createObject: parametric objects (sphere) are outside the GPU path's scope (triangle meshes only)"); return 0u; }
 void *yafaray_createVolumeRegion(yafaray_interface_t *yi, const char *) { fail(yi, "createVolumeRegion: volume regions are outside the GPU path's scope (volume integrator \"none\" only)"); return nullptr; }
-void *yafaray_createImageHandler(yafaray_interface_t *yi, const char *, yafaray_bool_t) { fail(yi, "createImageHandler: image files are written by the caller from the ColorOutput callbacks; no image handlers on the GPU path"); return nullptr; }
+// RenderEnvironment::createImageHandler (environment.cc) -> TgaHandler::factory (imagehandler_tga.cc:525-556), HdrHandler::factory,
+// PngHandler::factory: the same parameters in all three
+yafaray_image_handler_t *yafaray_createImageHandler(yafaray_interface_t *yi, const char *name, yafaray_bool_t add_to_table)
+{
+	const ParamMap &p = yi->params;
+	std::string type;
+	if(!name) { fail(yi, "createImageHandler: null name"); return nullptr; }
+	if(!p.get("type", type)) { fail(yi, "createImageHandler: type of image handler not specified (tga, hdr, pic and png files are written)"); return nullptr; }
+	auto ih = std::make_shared<yafaray_image_handler>();
+	if(type == "tga") ih->type = yafaray_image_handler::Tga;
+	else if(type == "hdr" || type == "pic") ih->type = yafaray_image_handler::Hdr;
+	else if(type == "png") ih->type = yafaray_image_handler::Png;
+	else if(type == "jpg" || type == "jpeg" || type == "tif" || type == "tiff" || type == "exr")
+	{ fail(yi, "createImageHandler: image type \"" + type + "\" has no encoder in this build (tga, hdr, pic and png files are written; JPEG, TIFF and OpenEXR need libraries this build lacks)"); return nullptr; }
+	else { fail(yi, "createImageHandler: unknown image type \"" + type + "\" (tga, hdr, pic and png files are written)"); return nullptr; }
+	if(add_to_table && yi->image_handlers.count(name)) { fail(yi, std::string("createImageHandler: an image handler named \"") + name + "\" already exists"); return nullptr; }
+	int width = 0, height = 0; bool with_alpha = false, for_output = true, grayscale = false, denoise = false;
+	p.get("width", width); p.get("height", height); p.get("alpha_channel", with_alpha); p.get("for_output", for_output);
+	p.get("denoiseEnabled", denoise); p.get("img_grayscale", grayscale);
+	if(denoise) { fail(yi, "createImageHandler: denoiseEnabled needs OpenCV, which this build lacks"); return nullptr; }
+	if(grayscale) { fail(yi, "createImageHandler: img_grayscale: grey image files are not written (the combined pass is a colour image)"); return nullptr; }
+	ih->for_output = for_output;
+	if(for_output)
+	{
+		if(width < 1 || height < 1) { fail(yi, "createImageHandler: width " + std::to_string(width) + " and height " + std::to_string(height) + " must both be at least 1"); return nullptr; }
+		if((uint64_t)width * (uint64_t)height > (1ull << 26)) { fail(yi, "createImageHandler: " + std::to_string(width) + " x " + std::to_string(height) + " is more than the 2^26 pixels an image may have"); return nullptr; }
+		if(ih->type == yafaray_image_handler::Tga && (width > 65535 || height > 65535)) { fail(yi, "createImageHandler: a TGA file holds at most 65535 pixels a side"); return nullptr; }
+		ih->width = width; ih->height = height;
+		ih->alpha = with_alpha && ih->type != yafaray_image_handler::Hdr;      // (HdrHandler::saveToFile: "Ignoring alpha channel")
+		try { ih->packed.assign((size_t)width * (size_t)height * 4, (uint8_t)0); }
+		catch(...) { fail(yi, "createImageHandler: out of memory"); return nullptr; }
+	}
+	if(add_to_table) yi->image_handlers[name] = ih; else yi->loose_image_handlers.push_back(ih);
+	return ih.get();
+}
+
+// ---- ImageOutput (common/output_image.cc) ---------------------------------------------------------------------------------------
+namespace {
+
+// ImageOutput::flush:106-114 for the combined pass with one view: the handler's saveToFile under the name as given.  `driven`: the pixels
+// came one by one and are packed here, as the device's output stage would have packed them
+bool image_output_save(yafaray_image_output *io)
+{
+	yafaray_image_handler &ih = *io->ih;
+	io->err.clear();
+	try
+	{
+		if(ih.driven)
+		{
+			const size_t n = (size_t)ih.width * (size_t)ih.height;
+			for(size_t i = 0; i < n; ++i)
+			{
+				if(ih.type == yafaray_image_handler::Hdr) yafimg::pack_rgbe(&ih.rgba[4 * i], &ih.packed[4 * i]);
+				else yafimg::pack_rgba8(&ih.rgba[4 * i], ih.alpha, &ih.packed[4 * i]);
+			}
+		}
+		switch(ih.type)
+		{
+			case yafaray_image_handler::Tga: return yafimg::write_tga(io->path, ih.width, ih.height, ih.alpha, ih.packed.data(), io->err);
+			case yafaray_image_handler::Hdr: return yafimg::write_hdr(io->path, ih.width, ih.height, ih.packed.data(), io->err);
+			default: return yafimg::write_png(io->path, ih.width, ih.height, ih.alpha, ih.packed.data(), io->err);
+		}
+	}
+	catch(...) {}
+	try { io->err = "image file '" + io->path + "': out of memory"; } catch(...) {}
+	return false;
+}
+// ImageOutput::putPixel (:39-45): image_->putPixel(x + b_x_, y + b_y_, col); a pixel outside the image is dropped
+yafaray_bool_t image_output_put_pixel(void *user, int, int x, int y, float r, float g, float b, float a)
+{
+	yafaray_image_output *io = (yafaray_image_output *)user;
+	if(!io) return 0;
+	yafaray_image_handler &ih = *io->ih;
+	const int64_t px = (int64_t)x + io->bx, py = (int64_t)y + io->by;
+	if(px < 0 || py < 0 || px >= ih.width || py >= ih.height) return 1;
+	try { if(ih.rgba.empty()) ih.rgba.assign((size_t)ih.width * (size_t)ih.height * 4, 0.f); }
+	catch(...) { return 0; }
+	ih.driven = true;
+	float *o = &ih.rgba[4 * ((size_t)py * (size_t)ih.width + (size_t)px)];
+	o[0] = r; o[1] = g; o[2] = b; o[3] = a;
+	return 1;
+}
+void image_output_flush(void *user, int num_view)
+{
+	yafaray_image_output *io = (yafaray_image_output *)user;
+	if(io && num_view == 0) (void)image_output_save(io);
+}
+// the image output behind a callback table: the table is recognised by its putPixel pointer
+yafaray_image_output *image_output_of(const yafaray_output_t *out)
+{
+	return (out && out->putPixel == image_output_put_pixel) ? (yafaray_image_output *)out->user : nullptr;
+}
+int color_space_code(const std::string &cs) { return cs == "sRGB" ? 0 : (cs == "XYZ" ? 1 : (cs == "Raw_Manual_Gamma" ? 3 : 2)); }      // to_output_space's cases: anything else stays linear
+
+} // namespace
+
+yafaray_image_output_t *yafaray_createImageOutput(yafaray_interface_t *yi, yafaray_image_handler_t *handler, const char *path, int border_x, int border_y)
+{
+	if(!yi) return nullptr;
+	if(!handler || !path || !*path) { fail(yi, "createImageOutput: null handler or empty path"); return nullptr; }
+	std::shared_ptr<yafaray_image_handler> ih;
+	for(const auto &kv : yi->image_handlers) if(kv.second.get() == handler) ih = kv.second;
+	for(const auto &h : yi->loose_image_handlers) if(h.get() == handler) ih = h;
+	if(!ih) { fail(yi, "createImageOutput: the handler is not one of this interface's image handlers (clearAll releases them)"); return nullptr; }
+	if(!ih->for_output) { fail(yi, "createImageOutput: the image handler was made with for_output = false: it has no image to fill"); return nullptr; }
+	if(border_x < 0 || border_y < 0) { fail(yi, "createImageOutput: negative border (" + std::to_string(border_x) + ", " + std::to_string(border_y) + ")"); return nullptr; }
+	yafaray_image_output *io = new(std::nothrow) yafaray_image_output();
+	if(!io) { fail(yi, "createImageOutput: out of memory"); return nullptr; }
+	try { io->ih = ih; io->path = path; }
+	catch(...) { delete io; fail(yi, "createImageOutput: out of memory"); return nullptr; }
+	io->bx = border_x; io->by = border_y;
+	io->table.user = io; io->table.putPixel = image_output_put_pixel; io->table.flush = image_output_flush;
+	return io;
+}
+void yafaray_destroyImageOutput(yafaray_image_output_t *image_output) { delete image_output; }
+const char *yafaray_imageOutputLastError(const yafaray_image_output_t *image_output) { return image_output ? image_output->err.c_str() : "null image output"; }
+const yafaray_output_t *yafaray_imageOutputCallbacks(yafaray_image_output_t *image_output) { return image_output ? &image_output->table : nullptr; }
 
 yafaray_bool_t yafaray_addTriangles(yafaray_interface_t *yi, int n_verts, const float *verts, int n_tris, const int *indices, const yafaray_material_t *mat)
 {
@@ -2133,6 +2275,7 @@ void yafaray_clearAll(yafaray_interface_t *yi)
 {
 	if(yi->gpu) { yafgpu_scene_destroy(yi->gpu); yi->gpu = nullptr; }
 	yi->materials.clear(); yi->material_order.clear(); yi->textures.clear(); yi->texture_order.clear(); yi->lights.clear(); yi->light_order.clear();
+	yi->image_handlers.clear(); yi->loose_image_handlers.clear();      // (an image output keeps its handler)
 	yi->cameras.clear(); yi->backgrounds.clear(); yi->integrators.clear(); yi->meshes.clear(); yi->instances.clear(); yi->curves.clear(); yi->cur_curve = nullptr; yi->last_is_curve = false;
 	yi->params.dicc.clear(); yi->eparams.clear(); yi->cparams = &yi->params;
 	yi->state = -1; yi->prepared = false; yi->scene_dirty = true; yi->geometry_changed = true; yi->film.clear();
@@ -2674,9 +2817,58 @@ static void to_output_space(const std::string &cs, float gamma, float c[4])
 	}
 	if(c[3] < 0.f) c[3] = 0.f; else if(c[3] > 1.f) c[3] = 1.f;
 }
-static void deliver_to(yafaray_interface_t *yi, const yafaray_output_t *out, const std::string &cs, float gamma)
+// why a render window at the output's border does not fit its handler's image ("" when it does): both sizes are named
+static std::string image_output_misfit(const yafaray_image_output *io, int w, int h)
 {
-	if(!out) return;
+	const yafaray_image_handler &ih = *io->ih;
+	if((int64_t)io->bx + w <= ih.width && (int64_t)io->by + h <= ih.height) return std::string();
+	return "the render window of " + std::to_string(w) + " x " + std::to_string(h) + " at the border (" + std::to_string(io->bx) + ", " + std::to_string(io->by) +
+	       ") does not fit the image handler's " + std::to_string(ih.width) + " x " + std::to_string(ih.height) + " (image file '" + io->path + "')";
+}
+// An upload of a host film, the output stage, a download: yafaray_filmToImage, and an image output whose scene holds the film no more
+static bool film_to_image_uploaded(const float *film, const yafgpu_image_desc &desc, void *out, size_t out_bytes, std::string &err)
+{
+	if(!yafgpu_film_to_image) { err = "no device unit in this build (the output stage is a device kernel)"; return false; }
+	const size_t film_bytes = (size_t)desc.width * (size_t)desc.height * 5 * sizeof(float);
+	void *d_film = nullptr, *d_image = nullptr;
+	hipError_t e = hipMalloc(&d_film, film_bytes);
+	if(e == hipSuccess) e = hipMalloc(&d_image, out_bytes);
+	if(e == hipSuccess) e = hipMemcpy(d_film, film, film_bytes, hipMemcpyHostToDevice);
+	bool ok = e == hipSuccess;
+	if(!ok) err = std::string("device memory for the film and the image: ") + hipGetErrorString(e);
+	if(ok && yafgpu_film_to_image((const float *)d_film, &desc, d_image, nullptr)) { ok = false; err = yafgpu_last_error(); }
+	if(ok && (e = hipMemcpy(out, d_image, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess) { ok = false; err = std::string("image download: ") + hipGetErrorString(e); }
+	if(d_film) (void)hipFree(d_film);
+	if(d_image) (void)hipFree(d_image);
+	return ok;
+}
+// An image output as the output of a render: one kernel launch on the film the scene's render targets hold, one download into the
+// handler's buffer, one file (ImageFilm::flush + ImageOutput::flush for the combined pass)
+static bool deliver_image(yafaray_interface_t *yi, yafaray_image_output *io, const std::string &cs, float gamma)
+{
+	yafaray_image_handler &ih = *io->ih;
+	const std::string misfit = image_output_misfit(io, yi->rp.width, yi->rp.height);
+	if(!misfit.empty()) return fail(yi, "image output: " + misfit);
+	yafgpu_image_desc d{};
+	d.width = yi->rp.width; d.height = yi->rp.height; d.color_space = color_space_code(cs); d.gamma = gamma; d.alpha = ih.alpha ? 1 : 0;
+	d.format = ih.type == yafaray_image_handler::Hdr ? YAFGPU_IMAGE_RGBE : YAFGPU_IMAGE_RGBA8;
+	d.image_width = ih.width; d.image_height = ih.height; d.border_x = io->bx; d.border_y = io->by;
+	if(!yafgpu_scene_film_to_image) return fail(yi, "image output: no device unit in this build (the output stage is a device kernel)");
+	const int rc = yi->gpu ? yafgpu_scene_film_to_image(yi->gpu, &d, ih.packed.data()) : -13;
+	if(rc == -13)
+	{	// the scene holds no film of this frame (-13): it was rebuilt or released since the render, so the host's copy of the film goes up again
+		std::string why;
+		if(!film_to_image_uploaded(yi->film.data(), d, ih.packed.data(), ih.packed.size(), why)) return fail(yi, "image output: " + why);
+	}
+	else if(rc) return fail(yi, std::string("image output: ") + yafgpu_last_error());
+	ih.driven = false;
+	if(!image_output_save(io)) return fail(yi, "image output: " + io->err);
+	return true;
+}
+static bool deliver_to(yafaray_interface_t *yi, const yafaray_output_t *out, const std::string &cs, float gamma)
+{
+	if(!out) return true;
+	if(yafaray_image_output *io = image_output_of(out)) return deliver_image(yi, io, cs, gamma);
 	const int w = yi->rp.width, h = yi->rp.height;
 	if(out->putPixel)
 	{
@@ -2692,11 +2884,13 @@ static void deliver_to(yafaray_interface_t *yi, const yafaray_output_t *out, con
 			}
 	}
 	if(out->flush) out->flush(out->user, 0);
+	return true;
 }
-static void deliver(yafaray_interface_t *yi, const yafaray_output_t *out)
+static bool deliver(yafaray_interface_t *yi, const yafaray_output_t *out)
 {
-	deliver_to(yi, out, yi->color_space, yi->gamma);
-	if(yi->has_output2) deliver_to(yi, &yi->output2, yi->color_space2, yi->gamma2);      // Interface::setOutput2, interface.cc:420-423
+	if(!deliver_to(yi, out, yi->color_space, yi->gamma)) return false;
+	if(yi->has_output2) return deliver_to(yi, &yi->output2, yi->color_space2, yi->gamma2);      // Interface::setOutput2, interface.cc:420-423
+	return true;
 }
 
 // ---- the rest of Interface's surface (interface.h:62-128): honoured where it touches this path, accepted where it only
@@ -2881,6 +3075,19 @@ static yafaray_bool_t render_checked(yafaray_interface_t *yi, const yafaray_outp
 	if(film_save && yi->shard_count > 1)
 		return fail(yi, "render: film_save_load = \"" + film_mode + "\" with a film path on a sharded frame (shard_count " + std::to_string(yi->shard_count) +
 		                "): a rank's film is its share of the frame, not a film of the frame");
+	// image outputs: what they cannot take is refused here, before anything is launched
+	for(const yafaray_output_t *o : {output, yi->has_output2 ? (const yafaray_output_t *)&yi->output2 : nullptr})
+		if(const yafaray_image_output *io = image_output_of(o))
+		{
+			std::string images_autosave = "none";
+			yi->params.get("images_autosave_interval_type", images_autosave);
+			if(images_autosave != "none")
+				return fail(yi, "render: images_autosave_interval_type = \"" + images_autosave + "\": saving the image between passes or on a timer is not supported by the GPU path (set it to \"none\")");
+			int width = 320, height = 240;      // read_render_setup's defaults
+			yi->params.get("width", width); yi->params.get("height", height);
+			const std::string misfit = image_output_misfit(io, width, height);
+			if(!misfit.empty()) return fail(yi, "render: " + misfit);
+		}
 	if(progress && progress->init) progress->init(progress->user, 100);
 	if(progress && progress->setTag) progress->setTag(progress->user, "Rendering...");
 	if(!yafaray_prepareRender(yi)) return 0;
@@ -2940,7 +3147,7 @@ static yafaray_bool_t render_checked(yafaray_interface_t *yi, const yafaray_outp
 	if(!source.warnings.empty()) yi->err = source.warnings;      // the render stands; the warnings are there to be read
 	if(progress && progress->update) progress->update(progress->user, 100);
 	if(progress && progress->done) progress->done(progress->user);
-	deliver(yi, output);
+	if(!deliver(yi, output)) { yi->err = "render: " + yi->err; return 0; }      // an image file that could not be written fails the render
 	return 1;
 }
 
@@ -2988,6 +3195,47 @@ yafaray_bool_t yafaray_readFilmFile(const char *path, yafaray_film_header_t *hdr
 	return 0;
 }
 
+// a film the caller holds -> packed pixels, through the device's output stage (no interface, no scene)
+yafaray_bool_t yafaray_filmToImage(const float *film_hw5, int w, int h, const char *color_space, float gamma, yafaray_bool_t alpha, int format, void *out)
+{
+	try
+	{
+		g_film_err.clear();
+		if(!film_hw5 || !out || !color_space) { g_film_err = "filmToImage: null argument"; return 0; }
+		if(w < 1 || h < 1 || (uint64_t)w * (uint64_t)h > (1ull << 26)) { g_film_err = "filmToImage: film size " + std::to_string(w) + " x " + std::to_string(h) + " out of range (1 x 1 to 2^26 pixels)"; return 0; }
+		if(format != YAFGPU_IMAGE_FLOAT && format != YAFGPU_IMAGE_RGBA8 && format != YAFGPU_IMAGE_RGBE) { g_film_err = "filmToImage: unknown pixel format " + std::to_string(format); return 0; }
+		const std::string cs = color_space;
+		if(cs != "sRGB" && cs != "XYZ" && cs != "LinearRGB" && cs != "Raw_Manual_Gamma") { g_film_err = "filmToImage: unknown colour space \"" + cs + "\""; return 0; }
+		yafgpu_image_desc d{};
+		d.width = d.image_width = w; d.height = d.image_height = h; d.color_space = color_space_code(cs); d.gamma = gamma; d.alpha = alpha ? 1 : 0; d.format = format;
+		const size_t out_bytes = (size_t)w * (size_t)h * (format == YAFGPU_IMAGE_FLOAT ? 16u : 4u);
+		std::string why;
+		if(film_to_image_uploaded(film_hw5, d, out, out_bytes, why)) return 1;
+		g_film_err = "filmToImage: " + why;
+	}
+	catch(...) {}
+	return 0;
+}
+// packed pixels -> an image file (host only)
+yafaray_bool_t yafaray_writeImageFile(const char *path, const char *file_type, int w, int h, yafaray_bool_t alpha, const void *packed_pixels)
+{
+	try
+	{
+		g_film_err.clear();
+		if(!path || !file_type) { g_film_err = "writeImageFile: null argument"; return 0; }
+		const std::string type = file_type;
+		bool ok = false;
+		if(type == "tga") ok = yafimg::write_tga(path, w, h, alpha != 0, (const uint8_t *)packed_pixels, g_film_err);
+		else if(type == "hdr" || type == "pic") ok = yafimg::write_hdr(path, w, h, (const uint8_t *)packed_pixels, g_film_err);
+		else if(type == "png") ok = yafimg::write_png(path, w, h, alpha != 0, (const uint8_t *)packed_pixels, g_film_err);
+		else g_film_err = "image type \"" + type + "\" has no encoder (tga, hdr, pic and png files are written)";
+		if(!ok) g_film_err = "writeImageFile: " + g_film_err;
+		return ok ? 1 : 0;
+	}
+	catch(...) {}
+	return 0;
+}
+
 void yafaray_abort(yafaray_interface_t *yi) { yi->abort_flag = 1; }
 void yafaray_internal_set_error(yafaray_interface_t *yi, const char *msg) { if(yi) yi->err = msg ? msg : ""; }
 void yafaray_internal_set_base_dir(yafaray_interface_t *yi, const char *dir) { if(yi) yi->base_dir = dir ? dir : ""; }
@@ -2995,7 +3243,7 @@ void yafaray_internal_set_base_dir(yafaray_interface_t *yi, const char *dir) { i
 yafaray_bool_t yafaray_getRenderedImage(yafaray_interface_t *yi, int num_view, const yafaray_output_t *output)
 {
 	if(num_view != 0 || yi->film.empty()) return fail(yi, "getRenderedImage: nothing rendered");
-	deliver(yi, output);
+	if(!deliver(yi, output)) { yi->err = "getRenderedImage: " + yi->err; return 0; }
 	return 1;
 }
 yafaray_bool_t yafaray_getFilm(yafaray_interface_t *yi, float *film, int width, int height)

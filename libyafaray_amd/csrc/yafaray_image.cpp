@@ -16,6 +16,7 @@
 #include "yafaray_image.h"
 
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -555,6 +556,192 @@ static bool load_checked(const std::string &path, Image &img, std::string &err)
 	}
 	err = "image format \"" + ext + "\" has no decoder in this build (TGA, HDR and PNG are read; JPEG, TIFF and OpenEXR need libraries this image lacks)";
 	return false;
+}
+
+// ---- image file encoders -------------------------------------------------------------------------------------------------------
+void pack_rgba8(const float c[4], bool alpha, uint8_t out[4])
+{
+	for(int k = 0; k < 4; ++k)
+	{
+		float v = c[k];
+		if(v < 0.f) v = 0.f; else if(v > 1.f) v = 1.f;       // clampRgba01 (color.h:100-105, :166-170)
+		out[k] = v == v ? (uint8_t)(v * 255.f) : (uint8_t)0;
+	}
+	if(!alpha) out[3] = 255;
+}
+void pack_rgbe(const float c[4], uint8_t out[4])
+{
+	const float v = std::max(c[0], std::max(c[1], c[2]));      // Rgb::maximum
+	out[0] = out[1] = out[2] = out[3] = 0;
+	if((double)v < 1e-32 || !std::isfinite(v)) return;
+	int e;
+	const float s = (float)((double)std::frexp(v, &e) * 255.9999 / (double)v);
+	for(int k = 0; k < 3; ++k) out[k] = c[k] > 0.f ? (uint8_t)(c[k] * s) : (uint8_t)0;      // (a negative or NaN channel: undefined in the reference, zero here)
+	out[3] = (uint8_t)(e + 128);
+}
+
+namespace {
+
+bool encode_size_ok(const std::string &path, const char *fmt, int w, int h, int max_side, const void *pixels, std::string &err)
+{
+	if(w < 1 || h < 1) { err = std::string(fmt) + " file '" + path + "': image size " + std::to_string(w) + " x " + std::to_string(h) + " is below 1 x 1"; return false; }
+	if(w > max_side || h > max_side) { err = std::string(fmt) + " file '" + path + "': image size " + std::to_string(w) + " x " + std::to_string(h) + " is more than the format holds (" + std::to_string(max_side) + " a side)"; return false; }
+	if((uint64_t)w * (uint64_t)h > kMaxPixels) { err = std::string(fmt) + " file '" + path + "': image size " + std::to_string(w) + " x " + std::to_string(h) + " out of range (at most " + std::to_string(kMaxPixels) + " pixels)"; return false; }
+	if(!pixels) { err = std::string(fmt) + " file '" + path + "': no pixels to write"; return false; }
+	return true;
+}
+
+bool write_bytes(const std::string &path, const char *fmt, const std::vector<uint8_t> &data, std::string &err)
+{
+	FILE *fp = std::fopen(path.c_str(), "wb");
+	if(!fp) { err = std::string(fmt) + " file '" + path + "' cannot be created: " + std::strerror(errno); return false; }
+	const size_t put = data.empty() ? 0 : std::fwrite(data.data(), 1, data.size(), fp);
+	const int write_errno = errno;
+	const bool closed = std::fclose(fp) == 0;
+	if(put != data.size()) { err = std::string(fmt) + " file '" + path + "': short write (" + std::to_string(put) + " of " + std::to_string(data.size()) + " bytes): " + std::strerror(write_errno); return false; }
+	if(!closed) { err = std::string(fmt) + " file '" + path + "': write error at close: " + std::strerror(errno); return false; }
+	return true;
+}
+
+bool write_tga_checked(const std::string &path, int w, int h, bool alpha, const uint8_t *px, std::string &err)
+{
+	if(!encode_size_ok(path, "TGA", w, h, 65535, px, err)) return false;
+	static const char id[] = "Image rendered with YafaRay";
+	const size_t id_len = sizeof id - 1, bpp = alpha ? 4 : 3, n = (size_t)w * (size_t)h;
+	std::vector<uint8_t> d(18 + id_len + n * bpp + 26, (uint8_t)0);
+	d[0] = (uint8_t)id_len; d[2] = 2;                                  // UncTrueColor
+	d[12] = (uint8_t)(w & 0xff); d[13] = (uint8_t)(w >> 8); d[14] = (uint8_t)(h & 0xff); d[15] = (uint8_t)(h >> 8);
+	d[16] = alpha ? 32 : 24; d[17] = (uint8_t)(0x20 | (alpha ? 0x08 : 0x00));      // TL | ALPHA_8
+	std::memcpy(&d[18], id, id_len);
+	uint8_t *o = &d[18 + id_len];
+	for(size_t i = 0; i < n; ++i, o += bpp)
+	{
+		const uint8_t *p = px + 4 * i;
+		o[0] = p[2]; o[1] = p[1]; o[2] = p[0];
+		if(alpha) o[3] = p[3];
+	}
+	// TgaFooter: two zero offsets, then "TRUEVISION-XFILE." and its terminator (18 bytes)
+	std::memcpy(o + 8, "TRUEVISION-XFILE.", 18);
+	return write_bytes(path, "TGA", d, err);
+}
+
+// HdrHandler::writeScanline (imagehandler_hdr.cc:462-533) for one channel of a scanline of w pixels, four bytes apart.  The reference
+// compares scanline[beg_run + run_count] before it checks beg_run + run_count < w, and so reads one or two pixels past the scanline;
+// whatever it reads there, the bound check that follows ends the loop, so checking the bound first writes the same bytes
+void hdr_channel_runs(const uint8_t *scan, int w, std::vector<uint8_t> &out)
+{
+	auto at = [scan](int x) { return scan[(size_t)x * 4]; };
+	int cur = 0;
+	while(cur < w)
+	{
+		int beg_run = cur, run_count = 0, old_run_count = 0;
+		while(run_count < 4 && beg_run < w)
+		{
+			beg_run += run_count;
+			old_run_count = run_count;
+			run_count = 1;
+			while(beg_run + run_count < w && run_count < 127 && at(beg_run) == at(beg_run + run_count)) ++run_count;
+		}
+		if(old_run_count > 1 && old_run_count == beg_run - cur)
+		{	// a short run
+			out.push_back((uint8_t)(128 + old_run_count)); out.push_back(at(cur));
+			cur = beg_run;
+		}
+		while(cur < beg_run)
+		{	// bytes that are no run, 128 at the most in one block
+			const int nonrun_count = std::min(128, beg_run - cur);
+			out.push_back((uint8_t)nonrun_count);
+			for(int i = 0; i < nonrun_count; ++i) out.push_back(at(cur + i));
+			cur += nonrun_count;
+		}
+		if(run_count >= 4)
+		{
+			out.push_back((uint8_t)(128 + run_count)); out.push_back(at(beg_run));
+			cur += run_count;
+		}
+	}
+}
+
+bool write_hdr_checked(const std::string &path, int w, int h, const uint8_t *px, std::string &err)
+{
+	if(!encode_size_ok(path, "HDR", w, h, std::numeric_limits<int>::max(), px, err)) return false;
+	// writeHeader (:443-458): program_type_ "RADIANCE", exposure_ 1.0f through operator<< ("1")
+	const std::string head = "#?RADIANCE\n# Image created with YafaRay\nEXPOSURE=1\nFORMAT=32-bit_rle_rgbe\n\n-Y " + std::to_string(h) + " +X " + std::to_string(w) + "\n";
+	std::vector<uint8_t> d(head.begin(), head.end());
+	const bool rle = w >= 8 && w <= 0x7fff;      // the scanline start signature holds the width in 15 bits, and readers take narrower lines as flat
+	d.reserve(d.size() + (size_t)w * (size_t)h * 4 + (rle ? (size_t)h * 4 : 0));
+	for(int y = 0; y < h; ++y)
+	{
+		const uint8_t *scan = px + (size_t)y * (size_t)w * 4;
+		if(!rle) { d.insert(d.end(), scan, scan + (size_t)w * 4); continue; }
+		d.push_back(2); d.push_back(2); d.push_back((uint8_t)(w >> 8)); d.push_back((uint8_t)(w & 0xff));      // RgbePixel::setScanlineStart
+		for(int chan = 0; chan < 4; ++chan) hdr_channel_runs(scan + chan, w, d);
+	}
+	return write_bytes(path, "HDR", d, err);
+}
+
+void png_chunk(std::vector<uint8_t> &d, const char type[4], const uint8_t *body, size_t n)
+{
+	const uint32_t len = (uint32_t)n;
+	const uint8_t head[8] = {(uint8_t)(len >> 24), (uint8_t)(len >> 16), (uint8_t)(len >> 8), (uint8_t)len, (uint8_t)type[0], (uint8_t)type[1], (uint8_t)type[2], (uint8_t)type[3]};
+	d.insert(d.end(), head, head + 8);
+	if(n) d.insert(d.end(), body, body + n);
+	uLong crc = crc32(0L, head + 4, 4);
+	if(n) crc = crc32(crc, body, (uInt)n);
+	const uint8_t tail[4] = {(uint8_t)(crc >> 24), (uint8_t)(crc >> 16), (uint8_t)(crc >> 8), (uint8_t)crc};
+	d.insert(d.end(), tail, tail + 4);
+}
+
+bool write_png_checked(const std::string &path, int w, int h, bool alpha, const uint8_t *px, std::string &err)
+{
+	if(!encode_size_ok(path, "PNG", w, h, std::numeric_limits<int>::max(), px, err)) return false;
+	const size_t ch = alpha ? 4 : 3, stride = (size_t)w * ch + 1;
+	std::vector<uint8_t> raw(stride * (size_t)h);           // at most 2^26 pixels: below 2^32 bytes, a chunk's limit and crc32's
+	for(int y = 0; y < h; ++y)
+	{
+		uint8_t *o = &raw[stride * (size_t)y];
+		*o++ = 0;                                            // row filter: none
+		const uint8_t *p = px + (size_t)y * (size_t)w * 4;
+		if(alpha) std::memcpy(o, p, (size_t)w * 4);
+		else for(int x = 0; x < w; ++x, o += 3, p += 4) { o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; }
+	}
+	uLongf z_len = compressBound((uLong)raw.size());
+	std::vector<uint8_t> z((size_t)z_len);
+	if(compress2(z.data(), &z_len, raw.data(), (uLong)raw.size(), Z_DEFAULT_COMPRESSION) != Z_OK) { err = "PNG file '" + path + "': deflate failed"; return false; }
+	if((uint64_t)z_len > 0x7fffffffull) { err = "PNG file '" + path + "': the pixel stream is too long for one chunk"; return false; }
+	static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+	std::vector<uint8_t> d(sig, sig + 8);
+	d.reserve(8 + 25 + 12 + (size_t)z_len + 12);
+	const uint8_t ihdr[13] = {(uint8_t)((uint32_t)w >> 24), (uint8_t)((uint32_t)w >> 16), (uint8_t)((uint32_t)w >> 8), (uint8_t)w,
+	                          (uint8_t)((uint32_t)h >> 24), (uint8_t)((uint32_t)h >> 16), (uint8_t)((uint32_t)h >> 8), (uint8_t)h,
+	                          8, (uint8_t)(alpha ? 6 : 2), 0, 0, 0};      // 8 bits, RGB / RGBA, deflate, adaptive filtering, no interlace
+	png_chunk(d, "IHDR", ihdr, sizeof ihdr);
+	png_chunk(d, "IDAT", z.data(), (size_t)z_len);
+	png_chunk(d, "IEND", nullptr, 0);
+	return write_bytes(path, "PNG", d, err);
+}
+
+template<typename F> bool encode_guarded(const char *fmt, const std::string &path, std::string &err, F f)
+{
+	try { return f(); }
+	catch(...) {}
+	try { err = std::string(fmt) + " file '" + path + "': out of memory while encoding"; } catch(...) {}
+	return false;
+}
+
+} // namespace
+
+bool write_tga(const std::string &path, int w, int h, bool alpha, const uint8_t *rgba8, std::string &err)
+{
+	return encode_guarded("TGA", path, err, [&] { return write_tga_checked(path, w, h, alpha, rgba8, err); });
+}
+bool write_hdr(const std::string &path, int w, int h, const uint8_t *rgbe, std::string &err)
+{
+	return encode_guarded("HDR", path, err, [&] { return write_hdr_checked(path, w, h, rgbe, err); });
+}
+bool write_png(const std::string &path, int w, int h, bool alpha, const uint8_t *rgba8, std::string &err)
+{
+	return encode_guarded("PNG", path, err, [&] { return write_png_checked(path, w, h, alpha, rgba8, err); });
 }
 
 // ---- film files --------------------------------------------------------------------------------------------------------------

@@ -1105,6 +1105,8 @@ struct yafgpu_scene
 	// render targets of the host-film entry points, kept between calls (allocating and freeing 100 MB per render cost up to half a
 	// second a call on this runtime — ten times the pass itself at 1024x1024)
 	DevMem<float> rt_planes, rt_film; DevMem<yafgpu_counters> rt_cnt;
+	int rt_film_w = 0, rt_film_h = 0;    // the frame whose finished film rt_film holds (0: none): what yafgpu_scene_film_to_image converts
+	DevMem<uint8_t> rt_image;            // the packed image of the output stage (yafgpu_scene_film_to_image)
 	DevMem<uint8_t> rt_flags;            // resample flags of the detection step between adaptive passes
 	int n_cus = 0;                                            // compute units of the device the scene lives on
 	uint32_t lc_host_counter = 0;                        // correlative_sample_number_ of a sharded render: the same value on every rank (lc_exchange_counts)
@@ -2802,12 +2804,30 @@ static int render_targets(yafgpu_scene *s, int w, int h, float **planes, float *
 	return 0;
 }
 
+// The output stage on the film a render left in the scene's render targets: converted where it lies, only the packed image comes down
+int yafgpu_scene_film_to_image(yafgpu_scene_t *s, const yafgpu_image_desc *desc, void *h_image)
+{
+	if(!s || !desc || !h_image) return fail(-1, "film to image: null argument");
+	if(s->rt_film_w <= 0 || !s->rt_film.p) return fail(-13, "film to image: the scene holds no finished film (render first)");
+	if(desc->width != s->rt_film_w || desc->height != s->rt_film_h)
+		return fail(-13, "film to image: the scene's film is " + std::to_string(s->rt_film_w) + " x " + std::to_string(s->rt_film_h) + ", not " +
+		                 std::to_string(desc->width) + " x " + std::to_string(desc->height));
+	const uint64_t bytes = yafgpu_image_bytes(desc->format, desc->image_width, desc->image_height);
+	if(bytes == 0 || bytes > ((uint64_t)1 << 32)) return fail(-10, "film to image: image size or format out of range");
+	HIP_OK(s->rt_image.reserve((size_t)bytes, nullptr));
+	const int rc = yafgpu_film_to_image(s->rt_film, desc, s->rt_image, nullptr);
+	if(rc) return rc;
+	HIP_OK(hipMemcpy(h_image, s->rt_image, (size_t)bytes, hipMemcpyDeviceToHost));
+	return 0;
+}
+
 int yafgpu_render_to_host(yafgpu_scene_t *s, const yafgpu_render_params *rp, float *h_film, yafgpu_counters *h_counters)
 {
 	if(!s || !rp || !h_film) return fail(-1, "null argument");
 	if(rp->width <= 0 || rp->height <= 0) return fail(-10, "empty image");
 	float *d_planes = nullptr, *d_film = nullptr; yafgpu_counters *d_cnt = nullptr;
 	const size_t film_bytes = (size_t)rp->width * (size_t)rp->height * YAFGPU_FILM_CHANNELS * sizeof(float);
+	s->rt_film_w = s->rt_film_h = 0;
 	int rc = render_targets(s, rp->width, rp->height, &d_planes, &d_film, &d_cnt);
 	if(rc) return rc;
 	HIP_OK(hipMemset(d_cnt, 0, sizeof(yafgpu_counters)));
@@ -2823,6 +2843,7 @@ int yafgpu_render_to_host(yafgpu_scene_t *s, const yafgpu_render_params *rp, flo
 		if(hipMemcpy(h_film, d_film, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(-100, "film download failed");
 		if(h_counters && hipMemcpy(h_counters, d_cnt, sizeof(yafgpu_counters), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(-100, "counter download failed");
 	}
+	if(!rc) { s->rt_film_w = rp->width; s->rt_film_h = rp->height; }
 	return rc;
 }
 
@@ -3014,6 +3035,7 @@ int yafgpu_render_passes_to_host(yafgpu_scene_t *s, const yafgpu_render_params *
 	if(w <= 0 || h <= 0) return fail(-10, "empty image");
 	float *d_planes = nullptr, *d_film = nullptr; yafgpu_counters *d_cnt = nullptr;
 	const size_t film_bytes = (size_t)w * (size_t)h * YAFGPU_FILM_CHANNELS * sizeof(float);
+	s->rt_film_w = s->rt_film_h = 0;
 	{ const int rc_t = render_targets(s, w, h, &d_planes, &d_film, &d_cnt); if(rc_t) return rc_t; }
 	HIP_OK(hipMemset(d_cnt, 0, sizeof(yafgpu_counters)));
 	auto film_now = [&](bool download = true) -> int {
@@ -3114,6 +3136,7 @@ int yafgpu_render_passes_to_host(yafgpu_scene_t *s, const yafgpu_render_params *
 		if(e != hipSuccess) rc = fail(-100, std::string("render: ") + hipGetErrorString(e));
 	}
 	if(!rc && h_counters && hipMemcpy(h_counters, d_cnt, sizeof(yafgpu_counters), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(-100, "counter download failed");
+	if(!rc) { s->rt_film_w = w; s->rt_film_h = h; }
 	return rc;
 }
 

@@ -80,6 +80,8 @@ C_API_SYMBOLS = [
     "yafaray_commGetUniqueId", "yafaray_commCreate", "yafaray_commDestroy", "yafaray_commRank", "yafaray_commWorld", "yafaray_commLastError",
     "yafaray_commBackend", "yafaray_reduceFilm", "yafaray_allReduce", "yafaray_commExchange", "yafaray_setComm",
     "yafaray_setFilmPath", "yafaray_getFilmPath", "yafaray_getFilmResume", "yafaray_writeFilmFile", "yafaray_readFilmFile", "yafaray_filmLastError",
+    "yafaray_createImageOutput", "yafaray_destroyImageOutput", "yafaray_imageOutputLastError", "yafaray_imageOutputCallbacks",
+    "yafaray_filmToImage", "yafaray_writeImageFile",
 ]
 GPU_ABI_SYMBOLS = [
     "yafgpu_last_error", "yafgpu_device_count", "yafgpu_set_device", "yafgpu_scene_create", "yafgpu_scene_destroy",
@@ -87,6 +89,7 @@ GPU_ABI_SYMBOLS = [
     "yafgpu_trace_closest", "yafgpu_trace_shadow", "yafgpu_trace_reservation", "yafgpu_trace_schedule", "yafgpu_scene_get_tree", "yafgpu_probe",
     "yafgpu_kdtree_build", "yafgpu_kdtree_build_device", "yafgpu_kdtree_info", "yafgpu_kdtree_get", "yafgpu_kdtree_destroy", "yafgpu_kdtree_treelets",
     "yafgpu_set_profiling", "yafgpu_scene_set_pass_pipelining", "yafgpu_get_profile", "yafgpu_scene_set_abort_flag", "yafgpu_scene_set_exchange", "yafgpu_glibc_rand",
+    "yafgpu_image_bytes", "yafgpu_film_to_image", "yafgpu_scene_film_to_image",
 ]
 
 
@@ -166,6 +169,9 @@ def load():
         "yafaray_getFilmResume": (None, [vp, C.POINTER(ci), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
         "yafaray_writeFilmFile": (ci, [cp, C.POINTER(FilmHeader), C.POINTER(cf)]),
         "yafaray_readFilmFile": (ci, [cp, C.POINTER(FilmHeader), C.POINTER(cf), C.c_uint64]), "yafaray_filmLastError": (cp, []),
+        "yafaray_createImageOutput": (vp, [vp, vp, cp, ci, ci]), "yafaray_destroyImageOutput": (None, [vp]),
+        "yafaray_imageOutputLastError": (cp, [vp]), "yafaray_imageOutputCallbacks": (C.POINTER(Output), [vp]),
+        "yafaray_filmToImage": (ci, [C.POINTER(cf), ci, ci, cp, cf, ci, ci, vp]), "yafaray_writeImageFile": (ci, [cp, cp, ci, ci, ci, vp]),
         "yafgpu_last_error": (cp, []), "yafgpu_device_count": (ci, []), "yafgpu_set_device": (ci, [ci]),
         "yafgpu_planes_bytes": (C.c_uint64, [ci, ci]),
         "yafgpu_film_combine": (ci, [vp, vp, ci, ci, vp]),
@@ -320,7 +326,33 @@ class Interface:
         return self._obj(self._L.yafaray_createVolumeRegion(self._h, _b(name)), "createVolumeRegion")
 
     def createImageHandler(self, name, add_to_table=True):
+        """type "tga" | "hdr" | "pic" | "png", width, height, alpha_channel, for_output from the current parameters -> a handle for ImageOutput"""
         return self._obj(self._L.yafaray_createImageHandler(self._h, _b(name), int(add_to_table)), "createImageHandler")
+
+    def createImageOutput(self, handler, path, border_x=0, border_y=0):
+        """-> an ImageOutput for render(output=...) / setOutput2, or None when it is refused (strict: raises)"""
+        h = self._obj(self._L.yafaray_createImageOutput(self._h, handler, _b(os.fspath(path)), int(border_x), int(border_y)), "createImageOutput")
+        return ImageOutput(self, h) if h else None
+
+    def _output_table(self, output, keep):
+        """the yafaray_output_t for `output`: an ImageOutput's own table, or thunks around an object with putPixel(view, x, y, rgba) [and flush(view)]"""
+        if output is None:
+            return None
+        if isinstance(output, ImageOutput):
+            return output.callbacks()
+        out = Output()
+        pp = PUTPIXEL(lambda u, v, x, y, r, g, b, a: int(bool(output.putPixel(v, x, y, (r, g, b, a)))))
+        fl = FLUSH(lambda u, v: output.flush(v) if hasattr(output, "flush") else None)
+        keep[:] = [pp, fl, out]
+        out.putPixel = pp
+        out.flush = fl
+        return C.pointer(out)
+
+    def setOutput2(self, output):
+        """Interface::setOutput2: a second output, fed in color_space2 / gamma2; None detaches it"""
+        self._keep2 = []
+        self._output2 = output
+        self._L.yafaray_setOutput2(self._h, self._output_table(output, self._keep2))
 
     def setLoggingAndBadgeSettings(self):
         return self._ok(self._L.yafaray_setLoggingAndBadgeSettings(self._h), "setLoggingAndBadgeSettings")
@@ -562,15 +594,14 @@ class Interface:
 
     # -- render
     def render(self, output=None, progress=None):
-        out = None
-        if output is not None:
-            out = Output()
-            pp = PUTPIXEL(lambda u, v, x, y, r, g, b, a: int(bool(output.putPixel(v, x, y, (r, g, b, a)))))
-            fl = FLUSH(lambda u, v: output.flush(v) if hasattr(output, "flush") else None)
-            self._keep = [pp, fl]
-            out.putPixel = pp
-            out.flush = fl
-        return self._ok(self._L.yafaray_render(self._h, C.byref(out) if out is not None else None, None), "render")
+        """output: None, an ImageOutput (the file is written from the device film) or an object with putPixel(view, x, y, rgba) [and flush(view)]"""
+        self._keep = []
+        return self._ok(self._L.yafaray_render(self._h, self._output_table(output, self._keep), None), "render")
+
+    def getRenderedImage(self, output, num_view=0):
+        """Interface::getRenderedImage: the last render's image once more, into `output` (and the second output, when one is set)"""
+        keep = []
+        return self._ok(self._L.yafaray_getRenderedImage(self._h, num_view, self._output_table(output, keep)), "getRenderedImage")
 
     def abort(self):
         self._L.yafaray_abort(self._h)
@@ -695,6 +726,77 @@ class Interface:
         s = RenderStats()
         self._L.yafaray_getRenderStats(self._h, C.byref(s))
         return s
+
+
+class ImageOutput:
+    """ImageOutput (common/output_image.cc) over a handler of createImageHandler: the render window goes into the handler's image at the
+    border and one file is written under the path.  Made by Interface.createImageOutput; pass it to render(output=...) or setOutput2."""
+
+    def __init__(self, interface, handle):
+        self._yi = interface          # the handler is the interface's: keep it alive
+        self._L = interface._L
+        self._h = handle
+
+    def callbacks(self):
+        """the yafaray_output_t the library recognises (a pointer into the image output): a caller may also drive it pixel by pixel"""
+        return self._L.yafaray_imageOutputCallbacks(self._h)
+
+    def putPixel(self, num_view, x, y, rgba):
+        t = self.callbacks().contents
+        return bool(t.putPixel(t.user, num_view, x, y, rgba[0], rgba[1], rgba[2], rgba[3]))
+
+    def flush(self, num_view=0):
+        """saves the file; False when it could not be written (getLastError())"""
+        t = self.callbacks().contents
+        t.flush(t.user, num_view)
+        return self.getLastError() == ""
+
+    def getLastError(self):
+        return self._L.yafaray_imageOutputLastError(self._h).decode()
+
+    def close(self):
+        if self._h:
+            self._L.yafaray_destroyImageOutput(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+IMAGE_FLOAT, IMAGE_RGBA8, IMAGE_RGBE = 0, 1, 2      # YAFGPU_IMAGE_* (include/yafgpu.h)
+
+
+def film_to_image(film, color_space="LinearRGB", gamma=1.0, alpha=True, format=IMAGE_RGBA8):
+    """A film ((h, w, 5) float32, what getFilm / read_film_file return) through the device's output stage: normalised, clamped, converted
+    to the colour space and packed -> (h, w, 4) float32 for IMAGE_FLOAT, (h, w, 4) uint8 r g b a for IMAGE_RGBA8 or r g b e for
+    IMAGE_RGBE.  Needs a GPU.  Raises YafaRayError with the cause on failure."""
+    px = np.ascontiguousarray(film, dtype=np.float32)
+    if px.ndim != 3 or px.shape[2] != 5:
+        raise ValueError("film must be (height, width, 5)")
+    h, w = px.shape[:2]
+    out = np.zeros((h, w, 4), dtype=np.float32 if format == IMAGE_FLOAT else np.uint8)
+    L = load()
+    if not L.yafaray_filmToImage(px.ctypes.data_as(C.POINTER(C.c_float)), w, h, _b(color_space), float(gamma), int(bool(alpha)), int(format),
+                                 out.ctypes.data_as(C.c_void_p)):
+        raise YafaRayError(L.yafaray_filmLastError().decode())
+    return out
+
+
+def write_image_file(path, file_type, pixels, alpha=False):
+    """Write packed pixels ((h, w, 4) uint8: r g b a for "tga" and "png", r g b e for "hdr" / "pic") as an image file, on the host.
+    Without alpha a tga / png file holds r g b alone.  False on failure, with the cause in film_last_error()."""
+    px = np.ascontiguousarray(pixels, dtype=np.uint8)
+    if px.ndim != 3 or px.shape[2] != 4:
+        raise ValueError("pixels must be (height, width, 4) uint8")
+    return bool(load().yafaray_writeImageFile(_b(os.fspath(path)), _b(file_type), px.shape[1], px.shape[0], int(bool(alpha)), px.ctypes.data_as(C.c_void_p)))
+
+
+# the C API's spelling
+filmToImage = film_to_image
+writeImageFile = write_image_file
 
 
 class TreeInfo(C.Structure):
