@@ -191,7 +191,13 @@ void yafaray_paramsEndList(yafaray_interface_t *yi);                            
  * with_caustic and with_diffuse are read and dropped.  `file` is an IES photometric file, looked up like a texture's filename; it is parsed
  * here, and a file that is missing, cut off, malformed or larger than 4096 angles a side is refused with its cause.  Without soft_shadows
  * the light is a Dirac light with a table lookup, with it a sampled light of `samples` samples that cannot be intersected.  Without a
- * `file` it is refused. */
+ * `file` it is refused.
+ * spotlight (light_spot.cc): from, to, color, power, cone_angle (45: half the opening, in (0, 180]), blend (0.15, in [0, 1]: the share of the
+ * angle over which the light falls off), soft_shadows (false), shadowFuzzyness (1), samples (8), light_enabled, cast_shadows; with_caustic
+ * and with_diffuse are read and dropped.  Accepted only when both `from` and `to` are given (the reference would aim the light from the
+ * origin down -z); refused as well: from equal to to, a cone_angle or blend outside its range or not finite, samples below 1 with
+ * soft_shadows.  Without soft_shadows a Dirac light, with it a sampled light of `samples` samples that takes both halves of the MIS pair
+ * (and is darker for it, as in the reference: SpotLight::intersect almost never answers the BSDF half). */
 yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name);            /* :92 */
 yafaray_texture_t *yafaray_createTexture(yafaray_interface_t *yi, const char *name);        /* :93: type "image" (TGA, HDR and PNG files; none /
                                                                                                bilinear interpolation); procedural types are refused */

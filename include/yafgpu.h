@@ -69,7 +69,12 @@ enum { YAFGPU_LIGHT_AREA = 0, YAFGPU_LIGHT_POINT = 1, YAFGPU_LIGHT_DIRECTIONAL =
        /* IesLight (light_ies.cc): a point with a measured distribution, a table looked up by two angles (yafgpu_scene_desc::ies_tables).
           Two types for its two behaviours, split by soft_shadows_: IES is a Dirac light (illuminate), IES_SOFT a sampled one that cannot be
           intersected (illumSample alone, the light half of the MIS pair, as the sphere light) */
-       YAFGPU_LIGHT_IES = 9, YAFGPU_LIGHT_IES_SOFT = 10 };
+       YAFGPU_LIGHT_IES = 9, YAFGPU_LIGHT_IES_SOFT = 10,
+       /* SpotLight (light_spot.cc): a point light with a cone and a smoothstep falloff towards its edge.  Two types for its two behaviours,
+          split by soft_shadows_ as the IES pair is: SPOT is a Dirac light (illuminate); SPOT_SOFT is sampled AND intersectable
+          (canIntersect() == soft_shadows_, light_spot.h), so it takes both halves of the MIS pair, although its intersect() almost never
+          answers true.  Not 13: the next unknown type stays unknown */
+       YAFGPU_LIGHT_SPOT = 11, YAFGPU_LIGHT_SPOT_SOFT = 12 };
 enum { YAFGPU_BACKGROUND_NONE = 0, YAFGPU_BACKGROUND_CONSTANT = 1, YAFGPU_BACKGROUND_TEXTURE = 2 };
 enum { YAFGPU_INTEGRATOR_PATH = 0, YAFGPU_INTEGRATOR_DIRECT = 1 };
 enum { YAFGPU_FILTER_BOX = 0, YAFGPU_FILTER_MITCHELL = 1, YAFGPU_FILTER_GAUSS = 2, YAFGPU_FILTER_LANCZOS = 3 };
@@ -191,7 +196,11 @@ typedef struct yafgpu_node
  *                color: what it emits is the scene's yafgpu_background times portal_power; single-sided, so double_sided stays 0
  *   ies, ies_soft  samples (1 for ies), position (from), direction (ndir_ = normalize(from - to)), du / dv (createCs__ of dir_ = -ndir_),
  *                cos_angle (cos_end_ = fCos__ of the largest vertical angle), color (col * power), ies_first, ies_n_hor, ies_n_vert,
- *                ies_type, ies_max_rad */
+ *                ies_type, ies_max_rad
+ *   spot, spot_soft  samples (1 for spot), position (from), direction (ndir_ = normalize(from - to)), du / dv (createCs__ of dir_ = -ndir_),
+ *                cos_angle (cos_end_ = fCos__ of the cone angle), spot_cos_start (cos_start_, where the falloff begins), spot_icos_diff
+ *                (icos_diff_ = 1 / (cos_start_ - cos_end_), infinite when blend is 0: the falloff branch is then unreachable),
+ *                spot_shadow_fuzzy (shadow_fuzzy_, scales the samples of spot_soft), color (col * power) */
 typedef struct yafgpu_light
 {
 	int32_t type, samples, cast_shadows;
@@ -230,6 +239,13 @@ typedef struct yafgpu_light
 			int32_t ies_n_hor, ies_n_vert;      /* at least 2 each */
 			int32_t ies_type;          /* the file's photometric type: 1 C, 2 B, anything else is read like 3, A (util_ies.h:72-86) */
 			float ies_max_rad;         /* max_rad_: 1 / the table's largest value, applied at lookup (util_ies.h:130) */
+		};
+		struct
+		{	/* spot, spot_soft: words 14-16 of the record, behind direction, du, dv and cos_angle (here cos_end_), which they share with the sun */
+			float spot_pad[10];
+			float spot_cos_start;      /* cos_start_ = fCos__(angle * (1 - blend)): at or above it the light is not affected by the falloff */
+			float spot_icos_diff;      /* icos_diff_ = 1 / (cos_start_ - cos_end_), a double quotient narrowed (light_spot.cc:42) */
+			float spot_shadow_fuzzy;   /* shadow_fuzzy_: illumSample scales both of its samples by it (light_spot.cc:127) */
 		};
 	};
 	float color[3];

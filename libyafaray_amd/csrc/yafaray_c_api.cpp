@@ -1153,6 +1153,35 @@ bool make_ieslight(yafaray_interface *yi, const ParamMap &p, yafgpu_light &l, ya
 	l.ies_first = -1; l.ies_n_hor = ies.n_hor; l.ies_n_vert = ies.n_vert; l.ies_type = ies.type; l.ies_max_rad = ies.max_rad;
 	return true;
 }
+// SpotLight::factory + ctor, light_spot.cc:258-296, :29-42.  The Pdf1D of the smoothstep and interv_1_ / interv_2_ (:44-68) serve photon
+// emission only; with_caustic and with_diffuse are read by the factory and dropped here.  The caller has made sure that `from` and `to` are
+// both there.  Returns whether the light was made; `enabled` is then light_enabled.
+bool make_spotlight(yafaray_interface *yi, const ParamMap &p, yafgpu_light &l, bool &enabled)
+{
+	float from[3] = {0, 0, 0}, to[3] = {0, 0, -1}, color[3] = {1, 1, 1};
+	float power = 1.f, angle = 45.f, falloff = 0.15f, ssfuzzy = 1.f; int samples = 8; bool soft = false, cast = true;
+	enabled = true;
+	p.getPoint("from", from); p.getPoint("to", to); p.getColor("color", color); p.get("power", power); p.get("cone_angle", angle); p.get("blend", falloff);
+	p.get("soft_shadows", soft); p.get("shadowFuzzyness", ssfuzzy); p.get("samples", samples); p.get("light_enabled", enabled); p.get("cast_shadows", cast);
+	if(from[0] == to[0] && from[1] == to[1] && from[2] == to[2]) { fail(yi, "createLight: spotlight: from and to are the same point, the light has no axis"); return false; }
+	if(!(std::isfinite(angle) && angle > 0.f && angle <= 180.f)) { fail(yi, "createLight: spotlight: cone_angle must lie in (0, 180]"); return false; }
+	if(!(std::isfinite(falloff) && falloff >= 0.f && falloff <= 1.f)) { fail(yi, "createLight: spotlight: blend must lie in [0, 1]"); return false; }
+	if(soft && samples < 1) { fail(yi, "createLight: spotlight: samples must be at least 1 with soft_shadows"); return false; }
+	std::memset(&l, 0, sizeof l);
+	l.type = soft ? YAFGPU_LIGHT_SPOT_SOFT : YAFGPU_LIGHT_SPOT; l.samples = soft ? samples : 1; l.cast_shadows = cast;
+	float dir[3];
+	for(int k = 0; k < 3; ++k) { l.position[k] = from[k]; l.direction[k] = from[k] - to[k]; l.color[k] = color[k] * power; }
+	ref_normalize(l.direction);                           // ndir_
+	for(int k = 0; k < 3; ++k) dir[k] = -l.direction[k];  // dir_
+	ref_create_cs(dir, l.du, l.dv);
+	const double rad_angle = (double)angle * 0.01745329251994329576922;      // DEG_TO_RAD(angle)
+	const double rad_inner_angle = rad_angle * (double)(1.f - falloff);
+	l.spot_cos_start = host_fsin_poly((float)rad_inner_angle + (float)1.57079632679489661923);      // fCos__ narrows its argument
+	l.cos_angle = host_fsin_poly((float)rad_angle + (float)1.57079632679489661923);                 // cos_end_
+	l.spot_icos_diff = (float)(1.0 / (double)(l.spot_cos_start - l.cos_angle));                     // infinite with blend 0: never read then
+	l.spot_shadow_fuzzy = ssfuzzy;
+	return true;
+}
 
 // PerspectiveCamera::factory, Camera::Camera, setAxis — camera_perspective.cc:198-243, camera.cc:46-66, :60-74
 bool make_camera(yafaray_interface *yi, const ParamMap &p, yafgpu_camera &c)
@@ -2112,7 +2141,7 @@ yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name)
 	if(yi->lights.count(name)) { fail(yi, std::string("createLight: \"") + name + "\" already defined"); return nullptr; }
 	if(!yi->params.get("type", type)) { fail(yi, "createLight: type of light not specified"); return nullptr; }
 	auto l = std::make_unique<yafaray_light>();
-	bool enabled, photon_only = false; int object = 0; std::string file;
+	bool enabled, photon_only = false; int object = 0; std::string file; float aim[3];
 	// light_area.cc:69, light_point.cc:40,60 (and light_directional.cc:62, light_sun.cc:55, light_sphere.cc:73): a photon-only light gives illumSample / illuminate nothing (and still counts among the lights the
 	// one-light estimator picks from): a photon-mapping setting, not taken over
 	if(yi->params.get("photon_only", photon_only) && photon_only) { fail(yi, "createLight: photon_only lights are outside the GPU path's scope (photon mapping)"); return nullptr; }
@@ -2124,10 +2153,12 @@ yafaray_light_t *yafaray_createLight(yafaray_interface_t *yi, const char *name)
 	else if(type == "meshlight" && yi->params.get("object", object)) enabled = make_meshlight(yi->params, l->l, l->object);
 	else if(type == "bgPortalLight" && yi->params.get("object", object)) enabled = make_portallight(yi->params, l->l, l->object);
 	else if(type == "ieslight" && yi->params.get("file", file)) { if(!make_ieslight(yi, yi->params, l->l, l->ies, enabled)) return nullptr; }
+	else if(type == "spotlight" && yi->params.getPoint("from", aim) && yi->params.getPoint("to", aim)) { if(!make_spotlight(yi, yi->params, l->l, enabled)) return nullptr; }
 	else
 	{	// (a meshlight or a bgPortalLight without an object has no mesh at all: the reference's dereferences a null distribution at its first sample;
-		// an ieslight without a file has nothing to parse, and the reference's factory returns no light either)
-		fail(yi, "createLight: " + std::string(type == "ieslight" ? "no file given: " : "") + "light type \"" + type + "\" is outside the GPU path's scope (arealight, pointlight, directionallight, sunlight, spherelight, meshlight or bgPortalLight with the object it lights from, and ieslight with the file it reads)");
+		// an ieslight without a file has nothing to parse, and the reference's factory returns no light either; a spotlight without its from
+		// or its to is the one deviation: the reference would aim it from the origin down -z, here the call that names neither stays refused)
+		fail(yi, "createLight: " + std::string(type == "ieslight" ? "no file given: " : type == "spotlight" ? "from and to are not both given: " : "") + "light type \"" + type + "\" is outside the GPU path's scope (arealight, pointlight, directionallight, sunlight, spherelight, meshlight or bgPortalLight with the object it lights from, ieslight with the file it reads, and spotlight with the from and to it aims along)");
 		return nullptr;
 	}
 	yafaray_light *raw = l.get();

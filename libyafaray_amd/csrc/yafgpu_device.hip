@@ -914,6 +914,37 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			o[0] = 1.f; o[1] = d.x; o[2] = d.y; o[3] = d.z; o[4] = tmax; o[5] = pdf; o[6] = c.r; o[7] = c.g; o[8] = c.b;
 			break;
 		}
+		// the spot light (ops 41-43), addressed like the others; either of its two types answers each op
+		case 41:
+		{	// SpotLight::illuminate: in p.xyz, k -> ok, wi.dir, wi.tmax, col (zeros where it refuses)
+			if(n_in < 4 || n_out < 8) break;
+			const uint32_t k = __float_as_uint(x[3]);
+			if(k >= (uint32_t)sc.n_lights || (sc.lights[k].type != YAFGPU_LIGHT_SPOT && sc.lights[k].type != YAFGPU_LIGHT_SPOT_SOFT)) break;
+			Col c = mkc(0.f, 0.f, 0.f); V3 d = mk(0.f, 0.f, 0.f); float tmax = 0.f;
+			if(!spotlight_illuminate(sc.lights[k], mk(x[0], x[1], x[2]), c, d, tmax)) break;
+			o[0] = 1.f; o[1] = d.x; o[2] = d.y; o[3] = d.z; o[4] = tmax; o[5] = c.r; o[6] = c.g; o[7] = c.b;
+			break;
+		}
+		case 42:
+		{	// SpotLight::illumSample: in p.xyz, s_1, s_2, k -> ok, wi.dir, wi.tmax, pdf, ls.col (zeros where it refuses)
+			if(n_in < 6 || n_out < 9) break;
+			const uint32_t k = __float_as_uint(x[5]);
+			if(k >= (uint32_t)sc.n_lights || (sc.lights[k].type != YAFGPU_LIGHT_SPOT && sc.lights[k].type != YAFGPU_LIGHT_SPOT_SOFT)) break;
+			V3 d = mk(0.f, 0.f, 0.f); float tmax = 0.f, pdf = 0.f; Col c = mkc(0.f, 0.f, 0.f);
+			if(!spotlight_illum_sample(sc.lights[k], mk(x[0], x[1], x[2]), x[3], x[4], d, tmax, pdf, c)) break;
+			o[0] = 1.f; o[1] = d.x; o[2] = d.y; o[3] = d.z; o[4] = tmax; o[5] = pdf; o[6] = c.r; o[7] = c.g; o[8] = c.b;
+			break;
+		}
+		case 43:
+		{	// SpotLight::intersect: in from.xyz, dir.xyz, k -> ok, t, ipdf, col (zeros where it refuses)
+			if(n_in < 7 || n_out < 6) break;
+			const uint32_t k = __float_as_uint(x[6]);
+			if(k >= (uint32_t)sc.n_lights || (sc.lights[k].type != YAFGPU_LIGHT_SPOT && sc.lights[k].type != YAFGPU_LIGHT_SPOT_SOFT)) break;
+			float t = 0.f, ipdf = 0.f; Col c = mkc(0.f, 0.f, 0.f);
+			if(!spotlight_intersect(sc.lights[k], mk(x[0], x[1], x[2]), mk(x[3], x[4], x[5]), t, c, ipdf)) break;
+			o[0] = 1.f; o[1] = t; o[2] = ipdf; o[3] = c.r; o[4] = c.g; o[5] = c.b;
+			break;
+		}
 		default: break;
 	}
 }
@@ -1257,6 +1288,23 @@ static int check_ies_lights(const yafgpu_scene_desc *d)
 	return 0;
 }
 
+// Spot lights: the record indexes nothing, so all there is to hold are its numbers: the two cosines and shadow_fuzzy_ finite, the axis a
+// vector of numbers; icos_diff_ may be infinite (blend 0, where the falloff branch is unreachable) but is no NaN.
+static int check_spot_lights(const yafgpu_scene_desc *d)
+{
+	for(int i = 0; i < d->n_lights; ++i)
+	{
+		const yafgpu_light &l = d->lights[i];
+		if(l.type != YAFGPU_LIGHT_SPOT && l.type != YAFGPU_LIGHT_SPOT_SOFT) continue;
+		const std::string who = "spot light " + std::to_string(i);
+		if(!(std::isfinite(l.cos_angle) && std::isfinite(l.spot_cos_start))) return fail(-3, who + ": the cosines of its cone are not finite");
+		if(std::isnan(l.spot_icos_diff)) return fail(-3, who + ": icos_diff is not a number");
+		if(!std::isfinite(l.spot_shadow_fuzzy)) return fail(-3, who + ": shadow_fuzzy is not finite");
+		for(int k = 0; k < 3; ++k) if(!std::isfinite(l.direction[k])) return fail(-3, who + ": its axis is not finite");
+	}
+	return 0;
+}
+
 // every reference inside a node range is -1 or names a node BEFORE the one that reads it (evaluation order): the device indexes a per-lane
 // result stack with them (nodes_eval, mat_resolve, nodes_eval_derivative)
 static bool node_range_ok(const yafgpu_node *nodes, int first, int count)
@@ -1289,7 +1337,7 @@ static int check_desc(const yafgpu_scene_desc *d)
 	for(int i = 0; i < d->n_tris; ++i)
 		if(d->tri_mat[i] < 0 || d->tri_mat[i] >= d->n_materials) return fail(-3, "triangle material index out of range");
 	for(int i = 0; i < d->n_lights; ++i)
-		if(d->lights[i].type < YAFGPU_LIGHT_AREA || (d->lights[i].type > YAFGPU_LIGHT_BACKGROUND && d->lights[i].type != YAFGPU_LIGHT_MESH && d->lights[i].type != YAFGPU_LIGHT_PORTAL && d->lights[i].type != YAFGPU_LIGHT_IES && d->lights[i].type != YAFGPU_LIGHT_IES_SOFT)) return fail(-2, "light " + std::to_string(i) + ": unknown type");
+		if(d->lights[i].type < YAFGPU_LIGHT_AREA || (d->lights[i].type > YAFGPU_LIGHT_BACKGROUND && d->lights[i].type != YAFGPU_LIGHT_MESH && d->lights[i].type != YAFGPU_LIGHT_PORTAL && d->lights[i].type != YAFGPU_LIGHT_IES && d->lights[i].type != YAFGPU_LIGHT_IES_SOFT && d->lights[i].type != YAFGPU_LIGHT_SPOT && d->lights[i].type != YAFGPU_LIGHT_SPOT_SOFT)) return fail(-2, "light " + std::to_string(i) + ": unknown type");
 	{	// the background and its light: one record, at most one light, and the light only with a background that asks for it
 		const yafgpu_background &b = d->background;
 		int n_bg_lights = 0;
@@ -1327,6 +1375,7 @@ static int check_desc(const yafgpu_scene_desc *d)
 	if(d->inst.n_segments > 0) { const int rc = check_instancing(d); if(rc) return rc; }
 	{ const int rc = check_mesh_lights(d); if(rc) return rc; }
 	{ const int rc = check_ies_lights(d); if(rc) return rc; }
+	{ const int rc = check_spot_lights(d); if(rc) return rc; }
 	const bool with_nodes = d->n_nodes > 0 && d->nodes;
 	if(with_nodes || d->background.kind == YAFGPU_BACKGROUND_TEXTURE)      // image textures: what the shader nodes and a texture background look up
 		for(int i = 0; i < d->n_textures; ++i)
@@ -1961,7 +2010,7 @@ static int validate(const yafgpu_scene *s, const yafgpu_render_params *rp)
 	// light-sample multiplier that grows over the passes of an adaptive render is caught when it gets there
 	for(const yafgpu_light &l : s->h_lights)
 		if(!light_type_is_dirac(l.type) && std::ceil((float)l.samples * rp->aa_light_sample_multiplier) > 4095.f)
-			return fail(-19, "a sampled light (area, sun, sphere) with more than 4095 samples per estimate (samples x AA light-sample multiplier): the device path counts them in 12 bits");
+			return fail(-19, "a sampled light (area, sun, sphere, mesh, portal, soft IES or soft spot) with more than 4095 samples per estimate (samples x AA light-sample multiplier): the device path counts them in 12 bits");
 	if(rp->do_ao && rp->integrator == YAFGPU_INTEGRATOR_DIRECT)
 	{	// ambient occlusion rides the light estimate as the light after the last one (yafgpu_wavefront.h, ao_candidate)
 		if(rp->ao_samples < 1) return fail(-19, "ao_samples < 1: the ambient occlusion estimate is divided by its sample count");
@@ -2080,6 +2129,8 @@ YG_DECLARE_SHADE_VARIANT(portal)
 YG_DECLARE_SHADE_VARIANT(blend_portal)
 YG_DECLARE_SHADE_VARIANT(ies)
 YG_DECLARE_SHADE_VARIANT(blend_ies)
+YG_DECLARE_SHADE_VARIANT(spot)
+YG_DECLARE_SHADE_VARIANT(blend_spot)
 #undef YG_DECLARE_SHADE_VARIANT
 }
 struct ShadeVariant
@@ -2116,8 +2167,13 @@ static const ShadeVariant kBlendPortalVariant = {"blend_portal", yafgpu_shade_bl
 // light of either kind picks one of them, whatever other lights stand beside it.
 static const ShadeVariant kIesVariant = {"ies", yafgpu_shade_ies_describe, yafgpu_shade_ies_kernel, yafgpu_shade_ies_launch};
 static const ShadeVariant kBlendIesVariant = {"blend_ies", yafgpu_shade_blend_ies_describe, yafgpu_shade_blend_ies_kernel, yafgpu_shade_blend_ies_launch};
+// And once more with the spot light's two types on top (bits YAFGPU_LIGHT_SPOT and YAFGPU_LIGHT_SPOT_SOFT): a spot light of either kind picks one of
+// them, before the IES light's, so that a scene with both finds the code of both.
+static const ShadeVariant kSpotVariant = {"spot", yafgpu_shade_spot_describe, yafgpu_shade_spot_kernel, yafgpu_shade_spot_launch};
+static const ShadeVariant kBlendSpotVariant = {"blend_spot", yafgpu_shade_blend_spot_describe, yafgpu_shade_blend_spot_kernel, yafgpu_shade_blend_spot_launch};
 static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, const Switches &sw, int frames, bool record_pass, bool want_multi, bool ao)
 {
+	if(s->light_mask & ((1u << (uint32_t)YAFGPU_LIGHT_SPOT) | (1u << (uint32_t)YAFGPU_LIGHT_SPOT_SOFT))) return s->has_blend ? &kBlendSpotVariant : &kSpotVariant;
 	if(s->has_ies) return s->has_blend ? &kBlendIesVariant : &kIesVariant;
 	if(s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_PORTAL)) return s->has_blend ? &kBlendPortalVariant : &kPortalVariant;
 	// a mesh light: the kernels that have its code, for the same reasons as the blend's below

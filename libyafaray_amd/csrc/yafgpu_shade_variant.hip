@@ -15,7 +15,8 @@
 // a blend in use and nothing else, pick_shade_variant; and the two units built with the mesh light's bit, YAFGPU_LIGHT_MASK & 0x80, which are
 // the general kernel and the blend's with that light's code, picked by a mesh light in the scene, and the two built with the portal light's
 // bit as well, YAFGPU_LIGHT_MASK & 0x100, picked by a portal light, and the two built with the IES light's bits on top of those,
-// YAFGPU_LIGHT_MASK & 0x600, picked by an IES light of either kind)
+// YAFGPU_LIGHT_MASK & 0x600, picked by an IES light of either kind, and the two built with the spot light's bits on top of all of them,
+// YAFGPU_LIGHT_MASK & 0x1800, picked by a spot light of either kind)
 //
 // and includes the main unit with everything but wf_shade and what it calls compiled out.  All of its symbols live in
 // their own namespace (the macro below renames `yafgpu`), so the variants and the main unit link into one library; the

@@ -30,7 +30,8 @@ namespace yafgpu {
 // but the mesh light (bit YAFGPU_LIGHT_MESH, 0x80), whose code lives in the two units built with 0xbf (csrc/build.sh: meshlight,
 // blend_meshlight), so that the general kernel stays the kernel it was for every scene without one; the portal light (bit
 // YAFGPU_LIGHT_PORTAL, 0x100) lives in two more built with 0x1bf (portal, blend_portal) for the same reason, and the IES light's two types
-// (bits YAFGPU_LIGHT_IES and YAFGPU_LIGHT_IES_SOFT, 0x600) in two built with 0x7bf (ies, blend_ies)
+// (bits YAFGPU_LIGHT_IES and YAFGPU_LIGHT_IES_SOFT, 0x600) in two built with 0x7bf (ies, blend_ies), and the spot light's two types (bits
+// YAFGPU_LIGHT_SPOT and YAFGPU_LIGHT_SPOT_SOFT, 0x1800) in two built with 0x1fbf (spot, blend_spot)
 #ifndef YAFGPU_LIGHT_MASK
 #define YAFGPU_LIGHT_MASK 0x3fu
 #endif
@@ -48,15 +49,20 @@ namespace yafgpu {
 // The IES light's two types (light_ies.cc: diracLight() is !soft_shadow_, canIntersect() false) are the exception: Dirac (YAFGPU_LIGHT_IES)
 // or sampled and not intersectable (YAFGPU_LIGHT_IES_SOFT), which only the units built with their bits (0x600: ies, blend_ies) answer, so
 // that every other unit keeps its code.  Host code asks light_type_is_dirac below, which is no unit's.
-__host__ inline bool light_type_is_dirac(int type) { return type == YAFGPU_LIGHT_POINT || type == YAFGPU_LIGHT_DIRECTIONAL || type == YAFGPU_LIGHT_IES; }
-#if (YAFGPU_LIGHT_MASK) & 0x600u        /* YAFGPU_LIGHT_IES, YAFGPU_LIGHT_IES_SOFT */
+// The spot light's two types (light_spot.h: diracLight() is !soft_shadows_, canIntersect() is soft_shadows_) follow the same rule with the
+// units built with their bits (0x1800: spot, blend_spot): Dirac (YAFGPU_LIGHT_SPOT), or sampled AND intersectable (YAFGPU_LIGHT_SPOT_SOFT:
+// neither Dirac, nor a sphere, nor a soft IES light, so light_can_intersect below says yes without naming it).
+__host__ inline bool light_type_is_dirac(int type) { return type == YAFGPU_LIGHT_POINT || type == YAFGPU_LIGHT_DIRECTIONAL || type == YAFGPU_LIGHT_IES || type == YAFGPU_LIGHT_SPOT; }
+#if (YAFGPU_LIGHT_MASK) & 0x1800u       /* YAFGPU_LIGHT_SPOT, YAFGPU_LIGHT_SPOT_SOFT */
+__host__ __device__ __forceinline__ bool light_is_dirac(int type) { return type == YAFGPU_LIGHT_POINT || type == YAFGPU_LIGHT_DIRECTIONAL || type == YAFGPU_LIGHT_IES || type == YAFGPU_LIGHT_SPOT; }
+#elif (YAFGPU_LIGHT_MASK) & 0x600u      /* YAFGPU_LIGHT_IES, YAFGPU_LIGHT_IES_SOFT */
 __host__ __device__ __forceinline__ bool light_is_dirac(int type) { return type == YAFGPU_LIGHT_POINT || type == YAFGPU_LIGHT_DIRECTIONAL || type == YAFGPU_LIGHT_IES; }
 #elif (YAFGPU_LIGHT_MASK) & 0x4u        /* YAFGPU_LIGHT_DIRECTIONAL */
 __host__ __device__ __forceinline__ bool light_is_dirac(int type) { return type == YAFGPU_LIGHT_POINT || type == YAFGPU_LIGHT_DIRECTIONAL; }
 #else
 __host__ __device__ __forceinline__ bool light_is_dirac(int type) { return type == YAFGPU_LIGHT_POINT; }
 #endif
-#if (YAFGPU_LIGHT_MASK) & 0x600u
+#if (YAFGPU_LIGHT_MASK) & 0x1e00u      /* the IES light's bits or the spot light's */
 __host__ __device__ __forceinline__ bool light_can_intersect(int type) { return !light_is_dirac(type) && type != YAFGPU_LIGHT_SPHERE && type != YAFGPU_LIGHT_IES_SOFT; }
 #elif (YAFGPU_LIGHT_MASK) & 0x10u       /* YAFGPU_LIGHT_SPHERE */
 __host__ __device__ __forceinline__ bool light_can_intersect(int type) { return !light_is_dirac(type) && type != YAFGPU_LIGHT_SPHERE; }

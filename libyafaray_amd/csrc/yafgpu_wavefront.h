@@ -444,6 +444,76 @@ YG_DEV bool ieslight_illum_sample(const DevScene &sc, const yafgpu_light &l, V3 
 	return true;
 }
 
+// ---- SpotLight, light_spot.cc: a point light with a cone (cos_angle = cos_end_) and a smoothstep falloff between spot_cos_start and the
+// cone's edge.  The falloff of a cosine below cos_start_ (:102-103, :135-136, :245-246)
+YG_DEV float spotlight_falloff(const yafgpu_light &l, float cosa)
+{
+	const float v = (cosa - l.cos_angle) * l.spot_icos_diff;
+	return v * v * (3.f - 2.f * v);
+}
+// SpotLight::illuminate, :81-110 (YAFGPU_LIGHT_SPOT)
+YG_DEV bool spotlight_illuminate(const yafgpu_light &l, V3 sp_p, Col &col, V3 &wi_dir, float &wi_tmax)
+{
+	V3 ldir = vec3(l.position) - sp_p;
+	const float dist_sqr = ldir.x * ldir.x + ldir.y * ldir.y + ldir.z * ldir.z;
+	const float dist = f_sqrt(dist_sqr);
+	if(dist == 0.f) return false;
+	const float idist_sqr = 1.f / dist_sqr;
+	const float inv = 1.f / dist;
+	ldir.x *= inv; ldir.y *= inv; ldir.z *= inv;
+	const float cosa = dot(vec3(l.direction), ldir);
+	if(cosa < l.cos_angle) return false;                  // outside the cone
+	if(cosa >= l.spot_cos_start) col = col3(l.color) * idist_sqr;
+	else col = col3(l.color) * (spotlight_falloff(l, cosa) * idist_sqr);
+	wi_tmax = dist;
+	wi_dir = ldir;
+	return true;
+}
+// SpotLight::illumSample, :112-151 (YAFGPU_LIGHT_SPOT_SOFT): a direction in a cone around the direction to the light, spanned by the LIGHT's
+// du / dv and as wide as the light's own cone, from samples scaled by shadow_fuzzy_ (sic); the pdf is the squared distance, and below 1 it
+// becomes 1 with the distance moved into the colour (:144-148)
+YG_DEV bool spotlight_illum_sample(const yafgpu_light &l, V3 sp_p, float s_1, float s_2, V3 &wi_dir, float &wi_tmax, float &pdf, Col &col)
+{
+	V3 ldir = vec3(l.position) - sp_p;
+	const float dist_sqr = ldir.x * ldir.x + ldir.y * ldir.y + ldir.z * ldir.z;
+	if(dist_sqr == 0.f) return false;
+	const float dist = f_sqrt(dist_sqr);
+	const float inv = 1.f / dist;
+	ldir.x *= inv; ldir.y *= inv; ldir.z *= inv;
+	const float cosa = dot(vec3(l.direction), ldir);
+	if(cosa < l.cos_angle) return false;                  // outside the cone
+	wi_tmax = dist;
+	wi_dir = sample_cone(ldir, vec3(l.du), vec3(l.dv), l.cos_angle, s_1 * l.spot_shadow_fuzzy, s_2 * l.spot_shadow_fuzzy);
+	if(cosa >= l.spot_cos_start) col = col3(l.color);
+	else col = col3(l.color) * spotlight_falloff(l, cosa);
+	pdf = dist_sqr;
+	if(pdf < 1.f)
+	{
+		pdf = 1.f;
+		col = mkc(col.r / dist_sqr, col.g / dist_sqr, col.b / dist_sqr);
+	}
+	return true;
+}
+// SpotLight::intersect, :219-256 (YAFGPU_LIGHT_SPOT_SOFT), quirks kept: the ray has to meet the plane through the light across its axis in a
+// point whose offset from the light is EXACTLY perpendicular to the axis as floats round it (:231), and that point has to lie within 0.1 of
+// the WORLD ORIGIN, not of the light (:233, p * p against the double 1e-2); the cone test is on the ray's direction against dir_ = -ndir_
+YG_DEV bool spotlight_intersect(const yafgpu_light &l, V3 from, V3 dir, float &t, Col &col, float &ipdf)
+{
+	const V3 axis = -vec3(l.direction);                   // dir_
+	const float cos_a = dot(axis, dir);
+	if(cos_a == 0.f) return false;
+	t = dot(axis, vec3(l.position) - from) / cos_a;
+	if(t < 0.f) return false;
+	const V3 p = from + dir * t;
+	if(!(dot(axis, p - vec3(l.position)) == 0.f)) return false;
+	if(!((double)dot(p, p) <= 1e-2)) return false;
+	if(cos_a < l.cos_angle) return false;                 // outside the cone
+	if(cos_a >= l.spot_cos_start) col = col3(l.color);
+	else col = col3(l.color) * spotlight_falloff(l, cos_a);
+	ipdf = 1.f / (t * t);
+	return true;
+}
+
 // Material::isFlat() as doLightEstimation reads it (:105, :189).  Off sp.material_: under a mask that is the mask's, false, while the chosen
 // material's own eval keeps its flag (yafgpu_material::flat 2).  Masks live in kernels with textures only; the others test the word as before.
 YG_DEV bool wf_is_flat(const yafgpu_material &mat) { return YAFGPU_FEAT_TEXTURE ? (mat.flat & 1) != 0 : mat.flat != 0; }
@@ -462,6 +532,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		Col lcol;
 		if(YG_LIGHT_IS(light, YAFGPU_LIGHT_DIRECTIONAL)) { if(!directionallight_illuminate(light, sp.p, lcol, r_dir, r_tmax)) return false; }
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_IES)) { if(!ieslight_illuminate(ra.sc, light, sp.p, lcol, r_dir, r_tmax)) return false; }
+		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPOT)) { if(!spotlight_illuminate(light, sp.p, lcol, r_dir, r_tmax)) return false; }
 		else if(!pointlight_illuminate(light, sp.p, lcol, r_dir, r_tmax)) return false;
 		r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
 		const float angle = wf_is_flat(mat) ? 1.f : fabsf(dot(sp.n, r_dir));
@@ -478,6 +549,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_MESH)) { if(!meshlight_illum_sample(ra.sc, light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf)) return false; }
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_PORTAL)) { if(!portallight_illum_sample(ra.sc, light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col)) return false; }
 		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_IES_SOFT)) { if(!ieslight_illum_sample(ra.sc, light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col)) return false; }
+		else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPOT_SOFT)) { if(!spotlight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf, l_col)) return false; }
 		else if(!arealight_illum_sample(light, sp.p, s_1, s_2, r_dir, r_tmax, ls_pdf)) return false;
 		r_tmin = ra.rp.shadow_bias_auto ? ra.shadow_bias * smax(1.f, length(sp.p)) : ra.shadow_bias;
 		if(ls_pdf > 1e-6f)
@@ -485,14 +557,15 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 			const Col surf_col = matb_eval(mat, dat, sp, wo, r_dir, kAll);
 			const float angle = wf_is_flat(mat) ? 1.f : fabsf(dot(sp.n, r_dir));
 			// the light colour of this half is what illumSample returned (ls.col_, :178-262): col_pdf for the sun, the background in the sampled
-			// direction for the background light and the portal, the fixed colour otherwise
+			// direction for the background light and the portal, the colour with the falloff (and, nearer than 1, the distance) for the soft
+			// spot light, the fixed colour otherwise
 			if(YG_LIGHT_HAS(YAFGPU_LIGHT_SPHERE) && !light_can_intersect(light.type))
 			{	// a light the BSDF half cannot hit takes no MIS weight (:244-258)
 				contrib = ((surf_col * l_col) * angle) / ls_pdf;
 				return true;
 			}
 			const float m_pdf = matb_pdf(mat, dat, sp, wo, r_dir, kMisFlags);
-			const Col ls_col = (YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) || YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND) || YG_LIGHT_IS(light, YAFGPU_LIGHT_PORTAL)) ? l_col : col3(light.color);
+			const Col ls_col = (YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) || YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND) || YG_LIGHT_IS(light, YAFGPU_LIGHT_PORTAL) || YG_LIGHT_IS(light, YAFGPU_LIGHT_SPOT_SOFT)) ? l_col : col3(light.color);
 			if(m_pdf > 1e-6f)
 			{
 				const float l_2 = ls_pdf * ls_pdf, m_2 = m_pdf * m_pdf;
@@ -514,6 +587,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND)) { if(!(bs.pdf > 1e-6f && bglight_intersect(light, ra.sc.bg, ra.sc.tex, r_dir, r_tmax, l_col, light_ipdf))) return false; }
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPHERE)) return false;      // (canIntersect() is false: st_dl_eval never asks)
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_IES_SOFT)) return false;    // (the same)
+	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_SPOT_SOFT)) { if(!(bs.pdf > 1e-6f && spotlight_intersect(light, sp.p, r_dir, r_tmax, l_col, light_ipdf))) return false; }
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_MESH)) { if(!(bs.pdf > 1e-6f && meshlight_intersect(ra.sc, light, sp.p, r_dir, r_tmin, r_tmax, light_ipdf))) return false; }
 	else if(YG_LIGHT_IS(light, YAFGPU_LIGHT_PORTAL)) { if(!(bs.pdf > 1e-6f && portallight_intersect(ra.sc, light, sp.p, r_dir, r_tmin, r_tmax, light_ipdf, l_col))) return false; }
 	else if(!(bs.pdf > 1e-6f && arealight_intersect(light, sp.p, r_dir, r_tmax, light_ipdf))) return false;
@@ -522,7 +596,7 @@ YG_DEV bool dl_candidate(const RenderArgs &ra, const yafgpu_light &light, int ph
 		const float l_pdf = 1.f / light_ipdf;
 		const float l_2 = l_pdf * l_pdf, m_2 = bs.pdf * bs.pdf;
 		const float w = m_2 / (l_2 + m_2);
-		contrib = ((surf_col * ((YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) || YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND) || YG_LIGHT_IS(light, YAFGPU_LIGHT_PORTAL)) ? l_col : col3(light.color))) * w) * W;
+		contrib = ((surf_col * ((YG_LIGHT_IS(light, YAFGPU_LIGHT_SUN) || YG_LIGHT_IS(light, YAFGPU_LIGHT_BACKGROUND) || YG_LIGHT_IS(light, YAFGPU_LIGHT_PORTAL) || YG_LIGHT_IS(light, YAFGPU_LIGHT_SPOT_SOFT)) ? l_col : col3(light.color))) * w) * W;
 	}
 	return true;
 }
