@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Regenerate tests/golden/ref_components_{fast,ieee}.json.gz (and their textures / lights / integrator siblings, and
+"""Regenerate tests/golden/ref_components_{fast,ieee}.json.gz (and their textures / lights / spot_ies / cameras / integrator siblings, and
 faure_tables.json.gz).
 
 Runs ONLY in the build container (needs /root/reference).  It builds the component-level
@@ -19,6 +19,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
@@ -27,16 +28,24 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 def main():
     if not os.path.isdir("/root/reference"):
         sys.exit("reference tree not present; fixtures can only be regenerated in the build container")
-    which = sys.argv[1:] or ["components", "textures", "lights", "integrator", "integrator_lights", "faure"]
+    which = sys.argv[1:] or ["components", "textures", "lights", "spot_ies", "cameras", "integrator", "integrator_lights", "faure"]
     if "faure" in which:
         which.remove("faure")
         faure()
     if which:
         subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True, timeout=900)
+    ies_dir = tempfile.TemporaryDirectory()
+    if "spot_ies" in which:     # the IES files the spot / IES harness reads: written here from tests/ies_fixture.py, named to the driver
+        sys.path.insert(0, ROOT)
+        from tests import ies_fixture
+        for n in ies_fixture.SPECS:
+            ies_fixture.write(ies_dir.name, n)
     for name in which:          # textures: image textures + shader nodes, oracle/ref_harness/ref_textures.cc
         for variant in ("fast", "ieee"):
             # integrator_lights: the integrator harness's second document (`ref_integrator lights`: the directional, sun and sphere light cases)
             exe, *args = (f"ref_{name}_{variant}",) if name != "integrator_lights" else (f"ref_integrator_{variant}", "lights")
+            if name == "spot_ies":
+                args = [ies_dir.name]
             out = subprocess.run([os.path.join(ROOT, "oracle", "_ref", exe), *args], check=True, capture_output=True, timeout=120).stdout
             out = out[out.index(b"{\n"):]          # the reference's handlers log to stdout before the document starts
             path = os.path.join(HERE, f"ref_{name}_{variant}.json.gz")

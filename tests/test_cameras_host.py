@@ -445,3 +445,117 @@ def test_prepare_render_accepts_the_camera(tmp_path, t):
     assert yi.loadXml(str(path)), yi.getLastError()
     ok, msg = prepare_only(yi)
     assert ok or ("camera" not in msg.lower() and "scope" not in msg), msg
+
+
+# ---- the reference's compiled cameras ----------------------------------------------------------------------------------
+# tests/golden/ref_cameras_{ieee,fast}.json.gz: ArchitectCamera, AngularCamera and EquirectangularCamera made by their factories in the
+# reference harness (oracle/ref_harness/ref_cameras.cc), the 26 configurations of tests/test_gpu_cameras.py::RAY_CONFIGS
+from tests import pin_fixture as pin                                   # noqa: E402
+from tests.test_oracle_golden import FAST_ATOL, FAST_RTOL              # noqa: E402
+
+PINNED = pin.load("cameras", "ieee")["sets"]
+
+
+def pinned_camera(doc, name):
+    return pin.params(doc, name)
+
+
+def rays_against(rec, inp, want, what, angular):
+    """shoot() against fixture rows (n, 9) as bit patterns -> the share of live rows that are not bit-exact.  wt bit for bit on every row;
+    the other words bit for bit too, but that an angular row may differ where a double libm result narrows to the neighbouring float: at
+    most 0.1 % of the live rows, each within 1e-6 per direction component, origins exact (the rule of
+    tests/test_gpu_cameras.py::test_rays_bit_for_bit)"""
+    frm, dr, tmin, tmax, wt = shoot(rec, inp[:, 0], inp[:, 1], inp[:, 2], inp[:, 3])
+    assert np.array_equal(wt.view(np.uint32), want[:, 8]), f"{what}: wt"
+    live = wt != 0
+    got = np.column_stack([frm, dr, tmin, tmax]).astype(F)
+    assert not got[~live].any() and not want[~live, :8].any()
+    g, w = got[live].view(np.uint32), want[live, :8]
+    differ = ((g != w) & ~(((g | w) & 0x7fffffff) == 0)).any(axis=1)
+    if not angular:
+        assert not differ.any(), f"{what}: {int(differ.sum())} rows differ, first {inp[live][differ][0]}: {got[live][differ][0]} vs {w[differ][0].view(F)}"
+        return 0.0
+    share = float(differ.mean())
+    worst = float(np.abs(got[live][differ, 3:6].astype(D) - w[differ, 3:6].view(F)).max()) if differ.any() else 0.0
+    assert share <= 0.001 and worst <= 1e-6, (what, share, worst)
+    assert np.array_equal(g[differ, :3], w[differ, :3])
+    return share
+
+
+def test_fixture_configurations_are_the_gpu_tests_configurations():
+    from tests.test_gpu_cameras import RAY_CONFIGS
+    doc = pin.load("cameras", "ieee")
+    assert [doc[n + "_label"] for n in doc["sets"]] == [what for what, _ in RAY_CONFIGS]
+    for name, (_, cam) in zip(doc["sets"], RAY_CONFIGS):
+        want = {k: (tuple(float(F(x)) for x in v) if isinstance(v, tuple) else (float(F(v)) if isinstance(v, float) else v)) for k, v in cam.items()}
+        got = {k: (float(F(v)) if isinstance(v, float) else v) for k, v in pinned_camera(doc, name).items()}
+        assert got == want, name
+
+
+@pytest.mark.parametrize("name", PINNED)
+def test_restatement_reproduces_the_reference(name):
+    """shoot() and screenproject() of the restated record against the IEEE fixture, the C ABI's record against the restated one (so its
+    words are held to the reference's factory and constructor through the rays), the rows the fixture promises, and the circle's radius
+    between the radii of the rows the reference took and refused"""
+    doc = pin.load("cameras", "ieee")
+    cam = pinned_camera(doc, name)
+    rec = assert_record(cam)
+    rec = {k: (np.asarray(v, F) if np.ndim(v) else v) for k, v in rec.items()}
+    inp, want, _ = pin.leaf(doc, name, "shoot")
+    angular = cam["type"] == "angular"
+    assert rays_against(RECORD[cam["type"]](cam), inp, want, doc[name + "_label"], angular) == rays_against(rec, inp, want, "the C ABI's record", angular)
+    # the 81 pixel-boundary rows (a 0 / 0 near distance moves a row a few float steps, ref_cameras.cc), the four corners, the exact centre
+    gx, gy = np.meshgrid(np.arange(0, 25, 3, dtype=F), np.arange(0, 17, 2, dtype=F))
+    assert np.abs(inp[:81, 0] - gx.ravel()).max() < 1e-5 and np.abs(inp[:81, 1] - gy.ravel()).max() < 1e-5
+    assert all(((inp[:81, 0] == a) & (inp[:81, 1] == b)).any() for a in (0, 24) for b in (0, 16))
+    assert np.array_equal(inp[81], np.array([12, 8, 0.5, 0.5], F))
+    out = want.view(F)
+    dead = out[:, 8] == 0
+    assert not np.isnan(out).any()
+    if angular and cam["circular"]:
+        assert 0.1 <= dead.mean() <= 0.9
+        r = RECORD["angular"](cam)
+        u = F(1) - F(2) * (inp[:, 0] / F(r["resx"]))
+        v = (F(2) * (inp[:, 1] / F(r["resy"])) - F(1)) * r["aspect_ratio"]
+        radius = fsqrt(u * u + v * v)
+        assert radius[~dead].max() <= rec["max_radius"] < radius[dead].min()
+        circle = slice(82, 82 + 16 * 7)
+        assert dead[circle].sum() >= 16 and (~dead[circle]).sum() >= 16
+        assert radius[dead].min() - radius[~dead].max() <= 2.0 ** -23, "rows within a float step either side of the circle"
+    else:
+        assert not dead.any()
+    p, want, _ = pin.leaf(doc, name, "project")
+    s = screenproject(rec, p)
+    pin.same(s, want, f"{name} screenproject")
+    assert np.isfinite(s).all() and len(np.unique(s[:, 0])) == len(p)
+
+
+def test_release_flag_build_of_the_reference_agrees():
+    """the two builds of the reference against each other (a sample without a ray in one and with one in the other: below 1 % per
+    configuration), then the restatement against the release-flag one with the tolerances every release-flag fixture is compared with"""
+    ieee, fast = pin.load("cameras", "ieee"), pin.load("cameras", "fast")
+    worst = 0.0
+    for name in ieee["sets"]:
+        cam = pinned_camera(ieee, name)
+        rec = RECORD[cam["type"]](cam)
+        inp, a, _ = pin.leaf(ieee, name, "shoot")
+        inp_f, b, _ = pin.leaf(fast, name, "shoot")
+        # the same questions, the rows moved off a 0 / 0 near distance included (both builds meet it at the same floats), and no NaN in either
+        assert np.array_equal(inp.view(np.uint32), inp_f.view(np.uint32)), name
+        assert not np.isnan(a.view(F)).any() and not np.isnan(b.view(F)).any(), name
+        a, b = a.view(F).astype(D), b.view(F).astype(D)
+        differ = a[:, 8] != b[:, 8]
+        assert differ.mean() < 0.01, (name, differ.mean())
+        frm, dr, tmin, tmax, wt = shoot(rec, inp_f[:, 0], inp_f[:, 1], inp_f[:, 2], inp_f[:, 3])
+        got = np.column_stack([frm, dr, tmin, tmax, wt]).astype(D)
+        agree = ~differ
+        with np.errstate(invalid="ignore"):
+            between = np.abs(a - b)[agree]
+            worst = max(worst, float(np.nanmax(between / np.maximum(np.abs(b[agree]), 1.0))))
+        close = np.isclose(got[agree], b[agree], rtol=FAST_RTOL, atol=FAST_ATOL)
+        assert close.all(), (name, inp_f[agree][~close.all(axis=1)][:3], got[agree][~close.all(axis=1)][:3], b[agree][~close.all(axis=1)][:3])
+        p, a, _ = pin.leaf(ieee, name, "project")
+        p_f, b, _ = pin.leaf(fast, name, "project")
+        assert np.array_equal(p.view(np.uint32), p_f.view(np.uint32))
+        assert np.isclose(screenproject(rec, p_f).astype(D), b.view(F).astype(D), rtol=FAST_RTOL, atol=FAST_ATOL).all(), name
+    print(f"largest difference between the two builds of the reference (relative, absolute below 1): {worst:.3g}")

@@ -1,13 +1,15 @@
 """The architect, angular and equirectangular cameras on the DEVICE, against the float32 restatement of tests/test_cameras_host.py:
 rays bit for bit (probe op 7), a level architect camera against the perspective camera, whole films against an expectation composed from
 restated rays and the device's own closest hits, samples without a ray (outside the angular camera's circle) through the film, the ray
-counts, the serial-state replay, shards, pipelined and adaptive passes, and the `window` texture coordinate.
+counts, the serial-state replay, shards, pipelined and adaptive passes, the `window` texture coordinate — and against the reference's own compiled cameras (tests/golden/ref_cameras_ieee):
+rays and `window` coordinates of all 26 ray configurations.
 
 Frames are 24 x 16 with tiles of 7 unless stated: the aspect ratio matters, the circle cuts through pixels, the last tile is odd."""
 import numpy as np
 import pytest
 
 from libyafaray_amd import Interface, scenes
+from tests import pin_fixture as pin
 from tests.film_fixture import BACKGROUND, FACE_COLOURS, H, TILE, W, box_scene, box_settings, sample_offsets
 from tests.test_cameras_host import (F, PROJECTIONS, RECORD, architect_record, screenproject, shoot)
 from tests.test_gpu_components import exact
@@ -337,6 +339,19 @@ def test_window_coordinates(what, cam):
     """a texture_mapper on `window` coordinates (plain mapping, unit scale: the texture point is Camera::screenproject(p)) at 40 surface
     points (probe op 14) against the texture looked up at the restated screenproject (probe op 13), bit for bit"""
     rng = np.random.default_rng(5)
+    yi = window_scene(cam, rng)
+    n = 40
+    p = rng.uniform(-3, 3, (n, 3)).astype(F)
+    got = window_lookup(yi, p)
+    s = screenproject(RECORD[cam["type"]](cam), p)
+    assert np.isfinite(s).all() and len(np.unique(s[:, 0])) == n
+    want = texture_at(yi, s)
+    assert len(np.unique(want[:, 0])) > n // 2, "the texture does not tell the points apart"
+    exact(got[:, :4], want[:, :4].view(np.uint32), f"{what}: window coordinates")
+
+
+def window_scene(cam, rng):
+    """one triangle whose material reads an image texture through a texture_mapper on `window` coordinates, seen by `cam`"""
     texels = rng.random((13, 17, 4)).astype(F)
     yi = Interface()
     yi.startScene(0)
@@ -368,19 +383,60 @@ def test_window_coordinates(what, cam):
     yi.paramsClearAll()
     yi.paramsSet({"camera_name": "cam", "integrator_name": "default", "volintegrator_name": "volintegr", "width": W, "height": H})
     assert yi.prepareRender()
-    n = 40
-    p = rng.uniform(-3, 3, (n, 3)).astype(F)
-    sp = np.zeros((n, 20), F)
+    return yi
+
+
+def window_lookup(yi, p):
+    """probe op 14: the material's texture_mapper evaluated at surface points p, its texture point Camera::screenproject(p)"""
+    sp = np.zeros((len(p), 20), F)
     sp[:, 0:3] = p
     sp[:, 3:6] = sp[:, 6:9] = (0, -1, 0)
     sp[:, 18] = np.array([0], np.uint32).view(F)[0]
     sp[:, 19] = np.array([1], np.uint32).view(F)[0]
-    got = yi.probe(14, sp, 5)
-    s = screenproject(RECORD[cam["type"]](cam), p)
-    assert np.isfinite(s).all() and len(np.unique(s[:, 0])) == n
-    at = np.zeros((n, 4), F)
+    return yi.probe(14, sp, 5)
+
+
+def texture_at(yi, s):
+    """probe op 13: the texture looked up at texture points s"""
+    at = np.zeros((len(s), 4), F)
     at[:, :3] = s
     at[:, 3] = np.array([0], np.uint32).view(F)[0]
-    want = yi.probe(13, at, 5)
-    assert len(np.unique(want[:, 0])) > n // 2, "the texture does not tell the points apart"
-    exact(got[:, :4], want[:, :4].view(np.uint32), f"{what}: window coordinates")
+    return yi.probe(13, at, 5)
+
+
+# ---- 8. the reference's compiled cameras ------------------------------------------------------------------------------
+PINNED = pin.load("cameras", "ieee")
+
+
+@pytest.mark.parametrize("name", PINNED["sets"], ids=[PINNED[n + "_label"] for n in PINNED["sets"]])
+def test_cameras_match_the_reference(name):
+    """tests/golden/ref_cameras_ieee: what the reference's own ArchitectCamera, AngularCamera and EquirectangularCamera, made by their
+    factories from the parameters stored there (RAY_CONFIGS, as tests/test_cameras_host.py asserts), gave.  shootRay through probe op 7
+    under the exactness rule of test_rays_bit_for_bit (wt, architect and equirectangular bit for bit; an angular row may differ where a
+    double libm result narrows to the neighbouring float, at most 0.1 % of the live rows, 1e-6 per direction component, origins exact);
+    screenproject through the `window` coordinate (probe op 14) against the texture at the REFERENCE's screen point (probe op 13), bit
+    for bit"""
+    doc = PINNED
+    cam = pin.params(doc, name)
+    what = doc[name + "_label"]
+    yi = window_scene(cam, np.random.default_rng(5))
+    inp, want, _ = pin.leaf(doc, name, "shoot")
+    got = yi.probe(7, inp, 9)
+    exact(got[:, 8], want[:, 8], f"{what}: wt")
+    live = want[:, 8] != 0
+    g, w = got[live, :8], want[live, :8].view(F)
+    assert not np.isnan(g).any(), f"{what}: a live ray has a NaN"
+    differ = ((g.view(np.uint32) != w.view(np.uint32)) & ~((g == 0) & (w == 0))).any(axis=1)
+    share = float(differ.mean())
+    worst = float(np.abs(g[differ, 3:6].astype(np.float64) - w[differ, 3:6]).max()) if differ.any() else 0.0
+    print(f"{what}: {len(inp)} rows, {float((~live).mean()):.3f} without a ray, {share:.5f} of the live rows not bit-exact, largest direction deviation {worst:.3g}")
+    if cam["type"] != "angular":
+        assert not differ.any(), f"{what}: {int(differ.sum())} rows differ; first {inp[live][differ][0]}: {g[differ][0]} vs {w[differ][0]}"
+    else:
+        assert share <= 0.001 and worst <= 1e-6, (what, share, worst)
+        assert np.array_equal(g[differ, :3].view(np.uint32), w[differ, :3].view(np.uint32))
+    p, s, _ = pin.leaf(doc, name, "project")
+    got = window_lookup(yi, p)
+    want = texture_at(yi, s.view(F))
+    assert len(np.unique(want[:, 0])) > len(p) // 2, "the texture does not tell the points apart"
+    exact(got[:, :4], want[:, :4].view(np.uint32), f"{what}: screenproject")

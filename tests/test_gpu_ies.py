@@ -300,3 +300,44 @@ def test_variant_choice(files, monkeypatch, capfd):
     assert without and "ies" not in without and "blend_ies" not in without
     render(plane_scene([point]), res=16)
     assert kernel() == without, "a scene without an IES light keeps the kernel it had"
+
+
+# ---- the reference's compiled IesLight and IesData -----------------------------------------------------------------------
+def test_leaf_functions_match_the_reference(files):
+    """tests/golden/ref_spot_ies_ieee: what the reference's own IesData (parseIesFile, then getRadiance) and IesLight, made by its factory
+    from the parameters stored there, gave on the seven files, each as a Dirac light and with soft_shadows.  All fourteen are the lights
+    of one scene; getRadiance, illuminate and illumSample (probe ops 38, 39, 40) bit for bit on every row without a mark (a marked row's
+    lookup lies at or beyond the last entry of an angle map, where the reference reads past its array: no fixture value); the flags
+    against what light_is_dirac / light_can_intersect (yafgpu_shading.h) make of the type word getLights() shows"""
+    import os
+    from tests import pin_fixture as pin
+    doc = pin.load("spot_ies", "ieee")
+    names = doc["ies_sets"]
+    d = os.path.dirname(files[NAMES[0]])
+    yi = Interface()
+    scenes.load_scene(yi, plane_scene([pin.params(doc, n, d) for n in names], res=8), scenes.render_settings(8, 8, 1, integrator="directlighting"))
+    yi.prepareRender()
+    rec = yi.getLights()
+    assert rec.shape[0] == len(names) == 2 * len(NAMES)
+    rows = 0
+
+    def held(got, want, keep, what):
+        assert keep.mean() >= 0.95, what
+        exact(got[keep], want[keep], what)
+        return int(keep.sum())
+
+    for k, name in enumerate(names):
+        dirac, can_intersect, n_samples = doc[name + "_flags3"]
+        t, n = (int(x) for x in rec[k, :2].view(np.int32))
+        assert t in (9, 10) and (dirac, can_intersect) == (int(t == 9), 0), name          # light_is_dirac; neither kind can be intersected
+        assert n == (1 if dirac else n_samples), name
+        file = os.path.splitext(doc[name + "_params"]["file"])[0]
+        inp, want, keep = pin.leaf(doc, f"file_{file}", "radiance")
+        o = yi.probe(38, np.hstack([inp, kbits(len(inp), k)]), 2)
+        assert (o[:, 0] == 1).all()
+        rows += held(o[:, 1:], want, keep, f"{name} getRadiance")
+        for fn, op in (("illuminate", 39), ("illum_sample", 40)):
+            inp, want, keep = pin.leaf(doc, name, fn)
+            rows += held(yi.probe(op, np.hstack([inp, kbits(len(inp), k)]), want.shape[1]), want, keep, f"{name} {fn}")
+    print(f"{rows} rows against the reference")
+    assert rows >= 10000

@@ -416,3 +416,33 @@ def test_xml_scene_renders_the_film_of_the_api_scene(tmp_path, soft):
     assert np.array_equal(yx.getLights().view(np.uint32), ya.getLights().view(np.uint32))
     fx, fa = yx.getFilm(res, res), ya.getFilm(res, res)
     assert fa[..., :3].max() > 0 and np.array_equal(fx, fa)
+
+
+# ---- 10. the reference's compiled SpotLight ------------------------------------------------------------------------------------
+def test_leaf_functions_match_the_reference():
+    """tests/golden/ref_spot_ies_ieee: what the reference's own SpotLight, made by its factory from the parameters stored there (the
+    eight lights of LEAF and the eight of ORIGIN_LIGHTS, as tests/test_spot_host.py asserts), gave.  All sixteen are the lights of one
+    scene; illuminate, illumSample and intersect (probe ops 41, 42, 43) bit for bit on every row; diracLight() and canIntersect() against
+    what light_is_dirac / light_can_intersect (yafgpu_shading.h) make of the type word getLights() shows, nSamples() against its word"""
+    from tests import pin_fixture as pin
+    doc = pin.load("spot_ies", "ieee")
+    names = doc["spot_sets"] + doc["intersect_sets"]
+    yi = Interface()
+    scenes.load_scene(yi, plane_scene([pin.params(doc, n) for n in names], res=8), scenes.render_settings(8, 8, 1, integrator="directlighting"))
+    yi.prepareRender()
+    rec = yi.getLights()
+    assert rec.shape[0] == len(names) == 16
+    rows = 0
+    for k, name in enumerate(names):
+        dirac, can_intersect, n_samples = doc[name + "_flags3"]
+        t, n = (int(x) for x in rec[k, :2].view(np.int32))
+        assert t in (spf.TYPE_SPOT, spf.TYPE_SPOT_SOFT)
+        assert (dirac, can_intersect) == (int(t == spf.TYPE_SPOT), int(t == spf.TYPE_SPOT_SOFT)), name      # light_is_dirac, light_can_intersect
+        assert n == (1 if dirac else n_samples), name
+        for fn, op in (("illuminate", 41), ("illum_sample", 42)) if name in doc["spot_sets"] else (("intersect", 43),):
+            inp, want, _ = pin.leaf(doc, name, fn)
+            exact(yi.probe(op, np.hstack([inp, kbits(len(inp), k)]), want.shape[1]), want, f"{name} {fn}")
+            assert 0.02 <= (want[:, 0] != 0).mean() <= 0.98 or fn == "intersect"
+            rows += len(inp)
+    print(f"{rows} rows against the reference")
+    assert rows >= 10000

@@ -351,3 +351,119 @@ def test_flat_render_stays_under_its_caps_by_the_restatement_alone():
         o = ief.illuminate(p, c, pts)
         rad = o[ok, 5].astype(np.float64) / (9.0 * idist_sqr[ok].astype(np.float64))
         assert np.abs(rad - 1).max() <= 2.0 ** -21 + 2.0 ** -23        # (the division above un-does two roundings of the colour)
+
+
+# ---- the reference's compiled IesLight and IesData ------------------------------------------------------------------------
+# tests/golden/ref_spot_ies_{ieee,fast}.json.gz: IesData::parseIesFile + getRadiance and IesLight made by its factory in the reference
+# harness (oracle/ref_harness/ref_spot_ies.cc) on the seven files of tests/ies_fixture.py.  A row whose lookup the reference takes at or
+# beyond the last entry of an angle map carries a mark and no value (the reference reads past its array there): skipped.
+from tests import pin_fixture as pin                                   # noqa: E402
+from tests.test_oracle_golden import FAST_ATOL, FAST_RTOL              # noqa: E402
+
+IES_LEAVES = (("illuminate", lambda t, c, x: ief.illuminate(t, c, x)), ("illum_sample", lambda t, c, x: ief.illum_sample(t, c, x[:, :3], x[:, 3], x[:, 4])))
+
+
+def file_of(p):
+    return os.path.splitext(p["file"])[0]
+
+
+def test_fixture_covers_every_file_in_both_modes_and_few_rows_are_marked():
+    doc = pin.load("spot_ies", "ieee")
+    assert doc["ies_files"] == NAMES
+    assert doc["ies_sets"] == [f"ies_{n}_{mode}" for n in NAMES for mode in ("dirac", "soft")]
+    for n in NAMES:
+        _, _, keep = pin.leaf(doc, f"file_{n}", "radiance")
+        assert len(keep) >= 500 and (~keep).mean() <= 0.05, (n, (~keep).mean())
+    for name in doc["ies_sets"]:
+        for fn, _ in IES_LEAVES:
+            _, out, keep = pin.leaf(doc, name, fn)
+            assert (~keep).mean() <= 0.05 and not out[~keep].any(), (name, fn, (~keep).mean())
+            assert 0.1 <= (out[keep, 0] != 0).mean(), (name, fn)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_restated_lookup_reproduces_the_reference_bit_for_bit(name):
+    doc = pin.load("spot_ies", "ieee")
+    inp, want, keep = pin.leaf(doc, f"file_{name}", "radiance")
+    t = ief.parsed(name)
+    pin.same(ief.radiance(t, inp[:, 0], inp[:, 1])[:, None], want, f"getRadiance, {name}", keep)
+    # every node of both maps is among the inputs, as either angle
+    for m in (t["hor"], t["vert"]):
+        assert all((inp[:, 0] == a).any() and (inp[:, 1] == a).any() for a in m), name
+    assert len(np.unique(want[keep])) > 50 or name == "FLAT"
+
+
+def record_consts(r):
+    """the constants the leaf functions read, taken from a yafgpu_light record's words"""
+    return {"ndir": r[W_DIR:W_DIR + 3], "du": r[W_DU:W_DU + 3], "dv": r[W_DV:W_DV + 3], "cos_end": r[W_COS], "color": r[W_COLOR:W_COLOR + 3],
+            "position": r[W_POS:W_POS + 3]}
+
+
+def test_restatement_reproduces_the_reference_bit_for_bit(files):
+    """tests/ies_fixture.py on the inputs of the IEEE fixture: every output word of illuminate and illumSample on the unmarked rows and the
+    three flags; and the same functions fed with the words of the record createLight makes of the stored parameters and with the tables
+    getIesLight() hands out, which holds colour times power, the axis, du / dv, the cone's cosine and the parsed file to the reference's
+    constructor and parser at once.  The record's cosine also lies between the cosines the reference refused and took."""
+    doc = pin.load("spot_ies", "ieee")
+    d = os.path.dirname(files["C1"])
+    for name in doc["ies_sets"]:
+        p = pin.params(doc, name, d)
+        t = ief.parsed(file_of(doc[name + "_params"]))
+        c = ief.consts(t, p["from"], p["to"], p["color"], p["power"])
+        yi, h = light_of({k: (color(*v) if k == "color" else v) for k, v in p.items()})
+        assert h, (name, yi.getLastError())
+        rec = yi.getLights()[0]
+        soft = bool(p["soft_shadows"])
+        assert doc[name + "_flags3"] == [int(not soft), 0, p["samples"]]
+        assert [int(x) for x in rec[:2].view(np.int32)] == [10 if soft else 9, p["samples"] if soft else 1]
+        got_t = yi.getIesLight("l")
+        for fn, restated in IES_LEAVES:
+            inp, want, keep = pin.leaf(doc, name, fn)
+            pin.same(restated(t, c, inp), want, f"{name} {fn}", keep)
+            pin.same(restated(got_t, record_consts(rec), inp), want, f"{name} {fn} from the record's words", keep)
+        inp, want, keep = pin.leaf(doc, name, "illuminate")
+        _, dist, _, cosa, _ = ief._to_light(record_consts(rec), inp)
+        ok = want[:, 0] != 0
+        refused = keep & ~ok & (dist != 0)
+        if refused.any():
+            assert cosa[refused].max() < rec[W_COS], name
+        assert rec[W_COS] <= cosa[keep & ok].min(), name
+
+
+def test_release_flag_build_of_the_reference_agrees():
+    """the two builds of the reference against each other, then the restatement against the release-flag one on the rows both builds
+    give a value for and agree on `ok`.  The table interpolation cancels ((1 - d) * a + d * b between entries that differ tenfold) and
+    d_x, d_y are quotients of differences of angles the builds form a float step apart; where that puts the two builds further apart
+    than the tolerances every release-flag fixture is compared with, the band is twice their own difference on that row ("IES
+    lights", has the largest measured one)"""
+    ieee, fast = pin.load("spot_ies", "ieee"), pin.load("spot_ies", "fast")
+    worst = {}
+    leaves = [(f"file_{n}", "radiance", n, None) for n in NAMES] + [(s, fn, file_of(ieee[s + "_params"]), r) for s in ieee["ies_sets"] for fn, r in IES_LEAVES]
+    for name, fn, file, restated in leaves:
+        inp, a, keep_a = pin.leaf(ieee, name, fn)
+        inp_f, b, keep_b = pin.leaf(fast, name, fn)
+        same_input = (inp.view(np.uint32) == inp_f.view(np.uint32)).all(axis=1)
+        # (the handful of rows on the cone's rim follow each build's own cosine; the rest are the same questions)
+        assert (~same_input).sum() <= 18, (name, fn, int((~same_input).sum()))
+        a, b = a.view(np.float32).astype(np.float64), b.view(np.float32).astype(np.float64)
+        t = ief.parsed(file)
+        if restated is None:
+            both = keep_a & keep_b & same_input
+            agree = both
+            got = ief.radiance(t, inp_f[:, 0], inp_f[:, 1])[:, None].astype(np.float64)
+        else:
+            p = pin.params(ieee, name)
+            both = keep_a & keep_b & same_input
+            differ = both & (a[:, 0] != b[:, 0])
+            assert differ.sum() < 0.01 * both.sum(), (name, fn, int(differ.sum()))
+            agree = both & ~differ
+            got = restated(t, ief.consts(t, p["from"], p["to"], p["color"], p["power"]), inp_f).astype(np.float64)
+        between = np.abs(a - b)
+        rel = between[agree] / np.maximum(np.abs(b[agree]), 1e-30)
+        worst[fn] = max(worst.get(fn, 0.0), float(rel[np.abs(b[agree]) > 1e-3].max()))
+        band = np.maximum(FAST_ATOL + FAST_RTOL * np.abs(b), 2.0 * between)
+        bad = (np.abs(got - b) > band) & agree[:, None]
+        assert not bad.any(), (name, fn, int(bad.sum()), np.nonzero(bad.any(axis=1))[0][:5])
+        wide = ((between > FAST_ATOL + FAST_RTOL * np.abs(b)) & agree[:, None]).any(axis=1).sum()
+        assert wide <= 0.02 * agree.sum(), (name, fn, int(wide))
+    print("largest relative difference between the two builds of the reference, per leaf:", {k: f"{v:.3g}" for k, v in worst.items()})

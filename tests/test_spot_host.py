@@ -233,3 +233,146 @@ def test_xml_scene_loads_to_the_records_of_the_api_calls(tmp_path):
     want1 = spf.record(spf.consts((-1, 0, 1.5), (0, 0, -1), (0.5, 0.5, 1.0), 2.0, 60.0, 0.15, 0.5), True, 3)
     want1[2] = 0                                                       # cast_shadows off
     assert np.array_equal(bits(got[1]), want1)
+
+
+# ---- the reference's compiled SpotLight -----------------------------------------------------------------------------------
+# tests/golden/ref_spot_ies_{ieee,fast}.json.gz: SpotLight made by its factory in the reference harness (oracle/ref_harness/ref_spot_ies.cc)
+from tests import pin_fixture as pin                                   # noqa: E402
+from tests.test_oracle_golden import FAST_ATOL, FAST_RTOL              # noqa: E402
+
+SPOT_LEAVES = (("illuminate", lambda c, x: spf.illuminate(c, x)), ("illum_sample", lambda c, x: spf.illum_sample(c, x[:, :3], x[:, 3], x[:, 4])),
+               ("intersect", lambda c, x: spf.intersect(c, x[:, :3], x[:, 3:6])))
+
+
+def pinned_consts(p):
+    return spf.consts(p["from"], p["to"], p["color"], p["power"], p.get("cone_angle", 45.0), p.get("blend", 0.15), p.get("shadowFuzzyness", 1.0))
+
+
+def record_consts(r):
+    """the constants the leaf functions read, taken from a yafgpu_light record's words"""
+    return {"ndir": r[4:7], "du": r[7:10], "dv": r[10:13], "cos_end": r[13], "cos_start": r[spf.W_COS_START], "icos_diff": r[spf.W_ICOS_DIFF],
+            "fuzzy": r[spf.W_FUZZY], "color": r[25:28], "position": r[29:32]}
+
+
+def spot_sets(doc):
+    return [(n, fns) for names, fns in ((doc["spot_sets"], SPOT_LEAVES[:2]), (doc["intersect_sets"], SPOT_LEAVES[2:])) for n in names]
+
+
+def test_fixture_lights_are_the_gpu_tests_lights():
+    from tests import test_gpu_spot as g
+    doc = pin.load("spot_ies", "ieee")
+    assert len(doc["spot_sets"]) == len(g.LEAF) and len(doc["intersect_sets"]) == len(g.ORIGIN_LIGHTS)
+    for name, (a, b, f, s) in zip(doc["spot_sets"], g.LEAF):
+        p = pin.params(doc, name)
+        assert (p["from"], p["to"], p["color"], p["power"]) == tuple(tuple(float(np.float32(v)) for v in t) if isinstance(t, tuple) else t
+                                                                      for t in (g.FROM, g.TO, g.COL, g.POWER))
+        assert (p["cone_angle"], np.float32(p["blend"]), p["shadowFuzzyness"], p["soft_shadows"]) == (a, np.float32(b), f, s)
+    for name, (frm, to) in zip(doc["intersect_sets"], g.ORIGIN_LIGHTS):
+        p = pin.params(doc, name)
+        assert p["from"] == tuple(float(np.float32(v)) for v in frm) and p["to"] == tuple(float(np.float32(v)) for v in to)
+        assert (p["cone_angle"], p["blend"], p["soft_shadows"]) == (45.0, 0.5, True)
+
+
+def test_restatement_reproduces_the_reference_bit_for_bit():
+    """tests/spot_fixture.py on the inputs of the IEEE fixture: every output word of illuminate, illumSample and intersect, the three
+    flags; and the same leaf functions fed with the words of the record createLight makes of the stored parameters, which holds
+    colour times power, the axis, du / dv, both cosines, icos_diff_ and the fuzzyness to the reference's constructor at once"""
+    doc = pin.load("spot_ies", "ieee")
+    for name, fns in spot_sets(doc):
+        p = pin.params(doc, name)
+        yi, h = light_of({k: (color(*v) if k == "color" else v) for k, v in p.items()})
+        assert h, (name, yi.getLastError())
+        rec = yi.getLights()[0]
+        soft = bool(p["soft_shadows"])
+        assert doc[name + "_flags3"] == [int(not soft), int(soft), p["samples"]]
+        assert [int(x) for x in rec[:2].view(np.int32)] == [spf.TYPE_SPOT_SOFT if soft else spf.TYPE_SPOT, p["samples"] if soft else 1]
+        for fn, restated in fns:
+            inp, want, _ = pin.leaf(doc, name, fn)
+            pin.same(restated(pinned_consts(p), inp), want, f"{name} {fn}")
+            pin.same(restated(record_consts(rec), inp), want, f"{name} {fn} from the record's words")
+
+
+def test_record_cosines_straddle_what_the_reference_took_and_refused():
+    """cos_end_: the largest cosine the reference refused lies below the record's word, the smallest it accepted at or above it.  cos_start_:
+    illumSample hands out colour times power untouched at or above it and scaled by the smoothstep below: every row whose colour is
+    smaller lies below the record's word, every row at or above it carries the record's colour bit for bit"""
+    doc = pin.load("spot_ies", "ieee")
+    for name in doc["spot_sets"]:
+        p = pin.params(doc, name)
+        yi, h = light_of({k: (color(*v) if k == "color" else v) for k, v in p.items()})
+        rec = yi.getLights()[0]
+        inp, want, _ = pin.leaf(doc, name, "illum_sample")
+        out = want.view(np.float32)
+        _, dist_sqr, dist, cosa, _ = spf._to_light(record_consts(rec), inp[:, :3])
+        ok = out[:, 0] == 1
+        away = dist != 0
+        assert cosa[away & ~ok].max() < rec[13] <= cosa[ok].min(), name
+        # the threshold rows sit ON the cone and on its float neighbour below (ref_spot_ies.cc places them there)
+        assert cosa[ok].min() == rec[13] and np.nextafter(cosa[away & ~ok].max(), np.float32(2)) == rec[13], name
+        far = ok & (out[:, 5] > 1)
+        full = (out[:, 6:9] == rec[25:28]).all(axis=1)
+        less = (out[:, 6:9] < rec[25:28]).all(axis=1)
+        assert (full | less)[far].all() and full[far].any(), name
+        assert full[far & (cosa >= rec[spf.W_COS_START])].all(), name
+        if p["blend"] > 0:
+            assert less[far].any() and cosa[far & less].max() < rec[spf.W_COS_START], name
+        else:
+            assert full[far].all() and rec[spf.W_COS_START] == rec[13]
+
+
+def falloff_step(c, pts, over_dist_sqr):
+    """what a float step of cos_end_ moves the colour by, (n, 3), in float64 from the formulas: the two builds of the reference form the
+    5 degree cone's cos_end_ a float step apart (2^-24 for a cosine in [0.5, 1)), which moves the smoothstep's argument v = (cosa - cos_end_)
+    * icos_diff_ by dv = 2^-24 * icos_diff_ and s(v) = v^2 (3 - 2 v) by at most s'(v) dv + 3 dv^2 with s'(v) = 6 v (1 - v); the colour is
+    colour x power x s(v), over the squared distance in illuminate and, nearer than 1, in illumSample.  (The caller doubles it: icos_diff_
+    moves with cos_end_ too, by the same relative amount.)"""
+    ldir = c["position"].astype(np.float64) - pts.astype(np.float64)
+    d2 = (ldir ** 2).sum(axis=1)
+    with np.errstate(all="ignore"):
+        cosa = ldir @ c["ndir"].astype(np.float64) / np.sqrt(d2)
+        v = np.clip((cosa - float(c["cos_end"])) * float(c["icos_diff"]), 0.0, 1.0)
+        dv = 2.0 ** -24 * float(c["icos_diff"]) if np.isfinite(c["icos_diff"]) else 0.0
+        ds = 6.0 * v * (1.0 - v) * dv + 3.0 * dv * dv
+        k = np.where(over_dist_sqr | (d2 < 1.0), 1.0 / d2, 1.0)
+    return np.nan_to_num(c["color"].astype(np.float64)[None, :] * (k * ds)[:, None], nan=0.0, posinf=0.0)
+
+
+def test_release_flag_build_of_the_reference_agrees():
+    """the two builds of the reference against each other, then the restatement against the release-flag one on the rows where the two
+    agree on `ok`.  The smoothstep's argument (cosa - cos_end_) * icos_diff_ cancels: one float step of cosa (6e-8) is a relative
+    6e-8 * icos_diff_ / v of v, unbounded towards the cone's edge.  So the band of a falloff row is twice what the two builds of the
+    reference differ by on that row ("Spot lights": the largest measured difference is written there), never less than the
+    tolerances every release-flag fixture is compared with"""
+    ieee, fast = pin.load("spot_ies", "ieee"), pin.load("spot_ies", "fast")
+    worst = 0.0
+    for name, fns in spot_sets(ieee):
+        p = pin.params(ieee, name)
+        assert pin.params(fast, name) == p
+        for fn, restated in fns:
+            inp, a, _ = pin.leaf(ieee, name, fn)
+            inp_f, b, _ = pin.leaf(fast, name, fn)
+            # the same rows, but for those the driver places ON a cone: they follow each build's own cosines, which differ by a float step
+            # for the 5 degree cone, so that each build's rows sit at its own threshold and on either side of it
+            same_input = (inp.view(np.uint32) == inp_f.view(np.uint32)).all(axis=1)
+            assert same_input.mean() > 0.6 and (same_input.all() or p["cone_angle"] == 5.0), (name, fn, same_input.mean())
+            # Such a row is a threshold row of a threshold the two builds put a float step apart: each build was asked its own question there.
+            # The comparison between the two fixtures leaves them out; the restatement is held to the release-flag build's own rows below.
+            a, b = a.view(np.float32).astype(np.float64), b.view(np.float32).astype(np.float64)
+            agree = (a[:, 0] == b[:, 0]) & same_input
+            assert (a[:, 0] != b[:, 0]).mean() < 0.01, (name, fn, (a[:, 0] != b[:, 0]).mean())
+            between = np.abs(a - b)
+            over = between - (FAST_ATOL + FAST_RTOL * np.abs(b))
+            worst = max(worst, float((between[agree] / np.maximum(np.abs(b[agree]), 1e-30)).max()))
+            band = np.maximum(FAST_ATOL + FAST_RTOL * np.abs(b), 2.0 * between)
+            got = restated(pinned_consts(p), inp_f).astype(np.float64)
+            bad = (np.abs(got - b) > band) & agree[:, None]
+            assert not bad.any(), (name, fn, int(bad.sum()), np.nonzero(bad.any(axis=1))[0][:5])
+            # the rows asked apart: the release-flag build's own question and answer against the restatement with the plain tolerances,
+            # wherever the restatement (IEEE thresholds, a float step from that build's) decides `ok` as that build did
+            apart = ~same_input & (got[:, 0] == b[:, 0])
+            tol = FAST_ATOL + FAST_RTOL * np.abs(b)
+            tol[:, -3:] += 2.0 * falloff_step(pinned_consts(p), inp_f[:, :3], fn == "illuminate")
+            assert (np.abs(got - b) <= tol)[apart].all(), (name, fn)
+            assert same_input.all() or apart.sum() >= 0.5 * (~same_input).sum(), (name, fn, int(apart.sum()))
+            print(f"{name} {fn}: {int((a[:, 0] != b[:, 0]).sum())} rows of {len(a)} differ in ok, {int((~same_input).sum())} were asked apart, {int((over[agree] > 0).any(axis=1).sum())} rows beyond the plain tolerances between the builds")
+    print(f"largest relative difference between the two builds of the reference: {worst:.3g}")
