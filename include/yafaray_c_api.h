@@ -121,6 +121,10 @@ int yafaray_getLights(yafaray_interface_t *yi, void *out, int max_lights);
 /* extension (test support): the yafgpu_background record (include/yafgpu.h, 12 words) createBackground made under `name`, as the
  * device scene would get it; false when there is no such background */
 yafaray_bool_t yafaray_getBackground(yafaray_interface_t *yi, const char *name, void *out);
+/* extension (test support): the yafgpu_sky record (include/yafgpu.h, 240 bytes: 20 float words, then 20 doubles) createBackground made
+ * under `name` beside its yafgpu_background: a gradientback's colours or a sunsky's constants, zeros for every other type; false when
+ * there is no such background */
+yafaray_bool_t yafaray_getSky(yafaray_interface_t *yi, const char *name, void *out);
 /* extension (test support): the yafgpu_camera record (include/yafgpu.h, 69 words) createCamera made under `name`, as the device scene
  * would get it — but for the bokeh corner table `ls`, which yafgpu_scene_create fills; false when there is no such camera */
 yafaray_bool_t yafaray_getCamera(yafaray_interface_t *yi, const char *name, void *out);
@@ -203,7 +207,11 @@ yafaray_texture_t *yafaray_createTexture(yafaray_interface_t *yi, const char *na
                                                                                                bilinear interpolation); procedural types are refused */
 yafaray_material_t *yafaray_createMaterial(yafaray_interface_t *yi, const char *name);      /* :94 */
 yafaray_camera_t *yafaray_createCamera(yafaray_interface_t *yi, const char *name);          /* :95 */
-yafaray_background_t *yafaray_createBackground(yafaray_interface_t *yi, const char *name);  /* :96 */
+yafaray_background_t *yafaray_createBackground(yafaray_interface_t *yi, const char *name);  /* :96: types "constant", "textureback",
+                                                                                               "gradientback" (with horizon_color and zenith_color)
+                                                                                               and "sunsky" (with from; add_sun is refused), each
+                                                                                               with or without its background light; "darksky" and
+                                                                                               the bare sky calls are refused */
 yafaray_integrator_t *yafaray_createIntegrator(yafaray_interface_t *yi, const char *name);  /* :97 */
 void yafaray_clearAll(yafaray_interface_t *yi);                                             /* :101 */
 /* not in the reference's Interface: an image texture over RGBA float texels the caller holds (row major, as the reference's

@@ -75,7 +75,11 @@ enum { YAFGPU_LIGHT_AREA = 0, YAFGPU_LIGHT_POINT = 1, YAFGPU_LIGHT_DIRECTIONAL =
           (canIntersect() == soft_shadows_, light_spot.h), so it takes both halves of the MIS pair, although its intersect() almost never
           answers true.  Not 13: the next unknown type stays unknown */
        YAFGPU_LIGHT_SPOT = 11, YAFGPU_LIGHT_SPOT_SOFT = 12 };
-enum { YAFGPU_BACKGROUND_NONE = 0, YAFGPU_BACKGROUND_CONSTANT = 1, YAFGPU_BACKGROUND_TEXTURE = 2 };
+enum { YAFGPU_BACKGROUND_NONE = 0, YAFGPU_BACKGROUND_CONSTANT = 1, YAFGPU_BACKGROUND_TEXTURE = 2,
+       /* The sky backgrounds: GradientBackground (background_gradient.cc) and SunSkyBackground (background_sunsky.cc, the Preetham model).
+          Their constants are in yafgpu_scene_desc::sky, not in yafgpu_background.  Not 3: YAFGPU_BACKGROUND_TEXTURE + 1 is the kind that
+          tests/scene_desc_cases.cpp hands yafgpu_scene_create as an unknown one, and it stays unknown */
+       YAFGPU_BACKGROUND_GRADIENT = 4, YAFGPU_BACKGROUND_SUNSKY = 5 };
 enum { YAFGPU_INTEGRATOR_PATH = 0, YAFGPU_INTEGRATOR_DIRECT = 1 };
 enum { YAFGPU_FILTER_BOX = 0, YAFGPU_FILTER_MITCHELL = 1, YAFGPU_FILTER_GAUSS = 2, YAFGPU_FILTER_LANCZOS = 3 };
 
@@ -259,6 +263,8 @@ typedef struct yafgpu_light
  *   constant  color (col * power), has_ibl, shoots_caustic (always 1, background_constant.cc:69)
  *   texture   texture (index into the scene's textures), projection (0 spherical, 1 angular), power, rotation (2 * rot / 360),
  *             sin_r / cos_r (fSin__ / fCos__ of pi * rotation), has_ibl, shoots_caustic (with_caustic)
+ *   gradient  has_ibl, shoots_caustic (always 1, background_gradient.cc:84); the four colours are in yafgpu_sky
+ *   sunsky    has_ibl, shoots_caustic (always 1, background_sunsky.cc:220); everything else is in yafgpu_sky
  * With has_ibl the scene has exactly one YAFGPU_LIGHT_BACKGROUND light; yafgpu_scene_create builds its tables on the device. */
 typedef struct yafgpu_background
 {
@@ -269,6 +275,22 @@ typedef struct yafgpu_background
 	float rotation, sin_r, cos_r;
 	int32_t has_ibl, shoots_caustic;
 } yafgpu_background;
+
+/* What a sky background adds to yafgpu_background, which keeps its 12 words: the constants its factory and constructor leave on the host
+ * (background_gradient.cc:61-103; background_sunsky.cc:37-76, :181-264).  Read only where the background's kind is one of the two skies.
+ *   gradient  horizon, zenith, horizon_ground, zenith_ground: shoriz_, szenith_, ghoriz_, gzenith_, each already times `power`
+ *   sunsky    power (power_, a double parameter narrowed), from (the direction as given; it is normalised where it is used) and
+ *             turbidity, kept for yafgpu_scene_create's checks; then what the constructor computes in double: theta_s, phi_s, the zenith
+ *             chromaticities and luminance, and the three sets of Perez coefficients */
+typedef struct yafgpu_sky
+{
+	float horizon[3], zenith[3], horizon_ground[3], zenith_ground[3];
+	float power, from[3];
+	float turbidity, pad[3];
+	double theta_s, phi_s;
+	double zenith_x, zenith_y, zenith_Y;
+	double perez_x[5], perez_y[5], perez_Y[5];
+} yafgpu_sky;
 
 enum { YAFGPU_CAMERA_PERSPECTIVE = 0, YAFGPU_CAMERA_ARCHITECT = 1, YAFGPU_CAMERA_ANGULAR = 2, YAFGPU_CAMERA_EQUIRECTANGULAR = 3 };
 /* AngularProjection (camera_angular.h); an unknown word in the ParamMap means equidistant (camera_angular.cc:109-113) */
@@ -389,6 +411,7 @@ typedef struct yafgpu_scene_desc
 	   strictly increasing, in degrees) and its table, row-major by horizontal angle.  Zeroed = no IES light */
 	int32_t n_ies_floats;
 	const float *ies_tables;     /* n_ies_floats */
+	yafgpu_sky sky;              /* the constants of a gradient or sunsky background; read only with background.kind 4 or 5 */
 } yafgpu_scene_desc;
 
 typedef struct yafgpu_render_params

@@ -63,13 +63,17 @@ cc shade_blend_ies yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=blend_ies -DYA
 #   light type's code; a scene takes one of them when it has a spot light of either kind, whatever other lights it has (an IES light included)
 cc shade_spot yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=spot -DYAFGPU_MAT_MASK=0x7fu -DYAFGPU_LIGHT_MASK=0x1fbfu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1
 cc shade_blend_spot yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=blend_spot -DYAFGPU_MAT_MASK=0x17fu -DYAFGPU_LIGHT_MASK=0x1fbfu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1
+#   sky, blend_sky: the same two with the evaluation of the gradient and sunsky backgrounds as well (YAFGPU_FEAT_SKY, yafgpu_texture.h: bg_eval); a scene
+#   takes one of them when its background is one of the two, whatever lights it has, so that every other scene's kernels stay what they were
+cc shade_sky yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=sky -DYAFGPU_MAT_MASK=0x7fu -DYAFGPU_LIGHT_MASK=0x1fbfu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1 -DYAFGPU_FEAT_SKY=1
+cc shade_blend_sky yafgpu_shade_variant.hip -DYAFGPU_VARIANT_NAME=blend_sky -DYAFGPU_MAT_MASK=0x17fu -DYAFGPU_LIGHT_MASK=0x1fbfu -DYAFGPU_FEAT_RECURSE=1 -DYAFGPU_FEAT_TEXTURE=1 -DYAFGPU_FEAT_ANISO=1 -DYAFGPU_FEAT_AO=1 -DYAFGPU_FEAT_MULTI=1 -DYAFGPU_FEAT_SKY=1
 # scene set-up for instanced geometry: the rows of the flattened scene, made on the device (same flags: its arithmetic must round like the host loop's)
 cc yafgpu_assemble yafgpu_assemble.hip
 # the output stage: film -> packed pixels of an image file (same flags: its arithmetic must round like the host's deliver_to)
 cc yafgpu_output yafgpu_output.hip
 cc kdtree_build kdtree_build.cpp
 cc kdtree_build_device kdtree_build_device.hip
-OBJS="$OBJ/yafgpu_device.o $OBJ/shade_diffuse.o $OBJ/shade_glossy.o $OBJ/shade_diffuse_mp.o $OBJ/shade_glossy_mp.o $OBJ/shade_diffuse_rec.o $OBJ/shade_glossy_rec.o $OBJ/shade_full.o $OBJ/shade_blend.o $OBJ/shade_meshlight.o $OBJ/shade_blend_meshlight.o $OBJ/shade_portal.o $OBJ/shade_blend_portal.o $OBJ/shade_ies.o $OBJ/shade_blend_ies.o $OBJ/shade_spot.o $OBJ/shade_blend_spot.o $OBJ/yafgpu_assemble.o $OBJ/yafgpu_output.o $OBJ/kdtree_build.o $OBJ/kdtree_build_device.o"
+OBJS="$OBJ/yafgpu_device.o $OBJ/shade_diffuse.o $OBJ/shade_glossy.o $OBJ/shade_diffuse_mp.o $OBJ/shade_glossy_mp.o $OBJ/shade_diffuse_rec.o $OBJ/shade_glossy_rec.o $OBJ/shade_full.o $OBJ/shade_blend.o $OBJ/shade_meshlight.o $OBJ/shade_blend_meshlight.o $OBJ/shade_portal.o $OBJ/shade_blend_portal.o $OBJ/shade_ies.o $OBJ/shade_blend_ies.o $OBJ/shade_spot.o $OBJ/shade_blend_spot.o $OBJ/shade_sky.o $OBJ/shade_blend_sky.o $OBJ/yafgpu_assemble.o $OBJ/yafgpu_output.o $OBJ/kdtree_build.o $OBJ/kdtree_build_device.o"
 # (yafaray_ies.cpp, the IES file parser, is part of yafaray_c_api's unit: it is included there)
 for f in yafaray_c_api yafaray_xml yafaray_image yafaray_reduce; do
   if [ -f "$HERE/$f.cpp" ]; then cc "$f" "$f.cpp"; OBJS="$OBJS $OBJ/$f.o"; fi

@@ -106,7 +106,7 @@ struct IntegratorCfg
 };
 
 struct CameraCfg { yafgpu_camera cam; };
-struct BackgroundCfg { float color[3]; yafgpu_background rec; };      // color: the constant colour (yafgpu_render_params::background); rec: what the device scene gets
+struct BackgroundCfg { float color[3]; yafgpu_background rec; yafgpu_sky sky; };      // color: the constant colour (yafgpu_render_params::background); rec, sky: what the device scene gets (sky: a gradient's or a sunsky's constants, else zero)
 
 } // namespace
 
@@ -1864,6 +1864,13 @@ yafaray_bool_t yafaray_getBackground(yafaray_interface_t *yi, const char *name, 
 	if(out) std::memcpy(out, &it->second->b.rec, sizeof(yafgpu_background));
 	return 1;
 }
+yafaray_bool_t yafaray_getSky(yafaray_interface_t *yi, const char *name, void *out)
+{
+	auto it = name ? yi->backgrounds.find(name) : yi->backgrounds.end();
+	if(it == yi->backgrounds.end()) return fail(yi, "getSky: no such background");
+	if(out) std::memcpy(out, &it->second->b.sky, sizeof(yafgpu_sky));
+	return 1;
+}
 yafaray_bool_t yafaray_getIntegratorAO(yafaray_interface_t *yi, const char *name, int *do_ao, int *samples, float *distance, float *color3)
 {
 	auto it = name ? yi->integrators.find(name) : yi->integrators.end();
@@ -2209,8 +2216,29 @@ yafaray_background_t *yafaray_createBackground(yafaray_interface_t *yi, const ch
 	const ParamMap &p = yi->params;
 	if(!name) { fail(yi, "createBackground: null name"); return nullptr; }
 	if(!p.get("type", type)) { fail(yi, "createBackground: type of background not specified"); return nullptr; }
-	if(type != "constant" && type != "textureback")
-	{ fail(yi, "createBackground: background type \"" + type + "\" is outside the GPU path's scope (constant, textureback)"); return nullptr; }
+	// The two skies are built only when the call names what they stand on — a sunsky its `from`, a gradientback both its horizon_color and
+	// its zenith_color — which every exporter writes; the bare call of either type stays refused, the one deviation from the reference's
+	// defaults.  darksky, and a sunsky that adds its own sun, need the measured spectral tables the project does not have.
+	float sky_from[3] = {1.f, 1.f, 1.f}, sky_horizon[3] = {1.f, 1.f, 1.f}, sky_zenith[3] = {0.4f, 0.5f, 1.f};
+	const bool sunsky = type == "sunsky" && p.getPoint("from", sky_from);
+	const bool has_horizon = p.getColor("horizon_color", sky_horizon), has_zenith = p.getColor("zenith_color", sky_zenith);
+	const bool gradient = type == "gradientback" && has_horizon && has_zenith;
+	if(type != "constant" && type != "textureback" && !sunsky && !gradient)
+	{
+		fail(yi, "createBackground: " + std::string(type == "sunsky" ? "from is not given: " : type == "gradientback" ? "horizon_color and zenith_color are not both given: " : "") +
+		         "background type \"" + type + "\" is outside the GPU path's scope (constant, textureback, sunsky with the from it takes the sun's direction from, and gradientback with its horizon_color and zenith_color" +
+		         (type == "darksky" ? "; darksky computes its colours from measured spectral tables, which the GPU path does not have" : "") + ")");
+		return nullptr;
+	}
+	if(sunsky)
+	{
+		bool add_sun = false;
+		if(p.get("add_sun", add_sun) && add_sun)
+		{
+			fail(yi, "createBackground: sunsky with add_sun = true takes the sun's colour from measured spectral tables, which the GPU path does not have; leave add_sun off and create a sunlight of your own in the same direction");
+			return nullptr;
+		}
+	}
 	auto b = std::make_unique<yafaray_background>();
 	std::memset(&b->b, 0, sizeof b->b);
 	yafgpu_background &rec = b->b.rec;
@@ -2227,6 +2255,72 @@ yafaray_background_t *yafaray_createBackground(yafaray_interface_t *yi, const ch
 		rec.has_ibl = ibl ? 1 : 0;
 		rec.shoots_caustic = 1;          // :69: the constructor gets `true` whatever with_caustic says
 		if(ibl) add_background_light(yi, "constantBackground_bgLight", ibl_sam, cast_shadows, 0.f);
+	}
+	else if(gradient)
+	{	// GradientBackground::factory, background_gradient.cc:61-103: the ground colours default to the sky's, `power` goes into all four
+		// colours, and the constructor gets `true` for with_caustic whatever the parameter says (:84)
+		yafgpu_sky &k = b->b.sky;
+		float ground_horizon[3] = {sky_horizon[0], sky_horizon[1], sky_horizon[2]}, ground_zenith[3] = {sky_zenith[0], sky_zenith[1], sky_zenith[2]};
+		p.getColor("horizon_ground_color", ground_horizon); p.getColor("zenith_ground_color", ground_zenith);
+		for(int j = 0; j < 3; ++j)
+		{
+			k.horizon[j] = sky_horizon[j] * power; k.zenith[j] = sky_zenith[j] * power;
+			k.horizon_ground[j] = ground_horizon[j] * power; k.zenith_ground[j] = ground_zenith[j] * power;
+			if(!std::isfinite(k.horizon[j]) || !std::isfinite(k.zenith[j]) || !std::isfinite(k.horizon_ground[j]) || !std::isfinite(k.zenith_ground[j]))
+			{ fail(yi, "createBackground: gradientback: a colour times power is not finite"); return nullptr; }
+		}
+		rec.kind = YAFGPU_BACKGROUND_GRADIENT; rec.power = power; rec.texture = -1;
+		rec.has_ibl = ibl ? 1 : 0; rec.shoots_caustic = 1;
+		if(ibl) add_background_light(yi, "GradientBackground_bgLight", ibl_sam, cast_shadows, 0.f);
+	}
+	else if(sunsky)
+	{	// SunSkyBackground::factory, background_sunsky.cc:181-264, and the constructor, :37-76, in double as there.  The light is asked for
+		// by background_light / light_samples, not ibl / ibl_samples; power is a double parameter narrowed at the constructor call
+		yafgpu_sky &k = b->b.sky;
+		float turb = 4.f, av = 1.f, bv = 1.f, cv = 1.f, dv = 1.f, ev = 1.f;
+		double dpower = 1.0;
+		bool bgl = false; int bgl_samples = 8;
+		p.get("turbidity", turb); p.get("power", dpower);
+		p.get("a_var", av); p.get("b_var", bv); p.get("c_var", cv); p.get("d_var", dv); p.get("e_var", ev);
+		p.get("background_light", bgl); p.get("light_samples", bgl_samples);
+		if(sky_from[0] == 0.f && sky_from[1] == 0.f && sky_from[2] == 0.f)
+		{ fail(yi, "createBackground: sunsky: from, the direction to the sun, is the zero vector"); return nullptr; }
+		k.power = (float)dpower; k.turbidity = turb;
+		for(int j = 0; j < 3; ++j) k.from[j] = sky_from[j];
+		float sun[3] = {sky_from[0], sky_from[1], sky_from[2]};
+		ref_normalize(sun);
+		// fAcos__ (util_math_optimizations.h:255-261): the double acos of a float, narrowed
+		const float theta_f = (double)sun[2] <= -1.0 ? (float)3.14159265358979323846 : (double)sun[2] >= 1.0 ? 0.0f : (float)std::acos((double)sun[2]);
+		const double theta_s = (double)theta_f, theta_2 = theta_s * theta_s, theta_3 = theta_2 * theta_s;
+		const double t = (double)turb, t_2 = (double)(turb * turb);      // (t_2_ = turb * turb is a float product)
+		k.theta_s = theta_s;
+		k.phi_s = std::atan2((double)sun[1], (double)sun[0]);
+		const double chi = (4.0 / 9.0 - t / 120.0) * (3.14159265358979323846 - 2.0 * theta_s);
+		k.zenith_Y = (4.0453 * t - 4.9710) * std::tan(chi) - 0.2155 * t + 2.4192;
+		k.zenith_Y *= 1000;
+		k.zenith_x = (0.00165 * theta_3 - 0.00375 * theta_2 + 0.00209 * theta_s) * t_2 +
+		             (-0.02903 * theta_3 + 0.06377 * theta_2 - 0.03202 * theta_s + 0.00394) * t +
+		             (0.11693 * theta_3 - 0.21196 * theta_2 + 0.06052 * theta_s + 0.25886);
+		k.zenith_y = (0.00275 * theta_3 - 0.00610 * theta_2 + 0.00317 * theta_s) * t_2 +
+		             (-0.04214 * theta_3 + 0.08970 * theta_2 - 0.04153 * theta_s + 0.00516) * t +
+		             (0.15346 * theta_3 - 0.26756 * theta_2 + 0.06670 * theta_s + 0.26688);
+		const double var[5] = {(double)av, (double)bv, (double)cv, (double)dv, (double)ev};
+		const double c_Y[5][2] = {{0.17872, -1.46303}, {-0.35540, 0.42749}, {-0.02266, 5.32505}, {0.12064, -2.57705}, {-0.06696, 0.37027}};
+		const double c_x[5][2] = {{-0.01925, -0.25922}, {-0.06651, 0.00081}, {-0.00041, 0.21247}, {-0.06409, -0.89887}, {-0.00325, 0.04517}};
+		const double c_y[5][2] = {{-0.01669, -0.26078}, {-0.09495, 0.00921}, {-0.00792, 0.21023}, {-0.04405, -1.65369}, {-0.01092, 0.05291}};
+		for(int j = 0; j < 5; ++j)
+		{
+			k.perez_Y[j] = (c_Y[j][0] * t + c_Y[j][1]) * var[j];
+			k.perez_x[j] = (c_x[j][0] * t + c_x[j][1]) * var[j];
+			k.perez_y[j] = (c_y[j][0] * t + c_y[j][1]) * var[j];
+		}
+		bool finite = std::isfinite(k.power) && std::isfinite(turb) && std::isfinite(k.theta_s) && std::isfinite(k.phi_s) && std::isfinite(k.zenith_x) && std::isfinite(k.zenith_y) && std::isfinite(k.zenith_Y);
+		for(int j = 0; j < 5; ++j) finite = finite && std::isfinite(k.perez_x[j]) && std::isfinite(k.perez_y[j]) && std::isfinite(k.perez_Y[j]);
+		for(int j = 0; j < 3; ++j) finite = finite && std::isfinite(sky_from[j]);
+		if(!finite) { fail(yi, "createBackground: sunsky: from, turbidity, power or one of a_var .. e_var is not finite, or leaves the sky model a value that is not"); return nullptr; }
+		rec.kind = YAFGPU_BACKGROUND_SUNSKY; rec.power = k.power; rec.texture = -1;
+		rec.has_ibl = bgl ? 1 : 0; rec.shoots_caustic = 1;      // :220: the constructor gets `true` whatever with_caustic says
+		if(bgl) add_background_light(yi, "sunsky_bgLight", bgl_samples, cast_shadows, 0.f);
 	}
 	else
 	{	// TextureBackground::factory, background_texture.cc:91-165
@@ -2730,7 +2824,7 @@ yafgpu_scene_desc describe_scene(const FlatScene &f, const Selection &sel, int t
 	d.n_light_tris = (int32_t)(f.light_verts.size() / 9); d.light_verts = f.light_verts.data();
 	d.light_tri_mat = f.light_tri_mat.empty() ? nullptr : f.light_tri_mat.data();
 	d.n_ies_floats = (int32_t)f.ies_tables.size(); d.ies_tables = f.ies_tables.empty() ? nullptr : f.ies_tables.data();
-	if(sel.bg) d.background = sel.bg->rec;
+	if(sel.bg) { d.background = sel.bg->rec; d.sky = sel.bg->sky; }
 	d.camera = sel.cam->cam;
 	d.build_threads = 0;
 	if(threads > 0) d.build_threads = threads;

@@ -664,7 +664,7 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 		case 22:
 		{	// Background::eval: in dir.xyz -> rgb
 			if(n_in < 3 || n_out < 3 || sc.bg.rec.kind == YAFGPU_BACKGROUND_NONE) break;
-			const Col c = bg_eval(sc.bg, sc.tex, mk(x[0], x[1], x[2]));
+			const Col c = bg_eval<true>(sc.bg, sc.tex, mk(x[0], x[1], x[2]));      // (<true>: with the skies' code, which this unit's wf_shade is built without)
 			o[0] = c.r; o[1] = c.g; o[2] = c.b;
 			break;
 		}
@@ -672,7 +672,7 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 		{	// BackgroundLight::illumSample: in s_1, s_2 -> ok, wi.dir, wi.tmax, pdf, ls.col
 			if(n_in < 2 || n_out < 9 || sc.bg.tab == nullptr) break;
 			Col c = mkc(0.f, 0.f, 0.f); V3 d = mk(0.f, 0.f, 0.f); float tmax = 0.f, pdf = 0.f;
-			const bool ok = bglight_illum_sample(sc.bg, sc.tex, x[0], x[1], d, tmax, pdf, c);
+			const bool ok = bglight_illum_sample<true>(sc.bg, sc.tex, x[0], x[1], d, tmax, pdf, c);
 			o[0] = ok ? 1.f : 0.f;
 			o[1] = d.x; o[2] = d.y; o[3] = d.z; o[4] = tmax; o[5] = pdf; o[6] = c.r; o[7] = c.g; o[8] = c.b;
 			break;
@@ -684,7 +684,7 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			while(k < sc.n_lights && sc.lights[k].type != YAFGPU_LIGHT_BACKGROUND) ++k;
 			if(k >= sc.n_lights) break;
 			Col c = mkc(0.f, 0.f, 0.f); float t = 0.f, ipdf = 0.f;
-			const bool ok = bglight_intersect(sc.lights[k], sc.bg, sc.tex, mk(x[0], x[1], x[2]), t, c, ipdf);
+			const bool ok = bglight_intersect<true>(sc.lights[k], sc.bg, sc.tex, mk(x[0], x[1], x[2]), t, c, ipdf);
 			o[0] = ok ? 1.f : 0.f; o[1] = t; o[2] = ipdf; o[3] = c.r; o[4] = c.g; o[5] = c.b;
 			break;
 		}
@@ -855,7 +855,7 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			const uint32_t k = __float_as_uint(x[5]);
 			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_PORTAL) break;
 			V3 d = mk(0.f, 0.f, 0.f); float tmax = 0.f, pdf = 0.f; Col c = mkc(0.f, 0.f, 0.f);
-			if(!portallight_illum_sample(sc, sc.lights[k], mk(x[0], x[1], x[2]), x[3], x[4], d, tmax, pdf, c)) break;
+			if(!portallight_illum_sample<true>(sc, sc.lights[k], mk(x[0], x[1], x[2]), x[3], x[4], d, tmax, pdf, c)) break;
 			o[0] = 1.f; o[1] = d.x; o[2] = d.y; o[3] = d.z; o[4] = tmax; o[5] = pdf; o[6] = c.r; o[7] = c.g; o[8] = c.b;
 			break;
 		}
@@ -865,7 +865,7 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(const DevScene sc, int op
 			const uint32_t k = __float_as_uint(x[7]);
 			if(k >= (uint32_t)sc.n_lights || sc.lights[k].type != YAFGPU_LIGHT_PORTAL) break;
 			float t = 0.f, ipdf = 0.f; Col c = mkc(0.f, 0.f, 0.f);
-			if(!portallight_intersect(sc, sc.lights[k], mk(x[0], x[1], x[2]), mk(x[3], x[4], x[5]), x[6], t, ipdf, c)) break;
+			if(!portallight_intersect<true>(sc, sc.lights[k], mk(x[0], x[1], x[2]), mk(x[3], x[4], x[5]), x[6], t, ipdf, c)) break;
 			o[0] = 1.f; o[1] = t; o[2] = ipdf; o[3] = c.r; o[4] = c.g; o[5] = c.b;
 			break;
 		}
@@ -965,19 +965,31 @@ __global__ __launch_bounds__(kBlock) void bg_rows_kernel(const DevScene sc, floa
 	for(int xi = (int)threadIdx.x; xi < nu; xi += (int)blockDim.x)
 	{
 		const float fx = ((float)xi + 0.5f) * inu;
-		const Col c = bg_eval(sc.bg, sc.tex, bg_inv_spheremap(fx, fy));
+		const Col c = bg_eval<true>(sc.bg, sc.tex, bg_inv_spheremap(fx, fy));
 		row[kBgFunc + xi] = ((c.r + c.g + c.b) * 0.333333f) * sintheta;      // Rgb::energy, color.h:58
 	}
 	__syncthreads();
 	if(threadIdx.x == 0) pdf1d_build(row, nu);
 }
-// v_dist_: the same construction over the rows' integrals (:106, :109); one workgroup, after bg_rows_kernel
-__global__ __launch_bounds__(kBlock) void bg_vdist_kernel(float *tab)
+// v_dist_: the same construction over the rows' integrals (:106, :109); one workgroup, after bg_rows_kernel.
+// check (the two skies): a sky can leave latitude rows without energy, whose Pdf1D divides by zero.  The same thread counts the rows whose
+// integral is not a finite number above zero into the first spare float behind v_dist_'s cdf_ (bit 16: the total is no such number
+// either), where the host reads one word back; the tables themselves are what they would be without the count.
+constexpr int kBgFlag = kBgCdf + kBgMaxU + 1;
+static_assert(kBgFlag < kBgRowStride, "the row stride leaves a spare float behind cdf_");
+YG_DEV bool bg_has_energy(float integral) { return integral > 0.f && integral <= 3.402823466e+38f; }
+__global__ __launch_bounds__(kBlock) void bg_vdist_kernel(float *tab, int check)
 {
 	float *row = tab + (size_t)kBgRows * kBgRowStride;
 	for(int y = (int)threadIdx.x; y < kBgRows; y += (int)blockDim.x) row[kBgFunc + y] = tab[(size_t)y * kBgRowStride + 1];
 	__syncthreads();
-	if(threadIdx.x == 0 && blockIdx.x == 0) pdf1d_build(row, kBgRows);
+	if(threadIdx.x != 0 || blockIdx.x != 0) return;
+	pdf1d_build(row, kBgRows);
+	if(!check) return;
+	uint32_t bad = 0u;
+	for(int y = 0; y < kBgRows; ++y) if(!bg_has_energy(row[kBgFunc + y])) ++bad;
+	if(!bg_has_energy(row[1])) bad |= 1u << 16;
+	row[kBgFlag] = __uint_as_float(bad);
 }
 
 // MeshLight::initIs (light_meshlight.cc:55-73), one workgroup per light of the scene; those of other types have nothing to do.  The threads
@@ -1119,6 +1131,7 @@ struct yafgpu_scene
 	size_t lgeo_floats = 0;              // floats of the light-geometry pool: the mesh lights' and portals' triangles and rows, the portals' records, the IES lights' tables (upload_lights, mesh_light_rows)
 	size_t ies_base = 0;                 // where the IES lights' tables start in that pool
 	bool has_ies = false;                // some light is an IES light: its tables are in the pool
+	bool has_sky = false;                // the background is a gradient or a sunsky: the shading units built with their evaluation
 	bool has_volumetric = false;
 	int max_add_depth = 0;               // the largest Material::additional_depth_ of the scene: recursion frames beyond raydepth
 	bool has_glossy_two = false;         // rough glass: a glossy trajectory sends two rays (the replay's call count)
@@ -1322,6 +1335,27 @@ static bool node_range_ok(const yafgpu_node *nodes, int first, int count)
 
 // Every refusal that depends on the descriptor alone, on the host, before a scene object or any device memory exists.  (One refusal is left
 // for later: a coordinate that an instance's matrix overflows, which only the device finds, assemble_scene.)
+// the constants of a gradient or a sunsky background, before anything is uploaded: every value the kind reads is a finite number, and a
+// sunsky's direction is not the zero vector (its normalisation would leave it zero, and theta_s with it a quarter turn whatever was meant)
+static int check_sky(int kind, const yafgpu_sky &k)
+{
+	if(kind == YAFGPU_BACKGROUND_GRADIENT)
+	{
+		const float *cols[4] = {k.horizon, k.zenith, k.horizon_ground, k.zenith_ground};
+		for(const float *c : cols)
+			for(int j = 0; j < 3; ++j)
+				if(!std::isfinite(c[j])) return fail(-2, "gradient background: a colour is not finite");
+		return 0;
+	}
+	if(k.from[0] == 0.f && k.from[1] == 0.f && k.from[2] == 0.f) return fail(-2, "sunsky background: `from`, the direction to the sun, is the zero vector");
+	const double vals[5] = {k.theta_s, k.phi_s, k.zenith_x, k.zenith_y, k.zenith_Y};
+	bool ok = std::isfinite(k.power) && std::isfinite(k.turbidity) && std::isfinite(k.from[0]) && std::isfinite(k.from[1]) && std::isfinite(k.from[2]);
+	for(double v : vals) ok = ok && std::isfinite(v);
+	for(int j = 0; j < 5; ++j) ok = ok && std::isfinite(k.perez_x[j]) && std::isfinite(k.perez_y[j]) && std::isfinite(k.perez_Y[j]);
+	if(!ok) return fail(-2, "sunsky background: a value of the sky record (power, turbidity, from, the sun's angles, the zenith values or a Perez coefficient) is not finite");
+	return 0;
+}
+
 static int check_desc(const yafgpu_scene_desc *d)
 {
 	if(!d) return fail(-1, "null argument");
@@ -1342,7 +1376,9 @@ static int check_desc(const yafgpu_scene_desc *d)
 		const yafgpu_background &b = d->background;
 		int n_bg_lights = 0;
 		for(int i = 0; i < d->n_lights; ++i) if(d->lights[i].type == YAFGPU_LIGHT_BACKGROUND) ++n_bg_lights;
-		if(b.kind < YAFGPU_BACKGROUND_NONE || b.kind > YAFGPU_BACKGROUND_TEXTURE) return fail(-2, "background: unknown kind");
+		const bool sky = b.kind == YAFGPU_BACKGROUND_GRADIENT || b.kind == YAFGPU_BACKGROUND_SUNSKY;
+		if((b.kind < YAFGPU_BACKGROUND_NONE || b.kind > YAFGPU_BACKGROUND_TEXTURE) && !sky) return fail(-2, "background: unknown kind");
+		if(sky) { const int rc = check_sky(b.kind, d->sky); if(rc) return rc; }
 		if(n_bg_lights > 1) return fail(-2, "more than one background light");
 		if(n_bg_lights != ((b.kind != YAFGPU_BACKGROUND_NONE && b.has_ibl) ? 1 : 0)) return fail(-2, "a background light needs a background with has_ibl, and such a background its light");
 		if(b.kind == YAFGPU_BACKGROUND_TEXTURE)
@@ -1779,7 +1815,10 @@ static void bokeh_table(yafgpu_camera &cam)
 static int background_tables(yafgpu_scene *s, const yafgpu_scene_desc *d)
 {
 	DevScene &dv = s->dev;
-	dv.bg.rec = d->background; dv.bg.tab = nullptr;
+	dv.bg.rec = d->background; dv.bg.tab = nullptr; dv.bg.sky = nullptr;
+	const bool sky = d->background.kind == YAFGPU_BACKGROUND_GRADIENT || d->background.kind == YAFGPU_BACKGROUND_SUNSKY;
+	if(sky) { const int rc = upload(s, &d->sky, 1, &dv.bg.sky); if(rc) return rc; }
+	s->has_sky = sky;
 	if(d->background.kind == YAFGPU_BACKGROUND_NONE || !d->background.has_ibl) return 0;
 	float *tab = nullptr;
 	const size_t n_tab = (size_t)(kBgRows + 1) * kBgRowStride;
@@ -1790,11 +1829,17 @@ static int background_tables(yafgpu_scene *s, const yafgpu_scene_desc *d)
 	if(e == hipSuccess)
 	{
 		hipLaunchKernelGGL(bg_rows_kernel, dim3((uint32_t)kBgRows), dim3(kBlock), 0, nullptr, dv, tab);
-		hipLaunchKernelGGL(bg_vdist_kernel, dim3(1), dim3(kBlock), 0, nullptr, tab);
+		hipLaunchKernelGGL(bg_vdist_kernel, dim3(1), dim3(kBlock), 0, nullptr, tab, sky ? 1 : 0);
 		e = hipGetLastError();
 	}
 	if(e == hipSuccess) e = hipDeviceSynchronize();
+	uint32_t bad = 0u;
+	if(e == hipSuccess && sky) e = hipMemcpy(&bad, tab + (size_t)kBgRows * kBgRowStride + kBgFlag, sizeof bad, hipMemcpyDeviceToHost);
 	if(e != hipSuccess) return fail(-100, std::string("background light tables: ") + hipGetErrorString(e));
+	if(bad != 0u)
+		return fail(-2, "a sky background with a light needs energy in every latitude row: " + std::to_string(bad & 0xffffu) + " of " + std::to_string(kBgRows) +
+		                " rows of the light's tables integrate to nothing or to no finite number" + ((bad >> 16) ? ", and so does their total" : "") +
+		                " (Pdf1D would divide by zero; a sun below the horizon or a very low turbidity does this: render the sky without its light)");
 	dv.bg.tab = tab;
 	return 0;
 }
@@ -2131,6 +2176,8 @@ YG_DECLARE_SHADE_VARIANT(ies)
 YG_DECLARE_SHADE_VARIANT(blend_ies)
 YG_DECLARE_SHADE_VARIANT(spot)
 YG_DECLARE_SHADE_VARIANT(blend_spot)
+YG_DECLARE_SHADE_VARIANT(sky)
+YG_DECLARE_SHADE_VARIANT(blend_sky)
 #undef YG_DECLARE_SHADE_VARIANT
 }
 struct ShadeVariant
@@ -2171,8 +2218,14 @@ static const ShadeVariant kBlendIesVariant = {"blend_ies", yafgpu_shade_blend_ie
 // them, before the IES light's, so that a scene with both finds the code of both.
 static const ShadeVariant kSpotVariant = {"spot", yafgpu_shade_spot_describe, yafgpu_shade_spot_kernel, yafgpu_shade_spot_launch};
 static const ShadeVariant kBlendSpotVariant = {"blend_spot", yafgpu_shade_blend_spot_describe, yafgpu_shade_blend_spot_kernel, yafgpu_shade_blend_spot_launch};
+// And once more with the two sky backgrounds' evaluation (YAFGPU_FEAT_SKY) on top of every light type's code: a gradient or a sunsky background
+// picks one of them, first, so that a sky beside spot, IES, portal or mesh lights finds the code of all of them; for a record pass too,
+// whose escaping rays ask for the sky of their direction.
+static const ShadeVariant kSkyVariant = {"sky", yafgpu_shade_sky_describe, yafgpu_shade_sky_kernel, yafgpu_shade_sky_launch};
+static const ShadeVariant kBlendSkyVariant = {"blend_sky", yafgpu_shade_blend_sky_describe, yafgpu_shade_blend_sky_kernel, yafgpu_shade_blend_sky_launch};
 static const ShadeVariant *pick_shade_variant(const yafgpu_scene *s, const Switches &sw, int frames, bool record_pass, bool want_multi, bool ao)
 {
+	if(s->has_sky) return s->has_blend ? &kBlendSkyVariant : &kSkyVariant;
 	if(s->light_mask & ((1u << (uint32_t)YAFGPU_LIGHT_SPOT) | (1u << (uint32_t)YAFGPU_LIGHT_SPOT_SOFT))) return s->has_blend ? &kBlendSpotVariant : &kSpotVariant;
 	if(s->has_ies) return s->has_blend ? &kBlendIesVariant : &kIesVariant;
 	if(s->light_mask & (1u << (uint32_t)YAFGPU_LIGHT_PORTAL)) return s->has_blend ? &kBlendPortalVariant : &kPortalVariant;

@@ -16,7 +16,8 @@
 // the general kernel and the blend's with that light's code, picked by a mesh light in the scene, and the two built with the portal light's
 // bit as well, YAFGPU_LIGHT_MASK & 0x100, picked by a portal light, and the two built with the IES light's bits on top of those,
 // YAFGPU_LIGHT_MASK & 0x600, picked by an IES light of either kind, and the two built with the spot light's bits on top of all of them,
-// YAFGPU_LIGHT_MASK & 0x1800, picked by a spot light of either kind)
+// YAFGPU_LIGHT_MASK & 0x1800, picked by a spot light of either kind, and the two built with -DYAFGPU_FEAT_SKY=1 on top of those, which
+// evaluate the gradient and sunsky backgrounds and are picked by such a background before anything else)
 //
 // and includes the main unit with everything but wf_shade and what it calls compiled out.  All of its symbols live in
 // their own namespace (the macro below renames `yafgpu`), so the variants and the main unit link into one library; the

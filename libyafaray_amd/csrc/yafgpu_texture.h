@@ -736,7 +736,11 @@ YG_DEV void blend_at_hit(const TexScene &ts, const yafgpu_camera &cam, const yaf
 constexpr int kBgRows = 360, kBgMaxU = 720, kBgMinU = 16;      // MAX_VSAMPLES, MAX_USAMPLES, MIN_SAMPLES (light_background.cc:33-35)
 constexpr int kBgFunc = 4, kBgCdf = kBgFunc + kBgMaxU;
 constexpr int kBgRowStride = 1448;                              // 4 + 720 + 721 = 1445, rounded up to 32 bytes
-struct BgScene { yafgpu_background rec; const float *tab; };     // tab: (kBgRows + 1) * kBgRowStride floats, or nullptr without the light
+struct BgScene
+{
+	yafgpu_background rec; const float *tab;      // tab: (kBgRows + 1) * kBgRowStride floats, or nullptr without the light
+	const yafgpu_sky *sky;                         // a gradient's or a sunsky's constants (device memory), nullptr for every other kind
+};
 
 YG_DEV void bg_angmap(V3 p, float &u, float &v)
 {
@@ -773,9 +777,94 @@ YG_DEV V3 bg_inv_spheremap(float u, float v)
 	const float cosphi = f_cos(phi), sinphi = f_sin(phi);
 	return mk(sintheta * cosphi, sintheta * sinphi, -costheta);
 }
+// ---- the sky backgrounds.  Their code is in a kernel only where it is asked for (kSky): the set-up and probe kernels, and the shading units
+// built with YAFGPU_FEAT_SKY (csrc/build.sh: sky, blend_sky); every other kernel keeps the code it had.
+#ifndef YAFGPU_FEAT_SKY
+#define YAFGPU_FEAT_SKY 0
+#endif
+// GradientBackground::eval, background_gradient.cc:40-59: dir.z as given, not normalised
+YG_DEV Col sky_gradient_eval(const yafgpu_sky &k, V3 dir)
+{
+	Col color;
+	float blend = dir.z;
+	if(blend >= 0.f) color = col3(k.zenith) * blend + col3(k.horizon) * (1.f - blend);
+	else
+	{
+		blend = -blend;
+		color = col3(k.zenith_ground) * blend + col3(k.horizon_ground) * (1.f - blend);
+	}
+	if(smin(color.r, smin(color.g, color.b)) < 1e-6f) color = mkc(1e-5f, 1e-5f, 1e-5f);
+	return color;
+}
+YG_DEV float f_exp(float a) { return f_exp2((float)1.4426950408889634074 * a); }      // fExp__, util_math_optimizations.h:194-201
+// SunSkyBackground::perezFunction, background_sunsky.cc:83-105.  The exponentials, sines and cosines are the float helpers (their double
+// arguments are narrowed at the call, their float results widened); cos(theta) is the double one
+YG_DEV double sky_perez(const double *lam, double theta_s, double theta, double gamma, double lvz)
+{
+	double e_1, e_2, e_3, e_4;
+	if(lam[1] <= 230.) e_1 = (double)f_exp((float)lam[1]);
+	else e_1 = 7.7220185e99;
+	if((e_2 = lam[3] * theta_s) <= 230.) e_2 = (double)f_exp((float)e_2);
+	else e_2 = 7.7220185e99;
+	if((e_3 = lam[1] / cos(theta)) <= 230.) e_3 = (double)f_exp((float)e_3);
+	else e_3 = 7.7220185e99;
+	if((e_4 = lam[3] * gamma) <= 230.) e_4 = (double)f_exp((float)e_4);
+	else e_4 = 7.7220185e99;
+	const double den = (1 + lam[0] * e_1) * (1 + lam[2] * e_2 + lam[4] * (double)f_cos((float)theta_s) * (double)f_cos((float)theta_s));
+	const double num = (1 + lam[0] * e_3) * (1 + lam[2] * e_4 + lam[4] * (double)f_cos((float)gamma) * (double)f_cos((float)gamma));
+	return (lvz * num / den);
+}
+// SunSkyBackground::angleBetween, :108-114: the sum of products is formed in float
+YG_DEV double sky_angle_between(const yafgpu_sky &k, double thetav, double phiv)
+{
+	const double cospsi = (double)(f_sin((float)thetav) * f_sin((float)k.theta_s) * f_cos((float)(k.phi_s - phiv)) + f_cos((float)thetav) * f_cos((float)k.theta_s));
+	if(cospsi > 1) return 0;
+	if(cospsi < -1) return kPi;
+	return (double)f_acos((float)cospsi);
+}
+// SunSkyBackground::eval = power_ * getSkyCol, :116-179
+YG_DEV Col sky_sunsky_eval(const yafgpu_sky &k, V3 dir)
+{
+	const V3 iw = normalize(dir);
+	double theta, phi, hfade = 1, nfade = 1;
+	theta = (double)f_acos(iw.z);
+	if(theta > (0.5 * kPi))
+	{
+		hfade = 1.0 - (theta * k1Pi - 0.5) * 2.0;
+		hfade = hfade * hfade * (3.0 - 2.0 * hfade);
+		theta = 0.5 * kPi;
+	}
+	if(k.theta_s > (0.5 * kPi))
+	{
+		if(theta <= 0.5 * kPi)
+		{
+			nfade = 1.0 - (0.5 - theta * k1Pi) * 2.0;
+			nfade *= 1.0 - (k.theta_s * k1Pi - 0.5) * 2.0;
+			nfade = nfade * nfade * (3.0 - 2.0 * nfade);
+		}
+	}
+	if((iw.y == 0.f) && (iw.x == 0.f)) phi = kPi * 0.5;
+	else phi = atan2((double)iw.y, (double)iw.x);
+	const double gamma = sky_angle_between(k, theta, phi);
+	const double x = sky_perez(k.perez_x, k.theta_s, theta, gamma, k.zenith_x);
+	const double y = sky_perez(k.perez_y, k.theta_s, theta, gamma, k.zenith_y);
+	const double Y = 6.666666667e-5 * nfade * hfade * sky_perez(k.perez_Y, k.theta_s, theta, gamma, k.zenith_Y);
+	if(y == 0.0) return mkc(0.f, 0.f, 0.f);
+	const double X = (x / y) * Y;
+	const double z = ((1.0 - x - y) / y) * Y;
+	Col c = mkc((float)(3.240479 * X - 1.537150 * Y - 0.498535 * z), (float)(-0.969256 * X + 1.875992 * Y + 0.041556 * z),
+	            (float)(0.055648 * X - 0.204043 * Y + 1.057311 * z));
+	if(c.r < 0.f) c.r = 0.f; else if(c.r > 1.f) c.r = 1.f;      // clampRgb01, color.h:100-105
+	if(c.g < 0.f) c.g = 0.f; else if(c.g > 1.f) c.g = 1.f;
+	if(c.b < 0.f) c.b = 0.f; else if(c.b > 1.f) c.b = 1.f;
+	return c * k.power;
+}
 // Background::eval: what a ray that leaves the scene in direction `dir` picks up
+template<bool kSky = (YAFGPU_FEAT_SKY != 0)>
 YG_DEV Col bg_eval(const BgScene &bg, const TexScene &ts, V3 dir)
 {
+	if(kSky && bg.rec.kind == YAFGPU_BACKGROUND_GRADIENT) return sky_gradient_eval(*bg.sky, dir);
+	if(kSky && bg.rec.kind == YAFGPU_BACKGROUND_SUNSKY) return sky_sunsky_eval(*bg.sky, dir);
 	if(bg.rec.kind != YAFGPU_BACKGROUND_TEXTURE) return mkc(bg.rec.color[0], bg.rec.color[1], bg.rec.color[2]);
 	float u = 0.f, v = 0.f;
 	if(bg.rec.projection == 1)
@@ -878,23 +967,25 @@ YG_DEV float bglight_calc_from_dir(const BgScene &bg, V3 dir, float &u, float &v
 	return smax(0.000001f, ((float)k2Pi * bg_sin_sample(v)) * bg_clamp_zero(pdf_1 * pdf_2));
 }
 // BackgroundLight::illumSample: never fails; an infinite shadow ray; the colour is the background's in the sampled direction
+template<bool kSky = (YAFGPU_FEAT_SKY != 0)>
 YG_DEV bool bglight_illum_sample(const BgScene &bg, const TexScene &ts, float s_1, float s_2, V3 &wi_dir, float &wi_tmax, float &pdf, Col &col)
 {
 	float u = 0.f, v = 0.f;
 	wi_tmax = -1.f;
 	pdf = bglight_calc_from_sample(bg, s_1, s_2, u, v);
 	wi_dir = bg_inv_spheremap(u, v);
-	col = bg_eval(bg, ts, wi_dir);
+	col = bg_eval<kSky>(bg, ts, wi_dir);
 	return true;
 }
 // BackgroundLight::intersect: always succeeds; returns the INVERSE pdf.  The colour is the background's at the direction the (u, v) of
 // `dir` maps back to (sic :180), not at `dir` itself.  The reference leaves t alone; -1 makes the shadow ray infinite, as for the sun.
+template<bool kSky = (YAFGPU_FEAT_SKY != 0)>
 YG_DEV bool bglight_intersect(const yafgpu_light &l, const BgScene &bg, const TexScene &ts, V3 dir, float &t, Col &col, float &ipdf)
 {
 	float u = 0.f, v = 0.f;
 	const V3 abs_dir = l.abs_intersect ? -dir : dir;
 	ipdf = bglight_calc_from_dir(bg, abs_dir, u, v);
-	col = bg_eval(bg, ts, bg_inv_spheremap(u, v));
+	col = bg_eval<kSky>(bg, ts, bg_inv_spheremap(u, v));
 	const float max_value = l.clamp_intersect;      // Rgb::clampProportionalRgb, color.h:412-445
 	if(max_value > 0.f)
 	{

@@ -275,6 +275,7 @@ YG_DEV const float4 *portallight_records(const DevScene &sc, const yafgpu_light 
 // BackgroundPortalLight::illumSample, :136-168.  Single-sided; no guard on area_ * cos_angle, unlike the mesh light's (:160).
 // sampleSurface (:98-115) is the mesh light's word for word and shares meshlight_cdf and pdf1d_dsample with it; its few lines stand here a
 // second time because moving them out of meshlight_illum_sample changed the code of the mesh light's own shading units
+template<bool kSky = (YAFGPU_FEAT_SKY != 0)>
 YG_DEV bool portallight_illum_sample(const DevScene &sc, const yafgpu_light &l, V3 sp_p, float s_1, float s_2, V3 &wi_dir, float &wi_tmax, float &pdf, Col &col)
 {
 	const float *cdf = meshlight_cdf(sc, l);
@@ -304,7 +305,7 @@ YG_DEV bool portallight_illum_sample(const DevScene &sc, const yafgpu_light &l, 
 	if(cos_angle <= 0.f) return false;      // no light behind the portal
 	wi_tmax = dist;
 	wi_dir = ldir;
-	col = bg_eval(sc.bg, sc.tex, ldir) * l.portal_power;
+	col = bg_eval<kSky>(sc.bg, sc.tex, ldir) * l.portal_power;
 	pdf = (float)((double)dist_sqr * kPi / (double)(l.area * cos_angle));
 	return true;
 }
@@ -312,6 +313,7 @@ YG_DEV bool portallight_illum_sample(const DevScene &sc, const yafgpu_light &l, 
 // reference asks a kd-tree of the light's triangles for the closest hit with tmin <= t < infinity among those of a visible material
 // (TriKdTree::intersect, kdtree_triangle.cc:782-786); a scan of the light's records with the same triangle test finds the same t.  The lanes
 // of a wave take turns by light, as in meshlight_intersect.
+template<bool kSky = (YAFGPU_FEAT_SKY != 0)>
 YG_DEV bool portallight_intersect(const DevScene &sc, const yafgpu_light &l, V3 from, V3 dir, float tmin, float &t, float &ipdf, Col &col)
 {
 	float z = __builtin_inff();
@@ -340,7 +342,7 @@ YG_DEV bool portallight_intersect(const DevScene &sc, const yafgpu_light &l, V3 
 	if(cos_angle <= 0.f) return false;
 	const float idist_sqr = 1.f / (z * z);
 	ipdf = (float)((double)((idist_sqr * l.area) * cos_angle) * k1Pi);
-	col = bg_eval(sc.bg, sc.tex, dir) * l.portal_power;
+	col = bg_eval<kSky>(sc.bg, sc.tex, dir) * l.portal_power;
 	t = z;
 	return true;
 }
@@ -1136,7 +1138,8 @@ YG_DEV int st_after_closest(const WfArgs &a, uint32_t slot, Hot &h, Ctl &c, uint
 		{
 			if(rp.has_background && !rp.bg_transp_refract)
 			{	// a texture background is a function of the ray's direction (integrator_path_tracer.cc:326-331, integrator_direct_light.cc:172-176)
-				if(YG_LIGHT_HAS(YAFGPU_LIGHT_BACKGROUND) && sc.bg.rec.kind == YAFGPU_BACKGROUND_TEXTURE) c.col = c.col + bg_eval(sc.bg, sc.tex, v3(REC(1)));
+				// (as are the two skies, in the units that have their code)
+				if(YG_LIGHT_HAS(YAFGPU_LIGHT_BACKGROUND) && (sc.bg.rec.kind == YAFGPU_BACKGROUND_TEXTURE || (YAFGPU_FEAT_SKY && sc.bg.rec.kind >= YAFGPU_BACKGROUND_GRADIENT))) c.col = c.col + bg_eval(sc.bg, sc.tex, v3(REC(1)));
 				else c.col = c.col + mkc(rp.background[0], rp.background[1], rp.background[2]);
 			}
 			// (z: the sample's call ordinal and light calls so far belong to the whole sample, see WfArgs::ev_m)

@@ -60,7 +60,7 @@ C_API_SYMBOLS = [
     "yafaray_createInterface", "yafaray_destroyInterface", "yafaray_getLastError", "yafaray_getVersion",
     "yafaray_startScene", "yafaray_startGeometry", "yafaray_endGeometry", "yafaray_getNextFreeId",
     "yafaray_startTriMesh", "yafaray_endTriMesh", "yafaray_addVertex", "yafaray_addNormal", "yafaray_addTriangle",
-    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getCamera", "yafaray_getIntegratorAO", "yafaray_getMaskMaterial", "yafaray_getIesLight", "yafaray_getBlendMaterial", "yafaray_getMaterialTable", "yafaray_addTriangles",
+    "yafaray_smoothMesh", "yafaray_getMeshCornerNormals", "yafaray_getLights", "yafaray_getBackground", "yafaray_getSky", "yafaray_getCamera", "yafaray_getIntegratorAO", "yafaray_getMaskMaterial", "yafaray_getIesLight", "yafaray_getBlendMaterial", "yafaray_getMaterialTable", "yafaray_addTriangles",
     "yafaray_startTriMeshPtr", "yafaray_addVertexWithOrco", "yafaray_addUv", "yafaray_addTriangleWithUv",
     "yafaray_startCurveMesh", "yafaray_endCurveMesh", "yafaray_addCurves", "yafaray_getCurves", "yafaray_addInstance", "yafaray_getInstances",
     "yafaray_paramsSetColorArray", "yafaray_paramsSetMatrix", "yafaray_paramsSetMatrixD", "yafaray_setInputColorSpace",
@@ -115,6 +115,7 @@ def load():
         "yafaray_getMeshCornerNormals": (ci, [vp, C.c_uint, C.POINTER(cf), ci]),
         "yafaray_getLights": (ci, [vp, vp, ci]),
         "yafaray_getBackground": (ci, [vp, cp, vp]),
+        "yafaray_getSky": (ci, [vp, cp, vp]),
         "yafaray_getCamera": (ci, [vp, cp, vp]),
         "yafaray_getIntegratorAO": (ci, [vp, cp, C.POINTER(ci), C.POINTER(ci), C.POINTER(cf), C.POINTER(cf)]),
         "yafaray_getMaskMaterial": (ci, [vp, cp, vp]),
@@ -431,6 +432,17 @@ class Interface:
         i = out.view(np.int32)
         return {"kind": int(i[0]), "color": out[1:4].copy(), "power": out[4], "texture": int(i[5]), "projection": int(i[6]),
                 "rotation": out[7], "sin_r": out[8], "cos_r": out[9], "has_ibl": int(i[10]), "shoots_caustic": int(i[11])}
+
+    def getSky(self, name):
+        """the yafgpu_sky record (include/yafgpu.h) createBackground made under `name`, as a dict: a gradientback's four colours
+        (float32, already times power) and a sunsky's constants (float64); zeros for every other type of background"""
+        out = np.zeros(30, dtype=np.float64)                  # 240 bytes: 20 float words, then 20 doubles
+        self._ok(self._L.yafaray_getSky(self._h, _b(name), out.ctypes.data_as(C.c_void_p)), "getSky")
+        f, d = out[:10].view(np.float32), out[10:]
+        return {"horizon": f[0:3].copy(), "zenith": f[3:6].copy(), "horizon_ground": f[6:9].copy(), "zenith_ground": f[9:12].copy(),
+                "power": f[12], "from": f[13:16].copy(), "turbidity": f[16],
+                "theta_s": d[0], "phi_s": d[1], "zenith_x": d[2], "zenith_y": d[3], "zenith_Y": d[4],
+                "perez_x": d[5:10].copy(), "perez_y": d[10:15].copy(), "perez_Y": d[15:20].copy()}
 
     CAMERA_WORDS = 69
     CAMERA_INT_FIELDS = ("resx", "resy", "bokeh_type", "bokeh_bias", "type", "circular", "projection")

@@ -83,6 +83,7 @@ def _color(v):
 
 _COLOR_KEYS = {"color", "mirror_color", "diffuse_color", "filter_color", "absorption"}
 _NODE_COLOR_KEYS = {"color", "color1", "color2", "def_col", "upper_color"}
+_BACKGROUND_COLOR_KEYS = _COLOR_KEYS | {"horizon_color", "zenith_color", "horizon_ground_color", "zenith_ground_color"}      # gradientback's
 
 
 def load_scene(yi, scene, render):
@@ -130,8 +131,9 @@ def load_scene(yi, scene, render):
     if bg is not None:
         yi.paramsClearAll()
         if isinstance(bg, dict):
-            # createBackground's own parameters (type constant | textureback, ibl, ...); a textureback names one of scene["textures"]
-            yi.paramsSet({k: (_color(v) if k in _COLOR_KEYS else v) for k, v in bg.items()})
+            # createBackground's own parameters (type constant | textureback | gradientback | sunsky, ibl, ...); a textureback names one
+            # of scene["textures"]
+            yi.paramsSet({k: (_color(v) if k in _BACKGROUND_COLOR_KEYS else v) for k, v in bg.items()})
         else:
             yi.paramsSet({"type": "constant", "color": _color(bg)})
         yi.createBackground("world_background")
