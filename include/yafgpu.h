@@ -625,6 +625,10 @@ void yafgpu_kdtree_get(const yafgpu_kdtree_t *tree, uint32_t *nodes, uint32_t *r
  * on return.  inline_leaves = 0 sends every non-empty leaf to the escape array.  0, or -2 when the tree is too large. */
 int32_t yafgpu_kdtree_treelets(const uint32_t *nodes, uint32_t n_nodes, int32_t inline_leaves, uint32_t *words, uint32_t *n_words,
                                uint32_t *leaves, uint32_t *n_leaves, uint32_t *root);
+/* Where the traversal's own copy of the triangle records keeps every triangle (kdtree_build.h, tri_order): pos[t] = the rank of
+ * triangle t's first occurrence in the n_refs leaf references as yafgpu_kdtree_get returns them, unreferenced triangles behind the
+ * referenced ones in id order.  pos has room for n_tris values.  (A scene created with YAFGPU_TRI_ORDER=id takes the identity.) */
+void yafgpu_kdtree_tri_order(const uint32_t *refs, uint32_t n_refs, uint32_t n_tris, uint32_t *pos);
 void yafgpu_kdtree_destroy(yafgpu_kdtree_t *tree);
 
 /* kd-tree built on the host, downloadable for inspection/tests: nodes = n_nodes*2 uint32, refs = n_leaf_refs uint32 */

@@ -413,6 +413,19 @@ int build_treelets(const std::vector<KdNode> &nodes, bool inline_leaves, Treelet
 	return overflow ? -2 : 0;
 }
 
+void tri_order(const uint32_t *refs, size_t n_refs, uint32_t n_tris, std::vector<uint32_t> &pos)
+{
+	constexpr uint32_t kNone = 0xffffffffu;
+	pos.assign((size_t)n_tris, kNone);
+	uint32_t rank = 0u;
+	for(size_t i = 0; i < n_refs; ++i)
+	{
+		const uint32_t t = refs[i];
+		if(t < n_tris && pos[t] == kNone) pos[t] = rank++;
+	}
+	for(uint32_t t = 0u; t < n_tris; ++t) if(pos[t] == kNone) pos[t] = rank++;
+}
+
 } // namespace yafgpu
 
 // ---- host-only C entry points (include/yafgpu.h) ----
@@ -458,6 +471,12 @@ void yafgpu_kdtree_get(const yafgpu_kdtree_t *k, uint32_t *nodes, uint32_t *refs
 	if(nodes && !k->t.nodes.empty()) std::memcpy(nodes, k->t.nodes.data(), k->t.nodes.size() * sizeof(yafgpu::KdNode));
 	if(refs && !k->t.refs.empty()) std::memcpy(refs, k->t.refs.data(), k->t.refs.size() * sizeof(uint32_t));
 	if(bound6) for(int i = 0; i < 3; ++i) { bound6[i] = k->t.bound_lo[i]; bound6[3 + i] = k->t.bound_hi[i]; }
+}
+void yafgpu_kdtree_tri_order(const uint32_t *refs, uint32_t n_refs, uint32_t n_tris, uint32_t *pos)
+{
+	std::vector<uint32_t> p;
+	yafgpu::tri_order(refs, (size_t)n_refs, n_tris, p);
+	if(pos && !p.empty()) std::memcpy(pos, p.data(), p.size() * sizeof(uint32_t));
 }
 void yafgpu_kdtree_destroy(yafgpu_kdtree_t *k) { delete k; }
 }

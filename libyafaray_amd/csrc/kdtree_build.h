@@ -59,4 +59,11 @@ struct TreeletLayout
 // treelets or escaped leaves for the link's index bits.
 int build_treelets(const std::vector<KdNode> &nodes, bool inline_leaves, TreeletLayout &out);
 
+// The order of wf_trace's own copy of the triangle records: pos[t] is the rank of triangle t's first occurrence in the leaf
+// references, which are in depth-first leaf order, so that leaves next to each other in space find their records next to each other
+// in memory; triangles that no leaf references follow, in id order.  A permutation of [0, n_tris); O(refs).
+//   refs 3 1 3 0 1 6 6 3 of 8 triangles: pos = 2 1 4 0 5 6 3 7
+// (a reference that is no triangle id is skipped)
+void tri_order(const uint32_t *refs, size_t n_refs, uint32_t n_tris, std::vector<uint32_t> &pos);
+
 } // namespace yafgpu

@@ -58,6 +58,10 @@ struct DevScene
 	uint32_t tl_root;            // the link every walk of wf_trace starts at
 	const uint32_t *refs;        // leaf references
 	const float4 *tri;           // 3 x float4 per triangle: (a, eps) (e1, mat|vis<<30) (e2, 0)
+	const float4 *tri_walk;      // wf_trace's own copy of the records, triangle t at position pos[t] (kdtree_build.h, tri_order: leaf order, or the
+	                             // identity with YAFGPU_TRI_ORDER=id), the spare word of its third float4 holding t as bits; everything that takes a
+	                             // hit's triangle id reads the arrays addressed by id
+	const uint32_t *refs_walk;   // refs_walk[i] = pos[refs[i]]: the leaf references as positions in tri_walk
 	const float4 *tri_ng;        // geometric normal + smooth flag
 	const float4 *tri_vn;        // 3 x float4 per triangle (vertex normals) or nullptr
 	const yafgpu_material *mats;
@@ -1029,6 +1033,28 @@ __global__ __launch_bounds__(kBlock) void portallight_rows_kernel(yafgpu_light *
 	lgeo_rows(lights, k, lgeo);
 }
 
+// wf_trace's own copy of the triangle records (DevScene::tri_walk, refs_walk): record t goes to position pos[t] with t in the spare
+// word of its third float4, and every leaf reference becomes the position of its triangle.  One grid-stride loop over both ranges.
+__global__ __launch_bounds__(kBlock) void walk_copy_kernel(const float4 *rec, const uint32_t *pos, uint32_t n_tris, const uint32_t *refs, uint32_t n_refs,
+                                                            float4 *tri_walk, uint32_t *refs_walk)
+{
+	const size_t stride = (size_t)gridDim.x * blockDim.x, i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	for(size_t t = i0; t < (size_t)n_tris; t += stride)
+	{
+		const size_t p = pos[t];
+		if(p >= (size_t)n_tris) continue;      // (pos is a permutation of [0, n_tris): never taken)
+		const float4 r2 = rec[3 * t + 2];
+		tri_walk[3 * p] = rec[3 * t];
+		tri_walk[3 * p + 1] = rec[3 * t + 1];
+		tri_walk[3 * p + 2] = make_float4(r2.x, r2.y, r2.z, __uint_as_float((uint32_t)t));
+	}
+	for(size_t i = i0; i < (size_t)n_refs; i += stride)
+	{
+		const uint32_t t = refs[i];
+		refs_walk[i] = t < n_tris ? pos[t] : 0u;      // (a reference is a triangle id: the builders make no other)
+	}
+}
+
 } // namespace yafgpu
 
 // ================================================================================================
@@ -1714,6 +1740,32 @@ static int upload_tree(yafgpu_scene *s)
 	return 0;
 }
 
+// wf_trace's own copy of the triangle records and of the leaf references (DevScene::tri_walk, refs_walk), in leaf order (kdtree_build.h,
+// tri_order).  The rows are on the device (assemble_scene may have made them there), so a kernel makes the copy.  YAFGPU_TRI_ORDER=id keeps
+// the copy in id order: the same kernels on the layout the arrays addressed by id have (a comparison aid).
+static int upload_walk_copy(yafgpu_scene *s, const AssembledRows &rows)
+{
+	DevScene &dv = s->dev;
+	const uint32_t n = rows.n, n_refs = (uint32_t)s->tree.refs.size();
+	std::vector<uint32_t> pos;
+	const char *e = std::getenv("YAFGPU_TRI_ORDER");
+	if(e && std::strcmp(e, "id") == 0) { pos.resize(n); for(uint32_t t = 0u; t < n; ++t) pos[t] = t; }
+	else tri_order(s->tree.refs.data(), s->tree.refs.size(), n, pos);
+	DevMem<uint32_t> d_pos;
+	float4 *tri_walk = nullptr; uint32_t *refs_walk = nullptr;
+	int rc = 0;
+	if((rc = temp_upload(d_pos, pos.data(), pos.size())) || (rc = scene_alloc(s, 3 * (size_t)n, &tri_walk)) || (rc = scene_alloc(s, (size_t)n_refs, &refs_walk))) return rc;
+	if(n)
+	{
+		const uint32_t blocks = std::min<uint32_t>((std::max(n, n_refs) + (uint32_t)kBlock - 1u) / (uint32_t)kBlock, 8192u);
+		hipLaunchKernelGGL(walk_copy_kernel, dim3(blocks), dim3(kBlock), 0, nullptr, rows.rec, (const uint32_t *)d_pos.p, n, dv.refs, n_refs, tri_walk, refs_walk);
+		HIP_OK(hipGetLastError());
+		HIP_OK(hipDeviceSynchronize());
+	}
+	dv.tri_walk = tri_walk; dv.refs_walk = refs_walk;
+	return 0;
+}
+
 static int upload_lights(yafgpu_scene *s, const yafgpu_scene_desc *d)
 {
 	s->h_lights.assign(d->lights, d->lights + d->n_lights);
@@ -1939,7 +1991,7 @@ int yafgpu_scene_create(const yafgpu_scene_desc *d, yafgpu_scene_t **out)
 	if((rc = build_tree(s, d, rows))) return rc;
 	const auto t1 = std::chrono::steady_clock::now();
 	DevScene &dv = s->dev;
-	if((rc = upload_tree(s)) || (rc = upload_rows(s, d, rows))) return rc;
+	if((rc = upload_tree(s)) || (rc = upload_rows(s, d, rows)) || (rc = upload_walk_copy(s, rows))) return rc;
 	dv.tri = rows.rec; dv.tri_ng = rows.ng; dv.tri_vn = rows.vn; dv.mats = rows.mats;
 	dv.n_tris = (int)rows.n; dv.n_mats = d->n_materials;
 	if((rc = upload_lights(s, d)) || (rc = upload_textures(s, d)) || (rc = upload_nodes(s, d, rows)) || (rc = upload_qmc_tables(s))) return rc;

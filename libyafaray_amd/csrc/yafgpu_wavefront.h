@@ -2350,7 +2350,7 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 	};
 	constexpr int kVoteNum = YAFGPU_VOTE_NUM, kVoteDen = YAFGPU_VOTE_DEN, kNodeBurst = YAFGPU_NODE_BURST;
 	uint32_t ws = kNoRay;
-	uint32_t p_cur = 0u, p_end = 0u, ti = 0u;       // pending leaf: references [p_cur, p_end) still to test, ti = refs[p_cur] (in flight)
+	uint32_t p_cur = 0u, p_end = 0u, ti = 0u;       // pending leaf: references [p_cur, p_end) still to test, ti = refs_walk[p_cur] (in flight): a position in tri_walk
 	float p_tmax = 0.f;                              // exit distance of the pending leaf's cell
 	bool done = false;
 	uint32_t spec = 0u;                              // kStats: node steps + leaves of the walk ahead of the pending leaf
@@ -2495,7 +2495,8 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 			else
 			{
 				const bool better = ok && t < z && t >= ray_tmin && (vis == 0u || vis == 1u);
-				z = better ? t : z; tri = better ? (int)ti : tri; bu = better ? u : bu; bv = better ? v : bv; hit = hit || better;
+				// ti is the record's position in the walk copy; the triangle's id travels in the record's spare word
+				z = better ? t : z; tri = better ? (int)__float_as_uint(r2.w) : tri; bu = better ? u : bu; bv = better ? v : bv; hit = hit || better;
 			}
 			++p_cur; ti = ref_v;
 			if(p_cur >= p_end)
@@ -2554,14 +2555,14 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 			else if(!YAFGPU_TRACE_POSTPONE)
 			{	// (comparison build) stop at every non-empty leaf until its tests are through
 				if(kStats) ++cn.leaves;
-				p_cur = first; p_end = first + np; p_tmax = tmax; ti = sc.refs[first]; ws = kBlocked;
+				p_cur = first; p_end = first + np; p_tmax = tmax; ti = sc.refs_walk[first]; ws = kBlocked;
 			}
 			else if(p_cur < p_end) ws = kBlocked;          // a second non-empty leaf: wait for the pending one (the link stays)
 			else
 			{
 				if(kStats) ++cn.leaves;
 				p_cur = first; p_end = first + np; p_tmax = tmax;
-				ti = sc.refs[first];                          // in flight while the lane walks on
+				ti = sc.refs_walk[first];                     // in flight while the lane walks on
 				leaf_end();
 			}
 		};
@@ -2571,8 +2572,8 @@ __global__ __launch_bounds__(kBlock, YAFGPU_TRACE_WAVES) void wf_trace(const WfA
 			if(has_pend)
 			{
 				uint32_t ref_v = 0u;
-				if(p_cur + 1u < p_end) ref_v = sc.refs[p_cur + 1u];
-				const float4 r0 = sc.tri[3u * ti], r1 = sc.tri[3u * ti + 1u], r2 = sc.tri[3u * ti + 2u];
+				if(p_cur + 1u < p_end) ref_v = sc.refs_walk[p_cur + 1u];
+				const float4 r0 = sc.tri_walk[3u * ti], r1 = sc.tri_walk[3u * ti + 1u], r2 = sc.tri_walk[3u * ti + 2u];
 				tri_step(r0, r1, r2, ref_v);
 			}
 		}

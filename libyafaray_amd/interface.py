@@ -87,7 +87,7 @@ GPU_ABI_SYMBOLS = [
     "yafgpu_last_error", "yafgpu_device_count", "yafgpu_set_device", "yafgpu_scene_create", "yafgpu_scene_destroy",
     "yafgpu_scene_info", "yafgpu_planes_bytes", "yafgpu_render_tiles", "yafgpu_film_combine", "yafgpu_render_to_host", "yafgpu_render_passes_to_host",
     "yafgpu_trace_closest", "yafgpu_trace_shadow", "yafgpu_trace_reservation", "yafgpu_trace_schedule", "yafgpu_scene_get_tree", "yafgpu_probe",
-    "yafgpu_kdtree_build", "yafgpu_kdtree_build_device", "yafgpu_kdtree_info", "yafgpu_kdtree_get", "yafgpu_kdtree_destroy", "yafgpu_kdtree_treelets",
+    "yafgpu_kdtree_build", "yafgpu_kdtree_build_device", "yafgpu_kdtree_info", "yafgpu_kdtree_get", "yafgpu_kdtree_destroy", "yafgpu_kdtree_treelets", "yafgpu_kdtree_tri_order",
     "yafgpu_set_profiling", "yafgpu_scene_set_pass_pipelining", "yafgpu_get_profile", "yafgpu_scene_set_abort_flag", "yafgpu_scene_set_exchange", "yafgpu_glibc_rand",
     "yafgpu_image_bytes", "yafgpu_film_to_image", "yafgpu_scene_film_to_image",
 ]
@@ -863,6 +863,19 @@ def build_treelets(nodes, inline_leaves=True):
     if rc:
         raise YafaRayError(f"treelet layout: {rc}")
     return words[:nw.value].reshape(-1, 8), leaves[:nl.value].reshape(-1, 2), root.value
+
+
+def tri_order(refs, n_tris):
+    """Where wf_trace's own copy of the triangle records keeps every triangle (kdtree_build.h, tri_order): pos (n_tris,) u32, from
+    the leaf references as build_kdtree returns them (no GPU needed).  YAFGPU_TRI_ORDER=id makes the scene take the identity instead."""
+    L = load()
+    up = C.POINTER(C.c_uint32)
+    L.yafgpu_kdtree_tri_order.argtypes = [up, C.c_uint32, C.c_uint32, up]
+    L.yafgpu_kdtree_tri_order.restype = None
+    r = np.ascontiguousarray(refs, dtype=np.uint32).reshape(-1)
+    pos = np.zeros(max(int(n_tris), 1), np.uint32)
+    L.yafgpu_kdtree_tri_order(r.ctypes.data_as(up), r.shape[0], int(n_tris), pos.ctypes.data_as(up))
+    return pos[:int(n_tris)]
 
 
 def trace_reservation(n, seen, waves):
